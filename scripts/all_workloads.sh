@@ -1,5 +1,6 @@
 set -e
-run() { echo "== $*"; python bench.py "$@" --no-cpu-baseline > gpurun_out/aw.json 2> gpurun_out/aw.err || { tail -5 gpurun_out/aw.err; exit 1; }; python scripts/show_bench.py gpurun_out/aw.json | head -3; }
+OUT=${OUT:-runs}; mkdir -p $OUT
+run() { echo "== $*"; python bench.py "$@" --full --no-cpu-baseline > $OUT/aw.json 2> $OUT/aw.err || { tail -5 $OUT/aw.err; exit 1; }; python scripts/show_bench.py $OUT/aw.json | head -3; }
 run --workload bench100
 run --workload poisson2d --steps 200 --warmup 20
 run --workload banded --steps 200 --warmup 20

@@ -113,3 +113,43 @@ def test_tile_plans_name_their_kernel_and_count_no_more_bytes():
     assert s["bytes_moved_per_launch"] == NNZ * 8 + 2 * N * 8 and s["kernel_id"] == 4
     assert s["bytes_moved_per_launch"] < bench.stream_info(FakeCsr(1, 7, 0, 781250, 675000), N, NNZ, 8)["bytes_moved_per_launch"]
     assert "spmv_tile_off_kernel" in bench.roofline_of(s, 740e-6, 201, N, NNZ, 8, 100)["kernel"]
+
+
+def test_dump_outputs_whole_sampled_and_complex(tmp_path, monkeypatch):
+    """--dump-outputs: float64 .npy files; a large x becomes the same seeded sample every time, a complex x (n, 2) pairs."""
+    x = np.arange(100, dtype=np.float64) * 0.5
+    bench.dump_outputs(str(tmp_path / "whole"), x)
+    assert np.array_equal(np.load(str(tmp_path / "whole" / "x.npy")), x)
+    monkeypatch.setattr(bench, "DUMP_MAX_VALUES", 16)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), x)
+    s1, s2 = (np.load(str(tmp_path / d / "x_sample.npy")) for d in ("s1", "s2"))
+    assert s1.dtype == np.float64 and 0 < s1.size <= 16 and np.array_equal(s1, s2) and np.all(np.diff(s1) > 0)
+    assert np.all(np.isin(s1, x))
+    z = (np.arange(6) + 1j * np.arange(6)[::-1]).astype(np.complex128)
+    bench.dump_outputs(str(tmp_path / "c"), z)
+    c = np.load(str(tmp_path / "c" / "x.npy"))
+    assert c.shape == (6, 2) and np.array_equal(c[:, 0], z.real) and np.array_equal(c[:, 1], z.imag)
+
+
+def test_plain_run_prints_the_headline_and_dumps_the_timed_result(tmp_path, oracle):
+    """A plain `--workload bench100` run (CPU only): one JSON line with the headline fields and none of --full's checks;
+    --dump-outputs writes the x of the timed K-iteration solve, bit for bit the oracle's."""
+    import subprocess
+    from sprsolve_amd import gen
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "bench100", "--steps", "7",
+                        "--dump-outputs", str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = p.stdout.splitlines()
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 7 and d["ms_per_step"] > 0 and d["unit"] == "iterations/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert "converge_check" not in d and "also" not in d and "all_cores" not in d["cpu_baseline"]
+    ip, ix, dv = gen.grid_laplacian_dirichlet(100, 100)
+    oracle.set_threads(4)
+    r = oracle.bicgstab(ip.astype(np.int64), ix.astype(np.int64), dv, gen.dirichlet_rhs(100, 100), np.zeros(10000), 7, 0.0,
+                        parallel=True)
+    x = np.load(str(out / "x.npy"))
+    assert x.dtype == np.float64 and np.array_equal(x, r.x)
