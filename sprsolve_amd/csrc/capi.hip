@@ -328,7 +328,7 @@ int mul_vec_host(const sprs_csr *A, const T *x, size_t x_len, T *y, size_t y_len
     T *dx = (T *)A->x_tmp, *dy = (T *)A->y_tmp;
     SPRS_HIP_TRY(c, hipMemcpyAsync(dx, x, sizeof(T) * x_len, hipMemcpyHostToDevice, c->stream));
     T *part = (T *)A->part;
-    SPRS_TRY(launch_spmv<T>(A, dx, dy, dot_out ? 1 : 0, dx, part, nullptr, nullptr));
+    SPRS_TRY(launch_spmv<T>(A, SpmvPart::Whole, dx, dy, dot_out ? 1 : 0, dx, part, nullptr, nullptr));
     const size_t ncopy = (size_t)A->nrows < y_len ? (size_t)A->nrows : y_len;
     SPRS_HIP_TRY(c, hipMemcpyAsync(y, dy, sizeof(T) * ncopy, hipMemcpyDeviceToHost, c->stream));
     if (dot_out) SPRS_TRY(reduce_partials_host<T>(c, part, spmv_num_partials(A), dot_out));   // mat.rs:151
@@ -343,10 +343,10 @@ int mul_vec_dev(const sprs_csr *A, const T *dx, T *dy, T *dot_out) {
     sprs_ctx *c = A->ctx;
     CtxLock lock(c);
     SPRS_HIP_TRY(c, hipSetDevice(c->device));
-    if (!dot_out) return launch_spmv<T>(A, dx, dy, 0, nullptr, nullptr, nullptr, nullptr);
+    if (!dot_out) return launch_spmv<T>(A, SpmvPart::Whole, dx, dy, 0, nullptr, nullptr, nullptr, nullptr);
     SPRS_TRY(ensure_tmp<T>(A));
     T *part = (T *)A->part;
-    SPRS_TRY(launch_spmv<T>(A, dx, dy, 1, dx, part, nullptr, nullptr));
+    SPRS_TRY(launch_spmv<T>(A, SpmvPart::Whole, dx, dy, 1, dx, part, nullptr, nullptr));
     return reduce_partials_host<T>(c, part, spmv_num_partials(A), dot_out);
 }
 
@@ -362,7 +362,7 @@ int mul_vec_timed(const sprs_csr *A, const T *dx, T *dy, int reps, double *ms) {
     SPRS_HIP_TRY(c, hipEventCreate(&e0));
     SPRS_HIP_TRY(c, hipEventCreate(&e1));
     SPRS_HIP_TRY(c, hipEventRecord(e0, c->stream));
-    for (int i = 0; i < reps; ++i) SPRS_TRY(launch_spmv<T>(A, dx, dy, 0, nullptr, nullptr, nullptr, nullptr));
+    for (int i = 0; i < reps; ++i) SPRS_TRY(launch_spmv<T>(A, SpmvPart::Whole, dx, dy, 0, nullptr, nullptr, nullptr, nullptr));
     SPRS_HIP_TRY(c, hipEventRecord(e1, c->stream));
     SPRS_HIP_TRY(c, hipEventSynchronize(e1));
     float t = 0.f;
@@ -568,17 +568,19 @@ int64_t sprs_csr_nnz(const sprs_csr *A) { return A ? A->nnz : -1; }
 int sprs_csr_wide_blocks(const sprs_csr *A, int64_t *n_blocks, int64_t *n_uniform) {
     if (!A || !n_blocks || !n_uniform) return SPRS_INVALID_ARGUMENT;
     *n_blocks = 0; *n_uniform = 0;
-    if (dict_mode(A) == 0) {       // plain CSR stream: the 64-row blocks; "uniform" = equal-length blocks, which read no row_ptr
+    const SpmvRoute r = spmv_route(A, SpmvPart::Whole, false);
+    if (r.format == 0) {       // plain CSR stream: the 64-row blocks; "uniform" = equal-length blocks, which read no row_ptr
         *n_blocks = A->n_rowblk; *n_uniform = A->blk_desc_eq ? A->n_eq_blocks : 0;
         return SPRS_OK;
     }
     // the descriptors the SpMV of this handle walks: 128-row blocks of the f64 pair-code stream, else the 64-row
-    // blocks of the offset-code stream
-    const bool wide = A->dict->wide_desc && A->dict->n_wide > 0 && dict_mode(A) == 2 && A->ctx->spmv_wide != 0;
-    // (the 64-row pair-code kernel, spmv_wide = 0, walks the plain descriptors: no uniform blocks)
-    const bool offs = dict_mode(A) == 1 && A->ctx->spmv_uniform != 0;
-    const void *src = wide ? A->dict->wide_desc : (offs ? A->dict->off_desc : nullptr);
-    const int64_t nb = wide ? A->dict->n_wide : (src ? A->n_rowblk : 0);
+    // blocks of the offset-code stream (the 64-row pair-code kernel walks the plain descriptors: no uniform blocks)
+    const sprs_dict *D = A->dict;
+    // (as always reported: a matrix of one row or column has its 128-row descriptors counted though the Pair2 guard walks it by 64-row blocks)
+    const bool one_line = r.format == 2 && D->wide_desc && (A->nrows < 2 || A->ncols < 2) && A->ctx->spmv_wide != 0;
+    const bool wide = (D->wide_desc && r.desc == D->wide_desc) || one_line;
+    const void *src = wide ? D->wide_desc : (D->off_desc && r.desc == D->off_desc ? D->off_desc : nullptr);
+    const int64_t nb = wide ? D->n_wide : (src ? A->n_rowblk : 0);
     if (!src || nb == 0) return SPRS_OK;
     sprs_ctx *c = A->ctx;
     CtxLock lock(c);
@@ -593,38 +595,30 @@ int sprs_csr_wide_blocks(const sprs_csr *A, int64_t *n_blocks, int64_t *n_unifor
 int sprs_csr_tile_plan(const sprs_csr *A, int64_t *n_tiles, int64_t *n_tile_blocks, int64_t *n_other_blocks) {
     if (!A || !n_tiles || !n_tile_blocks || !n_other_blocks) return SPRS_INVALID_ARGUMENT;
     *n_tiles = 0; *n_tile_blocks = 0; *n_other_blocks = 0;
-    const sprs_dict *D = A->dict;
-    if (!D || A->ctx->spmv_tile == 0 || A->ctx->spmv_wide == 0) return SPRS_OK;
-    const int dm = dict_mode(A);
-    if (dm != 1 && dm != 2) return SPRS_OK;
-    if (A->dist && A->dist->order_int) {
-        // a distributed operator with an interior / boundary split: the interior launch's plan (boundary blocks are walked singly)
-        const sprs_tile_plan &TI = A->dist->tile_int;
-        if (TI.n_tile <= 0 || A->dist->tile_int_off != (dm == 1)) return SPRS_OK;
-        *n_tiles = TI.n_tile; *n_tile_blocks = (int64_t)TI.n_tile * sprs::tile_blocks();
-        *n_other_blocks = (A->n_rowblk + 1) / 2 - *n_tile_blocks;
-        return SPRS_OK;
-    }
-    if (sprs::chain_plan_used(A)) return SPRS_OK;          // the chains run this handle's SpMV (sprs_csr_chain_plan)
-    const sprs_tile_plan &TP = dm == 2 ? D->tile_pair : D->tile_off;
-    if (TP.n_tile <= 0 || !sprs::tile_plan_used(A)) return SPRS_OK;
+    // a distributed operator with an interior / boundary split: the interior launch's plan (boundary blocks are walked singly)
+    const bool split = A->dist && A->dist->order_int;
+    const SpmvRoute r = spmv_route(A, split ? SpmvPart::Interior : SpmvPart::Whole, false);
+    if (r.kernel != SpmvKernel::TilePair && r.kernel != SpmvKernel::TileOff) return SPRS_OK;
+    const sprs_tile_plan &TP = *r.tile;
+    *n_tiles = TP.n_tile; *n_tile_blocks = (int64_t)TP.n_tile * sprs::tile_blocks();
     // the other blocks in 128-row units (the offset stream walks them as 64-row blocks)
-    *n_tiles = TP.n_tile; *n_tile_blocks = (int64_t)TP.n_tile * sprs::tile_blocks(); *n_other_blocks = dm == 2 ? TP.n_left : (TP.n_left + 1) / 2;
+    if (split) *n_other_blocks = (A->n_rowblk + 1) / 2 - *n_tile_blocks;
+    else *n_other_blocks = r.kernel == SpmvKernel::TilePair ? TP.n_left : (TP.n_left + 1) / 2;
     return SPRS_OK;
 }
 int sprs_csr_chain_plan(const sprs_csr *A, int64_t *n_tiles, int64_t *n_segments, int64_t *n_chains, int64_t *n_other_blocks) {
     if (!A || !n_tiles || !n_segments || !n_chains || !n_other_blocks) return SPRS_INVALID_ARGUMENT;
     *n_tiles = 0; *n_segments = 0; *n_chains = 0; *n_other_blocks = 0;
-    if (!A->dict || !sprs::chain_plan_used(A)) return SPRS_OK;
-    const sprs_chain_plan &CP = A->dict->chain_pair;
-    *n_tiles = CP.n_tile; *n_segments = CP.n_seg; *n_chains = CP.n_chain; *n_other_blocks = CP.n_left;
+    const SpmvRoute r = spmv_route(A, SpmvPart::Whole, false);
+    if (r.kernel != SpmvKernel::Chain) return SPRS_OK;
+    *n_tiles = r.chain->n_tile; *n_segments = r.chain->n_seg; *n_chains = r.chain->n_chain; *n_other_blocks = r.chain->n_left;
     return SPRS_OK;
 }
 int sprs_csr_stream_format(const sprs_csr *A, int *n_offsets, int *n_values) {
     if (!A) return -1;
     if (n_offsets) *n_offsets = A->dict ? A->dict->n_off : 0;
     if (n_values) *n_values = A->dict ? (A->dict->n_pair ? A->dict->n_pair : 0) : 0;
-    return dict_mode(A);
+    return spmv_route(A, SpmvPart::Whole, false).format;
 }
 
 int sprs_diag_precond_destroy(sprs_diag *P) {

@@ -187,20 +187,20 @@ int dist_spmv(const sprs_csr *A, T *x_ext, T *y, int dot_mode, const T *u, T *pa
         constexpr size_t W = sizeof(T) / sizeof(Real<T>);
         SPRS_NCCL_TRY(c, rccl().AllGather(x_ext, D->ag_buf, (size_t)D->ag_slice * W, sizeof(Real<T>) == 4 ? ncclFloat : ncclDouble,
                                           (ncclComm_t)D->comm->nccl, c->stream));
-        return launch_spmv<T>(A, reinterpret_cast<const T *>(D->ag_buf), y, dot_mode, u, part0, part1, status, conj_x, fin);
+        return launch_spmv<T>(A, SpmvPart::Whole, reinterpret_cast<const T *>(D->ag_buf), y, dot_mode, u, part0, part1, status, conj_x, fin);
     }
     if (!D->order_int) {
         SPRS_TRY(halo_exchange<T>(A, x_ext));
-        return launch_spmv<T>(A, x_ext, y, dot_mode, u, part0, part1, status, conj_x, fin);
+        return launch_spmv<T>(A, SpmvPart::Whole, x_ext, y, dot_mode, u, part0, part1, status, conj_x, fin);
     }
     SPRS_TRY(halo_begin<T>(A, x_ext));
-    SPRS_TRY(launch_spmv_subset<T>(A, D->order_int, D->n_int, x_ext, y, dot_mode, u, part0, part1, status, conj_x));
+    SPRS_TRY(launch_spmv<T>(A, SpmvPart::Interior, x_ext, y, dot_mode, u, part0, part1, status, conj_x));
     SPRS_TRY(halo_wait(A));
     // the boundary launch starts after the interior one has finished (same stream): its last workgroup finalizes the
     // concatenated partials of both
-    const int off = spmv_subset_grid(A, D->n_int);
-    return launch_spmv_subset<T>(A, D->order_bnd, D->n_bnd, x_ext, y, dot_mode, u, part0 ? part0 + off : nullptr,
-                                 part1 ? part1 + off : nullptr, status, conj_x, fin);
+    const int off = spmv_route(A, SpmvPart::Interior, conj_x).grid;
+    return launch_spmv<T>(A, SpmvPart::Boundary, x_ext, y, dot_mode, u, part0 ? part0 + off : nullptr, part1 ? part1 + off : nullptr,
+                          status, conj_x, fin);
 }
 template int dist_spmv<double>(const sprs_csr *, double *, double *, int, const double *, double *, double *, const int *, bool, const Fin *);
 template int dist_spmv<cplx>(const sprs_csr *, cplx *, cplx *, int, const cplx *, cplx *, cplx *, const int *, bool, const Fin *);
@@ -297,9 +297,10 @@ int dist_csr_create(sprs_comm *comm, int64_t n_local, int64_t n_ext, int64_t nnz
             // LDS-window tiles (spmv_dict.hip) of the stream this handle multiplies with: the interior launch keeps the tiles
             // that hold interior rows only (the last plane of a slab can look exactly like the stencil — its halo columns sit
             // one plane behind the local rows — and must wait for the halo) and walks the other interior blocks one by one
-            if (A->dict && sprs::tile_plan_used(A)) {
-                const bool off_stream = sprs::dict_mode(A) == 1;
-                const sprs_tile_plan &TP = off_stream ? A->dict->tile_off : A->dict->tile_pair;
+            const sprs::SpmvRoute rw = sprs::spmv_route(A, sprs::SpmvPart::Whole, false);
+            if (rw.kernel == sprs::SpmvKernel::TilePair || rw.kernel == sprs::SpmvKernel::TileOff) {
+                const bool off_stream = rw.kernel == sprs::SpmvKernel::TileOff;
+                const sprs_tile_plan &TP = *rw.tile;
                 const int nw = (A->n_rowblk + 1) / 2, TB = sprs::tile_blocks();
                 std::vector<char> bnd128((size_t)nw, 0), in_int_tile((size_t)nw, 0);
                 for (int j = 0; j < nw; ++j) {

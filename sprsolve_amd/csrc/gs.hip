@@ -182,7 +182,7 @@ int gs_solve_dev(sprs_gauss_seidel *G, const T *rhs, T *x, size_t max_iter, Real
     SPRS_TRY(norm2_host<T>(c, n, rhs, &b_norm));                            // :83 accumulated, :87 sqrt
     const R tol2 = eps * b_norm;
     auto residual = [&](const T *xx, R *res) -> int {
-        SPRS_TRY(launch_spmv<T>(G->A, xx, res_v, 0, nullptr, nullptr, nullptr, nullptr));     // :90 / :128
+        SPRS_TRY(launch_spmv<T>(G->A, SpmvPart::Whole, xx, res_v, 0, nullptr, nullptr, nullptr, nullptr));     // :90 / :128
         SPRS_TRY((launch_axpy<T, T>(c, n, sneg(sone<T>()), rhs, res_v)));                     // :97 / :131
         return norm2_host<T>(c, n, res_v, res);                                               // :104 / :133
     };

@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <ctime>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/sprsolve_hip.h"
@@ -272,36 +273,77 @@ struct sprs_diag {
 namespace sprs {
 
 // ---- spmv.hip
-// y = A x.  dot_mode 0: none; 1: part0[b] = sum conj(u_i) y_i; 2: part0 = sum conj(y_i) y_i, part1 = sum conj(y_i) u_i.
-// status (device int*, may be null): kernels return immediately when *status != 0.
+// Which kernel an SpMV launch takes, its grid and its block walk: spmv_route() is the one place that holds this policy and
+// the only code that reads the launch-time SpMV knobs.  It runs at every launch (a knob changed after creation is followed
+// by the next launch).  The launches of one operator application: the whole matrix, or the interior and the boundary row
+// blocks of a distributed operator split at creation (dist.hip), whose dot partials are concatenated.
+enum class SpmvPart { Whole, Interior, Boundary };
+enum class SpmvKernel {
+    Csr,        // spmv_kernel: plain CSR, 64-row blocks (spmv.hip)
+    CsrWide,    // spmv_wide_kernel: f64 plain CSR, 16-byte loads
+    Dict,       // spmv_dict_kernel: offset or pair codes, lane per row (spmv_dict.hip)
+    DictWide,   // spmv_dict_kernel: f64 offset codes, 16-byte value loads
+    Pair2,      // spmv_pair2_kernel: f64 pair codes, two rows per lane, 128-row blocks
+    TilePair,   // spmv_tile_kernel: LDS x-window tiles of the f64 pair-code stream (spmv_tile.hip)
+    TileOff,    // spmv_tile_off_kernel: ... of the f64 offset-code stream (spmv_tile_off.hip)
+    Chain,      // spmv_chain_kernel: plane-streaming chains of the f64 pair-code stream (spmv_chain.hip)
+};
+struct BlkDesc;
+struct SpmvRoute {
+    SpmvKernel kernel;
+    int format;                     // stream: 0 plain, 1 offset codes, 2 pair codes (offset + value)
+    int grid;                       // workgroups == partials this launch writes
+    int xcd_chunk;                  // block walk: one contiguous chunk per XCD (1) or round-robin (0)
+    const BlkDesc *desc;            // block descriptors the kernel walks
+    const int32_t *order;           // ... in this order (null: natural)
+    int count;                      // ... this many
+    const sprs_tile_plan *tile;     // TilePair / TileOff: the plan
+    const sprs_chain_plan *chain;   // Chain: the plan
+    bool y_nt;                      // CsrWide / Pair2: non-temporal y stores
+};
+SpmvRoute spmv_route(const sprs_csr *A, SpmvPart part, bool conj_x);
+// y = A x over the row blocks of `part`.  dot_mode 0: none; 1: part0[b] = sum conj(u_i) y_i; 2: part0 = sum conj(y_i) y_i,
+// part1 = sum conj(y_i) u_i.  status (device int*, may be null): kernels return immediately when *status != 0.
 // conj_x: gather conj(x[col]) instead of x[col] (CSMINRES: A * conj(q), cs_minres.rs:99-101, without materialising conj(q)).
 template <class T>
-int launch_spmv(const sprs_csr *A, const T *x, T *y, int dot_mode, const T *u, T *part0, T *part1, const int *status,
-                bool conj_x = false, const Fin *fin = nullptr);
+int launch_spmv(const sprs_csr *A, SpmvPart part, const T *x, T *y, int dot_mode, const T *u, T *part0, T *part1,
+                const int *status, bool conj_x = false, const Fin *fin = nullptr);
+int spmv_num_partials(const sprs_csr *A);  // partials of one operator application (both launches of a split one)
+// f(integral_constant<int, dot_mode>, bool_constant<flag>): the launch sites' one instantiation per (dot mode, flag)
+template <class F>
+inline void with_dot(int dot_mode, bool flag, F &&f) {
+    auto go = [&](auto dm) { if (flag) f(dm, std::true_type{}); else f(dm, std::false_type{}); };
+    if (dot_mode == 0) go(std::integral_constant<int, 0>{});
+    else if (dot_mode == 1) go(std::integral_constant<int, 1>{});
+    else go(std::integral_constant<int, 2>{});
+}
 int tile_blocks();   // 128-row blocks per LDS-window tile (spmv_dict.hip)
-bool tile_plan_used(const sprs_csr *A);   // the SpMV of this handle runs through its tile plan
-bool chain_plan_used(const sprs_csr *A);  // ... through its plane-streaming chains (spmv_chain.hip)
 int build_rowblocks(sprs_csr *A, const int32_t *host_row_ptr);   // host_row_ptr == null: row_ptr lives in HBM only (summaries first)
 int validate_cols_device(const sprs_csr *A);   // SPRS_INVALID_ARGUMENT if any col_idx is outside [0, ncols)
-int spmv_num_partials(const sprs_csr *A);  // workgroups launch_spmv uses == partials it writes
 // per-row-block column span (device kernel + D2H): lo/hi sized n_rowblk
 int rowblk_spans(const sprs_csr *A, std::vector<int32_t> &lo, std::vector<int32_t> &hi);
-// SpMV over a subset of the row blocks (order[0..count)); writes `subset_grid(count)` partials
-template <class T>
-int launch_spmv_subset(const sprs_csr *A, const int32_t *order, int count, const T *x, T *y, int dot_mode, const T *u,
-                       T *part0, T *part1, const int *status, bool conj_x, const Fin *fin = nullptr);
-int spmv_subset_grid(const sprs_csr *A, int count);
 // ---- spmv_dict.hip
 // SPRS_OK also when the matrix does not qualify (A->dict stays null); blk / blk_pa: the row blocks just built (first row / first entry)
 int build_dict(sprs_csr *A, bool has_vector_blocks, const std::vector<int32_t> &blk, const std::vector<int32_t> &blk_pa);
 void free_dict(sprs_csr *A);
-int dict_mode(const sprs_csr *A);                      // 0 plain, 1 offsets, 2 offsets + values: what launch_spmv will use
 // Should the fused recurrence kernels of a solve on A give every XCD one contiguous eighth of the vectors (spmv.hip)?
 bool fused_chunked(const sprs_csr *A);
-
+// the launches of routes Dict, DictWide (f64) and Pair2 (f64)
 template <class T>
-int launch_spmv_dict(const sprs_csr *A, int mode, const int32_t *order, int count, int g, int xcd_chunk, const T *x, T *y,
-                     int dot_mode, const T *u, T *part0, T *part1, const int *status, bool conj_x, const Fin &fin);
+int launch_dict(const sprs_csr *A, const SpmvRoute &r, const T *x, T *y, int dot_mode, const T *u, T *part0, T *part1,
+                const int *status, bool conj_x, const Fin &fin);
+int launch_dict_wide(const sprs_csr *A, const SpmvRoute &r, const double *x, double *y, int dot_mode, const double *u,
+                     double *part0, double *part1, const int *status, const Fin &fin);
+int launch_pair2(const sprs_csr *A, const SpmvRoute &r, const double *x, double *y, int dot_mode, const double *u,
+                 double *part0, double *part1, const int *status, const Fin &fin);
+// ... TilePair (spmv_tile.hip), TileOff (spmv_tile_off.hip), Chain (spmv_chain.hip): one launch = the tiles or chains of the
+// route's plan + the per-block walk over the blocks outside them
+int launch_tile_pair(const sprs_csr *A, const SpmvRoute &r, const double *x, double *y, int dot_mode, const double *u,
+                     double *part0, double *part1, const int *status, const Fin &fin);
+int launch_tile_off(const sprs_csr *A, const SpmvRoute &r, const double *x, double *y, int dot_mode, const double *u,
+                    double *part0, double *part1, const int *status, const Fin &fin);
+int launch_chain_pair(const sprs_csr *A, const SpmvRoute &r, const double *x, double *y, int dot_mode, const double *u,
+                      double *part0, double *part1, const int *status, const Fin &fin);
 
 // ---- blas1.hip  (all on ctx->stream, asynchronous)
 template <class T, class S> int launch_axpy(sprs_ctx *c, size_t n, S a, const T *x, T *y);

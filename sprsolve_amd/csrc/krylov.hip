@@ -350,7 +350,7 @@ int KrylovBase<T>::spmv(const T *x, T *y, int dot, const T *u, T *p0, T *p1, con
     const T *x_caller = x;
     const int st = profiled([&]() -> int {
         if (A->dist) return dist_spmv<T>(A, const_cast<T *>(x), y, dot, u, p0, p1, status, conj_x, fin);
-        return launch_spmv<T>(A, x, y, dot, u, p0, p1, status, conj_x, fin);
+        return launch_spmv<T>(A, SpmvPart::Whole, x, y, dot, u, p0, p1, status, conj_x, fin);
     }, !A->dist);
     if (profile && dot != 0 && u != x_caller) mark_step(1);
     return st;
@@ -517,9 +517,10 @@ int BicgStab<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T>
     // its operands' windows while other tiles are still reading them, so K2 writes p' to ANOTHER buffer: p alternates with a work
     // vector the unpreconditioned solve leaves unused (:28 allocates seven), and v and t swap roles every iteration (t is dead when K2
     // writes v', v when K4 writes t).
+    const SpmvRoute route = spmv_route(this->A, SpmvPart::Whole, false);     // the chains' plan and grid
     bool fuse = false;
     if constexpr (std::is_same<T, double>::value && std::is_same<V, double>::value)
-        fuse = !pc && !this->A->dist && c->spmv_fuse != 0 && chain_plan_used(this->A);
+        fuse = !pc && c->spmv_fuse != 0 && route.kernel == SpmvKernel::Chain;
     T *palt = fuse ? this->vec(5) : nullptr;
     int pend_k1 = -1, pend_k3 = -1;          // fused: the mode / breakdown flag of the update that the next SpMV forms
     bool s_pending = false;                  // fused: K4 formed s without storing it (K5 forms it again)
@@ -559,7 +560,7 @@ int BicgStab<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T>
             if (fuse && pend_k1 >= 0) {
                 const BicgK1<double, double, false> k1{d_state, qN.p, qRho.p, qN.P, pend_k1, v, r, p, nullptr, y, 0.0, 0.0};
                 pend_k1 = -1;
-                SPRS_TRY(this->profiled([&]() -> int { return launch_chain_k2f(this->A, GS, k1, v, p, r, palt, t, r0, partB, d_status); }, true));
+                SPRS_TRY(this->profiled([&]() -> int { return launch_chain_k2f(this->A, route, k1, v, p, r, palt, t, r0, partB, d_status); }, true));
                 this->stats.fused_k2 += 1;
                 this->mark_step(2 | 1);      // (its dot operand is r0)
                 std::swap(p, palt); y = p;   // p' lives in the other buffer
@@ -581,7 +582,7 @@ int BicgStab<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T>
             if (fuse && pend_k3 >= 0) {
                 const BicgK3<double, double, false> k3{d_state, qB.p, qB.P, pend_k3, v, r, nullptr, nullptr, 0.0};
                 pend_k3 = -1;
-                SPRS_TRY(this->profiled([&]() -> int { return launch_chain_k4f(this->A, GS, k3, r, v, nullptr, t, partTT, partTR, d_status); }, true));
+                SPRS_TRY(this->profiled([&]() -> int { return launch_chain_k4f(this->A, route, k3, r, v, nullptr, t, partTT, partTR, d_status); }, true));
                 this->stats.fused_k4 += 1;
                 this->mark_step(4);
                 s_pending = true;            // s was formed on the fly and not stored: K5 forms it again from r and v
@@ -902,7 +903,8 @@ int MinRes<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> t
     // and then also writes back the normalised form of a raw v, so that the plain kernels find what they expect.
     bool m3_fusable = false;
     if constexpr (std::is_same<T, double>::value || std::is_same<T, cplx>::value)
-        m3_fusable = !pc && !this->A->dist && spmv_scaled_available(this->A);
+        m3_fusable = !pc && !this->A->dist && c->spmv_fuse != 0 &&
+                     spmv_route(this->A, SpmvPart::Whole, false).kernel == (is_complex<T>::value ? SpmvKernel::Dict : SpmvKernel::DictWide);
     Real<T> *pbeta[2] = {this->dslot(0), this->dslot(1)};     // |v_new|^2 partials: MinresM23 reads one array while it writes the other
     int cur_pb = 0;
     bool deferred = false, v_raw = false, vold_raw = false;

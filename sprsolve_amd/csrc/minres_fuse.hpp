@@ -178,6 +178,5 @@ struct MinresM23 {
 // nothing of the solver's state is written).
 template <class T, bool SAUNDERS>
 int launch_spmv_scaled(const sprs_csr *A, const MinresM3<T, false, SAUNDERS> &m3, const T *raw, T *y, T *partAlpha);
-bool spmv_scaled_available(const sprs_csr *A);      // the handle's SpMV is one of those kernels (and the knob "spmv_fuse" allows it)
 
 }  // namespace sprs

@@ -608,43 +608,95 @@ int rowblk_spans(const sprs_csr *A, std::vector<int32_t> &lo, std::vector<int32_
     return SPRS_OK;
 }
 
-// number of workgroups launch_spmv uses == number of partials it writes
+// ---- which kernel an SpMV launch takes (internal.hpp)
 // Matrices whose whole stream fits the 256 MiB Infinity Cache behave differently from HBM-bound ones
 // (profiles/r01_tuning.md): they want one contiguous chunk of row blocks per XCD (x stays in that XCD's
 // L2); HBM-bound ones want the row blocks dealt round-robin over the XCDs.
 // (is_cache_resident: internal.hpp)
-// the 16-byte-per-lane kernel runs this handle's plain stream (f64, aligned arrays, knob "spmv_wideload")
-static inline bool wide_loads(const sprs_csr *A) { return A->tail != nullptr && A->ctx->spmv_wideload != 0 && dict_mode(A) == 0; }
-static inline int base_grid(const sprs_csr *A) {
-    int g = A->ctx->spmv_grid;
-    // measured (A/B on the full solve): 4 workgroups per CU, for HBM-bound and cache-resident matrices and for all
-    // three streams alike (the pair-code kernel runs its stand-alone best at 6 per CU but loses that inside the
-    // solve, where it alternates with the BLAS-1 kernels) — except the 16-byte-per-lane plain kernel on an HBM-sized
-    // stream: 3 per CU (profiles/r03_tuning.md §2; only multiples of the CU count spread evenly)
+SpmvRoute spmv_route(const sprs_csr *A, SpmvPart part, bool conj_x) {
+    const sprs_ctx *c = A->ctx;
+    const sprs_dict *D = A->dict;
+    const sprs_dist_info *P = A->dist;
+    const bool whole = part == SpmvPart::Whole, f64 = A->dtype == DT_D;
+    const bool wide = c->spmv_wide != 0, uni = c->spmv_uniform != 0, tiles = c->spmv_tile != 0 && wide;
+    const bool wideload = A->tail != nullptr && c->spmv_wideload != 0;    // 16-byte loads (f64, aligned arrays)
+    SpmvRoute r{};
+    // the stream: plain, offset codes, pair codes
+    // (the kernels address x, y, row_ptr and the codes with 32-bit byte offsets from their bases)
+    if (D && c->spmv_dict != 0 && (uint64_t)std::max(A->ncols, A->nrows + 1) * std::max<size_t>(dtype_size(A->dtype), 4) < (1ull << 32)) {
+        // offset codes + values for every REAL matrix that has them (measured, profiles/r02_tuning.md): HBM-sized ones
+        // (cfg-5 pattern, random values: 885 vs 1130 us) and cache-resident ones alike (cfg 3: 21.8 vs 23.9 us, MINRES
+        // 21.8 k vs 20.8 k it/s).  Complex ones run slower (cfg 4: 24.7 vs 15.0 us; 17 instead of 20 B/nnz is not worth
+        // the lane-per-row layout): auto keeps the plain stream for those.
+        if (D->pair_code && c->spmv_dict != 1) r.format = 2;
+        else if (c->spmv_dict != -1 || !dtype_is_complex(A->dtype)) r.format = 1;
+    }
+    const bool pair = r.format == 2;
+    // the whole matrix's plane-streaming chains, else its tile plan (which also sets the grid of a split operator's launches)
+    const sprs_chain_plan *chain = pair && !P && c->spmv_chain != 0 && tiles && uni && D->chain_pair.n_tile > 0 ? &D->chain_pair : nullptr;
+    const sprs_tile_plan *tile = !tiles ? nullptr
+                               : pair ? (D->tile_pair.n_tile > 0 ? &D->tile_pair : nullptr)
+                               : (r.format == 1 && wideload && uni && D->tile_off.n_tile > 0 ? &D->tile_off : nullptr);
+
+    // grid == partials.  Measured (A/B on the full solve): 4 workgroups per CU, for HBM-bound and cache-resident matrices and
+    // for all three streams alike (the pair-code kernel runs its stand-alone best at 6 per CU but loses that inside the solve,
+    // where it alternates with the BLAS-1 kernels) — except the 16-byte-per-lane plain kernel on an HBM-sized stream: 3 per CU
+    // (profiles/r03_tuning.md §2; only multiples of the CU count spread evenly)
+    int g = c->spmv_grid;
     if (g <= 0) {
-        g = A->ctx->num_cu * ((wide_loads(A) && !is_cache_resident(A)) ? 3 : 4);
-        // LDS-window tiles are coarse work items (4096 rows): a matrix with few of them gets fewer workgroups, about three
-        // tiles each, rather than 1024 workgroups with one or two (the N = 8 slab: 1525 tiles; profiles/r03_tuning.md §9)
-        if (chain_plan_used(A)) {
-            g = A->ctx->num_cu * 2;           // plane-streaming chains: three x windows = 72 KiB of LDS, two workgroups per CU, about one chain segment each
-        } else if (tile_plan_used(A)) {
-            const int nt = dict_mode(A) == 2 ? A->dict->tile_pair.n_tile : A->dict->tile_off.n_tile;
-            g = std::min(g, std::max(64, (nt / 3) & ~7));
+        if (chain) {
+            g = c->num_cu * 2;           // plane-streaming chains: three x windows = 72 KiB of LDS, two workgroups per CU, about one chain segment each
+        } else {
+            g = c->num_cu * ((r.format == 0 && wideload && !is_cache_resident(A)) ? 3 : 4);
+            // LDS-window tiles are coarse work items (4096 rows): a matrix with few of them gets fewer workgroups, about three
+            // tiles each, rather than 1024 workgroups with one or two (the N = 8 slab: 1525 tiles; profiles/r03_tuning.md §9)
+            if (tile) g = std::min(g, std::max(64, (tile->n_tile / 3) & ~7));
         }
     }
-    if (g < 8) g = 8;
-    if (g > MAX_GRID / 2) g = MAX_GRID / 2;
-    return g & ~7;
-}
-static inline int grid_for_blocks(const sprs_csr *A, int count) {
-    const int g = base_grid(A);
+    g = std::min(std::max(g, 8), MAX_GRID / 2) & ~7;
+    r.order = whole ? nullptr : part == SpmvPart::Interior ? P->order_int : P->order_bnd;
+    r.count = whole ? A->n_rowblk : part == SpmvPart::Interior ? P->n_int : P->n_bnd;
     // at least one row block per wavefront, keep it a multiple of 8 (one slice per XCD)
-    int need = (((count + NWAVE - 1) / NWAVE + 7) / 8) * 8;
-    if (need < 8) need = 8;
-    return g < need ? g : need;
+    const int need = std::max(8, (((r.count + NWAVE - 1) / NWAVE + 7) / 8) * 8);
+    r.grid = std::min(g, need);
+    // cache-resident matrices: one contiguous chunk of row blocks per XCD; HBM-bound ones: round-robin (see above)
+    r.xcd_chunk = c->xcd_chunk < 0 ? (is_cache_resident(A) ? 1 : 0) : c->xcd_chunk;
+    r.y_nt = stream_loads_nt(c, (size_t)A->nrows * dtype_size(A->dtype));     // HBM-sized result: non-temporal y stores (-1 %)
+
+    if (r.format == 0) {
+        r.kernel = f64 && wideload ? SpmvKernel::CsrWide : SpmvKernel::Csr;
+        r.desc = reinterpret_cast<const BlkDesc *>(A->blk_desc_eq ? A->blk_desc_eq : A->blk_desc);
+        return r;
+    }
+    // the period orders encode their XCD placement for the round-robin walk (this one is also taken by an f64 offset stream
+    // whose matrix has pair codes)
+    if (f64 && whole && c->spmv_period != 0 && D->wide_order) r.xcd_chunk = 0;
+    // the tile plan of this launch: the whole matrix's, or the interior one of a split operator (dist.hip)
+    const sprs_tile_plan *tp = whole ? tile : part == SpmvPart::Interior && tiles && P->tile_int.n_tile > 0 && P->tile_int_off == !pair ? &P->tile_int : nullptr;
+    if (f64 && pair) {
+        r.desc = reinterpret_cast<const BlkDesc *>(D->wide_desc);
+        if (chain && whole) { r.kernel = SpmvKernel::Chain; r.chain = chain; return r; }
+        if (tp) { r.kernel = SpmvKernel::TilePair; r.tile = tp; return r; }
+        // two rows per lane: the whole matrix in natural or period order, or the interior / boundary subsets of a split operator,
+        // made on pairs of 64-row blocks for this purpose (dist.hip); the same grid as the 64-row kernel
+        const int32_t *order_w = whole ? (c->spmv_period != 0 ? D->wide_order : nullptr) : part == SpmvPart::Interior ? P->order_int_w : P->order_bnd_w;
+        if (D->wide_desc && wide && (whole || order_w) && A->nrows >= 2 && A->ncols >= 2) {
+            r.kernel = SpmvKernel::Pair2;
+            r.order = order_w;
+            r.count = whole ? D->n_wide : part == SpmvPart::Interior ? P->n_int_w : P->n_bnd_w;
+            return r;
+        }
+    }
+    if (!pair && whole && c->spmv_period > 0 && D->off_order) { r.order = D->off_order; r.xcd_chunk = 0; }
+    // the offset-code stream runs on its own descriptors (uniform blocks flagged); same block numbering as blk_desc
+    r.desc = reinterpret_cast<const BlkDesc *>((!pair && D->off_desc && uni) ? D->off_desc : A->blk_desc);
+    r.kernel = SpmvKernel::Dict;
+    if (f64 && !pair && wideload) {
+        r.kernel = SpmvKernel::DictWide;
+        if (tp && D->owide_desc && uni && !conj_x) { r.kernel = SpmvKernel::TileOff; r.tile = tp; }
+    }
+    return r;
 }
-static inline int spmv_grid(const sprs_csr *A) { return grid_for_blocks(A, A->n_rowblk); }
-int spmv_subset_grid(const sprs_csr *A, int count) { return grid_for_blocks(A, count); }
 
 // The fused recurrence kernels deal their tiles round-robin over the workgroups, i.e. over the XCDs.  Where the SpMV
 // gives every XCD one contiguous eighth of the rows (cache-resident matrices, xcd_chunk) and nearly all of a row's columns
@@ -659,72 +711,54 @@ bool fused_chunked(const sprs_csr *A) {
 }
 
 template <class T>
-static int launch_spmv_impl(const sprs_csr *A, const int32_t *order, int count, int g, const T *x, T *y, int dot_mode,
-                            const T *u, T *part0, T *part1, const int *status, bool conj_x, const Fin *finp) {
+int launch_spmv(const sprs_csr *A, SpmvPart part, const T *x, T *y, int dot_mode, const T *u, T *part0, T *part1,
+                const int *status, bool conj_x, const Fin *finp) {
     const Fin fin = (finp && dot_mode != 0) ? *finp : Fin{};
+    const SpmvRoute r = spmv_route(A, part, conj_x);
     sprs_ctx *c = A->ctx;
     const T *v = reinterpret_cast<const T *>(A->val);
-    // cache-resident matrices: one contiguous chunk of row blocks per XCD; HBM-bound ones: round-robin (see above)
-    const int xcd_chunk = c->xcd_chunk < 0 ? (is_cache_resident(A) ? 1 : 0) : c->xcd_chunk;
-    if (const int dm = dict_mode(A))
-        return launch_spmv_dict<T>(A, dm, order, count, g, xcd_chunk, x, y, dot_mode, u, part0, part1, status, conj_x, fin);
+    const int eq = A->blk_desc_eq ? 1 : 0;
     if constexpr (dtype_of<T>::value == DT_D) {
-        if (wide_loads(A)) {
-            const BlkDesc *dsc = reinterpret_cast<const BlkDesc *>(A->blk_desc_eq ? A->blk_desc_eq : A->blk_desc);
-            const v4i32 *tc = reinterpret_cast<const v4i32 *>(A->tail);
-            const D2v *tv = reinterpret_cast<const D2v *>(reinterpret_cast<const char *>(A->tail) + 16);
-            const int g_last = (int)((A->nnz - 1) >> 2);
-#define SPRS_WIDE(D, YN)                                                                                             \
-    SPRS_LAUNCH_SPMV(c, (spmv_wide_kernel<D, YN>), g, count, xcd_chunk, A->blk_desc_eq ? 1 : 0, dsc, order, A->row_ptr, \
-                     A->col_idx, v, tc, tv, g_last, x, y, u, part0, part1, status, fin)
-            if (stream_loads_nt(c, (size_t)A->nrows * sizeof(T))) {       // HBM-sized result: non-temporal y stores (-1 %)
-                if (dot_mode == 0) SPRS_WIDE(0, true); else if (dot_mode == 1) SPRS_WIDE(1, true); else SPRS_WIDE(2, true);
-            } else {
-                if (dot_mode == 0) SPRS_WIDE(0, false); else if (dot_mode == 1) SPRS_WIDE(1, false); else SPRS_WIDE(2, false);
+        switch (r.kernel) {
+            case SpmvKernel::CsrWide: {
+                const v4i32 *tc = reinterpret_cast<const v4i32 *>(A->tail);
+                const D2v *tv = reinterpret_cast<const D2v *>(reinterpret_cast<const char *>(A->tail) + 16);
+                const int g_last = (int)((A->nnz - 1) >> 2);
+                with_dot(dot_mode, r.y_nt, [&](auto dm, auto ynt) {
+                    SPRS_LAUNCH_SPMV(c, (spmv_wide_kernel<decltype(dm)::value, decltype(ynt)::value>), r.grid, r.count, r.xcd_chunk, eq, r.desc,
+                                     r.order, A->row_ptr, A->col_idx, v, tc, tv, g_last, x, y, u, part0, part1, status, fin);
+                });
+                SPRS_HIP_TRY(c, hipGetLastError());
+                return SPRS_OK;
             }
-#undef SPRS_WIDE
-            SPRS_HIP_TRY(c, hipGetLastError());
-            return SPRS_OK;
+            case SpmvKernel::DictWide: return launch_dict_wide(A, r, x, y, dot_mode, u, part0, part1, status, fin);
+            case SpmvKernel::Pair2: return launch_pair2(A, r, x, y, dot_mode, u, part0, part1, status, fin);
+            case SpmvKernel::TilePair: return launch_tile_pair(A, r, x, y, dot_mode, u, part0, part1, status, fin);
+            case SpmvKernel::TileOff: return launch_tile_off(A, r, x, y, dot_mode, u, part0, part1, status, fin);
+            case SpmvKernel::Chain: return launch_chain_pair(A, r, x, y, dot_mode, u, part0, part1, status, fin);
+            default: break;
         }
     }
-#define SPRS_SPMV(D, CJ)                                                                                              \
-    SPRS_LAUNCH_SPMV(c, (spmv_kernel<T, D, CJ>), g, count,                                                            \
-                       xcd_chunk, A->blk_desc_eq ? 1 : 0, reinterpret_cast<const BlkDesc *>(A->blk_desc_eq ? A->blk_desc_eq : A->blk_desc), order, A->row_ptr, A->col_idx, v, x, y, u, part0, part1, status, fin)
-    if (conj_x && is_complex<T>::value) {  // only CSMINRES on complex data needs the conjugated gather
-        if (dot_mode == 0) SPRS_SPMV(0, true);
-        else if (dot_mode == 1) SPRS_SPMV(1, true);
-        else SPRS_SPMV(2, true);
-    } else {
-        if (dot_mode == 0) SPRS_SPMV(0, false);
-        else if (dot_mode == 1) SPRS_SPMV(1, false);
-        else SPRS_SPMV(2, false);
-    }
-#undef SPRS_SPMV
+    if (r.kernel == SpmvKernel::Dict) return launch_dict<T>(A, r, x, y, dot_mode, u, part0, part1, status, conj_x, fin);
+    if (r.kernel != SpmvKernel::Csr) return SPRS_INVALID_ARGUMENT;     // (f64 kernels: A->dtype does not match T)
+    // only CSMINRES on complex data needs the conjugated gather
+    with_dot(dot_mode, conj_x && is_complex<T>::value, [&](auto dm, auto cj) {
+        SPRS_LAUNCH_SPMV(c, (spmv_kernel<T, decltype(dm)::value, decltype(cj)::value>), r.grid, r.count, r.xcd_chunk, eq, r.desc, r.order,
+                         A->row_ptr, A->col_idx, v, x, y, u, part0, part1, status, fin);
+    });
     SPRS_HIP_TRY(c, hipGetLastError());
     return SPRS_OK;
 }
 
-template <class T>
-int launch_spmv(const sprs_csr *A, const T *x, T *y, int dot_mode, const T *u, T *part0, T *part1, const int *status,
-                bool conj_x, const Fin *fin) {
-    return launch_spmv_impl<T>(A, nullptr, (int)A->n_rowblk, spmv_grid(A), x, y, dot_mode, u, part0, part1, status, conj_x, fin);
-}
-
-template <class T>
-int launch_spmv_subset(const sprs_csr *A, const int32_t *order, int count, const T *x, T *y, int dot_mode, const T *u,
-                       T *part0, T *part1, const int *status, bool conj_x, const Fin *fin) {
-    return launch_spmv_impl<T>(A, order, count, grid_for_blocks(A, count), x, y, dot_mode, u, part0, part1, status, conj_x, fin);
-}
-
-// distributed operators with an interior/boundary split run two launches whose partials are concatenated
+// an operator split at creation runs two launches whose partials are concatenated
 int spmv_num_partials(const sprs_csr *A) {
-    if (A->dist && A->dist->order_int) return grid_for_blocks(A, A->dist->n_int) + grid_for_blocks(A, A->dist->n_bnd);
-    return spmv_grid(A);
+    if (A->dist && A->dist->order_int)
+        return spmv_route(A, SpmvPart::Interior, false).grid + spmv_route(A, SpmvPart::Boundary, false).grid;
+    return spmv_route(A, SpmvPart::Whole, false).grid;
 }
 
-#define SPRS_INST_SPMV(T)                                                                                              \
-    template int launch_spmv<T>(const sprs_csr *, const T *, T *, int, const T *, T *, T *, const int *, bool, const Fin *); \
-    template int launch_spmv_subset<T>(const sprs_csr *, const int32_t *, int, const T *, T *, int, const T *, T *, T *, const int *, bool, const Fin *);
+#define SPRS_INST_SPMV(T) \
+    template int launch_spmv<T>(const sprs_csr *, SpmvPart, const T *, T *, int, const T *, T *, T *, const int *, bool, const Fin *);
 SPRS_INST_SPMV(double)
 SPRS_INST_SPMV(cplx)
 SPRS_INST_SPMV(float)

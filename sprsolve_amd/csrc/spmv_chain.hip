@@ -269,11 +269,13 @@ __global__ __launch_bounds__(BLOCK) void spmv_chain_kernel(const int4 *__restric
 
 int chain_rows() { return CH_ROWS; }
 
-int launch_chain_pair(const sprs_csr *A, const sprs_chain_plan &CP, int g, const double *x, double *y, int dot_mode, const double *u,
+int launch_chain_pair(const sprs_csr *A, const SpmvRoute &r, const double *x, double *y, int dot_mode, const double *u,
                       double *part0, double *part1, const int *status, const Fin &fin) {
     sprs_ctx *c = A->ctx;
     const sprs_dict *D = A->dict;
-    const BlkDesc *wd = reinterpret_cast<const BlkDesc *>(D->wide_desc);
+    const sprs_chain_plan &CP = *r.chain;
+    const int g = r.grid;
+    const BlkDesc *wd = r.desc;
     const double *pvd = reinterpret_cast<const double *>(D->pair_val);
     TilePat tp;
     for (int t = 0; t < 8; ++t) { tp.off[t] = CP.off[t]; tp.val[t] = CP.val[t]; }
@@ -295,12 +297,13 @@ int launch_chain_pair(const sprs_csr *A, const sprs_chain_plan &CP, int g, const
 }
 
 
-int launch_chain_k4f(const sprs_csr *A, int g, const BicgK3<double, double, false> &pro, const double *r, const double *v, double *s_out,
+int launch_chain_k4f(const sprs_csr *A, const SpmvRoute &rt, const BicgK3<double, double, false> &pro, const double *r, const double *v, double *s_out,
                      double *t, double *partTT, double *partTR, const int *status) {
     sprs_ctx *c = A->ctx;
     const sprs_dict *D = A->dict;
-    const sprs_chain_plan &CP = D->chain_pair;
-    const BlkDesc *wd = reinterpret_cast<const BlkDesc *>(D->wide_desc);
+    const sprs_chain_plan &CP = *rt.chain;
+    const int g = rt.grid;
+    const BlkDesc *wd = rt.desc;
     const double *pvd = reinterpret_cast<const double *>(D->pair_val);
     TilePat tp;
     for (int k = 0; k < 8; ++k) { tp.off[k] = CP.off[k]; tp.val[k] = CP.val[k]; }
@@ -316,12 +319,13 @@ int launch_chain_k4f(const sprs_csr *A, int g, const BicgK3<double, double, fals
     return SPRS_OK;
 }
 
-int launch_chain_k2f(const sprs_csr *A, int g, const BicgK1<double, double, false> &pro, const double *v_old, const double *p, const double *r,
+int launch_chain_k2f(const sprs_csr *A, const SpmvRoute &rt, const BicgK1<double, double, false> &pro, const double *v_old, const double *p, const double *r,
                      double *p_out, double *v_out, const double *r0, double *partB, const int *status) {
     sprs_ctx *c = A->ctx;
     const sprs_dict *D = A->dict;
-    const sprs_chain_plan &CP = D->chain_pair;
-    const BlkDesc *wd = reinterpret_cast<const BlkDesc *>(D->wide_desc);
+    const sprs_chain_plan &CP = *rt.chain;
+    const int g = rt.grid;
+    const BlkDesc *wd = rt.desc;
     const double *pvd = reinterpret_cast<const double *>(D->pair_val);
     TilePat tp;
     for (int k = 0; k < 8; ++k) { tp.off[k] = CP.off[k]; tp.val[k] = CP.val[k]; }

@@ -34,7 +34,7 @@
 //   tile_mark_kernel / tile_flag_kernel                         runs of one pattern (creation)
 //   spmv_tile_kernel, spmv_tile_off_kernel                      LDS x-window tiles: f64 pair codes / f64 offset codes + values
 //   xcd_period_order, build_tile_plan, build_dict_t             schedules, tile plans, the creation driver
-//   launch_spmv_dict                                            which kernel a launch takes
+//   launch_dict, launch_dict_wide, launch_pair2, launch_spmv_scaled   the launches (which kernel a launch takes: spmv_route, spmv.hip)
 #include <algorithm>
 #include <cstring>
 #include <map>
@@ -1265,20 +1265,6 @@ int build_dict_t(sprs_csr *A, const std::vector<int32_t> &blk, const std::vector
 }  // namespace
 
 int tile_blocks() { return TILE_B; }
-bool tile_plan_used(const sprs_csr *A) {
-    const sprs_ctx *c = A->ctx;
-    if (!A->dict || c->spmv_tile == 0 || c->spmv_wide == 0) return false;
-    const int dm = dict_mode(A);
-    if (dm == 2) return A->dict->tile_pair.n_tile > 0;
-    return dm == 1 && A->dict->tile_off.n_tile > 0 && A->tail != nullptr && c->spmv_wideload != 0 && c->spmv_uniform != 0;
-}
-
-bool chain_plan_used(const sprs_csr *A) {
-    const sprs_ctx *c = A->ctx;
-    if (!A->dict || A->dist || c->spmv_chain == 0 || c->spmv_tile == 0 || c->spmv_wide == 0 || c->spmv_uniform == 0) return false;
-    return dict_mode(A) == 2 && A->dict->chain_pair.n_tile > 0;
-}
-
 void free_dict(sprs_csr *A) {
     if (!A || !A->dict) return;
     sprs_dict *D = A->dict;
@@ -1301,151 +1287,77 @@ int build_dict(sprs_csr *A, bool has_vector_blocks, const std::vector<int32_t> &
     }
 }
 
-int dict_mode(const sprs_csr *A) {
-    if (!A->dict || A->ctx->spmv_dict == 0) return 0;
-    // the kernel addresses x, y, row_ptr and the codes with 32-bit byte offsets from their bases
-    if ((uint64_t)std::max(A->ncols, A->nrows + 1) * std::max<size_t>(dtype_size(A->dtype), 4) >= (1ull << 32)) return 0;
-    if (A->dict->pair_code && A->ctx->spmv_dict != 1) return 2;
-    if (A->ctx->spmv_dict == -1) {
-        // offset codes + values for every REAL matrix that has them (measured, profiles/r02_tuning.md): HBM-sized ones
-        // (cfg-5 pattern, random values: 885 vs 1130 us) and cache-resident ones alike (cfg 3: 21.8 vs 23.9 us, MINRES
-        // 21.8 k vs 20.8 k it/s).  Complex ones run slower (cfg 4: 24.7 vs 15.0 us; 17 instead of 20 B/nnz is not worth
-        // the lane-per-row layout): auto keeps the plain stream for those.
-        if (dtype_is_complex(A->dtype)) return 0;
-    }
-    return 1;
-}
-
 template <class T>
-int launch_spmv_dict(const sprs_csr *A, int mode, const int32_t *order, int count, int g, int xcd_chunk, const T *x, T *y,
-                     int dot_mode, const T *u, T *part0, T *part1, const int *status, bool conj_x, const Fin &fin) {
+int launch_dict(const sprs_csr *A, const SpmvRoute &r, const T *x, T *y, int dot_mode, const T *u, T *part0, T *part1,
+                const int *status, bool conj_x, const Fin &fin) {
     sprs_ctx *c = A->ctx;
     const sprs_dict *D = A->dict;
-    const T *v = reinterpret_cast<const T *>(A->val);
-    const T *pv = reinterpret_cast<const T *>(D->pair_val);
-    const bool pair = has_pair_codes<T>::value && mode == 2;
-    if constexpr (sizeof(T) == 8 && !is_complex<T>::value) {
-        // f64 pair codes: two rows per lane
-        // ... on the whole matrix in natural order, or on the interior / boundary subsets of a distributed operator,
-        // whose split is made on pairs of 64-row blocks for this purpose (dist.hip)
-        const int32_t *order_w = nullptr;
-        int count_w = -1;
-        if (order == nullptr && count == A->n_rowblk) { count_w = D->n_wide; order_w = c->spmv_period != 0 ? D->wide_order : nullptr; if (order_w) xcd_chunk = 0; }   // the period order encodes its XCD placement for the round-robin walk
-        else if (A->dist && A->dist->order_int_w && order == A->dist->order_int && count == A->dist->n_int) { order_w = A->dist->order_int_w; count_w = A->dist->n_int_w; }
-        else if (A->dist && A->dist->order_bnd_w && order == A->dist->order_bnd && count == A->dist->n_bnd) { order_w = A->dist->order_bnd_w; count_w = A->dist->n_bnd_w; }
-        // which tile plan this launch runs through: the handle's (whole matrix) or the distributed operator's interior one
-        const bool whole = order == nullptr && count == A->n_rowblk;
-        const bool interior = A->dist && A->dist->order_int && order == A->dist->order_int && count == A->dist->n_int && A->dist->tile_int.n_tile > 0;
-        const sprs_tile_plan *tpp = nullptr;
-        if (pair && whole && D->tile_pair.n_tile > 0) tpp = &D->tile_pair;
-        else if (pair && interior && !A->dist->tile_int_off) tpp = &A->dist->tile_int;
-        if (pair && whole && g % 8 == 0 && chain_plan_used(A))      // plane-streaming chains + the per-block walk over the blocks outside them, one launch (spmv_chain.hip)
-            return launch_chain_pair(A, D->chain_pair, g, x, y, dot_mode, u, part0, part1, status, fin);
-        if (tpp && c->spmv_tile != 0 && c->spmv_wide != 0 && g % 8 == 0) {
-            // LDS x-window tiles + the per-block walk over the blocks outside them, one launch (spmv_tile.hip)
-            return launch_tile_pair(A, *tpp, g, x, y, dot_mode, u, part0, part1, status, fin);
-        }
-        if (pair && D->wide_desc && c->spmv_wide != 0 && count_w >= 0 && A->nrows >= 2 && A->ncols >= 2) {
-            const int gw = g;     // same grid as the 64-row kernel: the consumers reduce exactly spmv_num_partials(A) partials
-            const BlkDesc *wd = reinterpret_cast<const BlkDesc *>(D->wide_desc);
-            const double *pvd = reinterpret_cast<const double *>(D->pair_val);
-#define SPRS_WSPMV(DM, YN) SPRS_LAUNCH_SPMV(c, (spmv_pair2_kernel<DM, YN>), gw, count_w, xcd_chunk, wd, order_w, \
-                                          A->row_ptr, D->pair_code, D->pair_off, pvd, x, y, u, part0, part1, status, (int)A->nrows, (int)A->ncols, fin)
-            if (stream_loads_nt(c, (size_t)A->nrows * sizeof(T))) {          // HBM-sized result: non-temporal y stores
-                if (dot_mode == 0) SPRS_WSPMV(0, true); else if (dot_mode == 1) SPRS_WSPMV(1, true); else SPRS_WSPMV(2, true);
-            } else {
-                if (dot_mode == 0) SPRS_WSPMV(0, false); else if (dot_mode == 1) SPRS_WSPMV(1, false); else SPRS_WSPMV(2, false);
-            }
-#undef SPRS_WSPMV
-            SPRS_HIP_TRY(c, hipGetLastError());
-            return SPRS_OK;
-        }
-    }
+    const bool pair = r.format == 2;
     const uint8_t *code = pair ? D->pair_code : D->idx_code;
     const int32_t *otab = pair ? D->pair_off : D->off_tab;
-    if (!pair && order == nullptr && count == A->n_rowblk && c->spmv_period > 0 && D->off_order) { order = D->off_order; xcd_chunk = 0; }
-    // the offset-code stream runs on its own descriptors (uniform blocks flagged); same block numbering as blk_desc
-    const BlkDesc *dsc = reinterpret_cast<const BlkDesc *>((!pair && D->off_desc && c->spmv_uniform != 0) ? D->off_desc : A->blk_desc);
-    const V2d *tail2 = nullptr;
-    int g2_last = -1;
-    if constexpr (sizeof(T) == 8 && !is_complex<T>::value) {
-        if (!pair && A->tail && c->spmv_wideload != 0) {
-            // f64 offset codes: 16-byte value loads (the plain stream's measure, profiles/r03_tuning.md §2)
-            g2_last = (int)((A->nnz - 1) >> 1);
-            tail2 = reinterpret_cast<const V2d *>(reinterpret_cast<const char *>(A->tail) + 16) + (g2_last - 2 * (int)((A->nnz - 1) >> 2));
-            const bool whole = order == nullptr && count == A->n_rowblk;
-            const bool interior = A->dist && A->dist->order_int && order == A->dist->order_int && count == A->dist->n_int && A->dist->tile_int.n_tile > 0;
-            const sprs_tile_plan *tpp = nullptr;
-            if (whole && D->tile_off.n_tile > 0) tpp = &D->tile_off;
-            else if (interior && A->dist->tile_int_off) tpp = &A->dist->tile_int;
-            if (tpp && D->owide_desc && c->spmv_tile != 0 && c->spmv_wide != 0 && c->spmv_uniform != 0 && g % 8 == 0 && !conj_x) {
-                // LDS x-window tiles + the per-block walk over the 64-row blocks outside them, one launch (spmv_tile_off.hip)
-                return launch_tile_off(A, *tpp, g, dsc, x, y, dot_mode, u, part0, part1, status, fin, tail2, g2_last);
-            }
-#define SPRS_DSPMVW(DM) SPRS_LAUNCH_SPMV(c, (spmv_dict_kernel<T, DM, false, false, true>), g, count, xcd_chunk, dsc, order, A->row_ptr, \
-                                         code, otab, pv, v, x, y, u, part0, part1, status, fin, tail2, g2_last, (const T *)nullptr)
-            if (dot_mode == 0) SPRS_DSPMVW(0); else if (dot_mode == 1) SPRS_DSPMVW(1); else SPRS_DSPMVW(2);
-#undef SPRS_DSPMVW
-            SPRS_HIP_TRY(c, hipGetLastError());
-            return SPRS_OK;
-        }
-    }
-#define SPRS_DSPMV2(DM, CJ, PR)                                                                                         \
-    SPRS_LAUNCH_SPMV(c, (spmv_dict_kernel<T, DM, CJ, PR>), g, count, xcd_chunk,                                          \
-                       dsc, order, A->row_ptr, code, otab, pv, v, x, y, u,                                              \
-                       part0, part1, status, fin, tail2, g2_last, reinterpret_cast<const T *>(D->rowval))
-#define SPRS_DSPMV(DM, CJ) do { if (pair) SPRS_DSPMV2(DM, CJ, (has_pair_codes<T>::value)); else SPRS_DSPMV2(DM, CJ, false); } while (0)
-    if (conj_x && is_complex<T>::value) {
-        if (dot_mode == 0) SPRS_DSPMV(0, true);
-        else if (dot_mode == 1) SPRS_DSPMV(1, true);
-        else SPRS_DSPMV(2, true);
-    } else {
-        if (dot_mode == 0) SPRS_DSPMV(0, false);
-        else if (dot_mode == 1) SPRS_DSPMV(1, false);
-        else SPRS_DSPMV(2, false);
-    }
-#undef SPRS_DSPMV2
+    with_dot(dot_mode, conj_x && is_complex<T>::value, [&](auto dm, auto cj) {
+#define SPRS_DSPMV(PR) SPRS_LAUNCH_SPMV(c, (spmv_dict_kernel<T, decltype(dm)::value, decltype(cj)::value, PR>), r.grid, r.count, r.xcd_chunk, r.desc, \
+                                        r.order, A->row_ptr, code, otab, reinterpret_cast<const T *>(D->pair_val), reinterpret_cast<const T *>(A->val), \
+                                        x, y, u, part0, part1, status, fin, (const V2d *)nullptr, -1, reinterpret_cast<const T *>(D->rowval))
+        if (pair) SPRS_DSPMV((has_pair_codes<T>::value)); else SPRS_DSPMV(false);
 #undef SPRS_DSPMV
+    });
+    SPRS_HIP_TRY(c, hipGetLastError());
+    return SPRS_OK;
+}
+template int launch_dict<double>(const sprs_csr *, const SpmvRoute &, const double *, double *, int, const double *, double *, double *, const int *, bool, const Fin &);
+template int launch_dict<cplx>(const sprs_csr *, const SpmvRoute &, const cplx *, cplx *, int, const cplx *, cplx *, cplx *, const int *, bool, const Fin &);
+template int launch_dict<float>(const sprs_csr *, const SpmvRoute &, const float *, float *, int, const float *, float *, float *, const int *, bool, const Fin &);
+template int launch_dict<cplxf>(const sprs_csr *, const SpmvRoute &, const cplxf *, cplxf *, int, const cplxf *, cplxf *, cplxf *, const int *, bool, const Fin &);
+
+int launch_dict_wide(const sprs_csr *A, const SpmvRoute &r, const double *x, double *y, int dot_mode, const double *u,
+                     double *part0, double *part1, const int *status, const Fin &fin) {
+    sprs_ctx *c = A->ctx;
+    const sprs_dict *D = A->dict;
+    int g2_last;
+    const V2d *tail2 = dict_tail2(A, g2_last);
+    with_dot(dot_mode, false, [&](auto dm, auto) {
+        SPRS_LAUNCH_SPMV(c, (spmv_dict_kernel<double, decltype(dm)::value, false, false, true>), r.grid, r.count, r.xcd_chunk, r.desc, r.order,
+                         A->row_ptr, D->idx_code, D->off_tab, reinterpret_cast<const double *>(D->pair_val), reinterpret_cast<const double *>(A->val),
+                         x, y, u, part0, part1, status, fin, tail2, g2_last, (const double *)nullptr);
+    });
     SPRS_HIP_TRY(c, hipGetLastError());
     return SPRS_OK;
 }
 
-// ---- M3 deferred (spmv_dict_scaled_kernel): which handles, and the launch with the arguments launch_spmv_dict would take for the
-// whole matrix in natural order
-bool spmv_scaled_available(const sprs_csr *A) {
-    const sprs_ctx *c = A->ctx;
-    if (!A->dict || A->dist || c->spmv_fuse == 0) return false;
-    const int dm = dict_mode(A);
-    if (A->dtype == DT_D) return dm == 1 && !tile_plan_used(A) && A->tail != nullptr && c->spmv_wideload != 0;     // f64 offset codes, 16-byte value loads
-    if (A->dtype == DT_Z) return dm == 1 || dm == 2;
-    return false;
+int launch_pair2(const sprs_csr *A, const SpmvRoute &r, const double *x, double *y, int dot_mode, const double *u,
+                 double *part0, double *part1, const int *status, const Fin &fin) {
+    sprs_ctx *c = A->ctx;
+    const sprs_dict *D = A->dict;
+    with_dot(dot_mode, r.y_nt, [&](auto dm, auto ynt) {
+        SPRS_LAUNCH_SPMV(c, (spmv_pair2_kernel<decltype(dm)::value, decltype(ynt)::value>), r.grid, r.count, r.xcd_chunk, r.desc, r.order,
+                         A->row_ptr, D->pair_code, D->pair_off, reinterpret_cast<const double *>(D->pair_val), x, y, u, part0, part1, status,
+                         (int)A->nrows, (int)A->ncols, fin);
+    });
+    SPRS_HIP_TRY(c, hipGetLastError());
+    return SPRS_OK;
 }
 
+// ---- M3 deferred (spmv_dict_scaled_kernel): the launch the whole-matrix route names (DictWide for f64, Dict for c64)
 template <class T, bool SAUNDERS>
 int launch_spmv_scaled(const sprs_csr *A, const MinresM3<T, false, SAUNDERS> &m3, const T *raw, T *y, T *partAlpha) {
     sprs_ctx *c = A->ctx;
     const sprs_dict *D = A->dict;
-    const int dm = dict_mode(A);
-    const bool pair = has_pair_codes<T>::value && dm == 2;
-    const int g = spmv_num_partials(A);
-    int xcd_chunk = c->xcd_chunk < 0 ? (is_cache_resident(A) ? 1 : 0) : c->xcd_chunk;
-    const int32_t *order = nullptr;
-    const int count = A->n_rowblk;
+    const SpmvRoute r = spmv_route(A, SpmvPart::Whole, false);
+    const bool pair = r.format == 2;
     const uint8_t *code = pair ? D->pair_code : D->idx_code;
     const int32_t *otab = pair ? D->pair_off : D->off_tab;
-    if (!pair && c->spmv_period > 0 && D->off_order) { order = D->off_order; xcd_chunk = 0; }
-    const BlkDesc *dsc = reinterpret_cast<const BlkDesc *>((!pair && D->off_desc && c->spmv_uniform != 0) ? D->off_desc : A->blk_desc);
     const T *v = reinterpret_cast<const T *>(A->val);
     const T *pv = reinterpret_cast<const T *>(D->pair_val);
     typedef MinresM3<T, false, SAUNDERS> M3;
     constexpr bool CJ = SAUNDERS && is_complex<T>::value;      // CSMINRES multiplies A by conj(q) (cs_minres.rs:99)
     if constexpr (sizeof(T) == 8 && !is_complex<T>::value) {
-        const int g2_last = (int)((A->nnz - 1) >> 1);
-        const V2d *tail2 = reinterpret_cast<const V2d *>(reinterpret_cast<const char *>(A->tail) + 16) + (g2_last - 2 * (int)((A->nnz - 1) >> 2));
-        SPRS_LAUNCH_SPMV(c, (spmv_dict_scaled_kernel<T, false, false, true, M3>), g, count, xcd_chunk, dsc, order, A->row_ptr, code,
+        int g2_last;
+        const V2d *tail2 = dict_tail2(A, g2_last);
+        SPRS_LAUNCH_SPMV(c, (spmv_dict_scaled_kernel<T, false, false, true, M3>), r.grid, r.count, r.xcd_chunk, r.desc, r.order, A->row_ptr, code,
                          otab, pv, v, raw, y, partAlpha, tail2, g2_last, (const T *)nullptr, m3);
     } else {
-#define SPRS_M3L(PR) SPRS_LAUNCH_SPMV(c, (spmv_dict_scaled_kernel<T, CJ, PR, false, M3>), g, count, xcd_chunk, dsc, order, A->row_ptr, code, otab, pv, v, \
+#define SPRS_M3L(PR) SPRS_LAUNCH_SPMV(c, (spmv_dict_scaled_kernel<T, CJ, PR, false, M3>), r.grid, r.count, r.xcd_chunk, r.desc, r.order, A->row_ptr, code, otab, pv, v, \
                                       raw, y, partAlpha, (const V2d *)nullptr, -1, reinterpret_cast<const T *>(D->rowval), m3)
         if (pair) SPRS_M3L((has_pair_codes<T>::value)); else SPRS_M3L(false);
 #undef SPRS_M3L
@@ -1456,12 +1368,5 @@ int launch_spmv_scaled(const sprs_csr *A, const MinresM3<T, false, SAUNDERS> &m3
 template int launch_spmv_scaled<double, false>(const sprs_csr *, const MinresM3<double, false, false> &, const double *, double *, double *);
 template int launch_spmv_scaled<cplx, false>(const sprs_csr *, const MinresM3<cplx, false, false> &, const cplx *, cplx *, cplx *);
 template int launch_spmv_scaled<cplx, true>(const sprs_csr *, const MinresM3<cplx, false, true> &, const cplx *, cplx *, cplx *);
-
-#define SPRS_INST_DSPMV(T)                                                                                              \
-    template int launch_spmv_dict<T>(const sprs_csr *, int, const int32_t *, int, int, int, const T *, T *, int, const T *, T *, T *, const int *, bool, const Fin &);
-SPRS_INST_DSPMV(double)
-SPRS_INST_DSPMV(cplx)
-SPRS_INST_DSPMV(float)
-SPRS_INST_DSPMV(cplxf)
 
 }  // namespace sprs

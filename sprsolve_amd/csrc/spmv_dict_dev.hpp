@@ -714,14 +714,12 @@ constexpr int CH_B = 16;
 #define SPRS_CHAIN_SHAPES(X) X(7, true) X(7, false) X(5, true) X(5, false) X(3, true)
 }  // namespace
 
-// ---- spmv_chain.hip: the chains of plan CP + the per-block walk over the blocks outside them, one launch
-int launch_chain_pair(const sprs_csr *A, const sprs_chain_plan &CP, int g, const double *x, double *y, int dot_mode, const double *u,
-                      double *part0, double *part1, const int *status, const Fin &fin);
+// f64 offset codes with 16-byte value loads (DictWide, TileOff, M3 deferred): the zero-padded copy of the last value pair
+inline const V2d *dict_tail2(const sprs_csr *A, int &g2_last) {
+    g2_last = (int)((A->nnz - 1) >> 1);
+    return reinterpret_cast<const V2d *>(reinterpret_cast<const char *>(A->tail) + 16) + (g2_last - 2 * (int)((A->nnz - 1) >> 2));
+}
+
 int chain_rows();
-// ---- spmv_tile.hip / spmv_tile_off.hip: one launch = the tiles of plan TP + the per-block walk over the blocks outside them
-int launch_tile_pair(const sprs_csr *A, const sprs_tile_plan &TP, int g, const double *x, double *y, int dot_mode, const double *u,
-                     double *part0, double *part1, const int *status, const Fin &fin);
-int launch_tile_off(const sprs_csr *A, const sprs_tile_plan &TP, int g, const BlkDesc *desc64, const double *x, double *y, int dot_mode,
-                    const double *u, double *part0, double *part1, const int *status, const Fin &fin, const V2d *tail2, int g2_last);
 
 }  // namespace sprs

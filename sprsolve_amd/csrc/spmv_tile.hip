@@ -173,11 +173,13 @@ __global__ __launch_bounds__(BLOCK) void spmv_tile_kernel(const int2 *__restrict
 
 }  // namespace
 
-int launch_tile_pair(const sprs_csr *A, const sprs_tile_plan &TP, int g, const double *x, double *y, int dot_mode, const double *u,
+int launch_tile_pair(const sprs_csr *A, const SpmvRoute &r, const double *x, double *y, int dot_mode, const double *u,
                      double *part0, double *part1, const int *status, const Fin &fin) {
     sprs_ctx *c = A->ctx;
     const sprs_dict *D = A->dict;
-    const BlkDesc *wd = reinterpret_cast<const BlkDesc *>(D->wide_desc);
+    const sprs_tile_plan &TP = *r.tile;
+    const int g = r.grid;
+    const BlkDesc *wd = r.desc;
     const double *pvd = reinterpret_cast<const double *>(D->pair_val);
     TilePat tp;
     for (int t = 0; t < 8; ++t) { tp.off[t] = TP.off[t]; tp.val[t] = TP.val[t]; }

@@ -185,10 +185,15 @@ __global__ __launch_bounds__(BLOCK) void spmv_tile_off_kernel(const int2 *__rest
 
 }  // namespace
 
-int launch_tile_off(const sprs_csr *A, const sprs_tile_plan &TP, int g, const BlkDesc *desc64, const double *x, double *y, int dot_mode,
-                    const double *u, double *part0, double *part1, const int *status, const Fin &fin, const V2d *tail2, int g2_last) {
+int launch_tile_off(const sprs_csr *A, const SpmvRoute &r, const double *x, double *y, int dot_mode, const double *u,
+                    double *part0, double *part1, const int *status, const Fin &fin) {
     sprs_ctx *c = A->ctx;
     const sprs_dict *D = A->dict;
+    const sprs_tile_plan &TP = *r.tile;
+    const int g = r.grid;
+    const BlkDesc *desc64 = r.desc;       // the 64-row blocks outside the tiles
+    int g2_last;
+    const V2d *tail2 = dict_tail2(A, g2_last);
     TilePat tp;
     for (int t = 0; t < 8; ++t) { tp.off[t] = TP.off[t]; tp.val[t] = 0.0; }
     const bool ux = dot_mode != 0 && u == x;      // the dot operand is the input vector (mul_vec_dot, MINRES' v.Av, K4 without a preconditioner)
