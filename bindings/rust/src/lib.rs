@@ -73,6 +73,7 @@ pub mod sys {
         pub fn sprs_csr_stream_format(a: *const sprs_csr, n_offsets: *mut c_int, n_pairs: *mut c_int) -> c_int;
         pub fn sprs_csr_tile_plan(a: *const sprs_csr, n_tiles: *mut i64, n_tile_blocks: *mut i64, n_other_blocks: *mut i64) -> c_int;
         pub fn sprs_csr_chain_plan(a: *const sprs_csr, n_tiles: *mut i64, n_segments: *mut i64, n_chains: *mut i64, n_other_blocks: *mut i64) -> c_int;
+        pub fn sprs_csr_spmv_route(a: *const sprs_csr, part: c_int, conj_x: c_int, kernel: *mut c_int, format: *mut c_int, grid: *mut c_int, n_blocks: *mut i64, ordered: *mut c_int, y_nt: *mut c_int) -> c_int;
 
         pub fn sprs_mul_vec_d(a: *const sprs_csr, x: *const f64, x_len: usize, y: *mut f64, y_len: usize) -> c_int;
         pub fn sprs_mul_vec_z(a: *const sprs_csr, x: *const Complex64, x_len: usize, y: *mut Complex64, y_len: usize) -> c_int;
@@ -481,6 +482,15 @@ impl<T: HipScalar> HipCsr<T> {
         let (mut t, mut s, mut c, mut o) = (0i64, 0i64, 0i64, 0i64);
         ok_or_panic(unsafe { sys::sprs_csr_chain_plan(self.handle, &mut t, &mut s, &mut c, &mut o) });
         (t, s, c, o)
+    }
+    /// The kernel the next SpMV launch of this handle takes: (kernel, stream format, grid, row blocks walked, walked through an
+    /// order list, non-temporal y stores); kernel 0 Csr, 1 CsrWide, 2 Dict, 3 DictWide, 4 Pair2, 5 TilePair, 6 TileOff, 7 Chain.
+    /// part 0: the whole matrix; 1 / 2: the interior / boundary launch of a split distributed operator (`None` without a split).
+    pub fn spmv_route(&self, part: i32, conj_x: bool) -> Option<(i32, i32, i32, i64, bool, bool)> {
+        let (mut k, mut f, mut g, mut o, mut nt) = (0 as c_int, 0 as c_int, 0 as c_int, 0 as c_int, 0 as c_int);
+        let mut nb = 0i64;
+        ok_or_panic(unsafe { sys::sprs_csr_spmv_route(self.handle, part as c_int, conj_x as c_int, &mut k, &mut f, &mut g, &mut nb, &mut o, &mut nt) });
+        if k < 0 { None } else { Some((k, f, g, nb, o != 0, nt != 0)) }
     }
     /// `mul_vec_unchecked` on vectors that live in HBM (nothing crosses PCIe; asynchronous on the context's stream).
     pub fn mul_vec_dev(&self, v_in: &DevVec<T>, v_out: &mut DevVec<T>) {

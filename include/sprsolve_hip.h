@@ -173,6 +173,15 @@ int sprs_csr_tile_plan(const sprs_csr *A, int64_t *n_tiles, int64_t *n_tile_bloc
  * where a handle has both (sprs_csr_tile_plan then reports zeros): chain tiles (2048 rows each), chain segments (the work
  * items, about one per workgroup), chains, and the 128-row blocks the same launch walks one by one.  All zero otherwise. */
 int sprs_csr_chain_plan(const sprs_csr *A, int64_t *n_tiles, int64_t *n_segments, int64_t *n_chains, int64_t *n_other_blocks);
+/* Diagnostics: the kernel the next SpMV launch of this handle takes, as csrc/spmv.hip's routing function decides it now
+ * (the launch-time ctx knobs are read at the call).  part 0: the whole matrix; 1 / 2: the interior / boundary launch of a
+ * distributed operator that was split at creation — *kernel = -1 (and zeros) when the handle has no such split.
+ * *kernel: 0 Csr, 1 CsrWide, 2 Dict, 3 DictWide, 4 Pair2, 5 TilePair, 6 TileOff, 7 Chain (the order of SpmvKernel in
+ * csrc/internal.hpp); *format: 0 plain, 1 offset codes, 2 pair codes; *grid: workgroups = dot partials of the launch;
+ * *n_blocks: row blocks it walks; *ordered: 1 when it walks them through an order list (XCD-period order, the subsets of
+ * a split operator); *y_nt: 1 when the route asks for non-temporal y stores (CsrWide and Pair2 honour it). */
+int sprs_csr_spmv_route(const sprs_csr *A, int part, int conj_x, int *kernel, int *format, int *grid, int64_t *n_blocks,
+                        int *ordered, int *y_nt);
 
 /* MatVecMul::mul_vec / mul_vec_dot (mat.rs:49-64): host slices, checked — returns
  * SPRS_DIM_MISMATCH where the reference panics.  y = A x ; *dot_out = conj(x) . y

@@ -102,12 +102,33 @@ def make(n, kinds=None, vectorised=True):
     return indptr, cols, vals
 
 
-def run(budget=60.0, seed=12345, max_matrices=None, big_prob=0.04, small=True, verbose=True):
+def run(budget=60.0, seed=12345, max_matrices=None, big_prob=0.04, small=True, verbose=True, special_prob=0.0):
     """Fuzz for `budget` seconds or `max_matrices` matrices.  big_prob: share of 70-160 k-row stencil-like f64 matrices (the
     LDS-window tile plans); small=False skips the full knob product of the small matrices.  Returns a summary dict
-    (`mismatch` must be None)."""
+    (`mismatch` must be None).  special_prob > 0 (opt-in; the default run is unchanged and draws the same numbers): that share of
+    the entries of x and of the values is replaced by +-0.0, +-Inf, NaN, +-tiny, +-smallest subnormal, +-max (complex: either
+    part), drawn from a generator of their own, and y is compared with NaN by mask and bits elsewhere (tests/_special.py)."""
     global rng
     rng = np.random.default_rng(seed)
+    same = lambda a, b: np.array_equal(bits(a), bits(b))
+    if special_prob > 0:
+        sys.path.insert(0, __import__("os").path.join(__import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__))), "tests"))
+        import _special
+        srng = np.random.default_rng(seed + 1)
+
+        def same(a, b):
+            try:
+                _special.assert_same_special(a, b)
+                return True
+            except AssertionError:
+                return False
+
+        def salt(a):
+            fi = np.finfo(_special.real_dtype(a.dtype))
+            sp = np.array([0.0, -0.0, np.inf, -np.inf, np.nan, fi.tiny, -fi.tiny, fi.smallest_subnormal, -fi.smallest_subnormal, fi.max, -fi.max], dtype=fi.dtype)
+            c = _special.components(a).reshape(-1)
+            hit = np.flatnonzero(srng.uniform(size=c.size) < special_prob)
+            c[hit] = sp[srng.integers(0, sp.size, hit.size)]
     ctx = sa.default_ctx(0)
     t_end = time.time() + budget
     count = combos = tiled = 0
@@ -136,6 +157,9 @@ def run(budget=60.0, seed=12345, max_matrices=None, big_prob=0.04, small=True, v
             x = rng.uniform(-1, 1, n).astype(dtype)
             if np.dtype(dtype).kind == "c":
                 x = x + 1j * rng.uniform(-1, 1, n).astype(x.real.dtype)
+            if special_prob > 0:
+                d = np.ascontiguousarray(d); x = np.ascontiguousarray(x)
+                salt(d); salt(x)
             ref = oracle.spmv(indptr, cols, d, x)
             grid = (itertools.product((1, 2), (1,), (1,), (1,), (0, 1), (1,), (0, 1), (1,), (0, 1)) if big else
                     itertools.product((0, 1, 2), (0, 1), (0, 1), (0, 1), (0, 1), (0, 1), (0, 1), (0, 1), (-1,)) if small else
@@ -155,7 +179,7 @@ def run(budget=60.0, seed=12345, max_matrices=None, big_prob=0.04, small=True, v
                 A.mul_vec_dot(x, y2)
                 combos += 1
                 tiled += A.tile_plan()[0] > 0
-                if not (np.array_equal(bits(y), bits(ref)) and np.array_equal(bits(y2), bits(ref))):
+                if not (same(y, ref) and same(y2, ref)):
                     mismatch = dict(text="MISMATCH n=%d dtype=%s knobs dict=%d wide=%d uniform=%d eqrows=%d period=%d triple=%d seam=%d wideload=%d tile=%d stream=%s plan=%s bad=%d" % (
                         n, np.dtype(dtype).name, knob, wide, uni, eq, period, tri, seam, wl, tile, A.stream_format(), A.tile_plan(), int(np.sum(bits(y) != bits(ref)))),
                         arrays=dict(indptr=indptr, cols=cols, d=d, x=x))

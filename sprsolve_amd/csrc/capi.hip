@@ -614,6 +614,15 @@ int sprs_csr_chain_plan(const sprs_csr *A, int64_t *n_tiles, int64_t *n_segments
     *n_tiles = r.chain->n_tile; *n_segments = r.chain->n_seg; *n_chains = r.chain->n_chain; *n_other_blocks = r.chain->n_left;
     return SPRS_OK;
 }
+int sprs_csr_spmv_route(const sprs_csr *A, int part, int conj_x, int *kernel, int *format, int *grid, int64_t *n_blocks,
+                        int *ordered, int *y_nt) {
+    if (!A || part < 0 || part > 2 || !kernel || !format || !grid || !n_blocks || !ordered || !y_nt) return SPRS_INVALID_ARGUMENT;
+    *kernel = -1; *format = 0; *grid = 0; *n_blocks = 0; *ordered = 0; *y_nt = 0;
+    if (part != 0 && !(A->dist && A->dist->order_int)) return SPRS_OK;          // no interior / boundary split
+    const SpmvRoute r = spmv_route(A, part == 0 ? SpmvPart::Whole : part == 1 ? SpmvPart::Interior : SpmvPart::Boundary, conj_x != 0);
+    *kernel = (int)r.kernel; *format = r.format; *grid = r.grid; *n_blocks = r.count; *ordered = r.order ? 1 : 0; *y_nt = r.y_nt ? 1 : 0;
+    return SPRS_OK;
+}
 int sprs_csr_stream_format(const sprs_csr *A, int *n_offsets, int *n_values) {
     if (!A) return -1;
     if (n_offsets) *n_offsets = A->dict ? A->dict->n_off : 0;

@@ -117,6 +117,21 @@ class HipCsr(MatVecMul):
         check(_lib.lib().sprs_csr_chain_plan(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)), self.ctx.h)
         return a.value, b.value, c.value, d.value
 
+    SPMV_KERNELS = ("Csr", "CsrWide", "Dict", "DictWide", "Pair2", "TilePair", "TileOff", "Chain")      # SpmvKernel, csrc/internal.hpp
+
+    def spmv_route(self, part=0, conj_x=False):
+        """What the next SpMV launch takes (csrc/spmv.hip spmv_route, knobs read now): dict(kernel, format, grid, n_blocks, ordered,
+        y_nt).  part 0: the whole matrix; 1 / 2: the interior / boundary launch of a split distributed operator — None when the
+        handle has no such split."""
+        k, f, g, o, nt = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        nb = C.c_int64()
+        check(_lib.lib().sprs_csr_spmv_route(self.h, int(part), 1 if conj_x else 0, C.byref(k), C.byref(f), C.byref(g), C.byref(nb),
+                                             C.byref(o), C.byref(nt)), self.ctx.h)
+        if k.value < 0:
+            return None
+        return dict(kernel=self.SPMV_KERNELS[k.value], format=f.value, grid=g.value, n_blocks=nb.value, ordered=bool(o.value),
+                    y_nt=bool(nt.value))
+
     # -------------------------------------------------------------- MatVecMul
     def _s(self):
         return sfx(self.dtype)

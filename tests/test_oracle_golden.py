@@ -150,3 +150,116 @@ def test_gpu_order_reductions_are_a_reordering_only(oracle):
     assert a.status == b.status == oracle.OK and np.max(np.abs(a.x - b.x)) < 1e-9 and np.max(np.abs(b.x - p["exact"])) < 1e-9
     assert np.allclose(a.trace[0], b.trace[0], rtol=1e-12) and not np.array_equal(a.trace, b.trace)      # different order, same numbers
     assert np.array_equal(a.trace, c.trace) and np.array_equal(a.x, c.x) and a.its == c.its               # the default is untouched
+
+
+# ------------------------------------------------------------------ special values: the oracle's side (tests/_special.py)
+def _special_matrices(dtype):
+    """A small 3-D Poisson matrix (lines of 9 rows) and a ragged random one (empty rows, rows longer than a wavefront, more columns
+    than rows), each with one column no row references."""
+    import _special as S
+    from sprsolve_amd import gen
+    ip, ix, d, _ = gen.poisson3d(9, 7, 5)
+    d = d.astype(dtype)
+    if np.dtype(dtype).kind == "c":
+        d = d * (1 - 0.5j)
+    n = ip.size - 1
+    out = {"poisson3d": S.drop_column(ip, ix, d, n // 3) + (n, n, 9, n // 3)}
+    ip, ix, d = S.ragged_csr(700, 31, dtype, ncols=760)
+    out["ragged"] = S.drop_column(ip, ix, d, 333) + (700, 760, None, 333)
+    return out
+
+
+@pytest.mark.parametrize("name", ["poisson3d", "ragged"])
+@pytest.mark.parametrize("dtype", [np.float64, np.complex128, np.float32, np.complex64], ids=["f64", "c64", "f32", "c32"])
+def test_oracle_spmv_depends_on_exactly_the_stored_columns(oracle, dtype, name):
+    """The property tests/test_gpu_special_values.py holds every SpMV route to, on the reference side alone: y[i] depends on x[j] if
+    and only if row i stores column j.  With x[S] = NaN / +Inf / -Inf (complex: either part, both) rows that store no column of S
+    keep the bits of A x0 — the oracle's fold touches stored entries only; the share of (matrix, poison set) combinations where it
+    does not must be zero, so every one is asserted — and the touched rows equal an independent numpy restatement of the fold (NaN
+    by mask, bits elsewhere)."""
+    import _special as S
+    ip, ix, d, nrows, ncols, nx, free_col = _special_matrices(dtype)[name]
+    x0 = S.rand_vec(ncols, dtype, 3)
+    spmv = lambda x: oracle.spmv(ip, ix, d, x)
+    ref = lambda x: S.fold_spmv(ip, ix, d, x)
+    y0 = spmv(x0)
+    S.assert_same_special(y0, ref(x0), "clean x")
+    rng = np.random.default_rng(17)
+    sets = [("random%d" % k, S.random_poison_set(rng, ip, ix, ncols), "random") for k in range(3)]
+    sets += [(k, v, "structural") for k, v in S.structural_sets(ip, ix, nrows, ncols, nx).items()]
+    sets.append(("unreferenced", np.array([free_col]), "unreferenced"))
+    assert {"first", "last", "triple", "last_column"} <= {s[0] for s in sets}
+    for sname, cols, kind in sets:
+        for vname, value in S.poison_values(dtype):
+            _, y, touched = S.check_poison(spmv, ref, ip, ix, ncols, x0, y0, cols, value, kind, label="%s/%s/%s" % (name, sname, vname))
+            if kind != "unreferenced" and value[1] != value[1]:
+                assert np.isnan(S.components(y[touched])).any()            # (the poison arrives where it should)
+
+
+@pytest.mark.parametrize("name", ["poisson3d", "ragged"])
+@pytest.mark.parametrize("dtype", [np.float64, np.complex128, np.float32, np.complex64], ids=["f64", "c64", "f32", "c32"])
+def test_oracle_spmv_signed_zero_subnormal_overflow(oracle, dtype, name):
+    """The fold starts from +0.0 (oracle/krylov_tmpl.h): a row whose products are all -0.0 gives +0.0; subnormal products are kept,
+    not flushed; a partial sum that overflows stays +-Inf and +Inf meeting -Inf is NaN; complex products follow (ac - bd) + (ad + bc) i
+    through Inf and NaN.  The oracle against the independent numpy fold on every value variant of tests/_special.py."""
+    import _special as S
+    ip, ix, d, nrows, ncols, nx, free_col = _special_matrices(dtype)[name]
+    seen = set()
+    for vname, vals, x in S.special_variants(d, dtype, ncols, 5):
+        y = oracle.spmv(ip, ix, vals, x)
+        S.assert_same_special(y, S.fold_spmv(ip, ix, vals, x), "%s/%s" % (name, vname))
+        yc = S.components(y)
+        if vname in ("zeros_values_neg0_x", "neg0_x"):
+            assert not np.signbit(yc).any() and not yc.any(), vname            # sums of -0.0 products on top of +0.0: +0.0
+        if vname == "subnormal":
+            tiny = np.finfo(yc.dtype).tiny
+            assert ((yc != 0) & (np.abs(yc) < tiny)).any() and (np.abs(yc) == np.finfo(yc.dtype).smallest_subnormal).any()
+        if vname == "overflow":
+            assert np.isinf(yc).any() and np.isnan(yc).any() and np.isfinite(yc).any()
+        if vname == "complex_inf":
+            assert np.isnan(yc).any() and np.isfinite(yc).any()
+        seen.add(vname)
+    assert {"zeros_values", "neg0_x", "subnormal", "overflow"} <= seen
+
+
+def test_special_helpers_catch_a_multiply_by_zero_and_a_seeded_accumulator():
+    """The two assertion classes can fail: an SpMV that MULTIPLIES its padded slots by zero instead of selecting them away is
+    bit-identical on finite data and goes red in the poison check (0 * NaN, 0 * Inf); one that seeds its accumulator with the first
+    product goes red on the all -0.0 input (-0.0 where the reference gives +0.0).  assert_same_special itself: NaN by mask whatever
+    its sign and payload, everything else by bits (+0.0 is not -0.0, +Inf is not -Inf)."""
+    import _special as S
+    ip, ix, d = S.ragged_csr(120, 7, np.float64, long_rows=False)
+    ip, ix, d = S.drop_column(ip, ix, d, 40)
+    n = 120
+    x0 = S.rand_vec(n, np.float64, 1)
+    good = lambda x: S.fold_spmv(ip, ix, d, x)
+    wrong = lambda x: S.padded_spmv_multiplying_by_zero(ip, ix, d, x)
+    lens = np.diff(ip)
+    y0 = good(x0)
+    assert np.array_equal(S.bits(wrong(x0)[lens > 0]), S.bits(y0[lens > 0]))          # finite data cannot tell them apart
+    rng = np.random.default_rng(2)
+    cols = S.random_poison_set(rng, ip, ix, n)
+    for vname, value in S.poison_values(np.float64):
+        S.check_poison(good, good, ip, ix, n, x0, y0, cols, value, "random", label=vname)
+        with pytest.raises(AssertionError, match="untouched rows"):
+            S.check_poison(wrong, good, ip, ix, n, x0, wrong(x0), cols, value, "random", label=vname)
+    with pytest.raises(AssertionError):                                                  # a vacuous poison set is refused
+        S.check_poison(good, good, ip, ix, n, x0, y0, np.array([40]), ("re", np.nan), "random")
+    S.check_poison(good, good, ip, ix, n, x0, y0, np.array([40]), ("re", np.nan), "unreferenced")
+    neg0 = np.full(n, -0.0)
+    seeded = S.first_product_seeded_spmv(ip, ix, np.abs(d), neg0)
+    S.assert_same_special(good(neg0), np.zeros(n))
+    with pytest.raises(AssertionError, match="bits differ"):
+        S.assert_same_special(seeded, good(neg0), "seeded accumulator")
+    a = np.array([np.nan, 1.0, -0.0, np.inf])
+    b = np.array([-np.nan, 1.0, -0.0, np.inf])
+    b.view(np.uint64)[0] |= 0x1234                                                       # another payload, the other sign
+    S.assert_same_special(a, b)
+    for k, v in ((1, np.nan), (2, 0.0), (3, -np.inf), (0, 1.0)):
+        c = b.copy(); c[k] = v
+        with pytest.raises(AssertionError):
+            S.assert_same_special(c, a)
+    z = np.array([1 + 2j, np.nan + 1j], dtype=np.complex64)
+    S.assert_same_special(z, z.copy())
+    with pytest.raises(AssertionError):
+        S.assert_same_special(np.array([1 + 2j, 1 + np.nan * 1j], dtype=np.complex64), z)
