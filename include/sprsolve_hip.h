@@ -53,6 +53,7 @@ typedef struct sprs_diag sprs_diag;         /* DiagPrecond<T,V>              (pr
 typedef struct sprs_bicgstab sprs_bicgstab; /* BiCGStab<T,M>                 (bicg_stab.rs:17-31) */
 typedef struct sprs_minres sprs_minres;     /* MinRes<T,M>                   (minres.rs:13-27)    */
 typedef struct sprs_csminres sprs_csminres; /* CSMinRes<T,M>                 (cs_minres.rs:11-25) */
+typedef struct sprs_cg sprs_cg;             /* conjugate gradients (no reference analogue; "conjugate gradients" below) */
 typedef struct sprs_comm sprs_comm;         /* RCCL communicator of this rank (multi-GPU section)  */
 typedef struct sprs_gauss_seidel sprs_gauss_seidel; /* GaussSeidel<T>        (gauss_seidel.rs:8-31) */
 
@@ -306,6 +307,38 @@ int sprs_gauss_seidel_solve_s(sprs_gauss_seidel *G, const float *rhs, size_t rhs
 int sprs_gauss_seidel_solve_dev_d(sprs_gauss_seidel *G, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double eps, size_t *its_out, double *res_out);
 int sprs_gauss_seidel_solve_dev_s(sprs_gauss_seidel *G, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float eps, size_t *its_out, float *res_out);
 
+/* ---------------------------------------------------------------- conjugate gradients
+ * For Hermitian positive-definite A (A == A^H, x^H A x > 0); neither property is checked — on another matrix the solve
+ * ends in SPRS_BREAKDOWN, SPRS_INSUFFICIENT_ITER or a wrong answer.  The reference has no such solver; the conventions are its
+ * BiCGStab's: relative residual against |rhs|, a zero right-hand side answers x = 0, x is in/out and is left modified on
+ * error.  One SpMV and two dot products per iteration; the handle holds 4n of workspace (3n are used without a preconditioner).  P is the Jacobi
+ * preconditioner (any of its (T, V) pairs); its size / scalar type are checked as for the other solvers.
+ * All scalars are of type T, sign tests use the real part, conj_dot(a, b) = sum conj(a_i) b_i:
+ *     rhs_norm = norm2(rhs);  if rhs_norm <= eps: x = 0, return SPRS_OK with *its_out = 0, *res_out = rhs_norm
+ *     r = rhs*1 + (A x)*(-1);  if norm2(r) <= tol * rhs_norm: return SPRS_OK with *its_out = 0
+ *     z = P r (z is r itself without P);  p = z;  rho = conj_dot(r, z)
+ *     for its = 0 .. max_iter - 1:
+ *         q = A p;  pq = conj_dot(p, q);  unless re(pq) > 0: SPRS_BREAKDOWN, *its_out = its  (also where pq is NaN)
+ *         alpha = rho / pq;  x += p*alpha;  r += q*(-alpha)
+ *         if norm2(r) <= tol * rhs_norm: SPRS_OK, *its_out = its + 1, *res_out = norm2(r) / rhs_norm
+ *         z = P r;  rho_new = conj_dot(r, z);  with P, unless re(rho_new) > 0: SPRS_INVALID_PRECOND, *its_out = its,
+ *                                                                               *res_out = re(rho_new)
+ *         beta = rho_new / rho;  rho = rho_new;  p = z*1 + p*beta
+ *     SPRS_INSUFFICIENT_ITER, *its_out = max_iter
+ * So *its_out of SPRS_OK counts the SpMVs of the loop; of an error it is the 0-based iteration of the event.
+ * SPRS_INCOMPATIBLE_RHS_SIZE / SPRS_INCOMPATIBLE_X_SIZE as for BiCGStab.  Trace row (sprs_solver_set_trace), one per iteration
+ * that reached the p update: [its, r_norm, re(rho), im(rho), re(alpha), im(alpha), re(beta), im(beta)], rho = rho_new. */
+int sprs_cg_create_d(const sprs_csr *A, size_t size, sprs_cg **out);
+int sprs_cg_create_z(const sprs_csr *A, size_t size, sprs_cg **out);
+int sprs_cg_destroy(sprs_cg *S);               /* NULL is a no-op */
+int sprs_cg_solve_d(sprs_cg *S, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_cg_solve_z(sprs_cg *S, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_cg_precond_solve_d(sprs_cg *S, const sprs_diag *P, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_cg_precond_solve_z(sprs_cg *S, const sprs_diag *P, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+/* the same on device vectors (16-byte aligned ones are used in place) */
+int sprs_cg_solve_dev_d(sprs_cg *S, const sprs_diag *P_or_null, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_cg_solve_dev_z(sprs_cg *S, const sprs_diag *P_or_null, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+
 /* ---------------------------------------------------------------- f32 / Complex<f32>
  * The reference is generic over cauchy::Scalar = {f32, f64, c32, c64} and its unit tests exercise f32 / c32
  * BLAS-1 (src/vecalg.rs:647-658,669-677,771-798,816-830).  Every typed entry point above exists again with
@@ -373,6 +406,14 @@ int sprs_csminres_solve_c(sprs_csminres *S, const sprs_c32 *rhs, size_t rhs_len,
 int sprs_csminres_solve_s(sprs_csminres *S, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
 int sprs_csminres_solve_dev_c(sprs_csminres *S, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
 int sprs_csminres_solve_dev_s(sprs_csminres *S, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_cg_create_s(const sprs_csr *A, size_t size, sprs_cg **out);
+int sprs_cg_create_c(const sprs_csr *A, size_t size, sprs_cg **out);
+int sprs_cg_solve_s(sprs_cg *S, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_cg_solve_c(sprs_cg *S, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_cg_precond_solve_s(sprs_cg *S, const sprs_diag *P, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_cg_precond_solve_c(sprs_cg *S, const sprs_diag *P, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_cg_solve_dev_s(sprs_cg *S, const sprs_diag *P_or_null, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_cg_solve_dev_c(sprs_cg *S, const sprs_diag *P_or_null, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
 int sprs_dist_csr_create_dev_s(sprs_comm *comm, int64_t n_local, int64_t n_ext, int64_t nnz, const int32_t *dev_row_ptr, const int32_t *dev_col_idx_ext, const float *dev_val, int adopt, int n_peers, const int32_t *peer_rank, const int64_t *send_off, const int32_t *send_idx_dev, const int64_t *recv_off, sprs_csr **out);
 int sprs_dist_csr_create_dev_c(sprs_comm *comm, int64_t n_local, int64_t n_ext, int64_t nnz, const int32_t *dev_row_ptr, const int32_t *dev_col_idx_ext, const sprs_c32 *dev_val, int adopt, int n_peers, const int32_t *peer_rank, const int64_t *send_off, const int32_t *send_idx_dev, const int64_t *recv_off, sprs_csr **out);
 int sprs_dist_mul_vec_dev_s(const sprs_csr *A, float *x_ext_dev, float *y_local_dev);
@@ -440,13 +481,14 @@ int sprs_dist_mul_vec_dev_d(const sprs_csr *A, double *x_ext_dev, double *y_loca
 int sprs_dist_mul_vec_dev_z(const sprs_csr *A, sprs_c64 *x_ext_dev, sprs_c64 *y_local_dev);
 
 /* ---------------------------------------------------------------- solver options / instrumentation
- * `solver` is any of the three solver handle types. */
-enum { SPRS_SOLVER_BICGSTAB = 1, SPRS_SOLVER_MINRES = 2, SPRS_SOLVER_CSMINRES = 3 };
+ * `solver` is any of the four solver handle types. */
+enum { SPRS_SOLVER_BICGSTAB = 1, SPRS_SOLVER_MINRES = 2, SPRS_SOLVER_CSMINRES = 3, SPRS_SOLVER_CG = 4 };
 /* mode 0 (default): fused kernels, device-resident scalars, lazy host polling.
  * mode 1: "literal" — the reference's op list one kernel per op, every scalar consumed on the
  *         host exactly where the reference consumes it (bicg_stab.rs:122-197). */
 int sprs_solver_set_mode(void *solver, int kind, int mode);
-/* Per-iteration scalar trace (8 doubles per row: BiCGStab [its, r_norm, rho, alpha, w]; MINRES [its, beta, alpha, c, s, res_norm]): the solver
+/* Per-iteration scalar trace (8 doubles per row: BiCGStab [its, r_norm, rho, alpha, w]; MINRES [its, beta, alpha, c, s, res_norm];
+ * CG [its, r_norm, rho, alpha, beta]): the solver
  * synchronises every iteration while a trace buffer is set.  rows_out: rows written by the last solve. */
 int sprs_solver_set_trace(void *solver, int kind, double *trace_host, size_t capacity_rows);
 int sprs_solver_trace_rows(const void *solver, int kind, size_t *rows_out);
@@ -464,7 +506,7 @@ int sprs_solver_get_profile(const void *solver, int kind, double *spmv_ms_total,
 /* How many SpMV launches of the last solve formed their input vector on the fly (ctx knob "spmv_fuse"; MINRES: its SpMV launches that
  * multiplied by the un-normalised vector are reported in k2_fused): BiCGStab's K2 with K1's
  * update p = (v (-beta w) + p beta) + r inside, K4 with K3's r -= alpha v inside (bicg_stab.rs:155-156,172).  Zero for the other
- * solvers and wherever the five-launch iteration ran. */
+ * solvers (CG among them) and wherever the five-launch iteration ran. */
 int sprs_solver_get_fused_launches(const void *solver, int kind, int64_t *k2_fused, int64_t *k4_fused);
 
 #ifdef __cplusplus

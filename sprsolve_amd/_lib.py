@@ -15,7 +15,7 @@ CSRC = os.path.join(_HERE, "csrc")
  INVALID_ARGUMENT) = range(8)
 ZERO_DIAGONAL, NOT_SQUARE, NOT_CSR = 8, 9, 10
 ERR_HIP, ERR_RCCL, ERR_NO_DEVICE = 100, 101, 102
-SOLVER_BICGSTAB, SOLVER_MINRES, SOLVER_CSMINRES = 1, 2, 3
+SOLVER_BICGSTAB, SOLVER_MINRES, SOLVER_CSMINRES, SOLVER_CG = 1, 2, 3, 4
 
 
 class c64(C.Structure):
@@ -95,17 +95,17 @@ def _protos():
         P["sprs_axpby_" + s] = [_vp, _sz, sc, _vp, sc, _vp]
         P["sprs_diag_mul_vec_" + s] = [_vp, _vp, _sz, _vp, _sz]
         P["sprs_diag_mul_vec_dev_" + s] = [_vp, _vp, _vp]
-        for k in ("bicgstab", "minres", "csminres"):
+        for k in ("bicgstab", "minres", "csminres", "cg"):
             P["sprs_%s_create_%s" % (k, s)] = [_vp, _sz, _pp]
             P["sprs_%s_solve_%s" % (k, s)] = [_vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
-        for k in ("bicgstab", "minres"):
+        for k in ("bicgstab", "minres", "cg"):
             P["sprs_%s_precond_solve_%s" % (k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
             P["sprs_%s_solve_dev_%s" % (k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
         P["sprs_csminres_solve_dev_" + s] = [_vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
     P["sprs_axpy_zd"] = [_vp, _sz, _dbl, _vp, _vp]
     P["sprs_axpy_cs"] = [_vp, _sz, C.c_float, _vp, _vp]
     P["sprs_csr_destroy"] = [_vp]
-    for k in ("bicgstab", "minres", "csminres"):
+    for k in ("bicgstab", "minres", "csminres", "cg"):
         P["sprs_%s_destroy" % k] = [_vp]
     for s in ("d", "zd", "z", "s", "cs", "c"):
         P["sprs_diag_precond_create_" + s] = [_vp, _sz, _vp, _pp]

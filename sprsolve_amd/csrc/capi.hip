@@ -501,15 +501,17 @@ int solve_dev(SolverT *s, const sprs_diag *P, const T *rhs, size_t rl, T *x, siz
 
 template <class T, class H> BicgStab<T> *bi(H *h) { return (h && h->dtype == dtype_of<T>::value) ? (BicgStab<T> *)h->impl : nullptr; }
 template <class T, class H> MinRes<T> *mr(H *h) { return (h && h->dtype == dtype_of<T>::value) ? (MinRes<T> *)h->impl : nullptr; }
+template <class T, class H> Cg<T> *cgs(H *h) { return (h && h->dtype == dtype_of<T>::value) ? (Cg<T> *)h->impl : nullptr; }
 
 }  // namespace
 
-struct sprs_bicgstab; struct sprs_minres; struct sprs_csminres;
+struct sprs_bicgstab; struct sprs_minres; struct sprs_csminres; struct sprs_cg;
 static int base_of(void *solver, int kind, int *dtype, void **impl) {
     if (!solver) return SPRS_INVALID_ARGUMENT;
     if (kind == SPRS_SOLVER_BICGSTAB) { auto *h = (sprs_bicgstab *)solver; *dtype = h->dtype; *impl = h->impl; }
     else if (kind == SPRS_SOLVER_MINRES) { auto *h = (sprs_minres *)solver; *dtype = h->dtype; *impl = h->impl; }
     else if (kind == SPRS_SOLVER_CSMINRES) { auto *h = (sprs_csminres *)solver; *dtype = h->dtype; *impl = h->impl; }
+    else if (kind == SPRS_SOLVER_CG) { auto *h = (sprs_cg *)solver; *dtype = h->dtype; *impl = h->impl; }
     else return SPRS_INVALID_ARGUMENT;
     return SPRS_OK;
 }
@@ -520,6 +522,8 @@ static int with_base(void *solver, int kind, F &&f) {
     SPRS_TRY(base_of(solver, kind, &dt, &impl));
     if (kind == SPRS_SOLVER_BICGSTAB)
         return with_solver<BicgStab>(dt, impl, [&](auto *s) { return f(s); });
+    if (kind == SPRS_SOLVER_CG)
+        return with_solver<Cg>(dt, impl, [&](auto *s) { return f(s); });
     return with_solver<MinRes>(dt, impl, [&](auto *s) { return f(s); });
 }
 
@@ -642,6 +646,7 @@ int sprs_diag_precond_destroy(sprs_diag *P) {
 int sprs_bicgstab_destroy(sprs_bicgstab *S) { return solver_destroy<sprs_bicgstab, BicgStab>(S); }
 int sprs_minres_destroy(sprs_minres *S) { return solver_destroy<sprs_minres, MinRes>(S); }
 int sprs_csminres_destroy(sprs_csminres *S) { return solver_destroy<sprs_csminres, MinRes>(S); }
+int sprs_cg_destroy(sprs_cg *S) { return solver_destroy<sprs_cg, Cg>(S); }
 
 // ---- everything that exists once per scalar type.  X = suffix, T = device scalar, CT = C-ABI scalar
 // (passed by value / pointer), R = T::Real
@@ -719,6 +724,18 @@ int sprs_csminres_destroy(sprs_csminres *S) { return solver_destroy<sprs_csminre
     }                                                                                                                  \
     int sprs_csminres_solve_dev_##X(sprs_csminres *S, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
         SPRS_G(return solve_dev<T>(mr<T>(S), nullptr, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);)             \
+    }                                                                                                                  \
+    int sprs_cg_create_##X(const sprs_csr *A, size_t n, sprs_cg **out) {                                               \
+        SPRS_G(return (solver_create<T, sprs_cg, Cg>(A, n, out, [&](auto *s) { return s->create(A, n); }));)           \
+    }                                                                                                                  \
+    int sprs_cg_solve_##X(sprs_cg *S, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
+        SPRS_G(return solve_host<T>(cgs<T>(S), nullptr, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);)           \
+    }                                                                                                                  \
+    int sprs_cg_precond_solve_##X(sprs_cg *S, const sprs_diag *P, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
+        SPRS_G(if (!P) return SPRS_INVALID_ARGUMENT; return solve_host<T>(cgs<T>(S), P, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);) \
+    }                                                                                                                  \
+    int sprs_cg_solve_dev_##X(sprs_cg *S, const sprs_diag *P, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
+        SPRS_G(return solve_dev<T>(cgs<T>(S), P, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);)                  \
     }
 
 SPRS_API(d, double, double, double)

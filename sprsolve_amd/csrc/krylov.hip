@@ -2,6 +2,9 @@
 //
 // Reference: src/bicg_stab.rs:35-366, src/minres.rs:31-341, src/cs_minres.rs:29-158.
 //
+// Conjugate gradients (Cg<T>, at the end of this file) has no reference analogue: its recurrence is stated in
+// include/sprsolve_hip.h and follows BiCGStab's conventions.
+//
 // Two execution modes per solver (sprs_solver_set_mode):
 //  * fused (default): the reference's 13 (BiCGStab) / 11 (MINRES) full-vector passes per
 //    iteration are regrouped into 5 / 3 kernels.  Every scalar of the recurrence (rho, alpha, w,
@@ -26,6 +29,7 @@
 #include <utility>
 
 #include "bicg_fuse.hpp"
+#include "cg_fuse.hpp"
 #include "minres_fuse.hpp"
 #include "device.hpp"
 
@@ -1141,6 +1145,208 @@ int MinRes<T>::solve_dev(const sprs_diag *P, const T *rhs, size_t rhs_len, T *x,
     return st;
 }
 
+// ======================================================================= CG host
+// Conjugate gradients for Hermitian positive-definite A, optionally Jacobi-preconditioned.  The recurrence (the numbered
+// steps are those of the header's sprs_cg_* comment):
+//   r = rhs*1 + (A x)*(-1) ; z = M^-1 r ; p = z ; rho = conj(r).z
+//   loop:  q = A p ; pq = conj(p).q ; BreakDown unless re(pq) > 0 ; alpha = rho / pq ; x += p alpha ; r += q (-alpha) ;
+//          Ok(its + 1) if |r| <= tol |rhs| ; z = M^-1 r ; rho_new = conj(r).z ; InvalidPreconditioner unless re(rho_new) > 0 ;
+//          beta = rho_new / rho ; p = z*1 + p*beta
+// Fused: three launches per iteration (cg_fuse.hpp) — one SpMV and 6 + 3 vector passes (8 + 3 with Jacobi).
+template <class T>
+int Cg<T>::create(const sprs_csr *A, size_t size) {
+    SPRS_TRY(this->init(A, size, 4));   // r, p, q, z (z only with a preconditioner)
+    this->no_p2p = true;                // hand-offs through fin_for + red1 / redDT + the all-reduce only
+    SPRS_HIP_TRY(this->ctx, hipMalloc((void **)&d_state, sizeof(CgState<T>)));
+    SPRS_HIP_TRY(this->ctx, hipHostMalloc((void **)&h_state, sizeof(CgState<T>), hipHostMallocDefault));
+    return SPRS_OK;
+}
+template <class T>
+void Cg<T>::destroy() {
+    if (d_state) (void)hipFree(d_state);
+    if (h_state) (void)hipHostFree(h_state);
+    d_state = h_state = nullptr;
+    KrylovBase<T>::destroy();
+}
+
+template <class T>
+template <class V>
+int Cg<T>::start(const V *dinv, const T *rhs, T *x, Real<T> tol, Real<T> *rhs_norm, Real<T> *tol2, T *rho, int *done, Real<T> *res_out) {
+    sprs_ctx *c = this->ctx;
+    const size_t n = this->n;
+    T *r = this->vec(0), *p = this->vec(1), *z = dinv ? this->vec(3) : r;
+    *done = 1;
+    SPRS_TRY(this->norm2(rhs, rhs_norm));
+    if (*rhs_norm <= seps<Real<T>>()) {                                     // a zero right-hand side answers x = 0
+        SPRS_TRY(dzero(c, x, n));
+        *res_out = *rhs_norm;
+        return SPRS_OK;
+    }
+    *tol2 = tol * *rhs_norm;
+    SPRS_TRY(this->spmv(x, r, 0, nullptr, nullptr, nullptr, nullptr));      // r = A x
+    SPRS_TRY(launch_axpby<T>(c, n, sone<T>(), rhs, sneg(sone<T>()), r));    // r = rhs*1 + r*(-1)
+    Real<T> r_norm = 0.0;
+    SPRS_TRY(this->norm2(r, &r_norm));
+    if (r_norm <= *tol2) { *res_out = r_norm / *rhs_norm; return SPRS_OK; }
+    if (dinv) SPRS_TRY((launch_diag_apply<T, V>(c, n, dinv, r, z)));        // z = M^-1 r
+    SPRS_TRY(dcopy(c, p, z, n));                                            // p = z
+    SPRS_TRY(this->cdot(r, z, rho));                                        // rho = conj(r).z
+    *done = 0;
+    return SPRS_OK;
+}
+
+template <class T>
+template <class V>
+int Cg<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out) {
+    sprs_ctx *c = this->ctx;
+    const size_t n = this->n;
+    const bool pc = dinv != nullptr;
+    *its_out = 0; *res_out = 0.0;
+    T *r = this->vec(0), *p = this->vec(1), *q = this->vec(2), *z = pc ? this->vec(3) : r;
+
+    Real<T> rhs_norm = 0.0, tol2 = 0.0;
+    T rho = szero<T>();
+    int done = 0;
+    SPRS_TRY(start<V>(dinv, rhs, x, tol, &rhs_norm, &tol2, &rho, &done, res_out));
+    if (done) return SPRS_OK;
+
+    CgState<T> &H = *h_state;
+    memset(&H, 0, sizeof(H));
+    H.rho = rho; H.rho_prev = rho; H.tol2 = tol2;
+    H.its = 0; H.status = ST_RUNNING;
+    SPRS_HIP_TRY(c, hipMemcpyAsync(d_state, &H, sizeof(H), hipMemcpyHostToDevice, c->stream));
+    const int *d_status = &d_state->status;
+
+    const int G = this->ew_grid();
+    const int cw = fused_chunked(this->A) ? 1 : 0;      // XCD-chunked walk of the vector kernels (spmv.hip)
+    const int GS = spmv_num_partials(this->A);
+    Real<T> *partN = this->dslot(0);
+    T *partRZ = this->pslot(0), *partPQ = this->pslot(1);
+    typename KrylovBase<T>::PartT qPQ{partPQ, GS}, qRZ{partRZ, G};
+    typename KrylovBase<T>::PartD qN{partN, G};
+
+    auto CA = [&]() -> int {                                                // q = A p ; conj(p).q
+        const Fin f = this->fin_for(0, partPQ, nullptr, GS);
+        SPRS_TRY(this->spmv(p, q, 1, p, partPQ, nullptr, d_status, false, &f));
+        return this->red1(partPQ, GS, 0, &qPQ);
+    };
+    auto KB = [&]() -> int {
+        const Fin f = this->fin_for(1, partN, partRZ, G);
+        if (pc) SPRS_TRY(launch_fused<T>(c, n, G, cw, CgKB<T, V, true>{d_state, qPQ.p, qPQ.P, p, q, x, r, dinv, z, partN, partRZ, f, T(), T(), 0.0, T()}));
+        else SPRS_TRY(launch_fused<T>(c, n, G, cw, CgKB<T, V, false>{d_state, qPQ.p, qPQ.P, p, q, x, r, dinv, z, partN, partRZ, f, T(), T(), 0.0, T()}));
+        return this->redDT(partN, partRZ, G, 1, &qN, &qRZ);
+    };
+    auto KC = [&]() -> int {
+        if (pc) return launch_fused<T>(c, n, G, cw, CgKC<T, true>{d_state, qN.p, qRZ.p, qN.P, z, p, T(), T()});
+        return launch_fused<T>(c, n, G, cw, CgKC<T, false>{d_state, qN.p, qRZ.p, qN.P, z, p, T(), T()});
+    };
+    auto fetch = [&]() -> int {
+        SPRS_HIP_TRY(c, hipMemcpyAsync(&H, d_state, sizeof(H), hipMemcpyDeviceToHost, c->stream));
+        SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return (int)SPRS_OK;
+    };
+
+    const bool tracing = this->trace != nullptr;
+    const size_t poll = tracing ? 1 : (size_t)(c->poll < 1 ? 1 : c->poll);
+    size_t its = 0, since_poll = 0;
+    while (true) {
+        const bool done_enqueue = its >= max_iter;
+        if (!done_enqueue) {
+            SPRS_TRY(CA()); SPRS_TRY(KB()); SPRS_TRY(KC());
+            ++its; ++since_poll;
+        }
+        if (done_enqueue || since_poll >= poll) {
+            since_poll = 0;
+            SPRS_TRY(fetch());
+            if (H.status != ST_RUNNING && its > (size_t)H.its) this->profile_discard_last(its - (size_t)H.its - (H.status == ST_CONVERGED ? 0 : 1));
+            if (H.status == ST_CONVERGED) {
+                *its_out = (size_t)H.its; *res_out = H.r_norm / rhs_norm;
+                return SPRS_OK;
+            }
+            if (H.status == ST_BREAKDOWN) {
+                *its_out = (size_t)H.its;
+                return SPRS_BREAKDOWN;
+            }
+            if (H.status == ST_INVALID_PC) {
+                *its_out = (size_t)H.its; *res_out = H.pc_re;
+                return SPRS_INVALID_PRECOND;
+            }
+            if (tracing && !done_enqueue) this->trace_row((double)(H.its - 1), H.r_norm, H.rho, H.alpha, H.beta);
+            if (done_enqueue) break;
+        }
+    }
+    *its_out = max_iter;
+    return SPRS_INSUFFICIENT_ITER;
+}
+
+// literal mode: the recurrence op by op, one kernel per op, host-consumed scalars
+template <class T>
+template <class V>
+int Cg<T>::run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out) {
+    sprs_ctx *c = this->ctx;
+    const size_t n = this->n;
+    const bool pc = dinv != nullptr;
+    *its_out = 0; *res_out = 0.0;
+    T *r = this->vec(0), *p = this->vec(1), *q = this->vec(2), *z = pc ? this->vec(3) : r;
+    Real<T> rhs_norm = 0.0, tol2 = 0.0;
+    T rho = szero<T>();
+    int done = 0;
+    SPRS_TRY(start<V>(dinv, rhs, x, tol, &rhs_norm, &tol2, &rho, &done, res_out));
+    if (done) return SPRS_OK;
+    for (size_t its = 0; its < max_iter; ++its) {
+        SPRS_TRY(this->spmv(p, q, 0, nullptr, nullptr, nullptr, nullptr));
+        T pq;
+        SPRS_TRY(this->cdot(p, q, &pq));
+        if (!(sre(pq) > 0.0)) { *its_out = its; return SPRS_BREAKDOWN; }
+        const T alpha = sdiv(rho, pq);
+        SPRS_TRY((launch_axpy<T, T>(c, n, alpha, p, x)));
+        SPRS_TRY((launch_axpy<T, T>(c, n, sneg(alpha), q, r)));
+        Real<T> r_norm = 0.0;
+        SPRS_TRY(this->norm2(r, &r_norm));
+        if (r_norm <= tol2) { *its_out = its + 1; *res_out = r_norm / rhs_norm; return SPRS_OK; }
+        if (pc) SPRS_TRY((launch_diag_apply<T, V>(c, n, dinv, r, z)));
+        T rho_new;
+        SPRS_TRY(this->cdot(r, z, &rho_new));
+        if (pc && !(sre(rho_new) > 0.0)) { *its_out = its; *res_out = sre(rho_new); return SPRS_INVALID_PRECOND; }
+        const T beta = sdiv(rho_new, rho);
+        rho = rho_new;
+        SPRS_TRY(launch_axpby<T>(c, n, sone<T>(), z, beta, p));
+        this->trace_row((double)its, r_norm, rho, alpha, beta);
+    }
+    *its_out = max_iter;
+    return SPRS_INSUFFICIENT_ITER;
+}
+
+template <class T>
+int Cg<T>::solve_dev(const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
+                     size_t *its_out, Real<T> *res_out) {
+    size_t its_dummy; Real<T> res_dummy;
+    if (!its_out) its_out = &its_dummy;
+    if (!res_out) res_out = &res_dummy;
+    if (rhs_len != this->n) return SPRS_INCOMPATIBLE_RHS_SIZE;
+    if (x_len != this->n) return SPRS_INCOMPATIBLE_X_SIZE;
+    SPRS_TRY(check_diag<T>(P, this->n));
+    SPRS_TRY(this->begin_solve());
+    int st;
+    const bool lit = this->mode == 1;
+    if (P && P->v_complex) {
+        if constexpr (is_complex<T>::value) {
+            const T *d = (const T *)P->dinv;
+            st = lit ? run_literal<T>(d, rhs, x, max_iter, tol, its_out, res_out)
+                     : run<T>(d, rhs, x, max_iter, tol, its_out, res_out);
+        } else {
+            return SPRS_INVALID_ARGUMENT;
+        }
+    } else {
+        const Real<T> *d = P ? (const Real<T> *)P->dinv : nullptr;
+        st = lit ? run_literal<Real<T>>(d, rhs, x, max_iter, tol, its_out, res_out)
+                 : run<Real<T>>(d, rhs, x, max_iter, tol, its_out, res_out);
+    }
+    if (st >= SPRS_ERR_HIP) return st;
+    SPRS_TRY(this->end_solve());
+    return st;
+}
+
 template class KrylovBase<double>;
 template class KrylovBase<float>;
 template class KrylovBase<cplxf>;
@@ -1153,5 +1359,9 @@ template class MinRes<double>;
 template class MinRes<float>;
 template class MinRes<cplxf>;
 template class MinRes<cplx>;
+template class Cg<double>;
+template class Cg<float>;
+template class Cg<cplxf>;
+template class Cg<cplx>;
 
 }  // namespace sprs

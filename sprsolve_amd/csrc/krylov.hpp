@@ -1,4 +1,4 @@
-// Solver objects behind sprs_bicgstab / sprs_minres / sprs_csminres.
+// Solver objects behind sprs_bicgstab / sprs_minres / sprs_csminres / sprs_cg.
 #pragma once
 #include "internal.hpp"
 
@@ -27,6 +27,8 @@ struct MinresDev {
     long long its;   // 0-based iteration index of the event recorded in `status`
     int status, pad;
 };
+
+template <class T> struct CgState;   // cg_fuse.hpp
 
 struct SolverStats {
     double spmv_ms = 0.0, solve_ms = 0.0;
@@ -91,7 +93,8 @@ class KrylovBase {
     // `slot` picks a 16-byte cell of `red`.
     struct PartT { const T *p; int P; unsigned int tag = 0; };            // tag != 0: p = this rank's mailbox entries of the hand-off, P = world
     struct PartD { const Real<T> *p; int P; unsigned int tag = 0; };
-    bool use_p2p() const { return A->dist && A->dist->comm->p2p && ctx->p2p_allreduce != 0; }
+    bool no_p2p = false;         // this solver's hand-offs always take the all-reduce (CG: it has no mailbox consumers)
+    bool use_p2p() const { return !no_p2p && A->dist && A->dist->comm->p2p && ctx->p2p_allreduce != 0; }
     unsigned long long mb_timeout() const { return (unsigned long long)(ctx->p2p_timeout_ms < 1 ? 1 : ctx->p2p_timeout_ms) * 100000ull; }   // ticks of the 100 MHz wall clock
     const void *mbox_entries(int slot) const;    // this rank's mailbox at the CURRENT hand-off of `slot`
     int red1(const T *a, int P, int slot, PartT *oa);
@@ -135,6 +138,26 @@ class MinRes : public KrylovBase<T> {
     int run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
 };
 
+// Conjugate gradients for Hermitian positive-definite A (recurrence: include/sprsolve_hip.h, sprs_cg_*; kernels: cg_fuse.hpp)
+template <class T>
+class Cg : public KrylovBase<T> {
+   public:
+    CgState<T> *d_state = nullptr, *h_state = nullptr;
+    int create(const sprs_csr *A, size_t size);
+    void destroy();
+    int solve_dev(const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
+                  size_t *its_out, Real<T> *res_out);
+
+   private:
+    // the part both modes share: zero rhs, initial residual, z = M^-1 r, p = z, rho = conj(r).z; done = 1: answered already
+    template <class V>
+    int start(const V *dinv, const T *rhs, T *x, Real<T> tol, Real<T> *rhs_norm, Real<T> *tol2, T *rho, int *done, Real<T> *res_out);
+    template <class V>
+    int run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
+    template <class V>
+    int run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
+};
+
 template <class T>
 template <class F>
 int KrylovBase<T>::solve_host(const T *rhs, size_t rhs_len, T *x, size_t x_len, F &&dev_solve) {
@@ -166,6 +189,10 @@ struct sprs_minres {
     void *impl;
 };
 struct sprs_csminres {
+    int dtype;
+    void *impl;
+};
+struct sprs_cg {
     int dtype;
     void *impl;
 };

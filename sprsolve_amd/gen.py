@@ -229,6 +229,22 @@ def symmetric_banded(n, hbw=4, seed=SEED):
     return indptr, indices, data, rhs
 
 
+def hermitian_banded(n, hbw=4, seed=SEED):
+    """The complex sibling of symmetric_banded: Hermitian banded, a[i,i+k] = conj(a[i+k,i]) = U(-1,1) + i U(-1,1),
+    real diag = 1 + sum |off-diagonal of the row| (strictly dominant => Hermitian positive definite); rhs complex U(-1,1)."""
+    R = []; Cc = []; V = []
+    absrow = np.zeros(n)
+    r = np.arange(n)
+    for k in range(1, hbw + 1):
+        a = (uniform(seed, n, stream=60 + 2 * k) + 1j * uniform(seed, n, stream=61 + 2 * k))[: n - k]   # a[i, i+k]
+        R += [r[: n - k], r[k:]]; Cc += [r[k:], r[: n - k]]; V += [a, np.conj(a)]
+        absrow[: n - k] += np.abs(a); absrow[k:] += np.abs(a)
+    R.append(r); Cc.append(r); V.append((1.0 + absrow).astype(np.complex128))
+    indptr, indices, data = _coo_to_csr(n, np.concatenate(R), np.concatenate(Cc), np.concatenate(V))
+    rhs = uniform(seed, n, stream=58) + 1j * uniform(seed, n, stream=59)
+    return indptr, indices, data, rhs
+
+
 def poisson3d(nx, ny, nz, z0=0, z1=None, index_dtype=np.int32, values="poisson", seed=SEED):
     """cfg 5: 7-point 3-D Poisson on an nx*ny*nz grid (x fastest), diag +6, neighbours -1,
     truncated at the faces.  Returns the CSR row block for planes [z0, z1) with GLOBAL column
