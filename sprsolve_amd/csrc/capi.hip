@@ -427,7 +427,7 @@ int diag_apply_host(const sprs_diag *Pc, const T *in, size_t in_len, T *out, siz
 }
 
 // ------------------------------------------------------------------------------ solver handles
-// one opaque handle layout for the three solver kinds: { dtype, impl }
+// one opaque handle layout for every solver kind: sprs_solver_handle { dtype, impl }
 template <template <class> class S, class F>
 int with_solver(int dtype, void *impl, F &&f) {
     switch (dtype) {
@@ -457,74 +457,59 @@ int solver_create(const sprs_csr *A, size_t size, H **out, Mk mk) {
     return SPRS_OK;
 }
 
-template <class H, template <class> class S>
-int solver_destroy(H *h) {
+template <template <class> class S>
+int solver_destroy(sprs_solver_handle *h) {
     if (!h) return SPRS_OK;
     with_solver<S>(h->dtype, h->impl, [](auto *s) { (void)hipStreamSynchronize(s->ctx->stream); s->destroy(); delete s; return (int)SPRS_OK; });
     delete h;
     return SPRS_OK;
 }
 
-// host-slice solve: copy rhs/x in, run the device solve, copy x back
+// One solve.  Host slices (host = true), and device vectors that are not 16-byte aligned, go through the solver's aligned
+// rhs_buf / x_buf; other device vectors are used in place.
 template <class T, class SolverT>
-int solve_host(SolverT *s, const sprs_diag *P, const T *rhs, size_t rl, T *x, size_t xl, size_t max_iter, Real<T> tol,
-               size_t *its, Real<T> *res) {
+int solve(SolverT *s, bool host, const sprs_diag *P, const T *rhs, size_t rl, T *x, size_t xl, size_t max_iter, Real<T> tol,
+          size_t *its, Real<T> *res) {
     if (!s || !rhs || !x) return SPRS_INVALID_ARGUMENT;
-    CtxLock lock(s->ctx);   // one solve at a time per context (its stream, its scratch)
-    return s->solve_host(rhs, rl, x, xl, [&](T *drhs, T *dx) {
-        return s->solve_dev(P, drhs, rl, dx, xl, max_iter, tol, its, res);
-    });
-}
-
-// device-vector solve; stage through aligned buffers when the caller's vectors are not 16-byte aligned
-template <class T, class SolverT>
-int solve_dev(SolverT *s, const sprs_diag *P, const T *rhs, size_t rl, T *x, size_t xl, size_t max_iter, Real<T> tol,
-              size_t *its, Real<T> *res) {
-    if (!s || !rhs || !x) return SPRS_INVALID_ARGUMENT;
+    // size checks first (bicg_stab.rs:44-53): nothing is copied on a mismatch
     if (rl != s->n) return SPRS_INCOMPATIBLE_RHS_SIZE;
     if (xl != s->n) return SPRS_INCOMPATIBLE_X_SIZE;
     sprs_ctx *c = s->ctx;
-    CtxLock lock(c);
-    const bool al = ((reinterpret_cast<uintptr_t>(rhs) | reinterpret_cast<uintptr_t>(x)) & 15) == 0;
-    if (al) return s->solve_dev(P, rhs, rl, x, xl, max_iter, tol, its, res);
+    CtxLock lock(c);   // one solve at a time per context (its stream, its scratch)
+    if (!host && ((reinterpret_cast<uintptr_t>(rhs) | reinterpret_cast<uintptr_t>(x)) & 15) == 0)
+        return s->solve_dev(P, rhs, rl, x, xl, max_iter, tol, its, res);
+    const hipMemcpyKind in = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, out = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     SPRS_HIP_TRY(c, hipSetDevice(c->device));
     if (!s->rhs_buf) SPRS_HIP_TRY(c, hipMalloc((void **)&s->rhs_buf, sizeof(T) * s->stride));
     if (!s->x_buf) SPRS_HIP_TRY(c, hipMalloc((void **)&s->x_buf, sizeof(T) * s->stride));
-    SPRS_HIP_TRY(c, hipMemcpyAsync(s->rhs_buf, rhs, sizeof(T) * rl, hipMemcpyDeviceToDevice, c->stream));
-    SPRS_HIP_TRY(c, hipMemcpyAsync(s->x_buf, x, sizeof(T) * xl, hipMemcpyDeviceToDevice, c->stream));
+    SPRS_HIP_TRY(c, hipMemcpyAsync(s->rhs_buf, rhs, sizeof(T) * rl, in, c->stream));
+    SPRS_HIP_TRY(c, hipMemcpyAsync(s->x_buf, x, sizeof(T) * xl, in, c->stream));
     int st = s->solve_dev(P, s->rhs_buf, rl, s->x_buf, xl, max_iter, tol, its, res);
     if (st >= SPRS_ERR_HIP) return st;
-    SPRS_HIP_TRY(c, hipMemcpyAsync(x, s->x_buf, sizeof(T) * xl, hipMemcpyDeviceToDevice, c->stream));
+    // x is in/out in the reference and is left modified on Err as well
+    SPRS_HIP_TRY(c, hipMemcpyAsync(x, s->x_buf, sizeof(T) * xl, out, c->stream));
     SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
     return st;
 }
 
-template <class T, class H> BicgStab<T> *bi(H *h) { return (h && h->dtype == dtype_of<T>::value) ? (BicgStab<T> *)h->impl : nullptr; }
-template <class T, class H> MinRes<T> *mr(H *h) { return (h && h->dtype == dtype_of<T>::value) ? (MinRes<T> *)h->impl : nullptr; }
-template <class T, class H> Cg<T> *cgs(H *h) { return (h && h->dtype == dtype_of<T>::value) ? (Cg<T> *)h->impl : nullptr; }
+// the S<T> behind a handle, or null where the handle holds another scalar type
+template <template <class> class S, class T>
+S<T> *impl_of(sprs_solver_handle *h) { return (h && h->dtype == dtype_of<T>::value) ? (S<T> *)h->impl : nullptr; }
 
 }  // namespace
 
-struct sprs_bicgstab; struct sprs_minres; struct sprs_csminres; struct sprs_cg;
-static int base_of(void *solver, int kind, int *dtype, void **impl) {
-    if (!solver) return SPRS_INVALID_ARGUMENT;
-    if (kind == SPRS_SOLVER_BICGSTAB) { auto *h = (sprs_bicgstab *)solver; *dtype = h->dtype; *impl = h->impl; }
-    else if (kind == SPRS_SOLVER_MINRES) { auto *h = (sprs_minres *)solver; *dtype = h->dtype; *impl = h->impl; }
-    else if (kind == SPRS_SOLVER_CSMINRES) { auto *h = (sprs_csminres *)solver; *dtype = h->dtype; *impl = h->impl; }
-    else if (kind == SPRS_SOLVER_CG) { auto *h = (sprs_cg *)solver; *dtype = h->dtype; *impl = h->impl; }
-    else return SPRS_INVALID_ARGUMENT;
-    return SPRS_OK;
-}
 // every solver impl derives from KrylovBase<T>
 template <class F>
 static int with_base(void *solver, int kind, F &&f) {
-    int dt; void *impl;
-    SPRS_TRY(base_of(solver, kind, &dt, &impl));
-    if (kind == SPRS_SOLVER_BICGSTAB)
-        return with_solver<BicgStab>(dt, impl, [&](auto *s) { return f(s); });
-    if (kind == SPRS_SOLVER_CG)
-        return with_solver<Cg>(dt, impl, [&](auto *s) { return f(s); });
-    return with_solver<MinRes>(dt, impl, [&](auto *s) { return f(s); });
+    auto *h = (sprs_solver_handle *)solver;
+    if (!h) return SPRS_INVALID_ARGUMENT;
+    switch (kind) {
+        case SPRS_SOLVER_BICGSTAB: return with_solver<BicgStab>(h->dtype, h->impl, f);
+        case SPRS_SOLVER_CG: return with_solver<Cg>(h->dtype, h->impl, f);
+        case SPRS_SOLVER_MINRES:
+        case SPRS_SOLVER_CSMINRES: return with_solver<MinRes>(h->dtype, h->impl, f);
+    }
+    return SPRS_INVALID_ARGUMENT;
 }
 
 
@@ -643,10 +628,25 @@ int sprs_diag_precond_destroy(sprs_diag *P) {
     delete P;
     return SPRS_OK;
 }
-int sprs_bicgstab_destroy(sprs_bicgstab *S) { return solver_destroy<sprs_bicgstab, BicgStab>(S); }
-int sprs_minres_destroy(sprs_minres *S) { return solver_destroy<sprs_minres, MinRes>(S); }
-int sprs_csminres_destroy(sprs_csminres *S) { return solver_destroy<sprs_csminres, MinRes>(S); }
-int sprs_cg_destroy(sprs_cg *S) { return solver_destroy<sprs_cg, Cg>(S); }
+int sprs_bicgstab_destroy(sprs_bicgstab *S) { return solver_destroy<BicgStab>(S); }
+int sprs_minres_destroy(sprs_minres *S) { return solver_destroy<MinRes>(S); }
+int sprs_csminres_destroy(sprs_csminres *S) { return solver_destroy<MinRes>(S); }
+int sprs_cg_destroy(sprs_cg *S) { return solver_destroy<Cg>(S); }
+
+// ---- a solver's entry points per scalar type.  NAME = the handle is sprs_NAME, S = its class, CREATE = the arguments of S<T>::create
+#define SPRS_SOLVER_API(X, T, CT, R, NAME, S, CREATE)                                                                  \
+    int sprs_##NAME##_create_##X(const sprs_csr *A, size_t n, sprs_##NAME **out) {                                     \
+        SPRS_G(return (solver_create<T, sprs_##NAME, S>(A, n, out, [&](auto *s) { return s->create CREATE; }));)       \
+    }                                                                                                                  \
+    int sprs_##NAME##_solve_##X(sprs_##NAME *h, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
+        SPRS_G(return solve<T>(impl_of<S, T>(h), true, nullptr, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);)   \
+    }                                                                                                                  \
+    int sprs_##NAME##_precond_solve_##X(sprs_##NAME *h, const sprs_diag *P, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
+        SPRS_G(if (!P) return SPRS_INVALID_ARGUMENT; return solve<T>(impl_of<S, T>(h), true, P, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);) \
+    }                                                                                                                  \
+    int sprs_##NAME##_solve_dev_##X(sprs_##NAME *h, const sprs_diag *P, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
+        SPRS_G(return solve<T>(impl_of<S, T>(h), false, P, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);)        \
+    }
 
 // ---- everything that exists once per scalar type.  X = suffix, T = device scalar, CT = C-ABI scalar
 // (passed by value / pointer), R = T::Real
@@ -692,50 +692,18 @@ int sprs_cg_destroy(sprs_cg *S) { return solver_destroy<sprs_cg, Cg>(S); }
         SPRS_G(return diag_apply_host<T>(P, (const T *)in, il, (T *)out, ol);)                                         \
     }                                                                                                                  \
     int sprs_diag_mul_vec_dev_##X(const sprs_diag *P, const CT *in, CT *out) { return diag_apply_dev<T>(P, (const T *)in, (T *)out); } \
-    int sprs_bicgstab_create_##X(const sprs_csr *A, size_t n, sprs_bicgstab **out) {                                   \
-        SPRS_G(return (solver_create<T, sprs_bicgstab, BicgStab>(A, n, out, [&](auto *s) { return s->create(A, n); }));) \
-    }                                                                                                                  \
-    int sprs_minres_create_##X(const sprs_csr *A, size_t n, sprs_minres **out) {                                       \
-        SPRS_G(return (solver_create<T, sprs_minres, MinRes>(A, n, out, [&](auto *s) { return s->create(A, n, false); }));) \
-    }                                                                                                                  \
+    SPRS_SOLVER_API(X, T, CT, R, bicgstab, BicgStab, (A, n))                                                           \
+    SPRS_SOLVER_API(X, T, CT, R, minres, MinRes, (A, n, false))                                                        \
+    SPRS_SOLVER_API(X, T, CT, R, cg, Cg, (A, n))                                                                       \
+    /* CSMinRes has no precond_solve (cs_minres.rs) */                                                                  \
     int sprs_csminres_create_##X(const sprs_csr *A, size_t n, sprs_csminres **out) {                                   \
         SPRS_G(return (solver_create<T, sprs_csminres, MinRes>(A, n, out, [&](auto *s) { return s->create(A, n, true); }));) \
     }                                                                                                                  \
-    int sprs_bicgstab_solve_##X(sprs_bicgstab *S, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
-        SPRS_G(return solve_host<T>(bi<T>(S), nullptr, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);)            \
+    int sprs_csminres_solve_##X(sprs_csminres *h, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
+        SPRS_G(return solve<T>(impl_of<MinRes, T>(h), true, nullptr, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);) \
     }                                                                                                                  \
-    int sprs_bicgstab_precond_solve_##X(sprs_bicgstab *S, const sprs_diag *P, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
-        SPRS_G(if (!P) return SPRS_INVALID_ARGUMENT; return solve_host<T>(bi<T>(S), P, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);) \
-    }                                                                                                                  \
-    int sprs_bicgstab_solve_dev_##X(sprs_bicgstab *S, const sprs_diag *P, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
-        SPRS_G(return solve_dev<T>(bi<T>(S), P, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);)                   \
-    }                                                                                                                  \
-    int sprs_minres_solve_##X(sprs_minres *S, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
-        SPRS_G(return solve_host<T>(mr<T>(S), nullptr, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);)            \
-    }                                                                                                                  \
-    int sprs_minres_precond_solve_##X(sprs_minres *S, const sprs_diag *P, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
-        SPRS_G(if (!P) return SPRS_INVALID_ARGUMENT; return solve_host<T>(mr<T>(S), P, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);) \
-    }                                                                                                                  \
-    int sprs_minres_solve_dev_##X(sprs_minres *S, const sprs_diag *P, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
-        SPRS_G(return solve_dev<T>(mr<T>(S), P, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);)                   \
-    }                                                                                                                  \
-    int sprs_csminres_solve_##X(sprs_csminres *S, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
-        SPRS_G(return solve_host<T>(mr<T>(S), nullptr, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);)            \
-    }                                                                                                                  \
-    int sprs_csminres_solve_dev_##X(sprs_csminres *S, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
-        SPRS_G(return solve_dev<T>(mr<T>(S), nullptr, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);)             \
-    }                                                                                                                  \
-    int sprs_cg_create_##X(const sprs_csr *A, size_t n, sprs_cg **out) {                                               \
-        SPRS_G(return (solver_create<T, sprs_cg, Cg>(A, n, out, [&](auto *s) { return s->create(A, n); }));)           \
-    }                                                                                                                  \
-    int sprs_cg_solve_##X(sprs_cg *S, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
-        SPRS_G(return solve_host<T>(cgs<T>(S), nullptr, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);)           \
-    }                                                                                                                  \
-    int sprs_cg_precond_solve_##X(sprs_cg *S, const sprs_diag *P, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
-        SPRS_G(if (!P) return SPRS_INVALID_ARGUMENT; return solve_host<T>(cgs<T>(S), P, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);) \
-    }                                                                                                                  \
-    int sprs_cg_solve_dev_##X(sprs_cg *S, const sprs_diag *P, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
-        SPRS_G(return solve_dev<T>(cgs<T>(S), P, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);)                  \
+    int sprs_csminres_solve_dev_##X(sprs_csminres *h, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
+        SPRS_G(return solve<T>(impl_of<MinRes, T>(h), false, nullptr, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);) \
     }
 
 SPRS_API(d, double, double, double)

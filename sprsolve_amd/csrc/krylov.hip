@@ -20,6 +20,12 @@
 //    dot products / norms differs from the reference's serial fold.
 //  * literal: one kernel per reference op, scalars consumed on the host where the reference
 //    consumes them.  Slow (5 host syncs per iteration); kept as the on-GPU cross-check.
+//
+// What the solvers share on the host is written once, in KrylovBase (krylov.hpp): solve() (argument checks, the
+// preconditioner's element type, literal or fused), StateBlock (the device + pinned-host pair of the scalar state),
+// handoff() (a producer's partials to their consumer: single GPU / mailbox / all-reduce), zero_rhs(), poll_interval(),
+// comm_timeout(), and dispatch_bool() for the kernels' compile-time flags.  The main loops stay apart: BiCGStab's restart,
+// MINRES's deferred M3 and CG's accounting of idle launches have nothing in common.
 #include "krylov.hpp"
 
 #include <algorithm>
@@ -72,6 +78,10 @@ static int launch_fused(sprs_ctx *c, size_t n, int grid, int chunked_walk, F f) 
     SPRS_HIP_TRY(c, hipGetLastError());
     return SPRS_OK;
 }
+
+// a run-time flag as a template argument: f(std::true_type{}) or f(std::false_type{})
+template <class F>
+static int dispatch_bool(bool flag, F &&f) { return flag ? f(std::true_type{}) : f(std::false_type{}); }
 
 // (first_thread(), BicgK1 and BicgK3 live in bicg_fuse.hpp: the plane-streaming chain SpMV runs their prologues and their
 // element-wise updates inside its own launch — "fused SpMV input" below)
@@ -292,49 +302,22 @@ const void *KrylovBase<T>::mbox_entries(int slot) const {
     return reinterpret_cast<const char *>(cm->mbox) + mb_offset(slot, (int)(cm->seq[slot] & 1u));
 }
 template <class T>
-int KrylovBase<T>::red1(const T *a, int P, int slot, PartT *oa) {
-    if (!A->dist) { *oa = PartT{a, P}; return SPRS_OK; }
-    if (use_p2p()) { *oa = PartT{reinterpret_cast<const T *>(mbox_entries(slot)), comm()->world, comm()->seq[slot]}; return SPRS_OK; }
-    double *ra = red + 2 * slot;
-    SPRS_TRY(allreduce_sum(comm(), ra, 16 / sizeof(Real<T>), sizeof(Real<T>) == 4));
-    *oa = PartT{reinterpret_cast<const T *>(ra), 1};
-    return SPRS_OK;
-}
-template <class T>
-int KrylovBase<T>::red2(const T *a, const T *b, int P, int slot, PartT *oa, PartT *ob) {
-    if (!A->dist) { *oa = PartT{a, P}; *ob = PartT{b, P}; return SPRS_OK; }
-    if (use_p2p()) {
-        *oa = PartT{reinterpret_cast<const T *>(mbox_entries(slot)), comm()->world, comm()->seq[slot]};
-        *ob = *oa;
+template <class U, class W>
+int KrylovBase<T>::handoff(int slot, int P, const U *a, Part<U> *oa, const W *b, Part<W> *ob) {
+    if (!A->dist) {
+        *oa = Part<U>{a, P};
+        if (ob) *ob = Part<W>{b, P};
+        return SPRS_OK;
+    }
+    if (use_p2p()) {    // both values are in the same mailbox entries
+        *oa = Part<U>{reinterpret_cast<const U *>(mbox_entries(slot)), comm()->world, comm()->seq[slot]};
+        if (ob) *ob = Part<W>{reinterpret_cast<const W *>(mbox_entries(slot)), comm()->world, comm()->seq[slot]};
         return SPRS_OK;
     }
     double *ra = red + 2 * slot, *rb = red + 2 * slot + 2;
-    SPRS_TRY(allreduce_sum(comm(), ra, 32 / sizeof(Real<T>), sizeof(Real<T>) == 4));
-    *oa = PartT{reinterpret_cast<const T *>(ra), 1};
-    *ob = PartT{reinterpret_cast<const T *>(rb), 1};
-    return SPRS_OK;
-}
-template <class T>
-int KrylovBase<T>::redD1(const Real<T> *a, int P, int slot, PartD *oa) {
-    if (!A->dist) { *oa = PartD{a, P}; return SPRS_OK; }
-    if (use_p2p()) { *oa = PartD{reinterpret_cast<const Real<T> *>(mbox_entries(slot)), comm()->world, comm()->seq[slot]}; return SPRS_OK; }
-    double *ra = red + 2 * slot;
-    SPRS_TRY(allreduce_sum(comm(), ra, 16 / sizeof(Real<T>), sizeof(Real<T>) == 4));
-    *oa = PartD{reinterpret_cast<const Real<T> *>(ra), 1};
-    return SPRS_OK;
-}
-template <class T>
-int KrylovBase<T>::redDT(const Real<T> *a, const T *b, int P, int slot, PartD *oa, PartT *ob) {
-    if (!A->dist) { *oa = PartD{a, P}; *ob = PartT{b, P}; return SPRS_OK; }
-    if (use_p2p()) {
-        *oa = PartD{reinterpret_cast<const Real<T> *>(mbox_entries(slot)), comm()->world, comm()->seq[slot]};
-        *ob = PartT{reinterpret_cast<const T *>(mbox_entries(slot)), comm()->world, comm()->seq[slot]};
-        return SPRS_OK;
-    }
-    double *ra = red + 2 * slot, *rb = red + 2 * slot + 2;
-    SPRS_TRY(allreduce_sum(comm(), ra, 32 / sizeof(Real<T>), sizeof(Real<T>) == 4));
-    *oa = PartD{reinterpret_cast<const Real<T> *>(ra), 1};
-    *ob = PartT{reinterpret_cast<const T *>(rb), 1};
+    SPRS_TRY(allreduce_sum(comm(), ra, (ob ? 32 : 16) / sizeof(Real<T>), sizeof(Real<T>) == 4));
+    *oa = Part<U>{reinterpret_cast<const U *>(ra), 1};
+    if (ob) *ob = Part<W>{reinterpret_cast<const W *>(rb), 1};
     return SPRS_OK;
 }
 
@@ -389,12 +372,8 @@ int KrylovBase<T>::profiled(F &&run, bool one_kernel) {
         st = run();
         SPRS_HIP_TRY(ctx, hipEventRecord(ev[ev_used + 1], ctx->stream));
     }
-    ev_noop.resize(ev_used / 2 + 1, 0);
-    ev_noop[ev_used / 2] = 0;
-    ev_call.resize(ev_used / 2 + 1, 0);
-    ev_call[ev_used / 2] = call;
-    ev_kind.resize(ev_used / 2 + 1, 0);
-    ev_kind[ev_used / 2] = 0;
+    ev_pair.resize(ev_used / 2);
+    ev_pair.push_back(EvPair{call});
     last_pair = (long)(ev_used / 2);
     ev_used += 2;
     return st;
@@ -405,7 +384,7 @@ void KrylovBase<T>::profile_discard_last(size_t launches) {
     if (!profile) return;
     // the last `launches` STEPS were no-ops: the event pairs among them (all of them, or the sampled ones)
     const size_t first_noop = prof_calls > launches ? prof_calls - launches : 0;
-    for (size_t k = ev_used / 2; k > 1 && ev_call[k - 1] >= first_noop; --k) ev_noop[k - 1] = 1;     // pair 0 brackets the solve
+    for (size_t k = ev_used / 2; k > 1 && ev_pair[k - 1].call >= first_noop; --k) ev_pair[k - 1].noop = true;     // pair 0 brackets the solve
 }
 
 template <class T>
@@ -423,8 +402,7 @@ int KrylovBase<T>::begin_solve() {
         }
         ev_used = 2;  // ev[0], ev[1] bracket the whole solve
         prof_calls = 0;
-        ev_call.assign(1, 0);
-        ev_kind.assign(1, 0);
+        ev_pair.assign(1, EvPair{});
         last_pair = -1;
         SPRS_HIP_TRY(ctx, hipEventRecord(ev[0], ctx->stream));
     }
@@ -440,14 +418,14 @@ int KrylovBase<T>::end_solve() {
     SPRS_HIP_TRY(ctx, hipEventElapsedTime(&ms, ev[0], ev[1]));
     stats.solve_ms = ms;
     for (size_t k = 2; k + 1 < ev_used; k += 2) {
-        if (k / 2 < ev_noop.size() && ev_noop[k / 2]) continue;
+        const EvPair &p = ev_pair[k / 2];
+        if (p.noop) continue;
         SPRS_HIP_TRY(ctx, hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
         stats.spmv_ms += ms;
         stats.spmv_launches += 1;
-        const unsigned char kind = k / 2 < ev_kind.size() ? ev_kind[k / 2] : 0;
-        stats.timed_dot_other += (kind & 1) != 0;
-        stats.timed_fused_k2 += (kind & 2) != 0;
-        stats.timed_fused_k4 += (kind & 4) != 0;
+        stats.timed_dot_other += (p.kind & 1) != 0;
+        stats.timed_fused_k2 += (p.kind & 2) != 0;
+        stats.timed_fused_k4 += (p.kind & 4) != 0;
     }
     stats.steps = (int64_t)prof_calls;
     return SPRS_OK;
@@ -474,20 +452,66 @@ static int dzero(sprs_ctx *c, T *dst, size_t n) {
     return SPRS_OK;
 }
 
+// ======================================================================= what the solvers' hosts share
+template <class T>
+int KrylovBase<T>::zero_rhs(const T *rhs, T *x, Real<T> *rhs_norm, Real<T> *res_out, bool *zero) {
+    SPRS_TRY(norm2(rhs, rhs_norm));                                         // bicg_stab.rs:55, minres.rs:51
+    *zero = *rhs_norm <= seps<Real<T>>();                                   // bicg_stab.rs:56-60, minres.rs:52-56
+    if (*zero) {
+        SPRS_TRY(dzero(ctx, x, n));
+        *res_out = *rhs_norm;
+    }
+    return SPRS_OK;
+}
+
+template <class T>
+int KrylovBase<T>::comm_timeout() {
+    snprintf(ctx->err, sizeof(ctx->err), "a peer's hand-off did not reach this rank's mailbox within %d ms (p2p_timeout_ms)", ctx->p2p_timeout_ms);
+    return SPRS_ERR_RCCL;
+}
+
+template <class T>
+static int check_diag(const sprs_diag *P, size_t n) {
+    if (!P) return SPRS_OK;
+    if (P->n != n) return SPRS_DIM_MISMATCH;
+    if (P->t_dtype != dtype_of<T>::value) return SPRS_INVALID_ARGUMENT;
+    return SPRS_OK;
+}
+
+template <class T>
+template <class S>
+int KrylovBase<T>::solve(S &s, bool no_precond, const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter,
+                         Real<T> tol, size_t *its_out, Real<T> *res_out) {
+    size_t its_dummy; Real<T> res_dummy;
+    if (!its_out) its_out = &its_dummy;
+    if (!res_out) res_out = &res_dummy;
+    if (rhs_len != s.n) return SPRS_INCOMPATIBLE_RHS_SIZE;                  // bicg_stab.rs:44-48, minres.rs:40-44
+    if (x_len != s.n) return SPRS_INCOMPATIBLE_X_SIZE;                      // bicg_stab.rs:49-53, minres.rs:45-49
+    if (no_precond && P) return SPRS_INVALID_ARGUMENT;                      // CSMinRes has no precond_solve
+    SPRS_TRY(check_diag<T>(P, s.n));
+    SPRS_TRY(s.begin_solve());
+    auto run = [&](const auto *d) -> int {
+        using V = std::remove_cv_t<std::remove_pointer_t<decltype(d)>>;
+        return s.mode == 1 ? s.template run_literal<V>(d, rhs, x, max_iter, tol, its_out, res_out)
+                           : s.template run<V>(d, rhs, x, max_iter, tol, its_out, res_out);
+    };
+    int st;
+    if (P && P->v_complex) {
+        if constexpr (is_complex<T>::value) st = run((const T *)P->dinv);
+        else return SPRS_INVALID_ARGUMENT;
+    } else {
+        st = run(P ? (const Real<T> *)P->dinv : (const Real<T> *)nullptr);
+    }
+    if (st >= SPRS_ERR_HIP) return st;
+    SPRS_TRY(s.end_solve());
+    return st;
+}
+
 // ======================================================================= BiCGStab host
 template <class T>
 int BicgStab<T>::create(const sprs_csr *A, size_t size) {
     SPRS_TRY(this->init(A, size, 7));   // bicg_stab.rs:28 workspace 7n
-    SPRS_HIP_TRY(this->ctx, hipMalloc((void **)&d_state, sizeof(BicgState<T>)));
-    SPRS_HIP_TRY(this->ctx, hipHostMalloc((void **)&h_state, sizeof(BicgState<T>), hipHostMallocDefault));
-    return SPRS_OK;
-}
-template <class T>
-void BicgStab<T>::destroy() {
-    if (d_state) (void)hipFree(d_state);
-    if (h_state) (void)hipHostFree(h_state);
-    d_state = h_state = nullptr;
-    KrylovBase<T>::destroy();
+    return state.create(this->ctx);
 }
 
 template <class T>
@@ -499,12 +523,9 @@ int BicgStab<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T>
     *its_out = 0; *res_out = 0.0;
 
     Real<T> rhs_norm = 0.0;
-    SPRS_TRY(this->norm2(rhs, &rhs_norm));                          // :55
-    if (rhs_norm <= seps<Real<T>>()) {                                          // :56-60
-        SPRS_TRY(dzero(c, x, n));
-        *its_out = 0; *res_out = rhs_norm;
-        return SPRS_OK;
-    }
+    bool zero;
+    SPRS_TRY(this->zero_rhs(rhs, x, &rhs_norm, res_out, &zero));            // :55-60
+    if (zero) return SPRS_OK;
     const Real<T> tol2 = tol * rhs_norm;                             // :61
 
     // :64-69 / :234-241
@@ -541,13 +562,14 @@ int BicgStab<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T>
     Real<T> r0_norm_tol = r0_norm * seps<Real<T>>();                                     // :84
     r0_norm_tol = r0_norm_tol * r0_norm_tol;                                // :85
 
-    BicgState<T> &H = *h_state;
+    BicgState<T> &H = *state.host;
+    BicgState<T> *const d_state = state.dev;
     memset(&H, 0, sizeof(H));
     H.rho = sfromr<T>(r0_norm * r0_norm);                                   // :88
     H.rho_old = H.rho;
     H.r_norm = r0_norm; H.r0_norm_tol = r0_norm_tol; H.tol2 = tol2;
     H.its = 0; H.status = ST_RUNNING;
-    SPRS_HIP_TRY(c, hipMemcpyAsync(d_state, &H, sizeof(H), hipMemcpyHostToDevice, c->stream));
+    SPRS_TRY(state.push());
     const int *d_status = &d_state->status;
 
     const int G = this->ew_grid();
@@ -556,8 +578,8 @@ int BicgStab<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T>
     Real<T> *partN = this->dslot(0);
     T *partRho = this->pslot(0), *partB = this->pslot(1), *partTT = this->pslot(2), *partTR = this->pslot(3);
 
-    typename KrylovBase<T>::PartT qB{partB, GS}, qTT{partTT, GS}, qTR{partTR, GS}, qRho{partRho, G};
-    typename KrylovBase<T>::PartD qN{partN, G};
+    Part<T> qB{partB, GS}, qTT{partTT, GS}, qTR{partTR, GS}, qRho{partRho, G};
+    Part<Real<T>> qN{partN, G};
     auto K2 = [&]() -> int {                                                                 // :93/:160  v = A y ; r0.v
         const Fin f = this->fin_for(0, partB, nullptr, GS);
         if constexpr (std::is_same<T, double>::value && std::is_same<V, double>::value) {
@@ -569,16 +591,17 @@ int BicgStab<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T>
                 this->mark_step(2 | 1);      // (its dot operand is r0)
                 std::swap(p, palt); y = p;   // p' lives in the other buffer
                 std::swap(v, t);             // v' was written where t was
-                return this->red1(partB, GS, 0, &qB);
+                return this->handoff(0, GS, partB, &qB);
             }
         }
         SPRS_TRY(this->spmv(y, v, 1, r0, partB, nullptr, d_status, false, &f));
-        return this->red1(partB, GS, 0, &qB);
+        return this->handoff(0, GS, partB, &qB);
     };
     auto K3 = [&](int check) -> int {
         if (fuse) { pend_k3 = check; return (int)SPRS_OK; }     // formed by the next K4
-        if (pc) return launch_fused<T>(c, n, G, cw, BicgK3<T, V, true>{d_state, qB.p, qB.P, check, v, r, dinv, z, T(), qB.tag, this->mb_timeout()});
-        return launch_fused<T>(c, n, G, cw, BicgK3<T, V, false>{d_state, qB.p, qB.P, check, v, r, dinv, z, T(), qB.tag, this->mb_timeout()});
+        return dispatch_bool(pc, [&](auto pc_tag) {
+            return launch_fused<T>(c, n, G, cw, BicgK3<T, V, decltype(pc_tag)::value>{d_state, qB.p, qB.P, check, v, r, dinv, z, T(), qB.tag, this->mb_timeout()});
+        });
     };
     auto K4 = [&]() -> int {                                                                 // :104/:175 t = A s ; t.t, t.r
         const Fin f = this->fin_for(1, partTT, partTR, GS);
@@ -590,32 +613,28 @@ int BicgStab<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T>
                 this->stats.fused_k4 += 1;
                 this->mark_step(4);
                 s_pending = true;            // s was formed on the fly and not stored: K5 forms it again from r and v
-                return this->red2(partTT, partTR, GS, 1, &qTT, &qTR);
+                return this->handoff(1, GS, partTT, &qTT, partTR, &qTR);
             }
         }
         SPRS_TRY(this->spmv(pc ? z : r, t, 2, r, partTT, partTR, d_status, false, &f));
-        return this->red2(partTT, partTR, GS, 1, &qTT, &qTR);
+        return this->handoff(1, GS, partTT, &qTT, partTR, &qTR);
     };
     auto K5 = [&]() -> int {
         const Fin f = this->fin_for(3, partN, partRho, G);
-        if (s_pending) {
-            s_pending = false;
-            SPRS_TRY(launch_fused<T>(c, n, G, cw, BicgK5<T, false, true>{d_state, qTT.p, qTR.p, qTT.P, y, z, t, r0, x, r, partN, partRho, f, T(), T(), T(), 0.0, T(), qTT.tag, this->mb_timeout(), v}));
-            return this->redDT(partN, partRho, G, 3, &qN, &qRho);
-        }
-        if (pc) SPRS_TRY(launch_fused<T>(c, n, G, cw, BicgK5<T, true>{d_state, qTT.p, qTR.p, qTT.P, y, z, t, r0, x, r, partN, partRho, f, T(), T(), T(), 0.0, T(), qTT.tag, this->mb_timeout()}));
-        else SPRS_TRY(launch_fused<T>(c, n, G, cw, BicgK5<T, false>{d_state, qTT.p, qTR.p, qTT.P, y, z, t, r0, x, r, partN, partRho, f, T(), T(), T(), 0.0, T(), qTT.tag, this->mb_timeout()}));
-        return this->redDT(partN, partRho, G, 3, &qN, &qRho);
+        auto k5 = [&](auto pc_tag, auto sv_tag) {
+            constexpr bool PC = decltype(pc_tag)::value, SV = decltype(sv_tag)::value;
+            return launch_fused<T>(c, n, G, cw, BicgK5<T, PC, SV>{d_state, qTT.p, qTR.p, qTT.P, y, z, t, r0, x, r, partN, partRho, f, T(), T(), T(), 0.0, T(), qTT.tag, this->mb_timeout(), SV ? v : nullptr});
+        };
+        if (s_pending) SPRS_TRY(k5(std::false_type{}, std::true_type{}));      // (only ever without a preconditioner)
+        else SPRS_TRY(dispatch_bool(pc, [&](auto pc_tag) { return k5(pc_tag, std::false_type{}); }));
+        s_pending = false;
+        return this->handoff(3, G, partN, &qN, partRho, &qRho);
     };
     auto K1 = [&](int mode) -> int {
         if (fuse) { pend_k1 = mode; return (int)SPRS_OK; }      // formed by the next K2
-        if (pc) return launch_fused<T>(c, n, G, cw, BicgK1<T, V, true>{d_state, qN.p, qRho.p, qN.P, mode, v, r, p, dinv, y, T(), T(), qN.tag, this->mb_timeout()});
-        return launch_fused<T>(c, n, G, cw, BicgK1<T, V, false>{d_state, qN.p, qRho.p, qN.P, mode, v, r, p, dinv, y, T(), T(), qN.tag, this->mb_timeout()});
-    };
-    auto fetch = [&]() -> int {
-        SPRS_HIP_TRY(c, hipMemcpyAsync(&H, d_state, sizeof(H), hipMemcpyDeviceToHost, c->stream));
-        SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        return (int)SPRS_OK;
+        return dispatch_bool(pc, [&](auto pc_tag) {
+            return launch_fused<T>(c, n, G, cw, BicgK1<T, V, decltype(pc_tag)::value>{d_state, qN.p, qRho.p, qN.P, mode, v, r, p, dinv, y, T(), T(), qN.tag, this->mb_timeout()});
+        });
     };
 
     // ---- unrolled first iteration (:87-120 / :258-293)
@@ -628,12 +647,12 @@ int BicgStab<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T>
     SPRS_TRY(K2()); SPRS_TRY(K3(0)); SPRS_TRY(K4()); SPRS_TRY(K5());
     const bool tracing = this->trace != nullptr;
     if (tracing) {
-        SPRS_TRY(fetch());
+        SPRS_TRY(state.fetch());
         this->trace_row(0.0, r0_norm, H.rho, H.alpha, H.w);
     }
 
     // ---- main loop (:122-197)
-    const size_t poll = tracing ? 1 : (size_t)(c->poll < 1 ? 1 : c->poll);
+    const size_t poll = this->poll_interval();
     size_t its = 1, since_poll = 0;
     int resume_mode = 0;
     while (true) {
@@ -645,7 +664,7 @@ int BicgStab<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T>
         }
         if (done_enqueue || since_poll >= poll) {
             since_poll = 0;
-            SPRS_TRY(fetch());
+            SPRS_TRY(state.fetch());
             if (H.status == ST_CONVERGED) {                                 // :124-126
                 *its_out = (size_t)H.its; *res_out = H.r_norm / rhs_norm;
                 return SPRS_OK;
@@ -654,10 +673,7 @@ int BicgStab<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T>
                 *its_out = (size_t)H.its;
                 return SPRS_BREAKDOWN;
             }
-            if (H.status == ST_COMM_TIMEOUT) {
-                snprintf(c->err, sizeof(c->err), "a peer's hand-off did not reach this rank's mailbox within %d ms (p2p_timeout_ms)", c->p2p_timeout_ms);
-                return SPRS_ERR_RCCL;
-            }
+            if (H.status == ST_COMM_TIMEOUT) return this->comm_timeout();
             if (H.status == ST_RESTART) {                                   // :131-145, executed at iteration H.its
                 // K2 / K4 of the iterations enqueued from the requesting one on returned at their first instruction
                 this->profile_discard_last(2 * (its - (size_t)H.its));
@@ -674,7 +690,7 @@ int BicgStab<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T>
                 H.rho = sfromr<T>(rn * rn);                                         // :143
                 H.r0_norm_tol = sre(H.rho) * seps<Real<T>>() * seps<Real<T>>();                             // :144
                 H.status = ST_RUNNING;
-                SPRS_HIP_TRY(c, hipMemcpyAsync(d_state, &H, sizeof(H), hipMemcpyHostToDevice, c->stream));
+                SPRS_TRY(state.push());
                 its = (size_t)H.its;       // every kernel after the request was a no-op: redo from here
                 resume_mode = 1;
                 continue;
@@ -697,8 +713,9 @@ int BicgStab<T>::run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter,
     const bool pc = dinv != nullptr;
     *its_out = 0; *res_out = 0.0;
     Real<T> rhs_norm = 0.0;
-    SPRS_TRY(this->norm2(rhs, &rhs_norm));
-    if (rhs_norm <= seps<Real<T>>()) { SPRS_TRY(dzero(c, x, n)); *res_out = rhs_norm; return SPRS_OK; }
+    bool zero;
+    SPRS_TRY(this->zero_rhs(rhs, x, &rhs_norm, res_out, &zero));
+    if (zero) return SPRS_OK;
     const Real<T> tol2 = tol * rhs_norm;
     T *r = this->vec(0), *r0 = this->vec(1), *y = this->vec(2);
     T *p = pc ? this->vec(3) : y;
@@ -774,41 +791,9 @@ int BicgStab<T>::run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter,
 }
 
 template <class T>
-static int check_diag(const sprs_diag *P, size_t n) {
-    if (!P) return SPRS_OK;
-    if (P->n != n) return SPRS_DIM_MISMATCH;
-    if (P->t_dtype != dtype_of<T>::value) return SPRS_INVALID_ARGUMENT;
-    return SPRS_OK;
-}
-
-template <class T>
 int BicgStab<T>::solve_dev(const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter,
                            Real<T> tol, size_t *its_out, Real<T> *res_out) {
-    size_t its_dummy; Real<T> res_dummy;
-    if (!its_out) its_out = &its_dummy;
-    if (!res_out) res_out = &res_dummy;
-    if (rhs_len != this->n) return SPRS_INCOMPATIBLE_RHS_SIZE;             // :44-48
-    if (x_len != this->n) return SPRS_INCOMPATIBLE_X_SIZE;                 // :49-53
-    SPRS_TRY(check_diag<T>(P, this->n));
-    SPRS_TRY(this->begin_solve());
-    int st;
-    const bool lit = this->mode == 1;
-    if (P && P->v_complex) {
-        if constexpr (is_complex<T>::value) {
-            const T *d = (const T *)P->dinv;
-            st = lit ? run_literal<T>(d, rhs, x, max_iter, tol, its_out, res_out)
-                     : run<T>(d, rhs, x, max_iter, tol, its_out, res_out);
-        } else {
-            return SPRS_INVALID_ARGUMENT;
-        }
-    } else {
-        const Real<T> *d = P ? (const Real<T> *)P->dinv : nullptr;
-        st = lit ? run_literal<Real<T>>(d, rhs, x, max_iter, tol, its_out, res_out)
-                 : run<Real<T>>(d, rhs, x, max_iter, tol, its_out, res_out);
-    }
-    if (st >= SPRS_ERR_HIP) return st;
-    SPRS_TRY(this->end_solve());
-    return st;
+    return KrylovBase<T>::solve(*this, false, P, rhs, rhs_len, x, x_len, max_iter, tol, its_out, res_out);
 }
 
 // ======================================================================= MINRES / CSMINRES host
@@ -816,16 +801,7 @@ template <class T>
 int MinRes<T>::create(const sprs_csr *A, size_t size, bool saunders_) {
     saunders = saunders_;
     SPRS_TRY(this->init(A, size, 8));   // minres.rs:24 workspace 8n (cs_minres.rs:22 uses 7n)
-    SPRS_HIP_TRY(this->ctx, hipMalloc((void **)&d_state, sizeof(MinresDev<T>)));
-    SPRS_HIP_TRY(this->ctx, hipHostMalloc((void **)&h_state, sizeof(MinresDev<T>), hipHostMallocDefault));
-    return SPRS_OK;
-}
-template <class T>
-void MinRes<T>::destroy() {
-    if (d_state) (void)hipFree(d_state);
-    if (h_state) (void)hipHostFree(h_state);
-    d_state = h_state = nullptr;
-    KrylovBase<T>::destroy();
+    return state.create(this->ctx);
 }
 
 template <class T>
@@ -838,8 +814,9 @@ int MinRes<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> t
     *its_out = 0; *res_out = 0.0;
 
     Real<T> rhs_norm = 0.0;
-    SPRS_TRY(this->norm2(rhs, &rhs_norm));                          // :51
-    if (rhs_norm <= seps<Real<T>>()) { SPRS_TRY(dzero(c, x, n)); *res_out = rhs_norm; return SPRS_OK; }   // :52-56
+    bool zero;
+    SPRS_TRY(this->zero_rhs(rhs, x, &rhs_norm, res_out, &zero));            // :51-56
+    if (zero) return SPRS_OK;
     const Real<T> threshold = tol * rhs_norm;                                // :57
 
     T *v_old = this->vec(0), *v_new = this->vec(1), *v = this->vec(2);      // :68-70
@@ -870,7 +847,8 @@ int MinRes<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> t
     }
     SPRS_TRY(dzero(c, v, n)); SPRS_TRY(dzero(c, p_old, n)); SPRS_TRY(dzero(c, p, n));   // :86-88
 
-    MinresDev<T> &H = *h_state;
+    MinresDev<T> &H = *state.host;
+    MinresDev<T> *const d_state = state.dev;
     memset(&H, 0, sizeof(H));
     MinresState<T> &S0 = H.st[0];
     S0.c = sone<T>(); S0.c_old = sone<T>(); S0.eta = sone<T>(); S0.alpha = szero<T>();   // :60-64
@@ -879,7 +857,7 @@ int MinRes<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> t
     S0.res_norm = res_norm; S0.threshold = threshold;
     H.st[1] = S0;
     H.its = 0; H.status = ST_RUNNING;
-    SPRS_HIP_TRY(c, hipMemcpyAsync(d_state, &H, sizeof(H), hipMemcpyHostToDevice, c->stream));
+    SPRS_TRY(state.push());
     const int *d_status = &d_state->status;
 
     const int G = this->ew_grid();
@@ -887,13 +865,8 @@ int MinRes<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> t
     const int GS = spmv_num_partials(this->A);
     T *partAlpha = this->pslot(0), *partBeta2 = this->pslot(1);
 
-    auto fetch = [&]() -> int {
-        SPRS_HIP_TRY(c, hipMemcpyAsync(&H, d_state, sizeof(H), hipMemcpyDeviceToHost, c->stream));
-        SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        return (int)SPRS_OK;
-    };
     const bool tracing = this->trace != nullptr;
-    const size_t poll = tracing ? 1 : (size_t)(c->poll < 1 ? 1 : c->poll);
+    const size_t poll = this->poll_interval();
     size_t since_poll = 0;
 
     // ---- M3 deferred (no preconditioner, one GPU, the lane-per-row kernels of the compressed streams — cfg 3, cfg 4; knob
@@ -925,8 +898,8 @@ int MinRes<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> t
             const T *q = pc ? w : v;                                         // operand of A and source of p
             // M1: v_new = A q (CSMINRES: A conj(q)) ; alpha = conj(q).v_new   (:116 / :271 / cs:99-103)
             const Fin fA = this->fin_for(0, partAlpha, nullptr, GS);
-            typename KrylovBase<T>::PartT qA, qB2{partBeta2, G};
-            typename KrylovBase<T>::PartD qBt{pbeta[cur_pb], G};
+            Part<T> qA, qB2{partBeta2, G};
+            Part<Real<T>> qBt{pbeta[cur_pb], G};
             bool iteration_done = false;
             if constexpr (std::is_same<T, double>::value || std::is_same<T, cplx>::value) {
                 if (deferred) {
@@ -942,27 +915,22 @@ int MinRes<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> t
                         this->mark_step(2);
                         return launch_fused<T>(c, n, G, cw, MinresM23<T, SAU>{m3, partAlpha, GS, v, v_new, pbeta[cur_pb ^ 1], T(), T(), T(), 0.0});
                     };
-                    int st;
-                    if (sau) {
-                        if constexpr (is_complex<T>::value) st = two_launches(std::true_type{});
-                        else st = SPRS_INVALID_ARGUMENT;
-                    } else st = two_launches(std::false_type{});
-                    SPRS_TRY(st);
+                    if constexpr (is_complex<T>::value) SPRS_TRY(dispatch_bool(sau, two_launches));
+                    else SPRS_TRY(two_launches(std::false_type{}));      // (sau is false on real data, which has no conjugating kernels)
                     cur_pb ^= 1;
-                    qBt = typename KrylovBase<T>::PartD{pbeta[cur_pb], G};
+                    qBt = Part<Real<T>>{pbeta[cur_pb], G};
                     iteration_done = true;
                 }
             }
             if (!iteration_done) {
                 SPRS_TRY(this->spmv(q, v_new, 1, q, partAlpha, nullptr, d_status, sau, &fA));
-                SPRS_TRY(this->red1(partAlpha, GS, 0, &qA));
-                if (pc) {
-                    SPRS_TRY(launch_fused<T>(c, n, G, cw, MinresM2<T, V, true>{d_state, par, qA.p, qA.P, v_old, v, v_new, dinv, w_new, pbeta[cur_pb], partBeta2, this->fin_for(1, partBeta2, nullptr, G), T(), T(), 0.0, T(), qA.tag, this->mb_timeout()}));
-                    SPRS_TRY(this->red1(partBeta2, G, 1, &qB2));
-                } else {
-                    SPRS_TRY(launch_fused<T>(c, n, G, cw, MinresM2<T, V, false>{d_state, par, qA.p, qA.P, v_old, v, v_new, dinv, w_new, pbeta[cur_pb], partBeta2, this->fin_for(1, pbeta[cur_pb], nullptr, G), T(), T(), 0.0, T(), qA.tag, this->mb_timeout()}));
-                    SPRS_TRY(this->redD1(pbeta[cur_pb], G, 1, &qBt));
-                }
+                SPRS_TRY(this->handoff(0, GS, partAlpha, &qA));
+                // beta_new^2 comes from conj(v_new).w_new (partBeta2) with a preconditioner, else from |v_new|^2 (pbeta)
+                const Fin fB = this->fin_for(1, pc ? (const void *)partBeta2 : (const void *)pbeta[cur_pb], nullptr, G);
+                SPRS_TRY(dispatch_bool(pc, [&](auto pc_tag) {
+                    return launch_fused<T>(c, n, G, cw, MinresM2<T, V, decltype(pc_tag)::value>{d_state, par, qA.p, qA.P, v_old, v, v_new, dinv, w_new, pbeta[cur_pb], partBeta2, fB, T(), T(), 0.0, T(), qA.tag, this->mb_timeout()});
+                }));
+                SPRS_TRY(pc ? this->handoff(1, G, partBeta2, &qB2) : this->handoff(1, G, pbeta[cur_pb], &qBt));
             }
             { T *tp = p_oold; p_oold = p_old; p_old = p; p = tp; }           // :151-154
             if (will_defer) {
@@ -977,16 +945,15 @@ int MinRes<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> t
                     if (!PCF && v_raw) { m3.q_raw = 1; m3.q_back = v; }     // a raw v: used scaled, and left normalised for the plain kernels
                     return launch_fused<T>(c, n, G, cw, m3);
                 };
-                if (pc) SPRS_TRY(m3_alone(std::true_type{}, std::false_type{}));
-                else if (sau) SPRS_TRY(m3_alone(std::false_type{}, std::true_type{}));
-                else SPRS_TRY(m3_alone(std::false_type{}, std::false_type{}));
+                if (pc) SPRS_TRY(m3_alone(std::true_type{}, std::false_type{}));        // (CSMINRES takes no preconditioner)
+                else SPRS_TRY(dispatch_bool(sau, [&](auto sau_tag) { return m3_alone(std::false_type{}, sau_tag); }));
                 v_raw = false;
             }
             ++since_poll;
         }
         if (done_enqueue || since_poll >= poll) {
             since_poll = 0;
-            SPRS_TRY(fetch());
+            SPRS_TRY(state.fetch());
             if ((H.status & 15) == ST_CONVERGED) {                          // :165-167 (0-based its; the word carries the iteration, MinresM3)
                 *its_out = (size_t)H.its;
                 *res_out = H.st[(H.its + 1) & 1].res_norm / rhs_norm;
@@ -1001,10 +968,7 @@ int MinRes<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> t
                 *its_out = (size_t)H.its; *res_out = H.st[H.its & 1].pc_re;
                 return SPRS_INVALID_PRECOND;
             }
-            if (H.status == ST_COMM_TIMEOUT) {
-                snprintf(c->err, sizeof(c->err), "a peer's hand-off did not reach this rank's mailbox within %d ms (p2p_timeout_ms)", c->p2p_timeout_ms);
-                return SPRS_ERR_RCCL;
-            }
+            if (H.status == ST_COMM_TIMEOUT) return this->comm_timeout();
             if (done_enqueue) break;
             if (tracing) {
                 const MinresState<T> &N = H.st[(its + 1) & 1];
@@ -1027,8 +991,9 @@ int MinRes<T>::run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter, R
     const bool sau = saunders;
     *its_out = 0; *res_out = 0.0;
     Real<T> rhs_norm = 0.0;
-    SPRS_TRY(this->norm2(rhs, &rhs_norm));
-    if (rhs_norm <= seps<Real<T>>()) { SPRS_TRY(dzero(c, x, n)); *res_out = rhs_norm; return SPRS_OK; }
+    bool zero;
+    SPRS_TRY(this->zero_rhs(rhs, x, &rhs_norm, res_out, &zero));
+    if (zero) return SPRS_OK;
     const Real<T> threshold = tol * rhs_norm;
     T cc = sone<T>(), c_old = sone<T>(), eta = sone<T>();
     Real<T> s = 0.0, s_old = 0.0;
@@ -1117,32 +1082,7 @@ int MinRes<T>::run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter, R
 template <class T>
 int MinRes<T>::solve_dev(const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter,
                          Real<T> tol, size_t *its_out, Real<T> *res_out) {
-    size_t its_dummy; Real<T> res_dummy;
-    if (!its_out) its_out = &its_dummy;
-    if (!res_out) res_out = &res_dummy;
-    if (rhs_len != this->n) return SPRS_INCOMPATIBLE_RHS_SIZE;             // minres.rs:40-44
-    if (x_len != this->n) return SPRS_INCOMPATIBLE_X_SIZE;                 // :45-49
-    if (saunders && P) return SPRS_INVALID_ARGUMENT;                       // CSMinRes has no precond_solve
-    SPRS_TRY(check_diag<T>(P, this->n));
-    SPRS_TRY(this->begin_solve());
-    int st;
-    const bool lit = this->mode == 1;
-    if (P && P->v_complex) {
-        if constexpr (is_complex<T>::value) {
-            const T *d = (const T *)P->dinv;
-            st = lit ? run_literal<T>(d, rhs, x, max_iter, tol, its_out, res_out)
-                     : run<T>(d, rhs, x, max_iter, tol, its_out, res_out);
-        } else {
-            return SPRS_INVALID_ARGUMENT;
-        }
-    } else {
-        const Real<T> *d = P ? (const Real<T> *)P->dinv : nullptr;
-        st = lit ? run_literal<Real<T>>(d, rhs, x, max_iter, tol, its_out, res_out)
-                 : run<Real<T>>(d, rhs, x, max_iter, tol, its_out, res_out);
-    }
-    if (st >= SPRS_ERR_HIP) return st;
-    SPRS_TRY(this->end_solve());
-    return st;
+    return KrylovBase<T>::solve(*this, saunders, P, rhs, rhs_len, x, x_len, max_iter, tol, its_out, res_out);
 }
 
 // ======================================================================= CG host
@@ -1156,32 +1096,19 @@ int MinRes<T>::solve_dev(const sprs_diag *P, const T *rhs, size_t rhs_len, T *x,
 template <class T>
 int Cg<T>::create(const sprs_csr *A, size_t size) {
     SPRS_TRY(this->init(A, size, 4));   // r, p, q, z (z only with a preconditioner)
-    this->no_p2p = true;                // hand-offs through fin_for + red1 / redDT + the all-reduce only
-    SPRS_HIP_TRY(this->ctx, hipMalloc((void **)&d_state, sizeof(CgState<T>)));
-    SPRS_HIP_TRY(this->ctx, hipHostMalloc((void **)&h_state, sizeof(CgState<T>), hipHostMallocDefault));
-    return SPRS_OK;
-}
-template <class T>
-void Cg<T>::destroy() {
-    if (d_state) (void)hipFree(d_state);
-    if (h_state) (void)hipHostFree(h_state);
-    d_state = h_state = nullptr;
-    KrylovBase<T>::destroy();
+    this->no_p2p = true;                // hand-offs through fin_for + handoff + the all-reduce only
+    return state.create(this->ctx);
 }
 
 template <class T>
 template <class V>
-int Cg<T>::start(const V *dinv, const T *rhs, T *x, Real<T> tol, Real<T> *rhs_norm, Real<T> *tol2, T *rho, int *done, Real<T> *res_out) {
+int Cg<T>::start(const V *dinv, const T *rhs, T *x, Real<T> tol, Real<T> *rhs_norm, Real<T> *tol2, T *rho, bool *done, Real<T> *res_out) {
     sprs_ctx *c = this->ctx;
     const size_t n = this->n;
     T *r = this->vec(0), *p = this->vec(1), *z = dinv ? this->vec(3) : r;
-    *done = 1;
-    SPRS_TRY(this->norm2(rhs, rhs_norm));
-    if (*rhs_norm <= seps<Real<T>>()) {                                     // a zero right-hand side answers x = 0
-        SPRS_TRY(dzero(c, x, n));
-        *res_out = *rhs_norm;
-        return SPRS_OK;
-    }
+    SPRS_TRY(this->zero_rhs(rhs, x, rhs_norm, res_out, done));
+    if (*done) return SPRS_OK;
+    *done = true;
     *tol2 = tol * *rhs_norm;
     SPRS_TRY(this->spmv(x, r, 0, nullptr, nullptr, nullptr, nullptr));      // r = A x
     SPRS_TRY(launch_axpby<T>(c, n, sone<T>(), rhs, sneg(sone<T>()), r));    // r = rhs*1 + r*(-1)
@@ -1191,7 +1118,7 @@ int Cg<T>::start(const V *dinv, const T *rhs, T *x, Real<T> tol, Real<T> *rhs_no
     if (dinv) SPRS_TRY((launch_diag_apply<T, V>(c, n, dinv, r, z)));        // z = M^-1 r
     SPRS_TRY(dcopy(c, p, z, n));                                            // p = z
     SPRS_TRY(this->cdot(r, z, rho));                                        // rho = conj(r).z
-    *done = 0;
+    *done = false;
     return SPRS_OK;
 }
 
@@ -1206,15 +1133,16 @@ int Cg<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, 
 
     Real<T> rhs_norm = 0.0, tol2 = 0.0;
     T rho = szero<T>();
-    int done = 0;
+    bool done;
     SPRS_TRY(start<V>(dinv, rhs, x, tol, &rhs_norm, &tol2, &rho, &done, res_out));
     if (done) return SPRS_OK;
 
-    CgState<T> &H = *h_state;
+    CgState<T> &H = *state.host;
+    CgState<T> *const d_state = state.dev;
     memset(&H, 0, sizeof(H));
     H.rho = rho; H.rho_prev = rho; H.tol2 = tol2;
     H.its = 0; H.status = ST_RUNNING;
-    SPRS_HIP_TRY(c, hipMemcpyAsync(d_state, &H, sizeof(H), hipMemcpyHostToDevice, c->stream));
+    SPRS_TRY(state.push());
     const int *d_status = &d_state->status;
 
     const int G = this->ew_grid();
@@ -1222,32 +1150,29 @@ int Cg<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, 
     const int GS = spmv_num_partials(this->A);
     Real<T> *partN = this->dslot(0);
     T *partRZ = this->pslot(0), *partPQ = this->pslot(1);
-    typename KrylovBase<T>::PartT qPQ{partPQ, GS}, qRZ{partRZ, G};
-    typename KrylovBase<T>::PartD qN{partN, G};
+    Part<T> qPQ{partPQ, GS}, qRZ{partRZ, G};
+    Part<Real<T>> qN{partN, G};
 
     auto CA = [&]() -> int {                                                // q = A p ; conj(p).q
         const Fin f = this->fin_for(0, partPQ, nullptr, GS);
         SPRS_TRY(this->spmv(p, q, 1, p, partPQ, nullptr, d_status, false, &f));
-        return this->red1(partPQ, GS, 0, &qPQ);
+        return this->handoff(0, GS, partPQ, &qPQ);
     };
     auto KB = [&]() -> int {
         const Fin f = this->fin_for(1, partN, partRZ, G);
-        if (pc) SPRS_TRY(launch_fused<T>(c, n, G, cw, CgKB<T, V, true>{d_state, qPQ.p, qPQ.P, p, q, x, r, dinv, z, partN, partRZ, f, T(), T(), 0.0, T()}));
-        else SPRS_TRY(launch_fused<T>(c, n, G, cw, CgKB<T, V, false>{d_state, qPQ.p, qPQ.P, p, q, x, r, dinv, z, partN, partRZ, f, T(), T(), 0.0, T()}));
-        return this->redDT(partN, partRZ, G, 1, &qN, &qRZ);
+        SPRS_TRY(dispatch_bool(pc, [&](auto pc_tag) {
+            return launch_fused<T>(c, n, G, cw, CgKB<T, V, decltype(pc_tag)::value>{d_state, qPQ.p, qPQ.P, p, q, x, r, dinv, z, partN, partRZ, f, T(), T(), 0.0, T()});
+        }));
+        return this->handoff(1, G, partN, &qN, partRZ, &qRZ);
     };
     auto KC = [&]() -> int {
-        if (pc) return launch_fused<T>(c, n, G, cw, CgKC<T, true>{d_state, qN.p, qRZ.p, qN.P, z, p, T(), T()});
-        return launch_fused<T>(c, n, G, cw, CgKC<T, false>{d_state, qN.p, qRZ.p, qN.P, z, p, T(), T()});
-    };
-    auto fetch = [&]() -> int {
-        SPRS_HIP_TRY(c, hipMemcpyAsync(&H, d_state, sizeof(H), hipMemcpyDeviceToHost, c->stream));
-        SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        return (int)SPRS_OK;
+        return dispatch_bool(pc, [&](auto pc_tag) {
+            return launch_fused<T>(c, n, G, cw, CgKC<T, decltype(pc_tag)::value>{d_state, qN.p, qRZ.p, qN.P, z, p, T(), T()});
+        });
     };
 
     const bool tracing = this->trace != nullptr;
-    const size_t poll = tracing ? 1 : (size_t)(c->poll < 1 ? 1 : c->poll);
+    const size_t poll = this->poll_interval();
     size_t its = 0, since_poll = 0;
     while (true) {
         const bool done_enqueue = its >= max_iter;
@@ -1257,7 +1182,7 @@ int Cg<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, 
         }
         if (done_enqueue || since_poll >= poll) {
             since_poll = 0;
-            SPRS_TRY(fetch());
+            SPRS_TRY(state.fetch());
             if (H.status != ST_RUNNING && its > (size_t)H.its) this->profile_discard_last(its - (size_t)H.its - (H.status == ST_CONVERGED ? 0 : 1));
             if (H.status == ST_CONVERGED) {
                 *its_out = (size_t)H.its; *res_out = H.r_norm / rhs_norm;
@@ -1290,7 +1215,7 @@ int Cg<T>::run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<
     T *r = this->vec(0), *p = this->vec(1), *q = this->vec(2), *z = pc ? this->vec(3) : r;
     Real<T> rhs_norm = 0.0, tol2 = 0.0;
     T rho = szero<T>();
-    int done = 0;
+    bool done;
     SPRS_TRY(start<V>(dinv, rhs, x, tol, &rhs_norm, &tol2, &rho, &done, res_out));
     if (done) return SPRS_OK;
     for (size_t its = 0; its < max_iter; ++its) {
@@ -1320,31 +1245,7 @@ int Cg<T>::run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<
 template <class T>
 int Cg<T>::solve_dev(const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
                      size_t *its_out, Real<T> *res_out) {
-    size_t its_dummy; Real<T> res_dummy;
-    if (!its_out) its_out = &its_dummy;
-    if (!res_out) res_out = &res_dummy;
-    if (rhs_len != this->n) return SPRS_INCOMPATIBLE_RHS_SIZE;
-    if (x_len != this->n) return SPRS_INCOMPATIBLE_X_SIZE;
-    SPRS_TRY(check_diag<T>(P, this->n));
-    SPRS_TRY(this->begin_solve());
-    int st;
-    const bool lit = this->mode == 1;
-    if (P && P->v_complex) {
-        if constexpr (is_complex<T>::value) {
-            const T *d = (const T *)P->dinv;
-            st = lit ? run_literal<T>(d, rhs, x, max_iter, tol, its_out, res_out)
-                     : run<T>(d, rhs, x, max_iter, tol, its_out, res_out);
-        } else {
-            return SPRS_INVALID_ARGUMENT;
-        }
-    } else {
-        const Real<T> *d = P ? (const Real<T> *)P->dinv : nullptr;
-        st = lit ? run_literal<Real<T>>(d, rhs, x, max_iter, tol, its_out, res_out)
-                 : run<Real<T>>(d, rhs, x, max_iter, tol, its_out, res_out);
-    }
-    if (st >= SPRS_ERR_HIP) return st;
-    SPRS_TRY(this->end_solve());
-    return st;
+    return KrylovBase<T>::solve(*this, false, P, rhs, rhs_len, x, x_len, max_iter, tol, its_out, res_out);
 }
 
 template class KrylovBase<double>;

@@ -39,6 +39,44 @@ struct SolverStats {
     int64_t steps = 0;                    // SpMV-class steps of the solve, timed or not
 };
 
+// A solver's scalar state: the kernels' copy in HBM and the host's view of it in pinned memory.
+template <class S>
+struct StateBlock {
+    sprs_ctx *ctx = nullptr;
+    S *dev = nullptr, *host = nullptr;
+    int create(sprs_ctx *c) {
+        ctx = c;
+        SPRS_HIP_TRY(ctx, hipMalloc((void **)&dev, sizeof(S)));
+        SPRS_HIP_TRY(ctx, hipHostMalloc((void **)&host, sizeof(S), hipHostMallocDefault));
+        return SPRS_OK;
+    }
+    void destroy() {
+        if (dev) (void)hipFree(dev);
+        if (host) (void)hipHostFree(host);
+        dev = host = nullptr;
+    }
+    int push() {    // host -> device, in stream order
+        SPRS_HIP_TRY(ctx, hipMemcpyAsync(dev, host, sizeof(S), hipMemcpyHostToDevice, ctx->stream));
+        return SPRS_OK;
+    }
+    int fetch() {   // device -> host, and wait for it
+        SPRS_HIP_TRY(ctx, hipMemcpyAsync(host, dev, sizeof(S), hipMemcpyDeviceToHost, ctx->stream));
+        SPRS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return SPRS_OK;
+    }
+};
+
+// The partials of one reduction as their consumer kernel finds them (KrylovBase::handoff).
+template <class U>
+struct Part { const U *p; int P; unsigned int tag = 0; };   // tag != 0: p = this rank's mailbox entries of the hand-off, P = world
+
+// One profiled SpMV-class step (a pair of events).  Pair 0 brackets the whole solve.
+struct EvPair {
+    size_t call = 0;            // the step it brackets
+    unsigned char kind = 0;     // 1 = dot operand is not the input vector, 2 = fused K2, 4 = fused K4
+    bool noop = false;          // launched after a restart request, i.e. returned at once — not a measurement
+};
+
 template <class T>
 class KrylovBase {
    public:
@@ -56,13 +94,11 @@ class KrylovBase {
     int profile = 0;             // 0 off; 1: every SpMV launch between HIP events; k >= 2: one pair of consecutive launches in k (a sample:
                                  // the events cost ~6 us per launch, krylov.hip profiled())
     size_t prof_calls = 0;       // SpMV-class steps of this solve so far (sampled or not)
-    std::vector<size_t> ev_call; // per event pair: the step it brackets
-    std::vector<unsigned char> ev_kind;   // per event pair: 1 = dot operand is not the input vector, 2 = fused K2, 4 = fused K4
-    long last_pair = -1;         // the event pair of the last step (-1: it carried none)
-    void mark_step(unsigned char kind) { if (last_pair >= 0) ev_kind[(size_t)last_pair] |= kind; }
     std::vector<hipEvent_t> ev;
     size_t ev_used = 0;
-    std::vector<char> ev_noop;   // per profiled SpMV (event pair): launched after a restart request, i.e. returned at once — not a measurement
+    std::vector<EvPair> ev_pair; // one per pair of events in use: ev_pair[k] describes ev[2k], ev[2k + 1]
+    long last_pair = -1;         // the event pair of the last step (-1: it carried none)
+    void mark_step(unsigned char kind) { if (last_pair >= 0) ev_pair[(size_t)last_pair].kind |= kind; }
     SolverStats stats;
     // distributed operator (A->dist): all-reduced scalars live in `red`, 16-byte slots
     double *red = nullptr;       // device, 32 doubles
@@ -82,25 +118,27 @@ class KrylovBase {
     int begin_solve();
     int end_solve();
     void trace_row(double a0, double a1, T b, T c, T d);
-    // host-slice wrapper around a device solve
-    template <class F>
-    int solve_host(const T *rhs, size_t rhs_len, T *x, size_t x_len, F &&dev_solve);
+    // What the solvers' solve_dev share: argument defaults, size checks, the preconditioner's checks and element type, the
+    // literal-or-fused choice.  S supplies run<V> / run_literal<V>; no_precond: S takes no preconditioner (CSMINRES).
+    template <class S>
+    static int solve(S &s, bool no_precond, const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter,
+                     Real<T> tol, size_t *its_out, Real<T> *res_out);
+    // |rhs|; a zero right-hand side answers x = 0 (*zero = true: the solve is over, *res_out holds the norm)
+    int zero_rhs(const T *rhs, T *x, Real<T> *rhs_norm, Real<T> *res_out, bool *zero);
+    size_t poll_interval() const { return trace ? 1 : (size_t)(ctx->poll < 1 ? 1 : ctx->poll); }   // iterations between two reads of the status word
+    int comm_timeout();          // ST_COMM_TIMEOUT as the caller sees it: the error text and SPRS_ERR_RCCL
     int ew_grid() const;  // workgroups used by the fused element-wise kernels for this n
     sprs_comm *comm() const { return A->dist ? A->dist->comm : nullptr; }
     // Hand a producer's partials to its consumer kernel.  Single GPU: the consumer re-reduces the
     // P partials itself.  Distributed: the producer's last workgroup has reduced them into `red`
     // (fixed order; fin_for), these all-reduce over the ranks, and the consumer reads one value.
-    // `slot` picks a 16-byte cell of `red`.
-    struct PartT { const T *p; int P; unsigned int tag = 0; };            // tag != 0: p = this rank's mailbox entries of the hand-off, P = world
-    struct PartD { const Real<T> *p; int P; unsigned int tag = 0; };
+    // `slot` picks a 16-byte cell of `red`; a second value (b) travels in the cell after it.
     bool no_p2p = false;         // this solver's hand-offs always take the all-reduce (CG: it has no mailbox consumers)
     bool use_p2p() const { return !no_p2p && A->dist && A->dist->comm->p2p && ctx->p2p_allreduce != 0; }
     unsigned long long mb_timeout() const { return (unsigned long long)(ctx->p2p_timeout_ms < 1 ? 1 : ctx->p2p_timeout_ms) * 100000ull; }   // ticks of the 100 MHz wall clock
     const void *mbox_entries(int slot) const;    // this rank's mailbox at the CURRENT hand-off of `slot`
-    int red1(const T *a, int P, int slot, PartT *oa);
-    int red2(const T *a, const T *b, int P, int slot, PartT *oa, PartT *ob);
-    int redD1(const Real<T> *a, int P, int slot, PartD *oa);
-    int redDT(const Real<T> *a, const T *b, int P, int slot, PartD *oa, PartT *ob);
+    template <class U, class W = U>
+    int handoff(int slot, int P, const U *a, Part<U> *oa, const W *b = nullptr, Part<W> *ob = nullptr);
     int norm2(const T *x, Real<T> *out) { return norm2_host<T>(ctx, n, x, out, comm()); }
     int cdot(const T *x, const T *y, T *out) { return dot_host<T>(ctx, n, x, y, true, out, comm()); }
 };
@@ -108,13 +146,14 @@ class KrylovBase {
 template <class T>
 class BicgStab : public KrylovBase<T> {
    public:
-    BicgState<T> *d_state = nullptr, *h_state = nullptr;
+    StateBlock<BicgState<T>> state;
     int create(const sprs_csr *A, size_t size);
-    void destroy();
+    void destroy() { state.destroy(); KrylovBase<T>::destroy(); }
     int solve_dev(const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
                   size_t *its_out, Real<T> *res_out);
 
    private:
+    friend class KrylovBase<T>;
     template <class V>
     int run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
     template <class V>
@@ -124,14 +163,15 @@ class BicgStab : public KrylovBase<T> {
 template <class T>
 class MinRes : public KrylovBase<T> {
    public:
-    MinresDev<T> *d_state = nullptr, *h_state = nullptr;
+    StateBlock<MinresDev<T>> state;
     bool saunders = false;  // CSMINRES
     int create(const sprs_csr *A, size_t size, bool saunders_);
-    void destroy();
+    void destroy() { state.destroy(); KrylovBase<T>::destroy(); }
     int solve_dev(const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
                   size_t *its_out, Real<T> *res_out);
 
    private:
+    friend class KrylovBase<T>;
     template <class V>
     int run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
     template <class V>
@@ -142,57 +182,31 @@ class MinRes : public KrylovBase<T> {
 template <class T>
 class Cg : public KrylovBase<T> {
    public:
-    CgState<T> *d_state = nullptr, *h_state = nullptr;
+    StateBlock<CgState<T>> state;
     int create(const sprs_csr *A, size_t size);
-    void destroy();
+    void destroy() { state.destroy(); KrylovBase<T>::destroy(); }
     int solve_dev(const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
                   size_t *its_out, Real<T> *res_out);
 
    private:
+    friend class KrylovBase<T>;
     // the part both modes share: zero rhs, initial residual, z = M^-1 r, p = z, rho = conj(r).z; done = 1: answered already
     template <class V>
-    int start(const V *dinv, const T *rhs, T *x, Real<T> tol, Real<T> *rhs_norm, Real<T> *tol2, T *rho, int *done, Real<T> *res_out);
+    int start(const V *dinv, const T *rhs, T *x, Real<T> tol, Real<T> *rhs_norm, Real<T> *tol2, T *rho, bool *done, Real<T> *res_out);
     template <class V>
     int run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
     template <class V>
     int run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
 };
 
-template <class T>
-template <class F>
-int KrylovBase<T>::solve_host(const T *rhs, size_t rhs_len, T *x, size_t x_len, F &&dev_solve) {
-    // size checks first (bicg_stab.rs:44-53): nothing is copied on a mismatch
-    if (rhs_len != n) return SPRS_INCOMPATIBLE_RHS_SIZE;
-    if (x_len != n) return SPRS_INCOMPATIBLE_X_SIZE;
-    SPRS_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!rhs_buf) SPRS_HIP_TRY(ctx, hipMalloc((void **)&rhs_buf, sizeof(T) * stride));
-    if (!x_buf) SPRS_HIP_TRY(ctx, hipMalloc((void **)&x_buf, sizeof(T) * stride));
-    SPRS_HIP_TRY(ctx, hipMemcpyAsync(rhs_buf, rhs, sizeof(T) * n, hipMemcpyHostToDevice, ctx->stream));
-    SPRS_HIP_TRY(ctx, hipMemcpyAsync(x_buf, x, sizeof(T) * n, hipMemcpyHostToDevice, ctx->stream));
-    int st = dev_solve(rhs_buf, x_buf);
-    if (st >= SPRS_ERR_HIP) return st;
-    // x is in/out in the reference and is left modified on Err as well
-    SPRS_HIP_TRY(ctx, hipMemcpyAsync(x, x_buf, sizeof(T) * n, hipMemcpyDeviceToHost, ctx->stream));
-    SPRS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return st;
-}
-
 }  // namespace sprs
 
-// opaque C handles: type-erased over T
-struct sprs_bicgstab {
+// opaque C handles: type-erased over T, one layout
+struct sprs_solver_handle {
     int dtype;
     void *impl;
 };
-struct sprs_minres {
-    int dtype;
-    void *impl;
-};
-struct sprs_csminres {
-    int dtype;
-    void *impl;
-};
-struct sprs_cg {
-    int dtype;
-    void *impl;
-};
+struct sprs_bicgstab : sprs_solver_handle {};
+struct sprs_minres : sprs_solver_handle {};
+struct sprs_csminres : sprs_solver_handle {};
+struct sprs_cg : sprs_solver_handle {};
