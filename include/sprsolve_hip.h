@@ -54,6 +54,7 @@ typedef struct sprs_bicgstab sprs_bicgstab; /* BiCGStab<T,M>                 (bi
 typedef struct sprs_minres sprs_minres;     /* MinRes<T,M>                   (minres.rs:13-27)    */
 typedef struct sprs_csminres sprs_csminres; /* CSMinRes<T,M>                 (cs_minres.rs:11-25) */
 typedef struct sprs_cg sprs_cg;             /* conjugate gradients (no reference analogue; "conjugate gradients" below) */
+typedef struct sprs_gmres sprs_gmres;       /* restarted GMRES (no reference analogue; "restarted GMRES" below) */
 typedef struct sprs_comm sprs_comm;         /* RCCL communicator of this rank (multi-GPU section)  */
 typedef struct sprs_gauss_seidel sprs_gauss_seidel; /* GaussSeidel<T>        (gauss_seidel.rs:8-31) */
 
@@ -339,6 +340,60 @@ int sprs_cg_precond_solve_z(sprs_cg *S, const sprs_diag *P, const sprs_c64 *rhs,
 int sprs_cg_solve_dev_d(sprs_cg *S, const sprs_diag *P_or_null, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
 int sprs_cg_solve_dev_z(sprs_cg *S, const sprs_diag *P_or_null, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
 
+/* ---------------------------------------------------------------- restarted GMRES
+ * GMRES(m) for any non-singular A: right-preconditioned (Jacobi P, or none), the Arnoldi vector orthogonalised by classical
+ * Gram-Schmidt applied twice (CGS2), Givens rotations on the Hessenberg column.  The reference has no such solver; the
+ * conventions are its BiCGStab's: relative residual against |rhs|, a zero right-hand side answers x = 0, x is in/out and is
+ * left modified on error, the same status codes.  The residual estimate never increases and the method cannot break down
+ * before it has the solution.  The handle holds (m + 4) n of workspace.  `restart` = m, 0 means 30, at most
+ * SPRS_GMRES_MAX_RESTART; a larger one, or a null A, is SPRS_INVALID_ARGUMENT.
+ * Vectors v_0 .. v_m, w, z, u are of type T; h_i, c_i (pass 2), g_i, s_i, y_i and the entries of R are T; hn, beta, cs_i, d, aa
+ * are T::Real.  conj_dot(a, b) = sum conj(a_i) b_i.  Every line below is one library operation per element (axpy: y += x*a;
+ * axpby: y = x*a + y*b), each arithmetic operation rounded once:
+ *     rhs_norm = norm2(rhs);  if rhs_norm <= eps: x = 0, return SPRS_OK with *its_out = 0, *res_out = rhs_norm
+ *     tol2 = tol * rhs_norm;  its = 0
+ *     cycle:
+ *         v_0 = A x;  v_0 = rhs*1 + v_0*(-1);  beta = norm2(v_0)
+ *         if beta <= tol2: SPRS_OK, *its_out = its, *res_out = beta / rhs_norm
+ *         v_0 = v_0 * (1 / beta)  (real scale);  g_0 = beta
+ *         for j = 0 .. m - 1:
+ *             z = P v_j (z is v_j itself without P);  w = A z
+ *             pass 1:  h_i = conj_dot(v_i, w) for i = 0 .. j, all on the same w;  then for i = 0 .. j in order: w += v_i*(-h_i)
+ *             pass 2:  c_i = conj_dot(v_i, w) for i = 0 .. j, all on the same w;  then for i = 0 .. j in order: w += v_i*(-c_i);
+ *                      h_i = h_i + c_i
+ *             hn = norm2(w);  unless hn >= 0 (NaN): SPRS_BREAKDOWN, *its_out = its
+ *             for i = 0 .. j - 1 in order (the earlier rotations on the new column):
+ *                 t = h_i*cs_i + s_i*h_{i+1};  h_{i+1} = (-conj(s_i))*h_i + h_{i+1}*cs_i;  h_i = t
+ *             rotation j from a = h_j and the real hn:  aa = |a|;  d = sqrt(aa*aa + hn*hn)
+ *                 aa == 0:  cs_j = 0, s_j = 1          else:  cs_j = aa / d,  s_j = a * ((hn / d) / aa)   (real c, complex s)
+ *                 R_jj = a*cs_j + s_j*hn  (it keeps the phase of a);  R_ij = h_i for i < j
+ *                 g_{j+1} = (-conj(s_j))*g_j;  g_j = g_j*cs_j
+ *             its += 1
+ *             if |g_{j+1}| <= tol2, or hn == 0 (the Krylov space is exhausted), or its == max_iter: k = j + 1, leave the loop
+ *             v_{j+1} = w * (1 / hn)  (real scale)
+ *         (k = m where the loop ran out)
+ *         back substitution, for i = k - 1 .. 0:  t = g_i;  for l = i + 1 .. k - 1 in order: t = t - R_il*y_l;  y_i = t / R_ii
+ *         u = 0;  for i = 0 .. k - 1 in order: u += v_i*y_i;  u = P u;  x += u*1
+ *         if |g_k| <= tol2: SPRS_OK, *its_out = its, *res_out = |g_k| / rhs_norm
+ *         if its == max_iter: SPRS_INSUFFICIENT_ITER, *its_out = max_iter  (x holds the partial cycle's update)
+ *         else the next cycle
+ * max_iter == 0: SPRS_INSUFFICIENT_ITER after the first cycle's beta test, x untouched.
+ * `its` counts Arnoldi steps = the SpMVs inside the cycles (each cycle costs one more for its residual); |.| of a complex
+ * number is hypot.  Fused and literal modes differ only in the summation order of the dot products and norms.
+ * Trace row (sprs_solver_set_trace), one per Arnoldi step: [its (after the step), |g_{j+1}|, hn, re(R_jj), im(R_jj), cs_j,
+ * re(s_j), im(s_j)]. */
+#define SPRS_GMRES_MAX_RESTART 64
+int sprs_gmres_create_d(const sprs_csr *A, size_t size, size_t restart, sprs_gmres **out);
+int sprs_gmres_create_z(const sprs_csr *A, size_t size, size_t restart, sprs_gmres **out);
+int sprs_gmres_destroy(sprs_gmres *S);         /* NULL is a no-op */
+int sprs_gmres_solve_d(sprs_gmres *S, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_gmres_solve_z(sprs_gmres *S, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_gmres_precond_solve_d(sprs_gmres *S, const sprs_diag *P, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_gmres_precond_solve_z(sprs_gmres *S, const sprs_diag *P, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+/* the same on device vectors (16-byte aligned ones are used in place) */
+int sprs_gmres_solve_dev_d(sprs_gmres *S, const sprs_diag *P_or_null, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_gmres_solve_dev_z(sprs_gmres *S, const sprs_diag *P_or_null, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+
 /* ---------------------------------------------------------------- f32 / Complex<f32>
  * The reference is generic over cauchy::Scalar = {f32, f64, c32, c64} and its unit tests exercise f32 / c32
  * BLAS-1 (src/vecalg.rs:647-658,669-677,771-798,816-830).  Every typed entry point above exists again with
@@ -414,6 +469,14 @@ int sprs_cg_precond_solve_s(sprs_cg *S, const sprs_diag *P, const float *rhs, si
 int sprs_cg_precond_solve_c(sprs_cg *S, const sprs_diag *P, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
 int sprs_cg_solve_dev_s(sprs_cg *S, const sprs_diag *P_or_null, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
 int sprs_cg_solve_dev_c(sprs_cg *S, const sprs_diag *P_or_null, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_gmres_create_s(const sprs_csr *A, size_t size, size_t restart, sprs_gmres **out);
+int sprs_gmres_create_c(const sprs_csr *A, size_t size, size_t restart, sprs_gmres **out);
+int sprs_gmres_solve_s(sprs_gmres *S, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_gmres_solve_c(sprs_gmres *S, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_gmres_precond_solve_s(sprs_gmres *S, const sprs_diag *P, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_gmres_precond_solve_c(sprs_gmres *S, const sprs_diag *P, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_gmres_solve_dev_s(sprs_gmres *S, const sprs_diag *P_or_null, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_gmres_solve_dev_c(sprs_gmres *S, const sprs_diag *P_or_null, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
 int sprs_dist_csr_create_dev_s(sprs_comm *comm, int64_t n_local, int64_t n_ext, int64_t nnz, const int32_t *dev_row_ptr, const int32_t *dev_col_idx_ext, const float *dev_val, int adopt, int n_peers, const int32_t *peer_rank, const int64_t *send_off, const int32_t *send_idx_dev, const int64_t *recv_off, sprs_csr **out);
 int sprs_dist_csr_create_dev_c(sprs_comm *comm, int64_t n_local, int64_t n_ext, int64_t nnz, const int32_t *dev_row_ptr, const int32_t *dev_col_idx_ext, const sprs_c32 *dev_val, int adopt, int n_peers, const int32_t *peer_rank, const int64_t *send_off, const int32_t *send_idx_dev, const int64_t *recv_off, sprs_csr **out);
 int sprs_dist_mul_vec_dev_s(const sprs_csr *A, float *x_ext_dev, float *y_local_dev);
@@ -482,7 +545,7 @@ int sprs_dist_mul_vec_dev_z(const sprs_csr *A, sprs_c64 *x_ext_dev, sprs_c64 *y_
 
 /* ---------------------------------------------------------------- solver options / instrumentation
  * `solver` is any of the four solver handle types. */
-enum { SPRS_SOLVER_BICGSTAB = 1, SPRS_SOLVER_MINRES = 2, SPRS_SOLVER_CSMINRES = 3, SPRS_SOLVER_CG = 4 };
+enum { SPRS_SOLVER_BICGSTAB = 1, SPRS_SOLVER_MINRES = 2, SPRS_SOLVER_CSMINRES = 3, SPRS_SOLVER_CG = 4, SPRS_SOLVER_GMRES = 5 };
 /* mode 0 (default): fused kernels, device-resident scalars, lazy host polling.
  * mode 1: "literal" — the reference's op list one kernel per op, every scalar consumed on the
  *         host exactly where the reference consumes it (bicg_stab.rs:122-197). */

@@ -15,7 +15,8 @@ CSRC = os.path.join(_HERE, "csrc")
  INVALID_ARGUMENT) = range(8)
 ZERO_DIAGONAL, NOT_SQUARE, NOT_CSR = 8, 9, 10
 ERR_HIP, ERR_RCCL, ERR_NO_DEVICE = 100, 101, 102
-SOLVER_BICGSTAB, SOLVER_MINRES, SOLVER_CSMINRES, SOLVER_CG = 1, 2, 3, 4
+SOLVER_BICGSTAB, SOLVER_MINRES, SOLVER_CSMINRES, SOLVER_CG, SOLVER_GMRES = 1, 2, 3, 4, 5
+GMRES_MAX_RESTART = 64
 
 
 class c64(C.Structure):
@@ -98,14 +99,16 @@ def _protos():
         for k in ("bicgstab", "minres", "csminres", "cg"):
             P["sprs_%s_create_%s" % (k, s)] = [_vp, _sz, _pp]
             P["sprs_%s_solve_%s" % (k, s)] = [_vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
-        for k in ("bicgstab", "minres", "cg"):
+        P["sprs_gmres_create_" + s] = [_vp, _sz, _sz, _pp]
+        P["sprs_gmres_solve_" + s] = [_vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
+        for k in ("bicgstab", "minres", "cg", "gmres"):
             P["sprs_%s_precond_solve_%s" % (k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
             P["sprs_%s_solve_dev_%s" % (k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
         P["sprs_csminres_solve_dev_" + s] = [_vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
     P["sprs_axpy_zd"] = [_vp, _sz, _dbl, _vp, _vp]
     P["sprs_axpy_cs"] = [_vp, _sz, C.c_float, _vp, _vp]
     P["sprs_csr_destroy"] = [_vp]
-    for k in ("bicgstab", "minres", "csminres", "cg"):
+    for k in ("bicgstab", "minres", "csminres", "cg", "gmres"):
         P["sprs_%s_destroy" % k] = [_vp]
     for s in ("d", "zd", "z", "s", "cs", "c"):
         P["sprs_diag_precond_create_" + s] = [_vp, _sz, _vp, _pp]

@@ -10,16 +10,16 @@ from .error import check, solve_result
 
 class _SolverBase:
     KIND = None       # _lib.SOLVER_*
-    NAME = None       # "bicgstab" | "minres" | "csminres"
+    NAME = None       # "bicgstab" | "minres" | "csminres" | "cg" | "gmres"
 
-    def __init__(self, A, size):
+    def __init__(self, A, size, *create_args):
         self.A = A                      # borrowed, like `A: &'data M` (bicg_stab.rs:18)
         self.size = int(size)
         self.dtype = A.dtype
         from .device import sfx
         self.s = sfx(self.dtype)
         h = C.c_void_p()
-        st = getattr(_lib.lib(), "sprs_%s_create_%s" % (self.NAME, self.s))(A.h, self.size, C.byref(h))
+        st = getattr(_lib.lib(), "sprs_%s_create_%s" % (self.NAME, self.s))(A.h, self.size, *create_args, C.byref(h))
         check(st, A.ctx.h)
         self.h = h
         self._trace = None

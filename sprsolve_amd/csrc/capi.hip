@@ -506,6 +506,7 @@ static int with_base(void *solver, int kind, F &&f) {
     switch (kind) {
         case SPRS_SOLVER_BICGSTAB: return with_solver<BicgStab>(h->dtype, h->impl, f);
         case SPRS_SOLVER_CG: return with_solver<Cg>(h->dtype, h->impl, f);
+        case SPRS_SOLVER_GMRES: return with_solver<Gmres>(h->dtype, h->impl, f);
         case SPRS_SOLVER_MINRES:
         case SPRS_SOLVER_CSMINRES: return with_solver<MinRes>(h->dtype, h->impl, f);
     }
@@ -632,12 +633,10 @@ int sprs_bicgstab_destroy(sprs_bicgstab *S) { return solver_destroy<BicgStab>(S)
 int sprs_minres_destroy(sprs_minres *S) { return solver_destroy<MinRes>(S); }
 int sprs_csminres_destroy(sprs_csminres *S) { return solver_destroy<MinRes>(S); }
 int sprs_cg_destroy(sprs_cg *S) { return solver_destroy<Cg>(S); }
+int sprs_gmres_destroy(sprs_gmres *S) { return solver_destroy<Gmres>(S); }
 
 // ---- a solver's entry points per scalar type.  NAME = the handle is sprs_NAME, S = its class, CREATE = the arguments of S<T>::create
-#define SPRS_SOLVER_API(X, T, CT, R, NAME, S, CREATE)                                                                  \
-    int sprs_##NAME##_create_##X(const sprs_csr *A, size_t n, sprs_##NAME **out) {                                     \
-        SPRS_G(return (solver_create<T, sprs_##NAME, S>(A, n, out, [&](auto *s) { return s->create CREATE; }));)       \
-    }                                                                                                                  \
+#define SPRS_SOLVER_SOLVES(X, T, CT, R, NAME, S)                                                                       \
     int sprs_##NAME##_solve_##X(sprs_##NAME *h, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
         SPRS_G(return solve<T>(impl_of<S, T>(h), true, nullptr, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);)   \
     }                                                                                                                  \
@@ -647,6 +646,11 @@ int sprs_cg_destroy(sprs_cg *S) { return solver_destroy<Cg>(S); }
     int sprs_##NAME##_solve_dev_##X(sprs_##NAME *h, const sprs_diag *P, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
         SPRS_G(return solve<T>(impl_of<S, T>(h), false, P, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);)        \
     }
+#define SPRS_SOLVER_API(X, T, CT, R, NAME, S, CREATE)                                                                  \
+    int sprs_##NAME##_create_##X(const sprs_csr *A, size_t n, sprs_##NAME **out) {                                     \
+        SPRS_G(return (solver_create<T, sprs_##NAME, S>(A, n, out, [&](auto *s) { return s->create CREATE; }));)       \
+    }                                                                                                                  \
+    SPRS_SOLVER_SOLVES(X, T, CT, R, NAME, S)
 
 // ---- everything that exists once per scalar type.  X = suffix, T = device scalar, CT = C-ABI scalar
 // (passed by value / pointer), R = T::Real
@@ -695,6 +699,12 @@ int sprs_cg_destroy(sprs_cg *S) { return solver_destroy<Cg>(S); }
     SPRS_SOLVER_API(X, T, CT, R, bicgstab, BicgStab, (A, n))                                                           \
     SPRS_SOLVER_API(X, T, CT, R, minres, MinRes, (A, n, false))                                                        \
     SPRS_SOLVER_API(X, T, CT, R, cg, Cg, (A, n))                                                                       \
+    /* GMRES' create takes the restart length (0 = 30) */                                                              \
+    int sprs_gmres_create_##X(const sprs_csr *A, size_t n, size_t restart, sprs_gmres **out) {                         \
+        SPRS_G(if (restart > SPRS_GMRES_MAX_RESTART) return SPRS_INVALID_ARGUMENT;                                     \
+               return (solver_create<T, sprs_gmres, Gmres>(A, n, out, [&](auto *s) { return s->create(A, n, restart); }));) \
+    }                                                                                                                  \
+    SPRS_SOLVER_SOLVES(X, T, CT, R, gmres, Gmres)                                                                      \
     /* CSMinRes has no precond_solve (cs_minres.rs) */                                                                  \
     int sprs_csminres_create_##X(const sprs_csr *A, size_t n, sprs_csminres **out) {                                   \
         SPRS_G(return (solver_create<T, sprs_csminres, MinRes>(A, n, out, [&](auto *s) { return s->create(A, n, true); }));) \

@@ -1,4 +1,4 @@
-// Solver objects behind sprs_bicgstab / sprs_minres / sprs_csminres / sprs_cg.
+// Solver objects behind sprs_bicgstab / sprs_minres / sprs_csminres / sprs_cg / sprs_gmres.
 #pragma once
 #include "internal.hpp"
 
@@ -29,6 +29,7 @@ struct MinresDev {
 };
 
 template <class T> struct CgState;   // cg_fuse.hpp
+template <class T> struct GmresState;   // gmres_fuse.hpp
 
 struct SolverStats {
     double spmv_ms = 0.0, solve_ms = 0.0;
@@ -55,12 +56,13 @@ struct StateBlock {
         if (host) (void)hipHostFree(host);
         dev = host = nullptr;
     }
-    int push() {    // host -> device, in stream order
-        SPRS_HIP_TRY(ctx, hipMemcpyAsync(dev, host, sizeof(S), hipMemcpyHostToDevice, ctx->stream));
+    // `bytes`: only the leading part of S travels (GMRES polls the head of a state that also holds the packed R)
+    int push(size_t bytes = sizeof(S)) {    // host -> device, in stream order
+        SPRS_HIP_TRY(ctx, hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, ctx->stream));
         return SPRS_OK;
     }
-    int fetch() {   // device -> host, and wait for it
-        SPRS_HIP_TRY(ctx, hipMemcpyAsync(host, dev, sizeof(S), hipMemcpyDeviceToHost, ctx->stream));
+    int fetch(size_t bytes = sizeof(S)) {   // device -> host, and wait for it
+        SPRS_HIP_TRY(ctx, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
         SPRS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         return SPRS_OK;
     }
@@ -199,6 +201,33 @@ class Cg : public KrylovBase<T> {
     int run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
 };
 
+// Restarted GMRES for any non-singular A (recurrence: include/sprsolve_hip.h, sprs_gmres_*; kernels: gmres_fuse.hpp)
+template <class T>
+class Gmres : public KrylovBase<T> {
+   public:
+    StateBlock<GmresState<T>> state;     // the host pushes and polls only its head (GmresHead)
+    int m = 30;                  // restart length
+    T *dots = nullptr;           // [m][dots_grid] partials of the multi-dots
+    int dots_grid = 0;
+    T *coefs = nullptr;          // distributed: the m reduced coefficients of a pass, all-reduced in place
+    int create(const sprs_csr *A, size_t size, size_t restart);
+    void destroy();
+    int solve_dev(const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
+                  size_t *its_out, Real<T> *res_out);
+
+   private:
+    friend class KrylovBase<T>;
+    T *basis(int i) { return this->vec(i); }                 // v_0 .. v_m
+    T *wvec() { return this->vec(m + 1); }
+    T *zvec() { return this->vec(m + 2); }
+    T *uvec() { return this->vec(m + 3); }                   // literal mode's x update
+    void trace_step(double its, double g, double hn, T r, double c, T s);
+    template <class V>
+    int run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
+    template <class V>
+    int run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
+};
+
 }  // namespace sprs
 
 // opaque C handles: type-erased over T, one layout
@@ -210,3 +239,4 @@ struct sprs_bicgstab : sprs_solver_handle {};
 struct sprs_minres : sprs_solver_handle {};
 struct sprs_csminres : sprs_solver_handle {};
 struct sprs_cg : sprs_solver_handle {};
+struct sprs_gmres : sprs_solver_handle {};

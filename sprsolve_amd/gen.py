@@ -245,6 +245,32 @@ def hermitian_banded(n, hbw=4, seed=SEED):
     return indptr, indices, data, rhs
 
 
+def convection_diffusion_2d(rows, cols, cx=0.3, cy=0.2, dtype=np.float64):
+    """A non-symmetric 5-point operator for GMRES / BiCGStab (no reference analogue: the reference's grids are all symmetric,
+    Hermitian or complex-symmetric): central differences of -laplace(u) + c . grad(u) on a rows x cols grid, diag 4, the
+    neighbours at column j -+ 1 are -1 -+ cx, those at row i -+ 1 are -1 -+ cy (|cx|, |cy| < 1 keeps it diagonally
+    dominant).  The complex dtypes multiply every entry by 1 + 0.25i.  rhs = A * x with x[i*cols + j] = 1 + (i + 2j) / (rows + cols)
+    (times 1 - 0.5i for the complex dtypes), formed in the dtype.  Returns (indptr, indices, data, rhs)."""
+    dt = np.dtype(dtype)
+    fac = (1.0 + 0.25j) if dt.kind == "c" else 1.0
+    i, j = np.meshgrid(np.arange(rows), np.arange(cols), indexing="ij")
+    i = i.ravel(); j = j.ravel()
+    vid = i * cols + j
+    n = rows * cols
+    R = [vid]; Cc = [vid]; V = [np.full(n, 4.0 * fac)]
+    for di, dj, val in ((-1, 0, -1.0 - cy), (1, 0, -1.0 + cy), (0, -1, -1.0 - cx), (0, 1, -1.0 + cx)):
+        ni = i + di; nj = j + dj
+        ok = (ni >= 0) & (ni < rows) & (nj >= 0) & (nj < cols)
+        R.append(vid[ok]); Cc.append((ni * cols + nj)[ok]); V.append(np.full(int(ok.sum()), val * fac))
+    indptr, indices, data = _coo_to_csr(n, np.concatenate(R), np.concatenate(Cc), np.concatenate(V))
+    data = data.astype(dt)
+    xs = (1.0 + (i + 2.0 * j) / float(rows + cols)) * ((1.0 - 0.5j) if dt.kind == "c" else 1.0)
+    rows_of = np.repeat(np.arange(n), np.diff(indptr))
+    rhs = np.zeros(n, dt)
+    np.add.at(rhs, rows_of, data * xs.astype(dt)[indices])
+    return indptr, indices, data, rhs
+
+
 def poisson3d(nx, ny, nz, z0=0, z1=None, index_dtype=np.int32, values="poisson", seed=SEED):
     """cfg 5: 7-point 3-D Poisson on an nx*ny*nz grid (x fastest), diag +6, neighbours -1,
     truncated at the faces.  Returns the CSR row block for planes [z0, z1) with GLOBAL column
