@@ -54,6 +54,7 @@ typedef struct sprs_bicgstab sprs_bicgstab; /* BiCGStab<T,M>                 (bi
 typedef struct sprs_minres sprs_minres;     /* MinRes<T,M>                   (minres.rs:13-27)    */
 typedef struct sprs_csminres sprs_csminres; /* CSMinRes<T,M>                 (cs_minres.rs:11-25) */
 typedef struct sprs_cg sprs_cg;             /* conjugate gradients (no reference analogue; "conjugate gradients" below) */
+typedef struct sprs_cg_many sprs_cg_many;   /* conjugate gradients on several right-hand sides at once ("several right-hand sides" below) */
 typedef struct sprs_gmres sprs_gmres;       /* restarted GMRES (no reference analogue; "restarted GMRES" below) */
 typedef struct sprs_comm sprs_comm;         /* RCCL communicator of this rank (multi-GPU section)  */
 typedef struct sprs_gauss_seidel sprs_gauss_seidel; /* GaussSeidel<T>        (gauss_seidel.rs:8-31) */
@@ -340,6 +341,36 @@ int sprs_cg_precond_solve_z(sprs_cg *S, const sprs_diag *P, const sprs_c64 *rhs,
 int sprs_cg_solve_dev_d(sprs_cg *S, const sprs_diag *P_or_null, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
 int sprs_cg_solve_dev_z(sprs_cg *S, const sprs_diag *P_or_null, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
 
+/* ---------------------------------------------------------------- several right-hand sides at once: SpMM and batched CG
+ * A block of k vectors (1 <= k <= 8) is an n x k ROW-MAJOR array: the k values of row i are contiguous (numpy's C order
+ * of an (n, k) array).  Single GPU: a distributed operator is refused with SPRS_INVALID_ARGUMENT (text in sprs_last_error).
+ *
+ * sprs_mul_mat_*: Y = A X on the plain CSR arrays, one pass over the matrix for all k columns.  Column c of Y is bit-identical
+ * to sprs_mul_vec_dev_* on column c of X.  The host entries check x_len == ncols * k and y_len == nrows * k
+ * (SPRS_DIM_MISMATCH); k outside 1..8, a null handle and a handle of another scalar type are SPRS_INVALID_ARGUMENT.
+ *
+ * sprs_cgmany_* on a sprs_cg_many handle (the functions carry no `sprs_cg_` prefix: that one names the single-vector solver's
+ * entry points): conjugate gradients ("conjugate gradients" above) on k right-hand sides in three launches per iteration
+ * whatever k is.  Column j runs exactly that recurrence on its own rho, alpha, beta, |r| and tol * |rhs_j|, with its own
+ * zero-right-hand-side and converged-at-the-start rules, and stops on its own event; from then on its x is not written.
+ * create's k is the most columns a solve may carry; a solve takes any 1 <= k <= that (else SPRS_INVALID_ARGUMENT) and
+ * rhs_len == x_len == size * k (SPRS_INCOMPATIBLE_RHS_SIZE / SPRS_INCOMPATIBLE_X_SIZE).  its_out[j], res_out[j] are what
+ * sprs_cg_solve_* reports for column j's event and status_out[j] is that event's status code (each array: k entries, or
+ * NULL).  Returns SPRS_OK if every column did, else the status of the lowest-numbered column that did not.  Argument and
+ * size errors return at once and write nothing.  The handle holds 5 blocks of size x k' (k' = k rounded up to a power of
+ * two).  No literal mode, trace or profile. */
+int sprs_cgmany_destroy(sprs_cg_many *S);     /* NULL is a no-op */
+int sprs_mul_mat_d(const sprs_csr *A, const double *x_host, size_t x_len, double *y_host, size_t y_len, size_t k);
+int sprs_mul_mat_dev_d(const sprs_csr *A, const double *x_dev, double *y_dev, size_t k);
+int sprs_cgmany_create_d(const sprs_csr *A, size_t size, size_t k, sprs_cg_many **out);
+int sprs_cgmany_solve_d(sprs_cg_many *S, const sprs_diag *P_or_null, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t k, size_t max_iter, double tol, size_t *its_out, double *res_out, int *status_out);
+int sprs_cgmany_solve_dev_d(sprs_cg_many *S, const sprs_diag *P_or_null, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t k, size_t max_iter, double tol, size_t *its_out, double *res_out, int *status_out);
+int sprs_mul_mat_z(const sprs_csr *A, const sprs_c64 *x_host, size_t x_len, sprs_c64 *y_host, size_t y_len, size_t k);
+int sprs_mul_mat_dev_z(const sprs_csr *A, const sprs_c64 *x_dev, sprs_c64 *y_dev, size_t k);
+int sprs_cgmany_create_z(const sprs_csr *A, size_t size, size_t k, sprs_cg_many **out);
+int sprs_cgmany_solve_z(sprs_cg_many *S, const sprs_diag *P_or_null, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t k, size_t max_iter, double tol, size_t *its_out, double *res_out, int *status_out);
+int sprs_cgmany_solve_dev_z(sprs_cg_many *S, const sprs_diag *P_or_null, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t k, size_t max_iter, double tol, size_t *its_out, double *res_out, int *status_out);
+
 /* ---------------------------------------------------------------- restarted GMRES
  * GMRES(m) for any non-singular A: right-preconditioned (Jacobi P, or none), the Arnoldi vector orthogonalised by classical
  * Gram-Schmidt applied twice (CGS2), Givens rotations on the Hessenberg column.  The reference has no such solver; the
@@ -469,6 +500,16 @@ int sprs_cg_precond_solve_s(sprs_cg *S, const sprs_diag *P, const float *rhs, si
 int sprs_cg_precond_solve_c(sprs_cg *S, const sprs_diag *P, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
 int sprs_cg_solve_dev_s(sprs_cg *S, const sprs_diag *P_or_null, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
 int sprs_cg_solve_dev_c(sprs_cg *S, const sprs_diag *P_or_null, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_mul_mat_s(const sprs_csr *A, const float *x_host, size_t x_len, float *y_host, size_t y_len, size_t k);
+int sprs_mul_mat_dev_s(const sprs_csr *A, const float *x_dev, float *y_dev, size_t k);
+int sprs_cgmany_create_s(const sprs_csr *A, size_t size, size_t k, sprs_cg_many **out);
+int sprs_cgmany_solve_s(sprs_cg_many *S, const sprs_diag *P_or_null, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t k, size_t max_iter, float tol, size_t *its_out, float *res_out, int *status_out);
+int sprs_cgmany_solve_dev_s(sprs_cg_many *S, const sprs_diag *P_or_null, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t k, size_t max_iter, float tol, size_t *its_out, float *res_out, int *status_out);
+int sprs_mul_mat_c(const sprs_csr *A, const sprs_c32 *x_host, size_t x_len, sprs_c32 *y_host, size_t y_len, size_t k);
+int sprs_mul_mat_dev_c(const sprs_csr *A, const sprs_c32 *x_dev, sprs_c32 *y_dev, size_t k);
+int sprs_cgmany_create_c(const sprs_csr *A, size_t size, size_t k, sprs_cg_many **out);
+int sprs_cgmany_solve_c(sprs_cg_many *S, const sprs_diag *P_or_null, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t k, size_t max_iter, float tol, size_t *its_out, float *res_out, int *status_out);
+int sprs_cgmany_solve_dev_c(sprs_cg_many *S, const sprs_diag *P_or_null, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t k, size_t max_iter, float tol, size_t *its_out, float *res_out, int *status_out);
 int sprs_gmres_create_s(const sprs_csr *A, size_t size, size_t restart, sprs_gmres **out);
 int sprs_gmres_create_c(const sprs_csr *A, size_t size, size_t restart, sprs_gmres **out);
 int sprs_gmres_solve_s(sprs_gmres *S, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);

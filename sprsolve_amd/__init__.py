@@ -8,6 +8,7 @@ package does not load it, using it does, and there is no CPU fallback.
 from . import error, precond, vecalg  # noqa: F401
 from .bicg_stab import BiCGStab  # noqa: F401
 from .cg import CG  # noqa: F401
+from .cg_many import CGMany  # noqa: F401
 from .cs_minres import CSMinRes  # noqa: F401
 from .gauss_seidel import GaussSeidel  # noqa: F401
 from .gmres import GMRES  # noqa: F401

@@ -86,6 +86,11 @@ def _protos():
         P["sprs_mul_vec_dev_" + s] = [_vp, _vp, _vp]
         P["sprs_mul_vec_dot_dev_" + s] = [_vp, _vp, _vp, _vp]
         P["sprs_mul_vec_dev_timed_" + s] = [_vp, _vp, _vp, _int, _pd]
+        P["sprs_mul_mat_" + s] = [_vp, _vp, _sz, _vp, _sz, _sz]
+        P["sprs_mul_mat_dev_" + s] = [_vp, _vp, _vp, _sz]
+        P["sprs_cgmany_create_" + s] = [_vp, _sz, _sz, _pp]
+        for k in ("solve", "solve_dev"):
+            P["sprs_cgmany_%s_%s" % (k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, _sz, re_, _psz, pre, C.POINTER(_int)]
         P["sprs_dot_" + s] = [_vp, _sz, _vp, _vp, _vp]
         P["sprs_conj_dot_" + s] = [_vp, _sz, _vp, _vp, _vp]
         P["sprs_norm2_" + s] = [_vp, _sz, _vp, pre]
@@ -108,7 +113,7 @@ def _protos():
     P["sprs_axpy_zd"] = [_vp, _sz, _dbl, _vp, _vp]
     P["sprs_axpy_cs"] = [_vp, _sz, C.c_float, _vp, _vp]
     P["sprs_csr_destroy"] = [_vp]
-    for k in ("bicgstab", "minres", "csminres", "cg", "gmres"):
+    for k in ("bicgstab", "minres", "csminres", "cg", "gmres", "cgmany"):
         P["sprs_%s_destroy" % k] = [_vp]
     for s in ("d", "zd", "z", "s", "cs", "c"):
         P["sprs_diag_precond_create_" + s] = [_vp, _sz, _vp, _pp]

@@ -350,6 +350,46 @@ int mul_vec_dev(const sprs_csr *A, const T *dx, T *dy, T *dot_out) {
     return reduce_partials_host<T>(c, part, spmv_num_partials(A), dot_out);
 }
 
+// Y = A X for a row-major block of k <= 8 vectors (spmm.hip)
+template <class T>
+int mul_mat_dev(const sprs_csr *A, const T *dx, T *dy, size_t k) {
+    if (!A || !dx || !dy) return SPRS_INVALID_ARGUMENT;
+    if (A->dtype != dtype_of<T>::value) return SPRS_INVALID_ARGUMENT;
+    if (k < 1 || k > 8) return SPRS_INVALID_ARGUMENT;
+    sprs_ctx *c = A->ctx;
+    CtxLock lock(c);
+    if (A->dist) {
+        snprintf(c->err, sizeof(c->err), "sprs_mul_mat: distributed operators are not supported (single GPU only)");
+        return SPRS_INVALID_ARGUMENT;
+    }
+    SPRS_HIP_TRY(c, hipSetDevice(c->device));
+    return launch_spmm<T>(A, dx, dy, (int)k, (int)k, 0, nullptr, nullptr, nullptr);
+}
+
+template <class T>
+int mul_mat_host(const sprs_csr *A, const T *x, size_t x_len, T *y, size_t y_len, size_t k) {
+    if (!A || !x || !y) return SPRS_INVALID_ARGUMENT;
+    if (A->dtype != dtype_of<T>::value) return SPRS_INVALID_ARGUMENT;
+    if (k < 1 || k > 8) return SPRS_INVALID_ARGUMENT;
+    if ((size_t)A->ncols * k != x_len || (size_t)A->nrows * k != y_len) return SPRS_DIM_MISMATCH;
+    sprs_ctx *c = A->ctx;
+    CtxLock lock(c);
+    if (A->dist) {
+        snprintf(c->err, sizeof(c->err), "sprs_mul_mat: distributed operators are not supported (single GPU only)");
+        return SPRS_INVALID_ARGUMENT;
+    }
+    SPRS_HIP_TRY(c, hipSetDevice(c->device));
+    T *dx = nullptr, *dy = nullptr;
+    struct Free { T *&a, *&b; ~Free() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); } } guard{dx, dy};   // every return path
+    SPRS_HIP_TRY(c, hipMalloc((void **)&dx, sizeof(T) * (x_len ? x_len : 1)));
+    SPRS_HIP_TRY(c, hipMalloc((void **)&dy, sizeof(T) * (y_len ? y_len : 1)));
+    SPRS_HIP_TRY(c, hipMemcpyAsync(dx, x, sizeof(T) * x_len, hipMemcpyHostToDevice, c->stream));
+    SPRS_TRY(launch_spmm<T>(A, dx, dy, (int)k, (int)k, 0, nullptr, nullptr, nullptr));
+    SPRS_HIP_TRY(c, hipMemcpyAsync(y, dy, sizeof(T) * y_len, hipMemcpyDeviceToHost, c->stream));
+    SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SPRS_OK;
+}
+
 template <class T>
 int mul_vec_timed(const sprs_csr *A, const T *dx, T *dy, int reps, double *ms) {
     if (!A || !dx || !dy || !ms || reps < 1) return SPRS_INVALID_ARGUMENT;
@@ -488,6 +528,31 @@ int solve(SolverT *s, bool host, const sprs_diag *P, const T *rhs, size_t rl, T 
     if (st >= SPRS_ERR_HIP) return st;
     // x is in/out in the reference and is left modified on Err as well
     SPRS_HIP_TRY(c, hipMemcpyAsync(x, s->x_buf, sizeof(T) * xl, out, c->stream));
+    SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return st;
+}
+
+// One batched CG solve (n x k row-major blocks).  Host slices go through the solver's staging buffers; device blocks are
+// read and written in place (the solver copies them into its padded work blocks, so no alignment is asked of them).
+template <class T>
+int solve_many(CgMany<T> *s, bool host, const sprs_diag *P, const T *rhs, size_t rl, T *x, size_t xl, size_t k, size_t max_iter,
+               Real<T> tol, size_t *its, Real<T> *res, int *status) {
+    if (!s || !rhs || !x) return SPRS_INVALID_ARGUMENT;
+    if (k < 1 || k > (size_t)s->kmax) return SPRS_INVALID_ARGUMENT;
+    if (rl != s->n * k) return SPRS_INCOMPATIBLE_RHS_SIZE;
+    if (xl != s->n * k) return SPRS_INCOMPATIBLE_X_SIZE;
+    sprs_ctx *c = s->ctx;
+    CtxLock lock(c);
+    if (!host) return s->solve_dev(P, rhs, rl, x, xl, k, max_iter, tol, its, res, status);
+    SPRS_HIP_TRY(c, hipSetDevice(c->device));
+    const size_t cap = (s->n * (size_t)s->kmax) + 1;
+    if (!s->rhs_buf) SPRS_HIP_TRY(c, hipMalloc((void **)&s->rhs_buf, sizeof(T) * cap));
+    if (!s->x_buf) SPRS_HIP_TRY(c, hipMalloc((void **)&s->x_buf, sizeof(T) * cap));
+    SPRS_HIP_TRY(c, hipMemcpyAsync(s->rhs_buf, rhs, sizeof(T) * rl, hipMemcpyHostToDevice, c->stream));
+    SPRS_HIP_TRY(c, hipMemcpyAsync(s->x_buf, x, sizeof(T) * xl, hipMemcpyHostToDevice, c->stream));
+    int st = s->solve_dev(P, s->rhs_buf, rl, s->x_buf, xl, k, max_iter, tol, its, res, status);
+    if (st >= SPRS_ERR_HIP || st == SPRS_DIM_MISMATCH || st == SPRS_INVALID_ARGUMENT) return st;
+    SPRS_HIP_TRY(c, hipMemcpyAsync(x, s->x_buf, sizeof(T) * xl, hipMemcpyDeviceToHost, c->stream));
     SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
     return st;
 }
@@ -634,6 +699,7 @@ int sprs_minres_destroy(sprs_minres *S) { return solver_destroy<MinRes>(S); }
 int sprs_csminres_destroy(sprs_csminres *S) { return solver_destroy<MinRes>(S); }
 int sprs_cg_destroy(sprs_cg *S) { return solver_destroy<Cg>(S); }
 int sprs_gmres_destroy(sprs_gmres *S) { return solver_destroy<Gmres>(S); }
+int sprs_cgmany_destroy(sprs_cg_many *S) { return solver_destroy<CgMany>(S); }
 
 // ---- a solver's entry points per scalar type.  NAME = the handle is sprs_NAME, S = its class, CREATE = the arguments of S<T>::create
 #define SPRS_SOLVER_SOLVES(X, T, CT, R, NAME, S)                                                                       \
@@ -680,6 +746,23 @@ int sprs_gmres_destroy(sprs_gmres *S) { return solver_destroy<Gmres>(S); }
     }                                                                                                                  \
     int sprs_mul_vec_dev_timed_##X(const sprs_csr *A, const CT *x, CT *y, int reps, double *ms) {                      \
         return mul_vec_timed<T>(A, (const T *)x, (T *)y, reps, ms);                                                    \
+    }                                                                                                                  \
+    int sprs_mul_mat_##X(const sprs_csr *A, const CT *x, size_t xl, CT *y, size_t yl, size_t k) {                      \
+        SPRS_G(return mul_mat_host<T>(A, (const T *)x, xl, (T *)y, yl, k);)                                            \
+    }                                                                                                                  \
+    int sprs_mul_mat_dev_##X(const sprs_csr *A, const CT *x, CT *y, size_t k) { return mul_mat_dev<T>(A, (const T *)x, (T *)y, k); } \
+    /* batched CG: k = the most columns a solve may carry */                                                           \
+    int sprs_cgmany_create_##X(const sprs_csr *A, size_t n, size_t k, sprs_cg_many **out) {                           \
+        SPRS_G(if (k < 1 || k > 8) { if (out) *out = nullptr; return SPRS_INVALID_ARGUMENT; }                          \
+               return (solver_create<T, sprs_cg_many, CgMany>(A, n, out, [&](auto *s) { return s->create(A, n, k); }));) \
+    }                                                                                                                  \
+    int sprs_cgmany_solve_##X(sprs_cg_many *h, const sprs_diag *P, const CT *rhs, size_t rl, CT *x, size_t xl, size_t k, size_t mi, R tol, \
+                               size_t *its, R *res, int *status) {                                                     \
+        SPRS_G(return solve_many<T>(impl_of<CgMany, T>(h), true, P, (const T *)rhs, rl, (T *)x, xl, k, mi, tol, its, res, status);) \
+    }                                                                                                                  \
+    int sprs_cgmany_solve_dev_##X(sprs_cg_many *h, const sprs_diag *P, const CT *rhs, size_t rl, CT *x, size_t xl, size_t k, size_t mi, R tol, \
+                                   size_t *its, R *res, int *status) {                                                 \
+        SPRS_G(return solve_many<T>(impl_of<CgMany, T>(h), false, P, (const T *)rhs, rl, (T *)x, xl, k, mi, tol, its, res, status);) \
     }                                                                                                                  \
     int sprs_dot_##X(sprs_ctx *c, size_t n, const CT *x, const CT *y, CT *o) { SPRS_CHK(c && o); return dot_host<T>(c, n, (const T *)x, (const T *)y, false, (T *)o); } \
     int sprs_conj_dot_##X(sprs_ctx *c, size_t n, const CT *x, const CT *y, CT *o) { SPRS_CHK(c && o); return dot_host<T>(c, n, (const T *)x, (const T *)y, true, (T *)o); } \

@@ -345,6 +345,14 @@ int launch_tile_off(const sprs_csr *A, const SpmvRoute &r, const double *x, doub
 int launch_chain_pair(const sprs_csr *A, const SpmvRoute &r, const double *x, double *y, int dot_mode, const double *u,
                       double *part0, double *part1, const int *status, const Fin &fin);
 
+// ---- spmm.hip
+// Y = A X on the plain CSR arrays for a row-major block of k <= 8 vectors with leading dimension ld >= k (X: ncols x ld,
+// Y: nrows x ld); column c of Y has the bits of the SpMV of column c.  dot_mode 1: part[c * spmm_grid(A) + b] = workgroup b's
+// partial of sum conj(u_ic) y_ic.  running (device int*, may be null): the launch returns at once when *running == 0.
+template <class T>
+int launch_spmm(const sprs_csr *A, const T *x, T *y, int ld, int k, int dot_mode, const T *u, T *part, const int *running);
+int spmm_grid(const sprs_csr *A);   // workgroups == partials per column of one launch
+
 // ---- blas1.hip  (all on ctx->stream, asynchronous)
 template <class T, class S> int launch_axpy(sprs_ctx *c, size_t n, S a, const T *x, T *y);
 template <class T> int launch_axpby(sprs_ctx *c, size_t n, T a, const T *x, T b, T *y);

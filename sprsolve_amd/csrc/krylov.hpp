@@ -228,6 +228,33 @@ class Gmres : public KrylovBase<T> {
     int run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
 };
 
+// Conjugate gradients on a block of up to kmax <= 8 right-hand sides at once (cg_many.hip; kernels: spmm.hip, cg_many_fuse.hpp).
+// Every column runs Cg<T>'s recurrence on its own scalars and stops on its own events.  Single GPU, fused mode only.
+template <class T> struct CgManyState;   // cg_many_fuse.hpp
+template <class T>
+class CgMany {
+   public:
+    sprs_ctx *ctx = nullptr;
+    const sprs_csr *A = nullptr;
+    size_t n = 0, n_pad = 0;     // rows; rows of the work blocks (a multiple of 4)
+    int kmax = 0, kp = 0, lg = 0;   // the most columns a solve may carry; the blocks' column stride (a power of two) and its log2
+    T *work = nullptr;           // x, r, p, q, z: five n_pad x kp blocks
+    T *rhs_buf = nullptr, *x_buf = nullptr;   // staging of the host entry points (n x kmax)
+    T *partPQ = nullptr, *partRZ = nullptr;   // [column][workgroup] partials
+    Real<T> *partN = nullptr;
+    StateBlock<CgManyState<T>> state;
+    int create(const sprs_csr *A, size_t size, size_t k);
+    void destroy();
+    T *blk(int i) { return work + (size_t)i * n_pad * (size_t)kp; }
+    // rhs, x: device, n x k row-major.  its_out / res_out / status_out: host arrays of k entries (each may be null)
+    int solve_dev(const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t k, size_t max_iter, Real<T> tol,
+                  size_t *its_out, Real<T> *res_out, int *status_out);
+
+   private:
+    template <class V>
+    int run(const V *dinv, const T *rhs, T *x, int k, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out, int *status_out);
+};
+
 }  // namespace sprs
 
 // opaque C handles: type-erased over T, one layout
@@ -240,3 +267,4 @@ struct sprs_minres : sprs_solver_handle {};
 struct sprs_csminres : sprs_solver_handle {};
 struct sprs_cg : sprs_solver_handle {};
 struct sprs_gmres : sprs_solver_handle {};
+struct sprs_cg_many : sprs_solver_handle {};

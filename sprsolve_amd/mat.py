@@ -181,6 +181,34 @@ class HipCsr(MatVecMul):
         check(st, self.ctx.h)
         return out.value if s in "ds" else out.py()
 
+    def mul_mat(self, V_in, V_out):
+        """V_out = A V_in for a block of k <= 8 vectors: C-contiguous 2-D arrays of shape (cols, k) and (rows, k) — the k values of
+        a row are contiguous.  One pass over the matrix for all k columns (csrc/spmm.hip); column c of V_out is bit-identical
+        to mul_vec on column c of V_in.  Host arrays, or device vectors holding such blocks."""
+        L = _lib.lib()
+        if is_device_array(V_in):
+            # a flat device vector (DevVec) or a 2-D torch tensor: k follows from the lengths
+            k = dev_len(V_in) // self.cols() if self.cols() else 0
+            if k < 1 or dev_len(V_in) != self.cols() * k or dev_len(V_out) != self.rows() * k:
+                from .error import DimensionMismatch
+                raise DimensionMismatch("Dimension mismatch")
+            pre_sync(V_in, V_out)
+            check(getattr(L, "sprs_mul_mat_dev_" + self._s())(self.h, dev_ptr(V_in), dev_ptr(V_out), int(k)), self.ctx.h)
+            self.ctx.sync()
+            return
+        X = np.asarray(V_in)
+        if X.ndim != 2 or not isinstance(V_out, np.ndarray) or V_out.ndim != 2:
+            raise TypeError("mul_mat takes 2-D (n, k) blocks")
+        X = np.ascontiguousarray(X, dtype=self.dtype)
+        if not (V_out.dtype == self.dtype and V_out.flags.c_contiguous):
+            raise TypeError("V_out must be a C-contiguous %s ndarray (it is written in place)" % self.dtype)
+        if V_out.shape[1] != X.shape[1]:
+            from .error import DimensionMismatch
+            raise DimensionMismatch("Dimension mismatch")
+        st = getattr(L, "sprs_mul_mat_" + self._s())(self.h, X.ctypes.data_as(C.c_void_p), X.size, V_out.ctypes.data_as(C.c_void_p),
+                                                     V_out.size, int(X.shape[1]))
+        check(st, self.ctx.h)
+
     def time_mul_vec(self, v_in, v_out, reps=20):
         """Mean device milliseconds of one SpMV launch (HIP events on the library's stream)."""
         pre_sync(v_in, v_out)
