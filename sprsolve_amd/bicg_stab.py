@@ -5,7 +5,7 @@ from ._solver import _SolverBase
 
 class BiCGStab(_SolverBase):
     """`BiCGStab::new(&A, size)` (bicg_stab.rs:25); the recurrence runs in C++ on device-resident
-    vectors and scalars (sprsolve_amd/csrc/krylov.hip)."""
+    vectors and scalars (sprsolve_amd/csrc/bicgstab.hip)."""
     KIND = _lib.SOLVER_BICGSTAB
     NAME = "bicgstab"
 

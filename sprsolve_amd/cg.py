@@ -6,7 +6,7 @@ from ._solver import _SolverBase
 class CG(_SolverBase):
     """`CG.new(A, size)`; A must be Hermitian positive definite (not checked).  The recurrence is stated in
     include/sprsolve_hip.h (sprs_cg_*) and runs in C++ on device-resident vectors and scalars
-    (sprsolve_amd/csrc/krylov.hip, cg_fuse.hpp).  Conventions as BiCGStab's: relative residual against |rhs|, x in/out."""
+    (sprsolve_amd/csrc/cg.hip, cg_fuse.hpp).  Conventions as BiCGStab's: relative residual against |rhs|, x in/out."""
     KIND = _lib.SOLVER_CG
     NAME = "cg"
 

@@ -1,14 +1,12 @@
-// BiCGStab's vector-update kernels K1 and K3 (krylov.hip) as structures other translation units can run: the plane-streaming
+// BiCGStab's vector-update kernels (host: bicgstab.hip), K1 and K3 as structures other translation units can run: the plane-streaming
 // chain SpMV (spmv_chain.hip) executes their PROLOGUES (the scalar logic of the recurrence: convergence / restart / breakdown
 // tests, beta, alpha) at the top of its own launch and forms their element-wise results while it stages its x windows — the
-// updated vector is consumed without a pass of its own ("fused SpMV input", krylov.hip).
+// updated vector is consumed without a pass of its own ("fused SpMV input", bicgstab.hip).
 #pragma once
-#include "device.hpp"
+#include "fused_launch.hpp"
 #include "krylov.hpp"
 
 namespace sprs {
-
-__device__ __forceinline__ bool first_thread() { return blockIdx.x == 0 && threadIdx.x == 0; }
 
 // ======================================================================= BiCGStab kernels
 // K1  bicg_stab.rs:123-156 (+ :321-328 with a preconditioner)
@@ -135,5 +133,75 @@ int launch_chain_k4f(const sprs_csr *A, const SpmvRoute &rt, const BicgK3<double
 //   v' = A p' -> v_out ; partials of r0.v'
 int launch_chain_k2f(const sprs_csr *A, const SpmvRoute &rt, const BicgK1<double, double, false> &pro, const double *v_old, const double *p, const double *r,
                      double *p_out, double *v_out, const double *r0, double *partB, const int *status);
+
+// K5  bicg_stab.rs:178-196:  w = (t.t > 0) ? t.r / t.t : 0 ; x -= alpha*y ; x -= w*s ; r -= w*t
+//     + partials of norm2(r)^2 and r0.r for the next iteration's K1 (:123,:128)
+// SV (fused SpMV input, bicgstab.hip): K4 formed s = r + v (-alpha) on the fly and did NOT store it — a store of s costs the fused K4
+// 80 of its 294 us (scripts/micro/fused_window.hip, profiles/r04_tuning.md §3) — so s is formed again here from r and v with the
+// same expression (K3's, bicg_stab.rs:172): one more read, which finds r and v in the Infinity Cache behind K4's reads; r' = s - w t
+// is written over r.
+template <class T, bool PC, bool SV = false>
+struct BicgK5 {
+    BicgState<T> *S; const T *partTT; const T *partTR; int P;
+    const T *y; const T *z; const T *t; const T *r0; T *x; T *r; Real<T> *partN; T *partRho;
+    Fin fin;                    // distributed: the last workgroup reduces (partN, partRho) for the all-reduce
+    T na, nw, w;
+    Real<T> accN; T accR;
+    unsigned int tag = 0; unsigned long long mb_timeout = 0;     // peer-to-peer hand-off (see BicgK1): partTT = this rank's mailbox entries
+    const T *sv = nullptr;                                       // SV: the v of s = r + v (-alpha)
+    __device__ __forceinline__ bool prologue() {
+        __shared__ T smT[NWAVE];
+        __shared__ T smT2[NWAVE];
+        const int status = S->status;                               // requested together with the partials
+        const T alpha = S->alpha;
+        T tt, tr;
+        if (tag != 0) {
+            if (status != ST_RUNNING) { fin_idle(fin, true); return false; }
+            if (!mbox_sum2(MboxSrc{reinterpret_cast<const unsigned long long *>(partTT), P, tag, mb_timeout}, tt, tr)) {
+                if (first_thread()) S->status = ST_COMM_TIMEOUT;
+                return false;
+            }
+        } else {
+            reduce_partials2(partTT, partTR, P, smT, smT2, tt, tr); // :178, :183
+        }
+        if (status != ST_RUNNING) { fin_idle(fin, true); return false; }
+        w = (sre(tt) > 0.0) ? sdiv(tr, tt) : szero<T>();            // :179-186
+        na = sneg(alpha); nw = sneg(w);
+        accN = 0.0; accR = szero<T>();
+        return true;
+    }
+    template <int PK, bool NT> __device__ __forceinline__ void run(int64_t i) {
+        auto xv = ldp<T, PK, NT>(x, i); auto yv = ldp<T, PK, NT>(y, i); auto rv = ldp<T, PK, NT>(r, i);
+        auto tv = ldp<T, PK, NT>(t, i); auto qv = ldp<T, PK, NT>(r0, i);
+        [[maybe_unused]] Pack<T, PK> zv;
+        if (PC) zv = ldp<T, PK, NT>(z, i);
+        if constexpr (SV) {
+            const auto vv = ldp<T, PK, NT>(sv, i);
+#pragma unroll
+            for (int e = 0; e < PK; ++e) rv.v[e] = sadd(rv.v[e], smul(vv.v[e], na));    // :172  s = r - alpha v (K3's expression)
+        }
+#pragma unroll
+        for (int e = 0; e < PK; ++e) {
+            T xx = sadd(xv.v[e], smul(yv.v[e], na));                // :188
+            xx = sadd(xx, smul(PC ? zv.v[e] : rv.v[e], nw));        // :191 / :357
+            xv.v[e] = xx;
+            const T rr = sadd(rv.v[e], smul(tv.v[e], nw));          // :196
+            rv.v[e] = rr;
+            accN = accN + ssq(rr);
+            accR = sadd(accR, smul(sconj(qv.v[e]), rr));
+        }
+        stp<T, PK, NT>(x, i, xv);
+        stp<T, PK, NT>(r, i, rv);
+    }
+    __device__ __forceinline__ void epilogue() {
+        __shared__ Real<T> smD[NWAVE];
+        __shared__ T smT[NWAVE];
+        const Real<T> sN = block_sum(accN, smD);
+        const T sR = block_sum(accR, smT);
+        if (threadIdx.x == 0) { st_partial(fin, partN + blockIdx.x, sN); st_partial(fin, partRho + blockIdx.x, sR); }
+        if (first_thread()) { S->w = w; S->rho_old = S->rho; S->its = S->its + 1; }
+        if (fin.counter) finalize_last_block<Real<T>, T>(fin, true, smD, smT);
+    }
+};
 
 }  // namespace sprs

@@ -1,7 +1,7 @@
 // BLAS-1 kernels of the hot path (reference src/vecalg.rs:556-605, src/precond.rs:20-52) as
 // stand-alone launches.  HBM-bound streaming kernels: 16 bytes per lane per access, grid-stride,
 // two-stage deterministic reductions (wavefront butterfly -> LDS -> one partial per workgroup ->
-// fixed-order final pass).  The fused solver kernels in krylov.hip reuse the same arithmetic.
+// fixed-order final pass).  The fused solver kernels (*_fuse.hpp) reuse the same arithmetic.
 #include "device.hpp"
 
 namespace sprs {

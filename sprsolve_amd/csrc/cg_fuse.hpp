@@ -1,4 +1,4 @@
-// Conjugate gradients' two vector kernels (the solver itself: Cg<T> in krylov.hip).  No reference analogue — the recurrence is
+// Conjugate gradients' two vector kernels (the solver itself: Cg<T> in cg.hip).  No reference analogue — the recurrence is
 // the one stated in the header (sprs_cg_*), in the conventions of the library's BiCGStab.  A fused iteration is three launches:
 //   CA    q = A p with the partials of conj(p).q                      (KrylovBase::spmv, any SpMV route)
 //   CgKB  alpha = rho / (p.q) ; x += p alpha ; r += q (-alpha) ; [z = M^-1 r] ; partials of |r|^2 and conj(r).z
@@ -7,7 +7,7 @@
 // order => the same bits everywhere) with all its loads issued before any is consumed, workgroup 0 records the scalars, and once
 // the status word leaves ST_RUNNING every later kernel returns at its first instruction.
 #pragma once
-#include "bicg_fuse.hpp"
+#include "fused_launch.hpp"
 
 namespace sprs {
 

@@ -4,27 +4,10 @@
 #include "krylov.hpp"
 
 #include <algorithm>
-#include <type_traits>
 
 #include "cg_many_fuse.hpp"
-#include "device.hpp"
 
 namespace sprs {
-
-template <class T, class F>
-static int launch_many(sprs_ctx *c, int64_t np, size_t bytes, int grid, int chunked_walk, F f) {
-    constexpr int PKW = pack_width<T>::value;
-    const int chunked = (chunked_walk && grid % 8 == 0 && grid >= 8) ? 1 : 0;
-    if (stream_loads_nt(c, bytes))
-        hipLaunchKernelGGL((cg_many_kernel<PKW, true, F>), dim3(grid), dim3(BLOCK), 0, c->stream, np, f, chunked);
-    else
-        hipLaunchKernelGGL((cg_many_kernel<PKW, false, F>), dim3(grid), dim3(BLOCK), 0, c->stream, np, f, chunked);
-    SPRS_HIP_TRY(c, hipGetLastError());
-    return SPRS_OK;
-}
-
-template <class F>
-static int dispatch_pc(bool flag, F &&f) { return flag ? f(std::true_type{}) : f(std::false_type{}); }
 
 template <class T>
 int CgMany<T>::create(const sprs_csr *A_, size_t size, size_t k) {
@@ -73,7 +56,6 @@ int CgMany<T>::run(const V *dinv, const T *rhs, T *x, int k, size_t max_iter, Re
     constexpr int PKW = pack_width<T>::value;
     const bool pc = dinv != nullptr;
     const int64_t rows = (int64_t)n, elems = (int64_t)n_pad << lg, np = elems / PKW;
-    const size_t bytes = (size_t)elems * sizeof(T);
     T *X = blk(0), *r = blk(1), *p = blk(2), *q = blk(3), *z = pc ? blk(4) : r;
 
     const int G = balanced_grid(c, (np + BLOCK - 1) / BLOCK);
@@ -93,26 +75,26 @@ int CgMany<T>::run(const V *dinv, const T *rhs, T *x, int k, size_t max_iter, Re
 
     Real<T> *partRhs = reinterpret_cast<Real<T> *>(partPQ);     // S1 reads these while it writes partN: another array (idle until the first SpMM)
     // start: |rhs_c| ; r = rhs - A x ; z ; p ; rho_c ; which columns iterate
-    SPRS_TRY(launch_many<T>(c, np, bytes, G, cw, CgManyS0<T>{r, partRhs, kp, lg, rows, {}}));
+    SPRS_TRY(launch_fused<T>(c, (size_t)elems, G, cw, CgManyS0<T>{r, partRhs, kp, lg, rows, {}}));
     SPRS_TRY(launch_spmm<T>(A, X, q, kp, kp, 0, nullptr, nullptr, nullptr));
-    SPRS_TRY(dispatch_pc(pc, [&](auto pc_tag) {
-        return launch_many<T>(c, np, bytes, G, cw, CgManyS1<T, V, decltype(pc_tag)::value>{d_state, partRhs, G, tol, q, X, r, p, dinv, z, partN, partRZ, kp, lg, rows, {}, {}});
+    SPRS_TRY(dispatch_bool(pc, [&](auto pc_tag) {
+        return launch_fused<T>(c, (size_t)elems, G, cw, CgManyS1<T, V, decltype(pc_tag)::value>{d_state, partRhs, G, tol, q, X, r, p, dinv, z, partN, partRZ, kp, lg, rows, {}, {}});
     }));
-    SPRS_TRY(launch_many<T>(c, 0, bytes, 1, 0, CgManyS2<T>{d_state, partN, partRZ, G, kp}));
+    SPRS_TRY(launch_fused<T>(c, 0, 1, 0, CgManyS2<T>{d_state, partN, partRZ, G, kp}));
 
     auto CA = [&]() -> int { return launch_spmm<T>(A, p, q, kp, kp, 1, p, partPQ, d_running); };   // Q = A P ; conj(p_c).q_c
     auto KB = [&]() -> int {
-        return dispatch_pc(pc, [&](auto pc_tag) {
-            return launch_many<T>(c, np, bytes, G, cw, CgManyKB<T, V, decltype(pc_tag)::value>{d_state, partPQ, GS, GS, p, q, X, r, dinv, z, partN, partRZ, kp, lg, rows, {}, {}, {}});
+        return dispatch_bool(pc, [&](auto pc_tag) {
+            return launch_fused<T>(c, (size_t)elems, G, cw, CgManyKB<T, V, decltype(pc_tag)::value>{d_state, partPQ, GS, GS, p, q, X, r, dinv, z, partN, partRZ, kp, lg, rows, {}, {}, {}});
         });
     };
     auto KC = [&]() -> int {
-        return dispatch_pc(pc, [&](auto pc_tag) {
-            return launch_many<T>(c, np, bytes, G, cw, CgManyKC<T, decltype(pc_tag)::value>{d_state, partN, partRZ, G, z, p, kp, lg, rows, {}, {}});
+        return dispatch_bool(pc, [&](auto pc_tag) {
+            return launch_fused<T>(c, (size_t)elems, G, cw, CgManyKC<T, decltype(pc_tag)::value>{d_state, partN, partRZ, G, z, p, kp, lg, rows, {}, {}});
         });
     };
 
-    const size_t poll = (size_t)(c->poll < 1 ? 1 : c->poll);
+    const size_t poll = poll_interval(c);
     size_t its = 0, since_poll = 0;
     while (true) {
         const bool done_enqueue = its >= max_iter;
@@ -154,16 +136,10 @@ int CgMany<T>::solve_dev(const sprs_diag *P, const T *rhs, size_t rhs_len, T *x,
     if (k < 1 || k > (size_t)kmax) return SPRS_INVALID_ARGUMENT;
     if (rhs_len != n * k) return SPRS_INCOMPATIBLE_RHS_SIZE;
     if (x_len != n * k) return SPRS_INCOMPATIBLE_X_SIZE;
-    if (P) {
-        if (P->n != n) return SPRS_DIM_MISMATCH;
-        if (P->t_dtype != dtype_of<T>::value) return SPRS_INVALID_ARGUMENT;
-    }
-    SPRS_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (P && P->v_complex) {
-        if constexpr (is_complex<T>::value) return run<T>((const T *)P->dinv, rhs, x, (int)k, max_iter, tol, its_out, res_out, status_out);
-        else return SPRS_INVALID_ARGUMENT;
-    }
-    return run<Real<T>>(P ? (const Real<T> *)P->dinv : (const Real<T> *)nullptr, rhs, x, (int)k, max_iter, tol, its_out, res_out, status_out);
+    return with_dinv<T>(P, n, [&](const auto *d) -> int {
+        SPRS_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        return run(d, rhs, x, (int)k, max_iter, tol, its_out, res_out, status_out);
+    });
 }
 
 template class CgMany<double>;

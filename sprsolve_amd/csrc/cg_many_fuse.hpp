@@ -1,5 +1,5 @@
 // Batched conjugate gradients: the vector kernels of CgMany<T> (cg_many.hip), CgKB / CgKC (cg_fuse.hpp) for a block of k <= 8
-// right-hand sides.  Every column runs the recurrence of the header's sprs_cg_* comment on its own scalars.  A fused
+// right-hand sides, run by fused_kernel (fused_launch.hpp) over the n_pad * KP elements of a block.  Every column runs the recurrence of the header's sprs_cg_* comment on its own scalars.  A fused
 // iteration is three launches whatever k is:
 //   SpMM      Q = A P with the per-column partials of conj(p_c).q_c                          (spmm.hip)
 //   CgManyKB  alpha_c = rho_c / (p_c.q_c) ; x += p alpha ; r += q (-alpha) ; [z = M^-1 r] ; partials of |r_c|^2, conj(r_c).z_c
@@ -23,7 +23,7 @@
 //     exception CgKB makes too: status[c] and `running` are written by workgroup 0 from values every workgroup computes for
 //     itself, so a reader that sees the new value takes the branch it would have taken anyway.
 #pragma once
-#include "bicg_fuse.hpp"
+#include "fused_launch.hpp"
 
 namespace sprs {
 
@@ -117,17 +117,17 @@ struct CgManyLane {
     int col[PKW];                // column of pack element e (the same on every trip)
     bool act[PKW];               // ... and whether that column is updated by this launch
     Real<T> accN[PKW]; T accR[PKW];
-    template <int PK> __device__ __forceinline__ void init(int kp) {
+    __device__ __forceinline__ void init(int kp) {
 #pragma unroll
-        for (int e = 0; e < PK; ++e) {
-            col[e] = (int)((threadIdx.x * PK + e) & (unsigned)(kp - 1));
+        for (int e = 0; e < PKW; ++e) {
+            col[e] = (int)((threadIdx.x * PKW + e) & (unsigned)(kp - 1));
             act[e] = false; accN[e] = 0.0; accR[e] = szero<T>();
         }
     }
     // row of element e of pack i (lg = log2 of the column stride)
     template <int PK> __device__ __forceinline__ static int64_t row_of(int64_t i, int e, int lg) { return (i * PK + e) >> lg; }
     // partials of this workgroup: [column][workgroup]
-    template <int PK, bool TWO> __device__ __forceinline__ void hand_over(int kp, Real<T> *partN, T *partRZ) {
+    template <bool TWO> __device__ __forceinline__ void hand_over(int kp, Real<T> *partN, T *partRZ) {
         __shared__ Real<T> smD[CGM_MAXK * NWAVE];
         __shared__ T smT[CGM_MAXK * NWAVE];
         Real<T> a[CGM_MAXK]; T b[CGM_MAXK];
@@ -135,7 +135,7 @@ struct CgManyLane {
         for (int c = 0; c < CGM_MAXK; ++c) {
             a[c] = 0.0; b[c] = szero<T>();
 #pragma unroll
-            for (int e = 0; e < PK; ++e) {
+            for (int e = 0; e < PKW; ++e) {
                 if (col[e] == c) { a[c] = a[c] + accN[e]; if (TWO) b[c] = sadd(b[c], accR[e]); }
             }
         }
@@ -158,14 +158,15 @@ template <class T>
 struct CgManyS0 {
     const T *r; Real<T> *partN; int kp, lg; int64_t n;
     CgManyLane<T> L;
-    template <int PK> __device__ __forceinline__ bool prologue() { L.template init<PK>(kp); return true; }
+    static constexpr bool whole_packs = true;      // a block is whole packs: fused_kernel (fused_launch.hpp) needs no scalar tail
+    __device__ __forceinline__ bool prologue() { L.init(kp); return true; }
     template <int PK, bool NT> __device__ __forceinline__ void run(int64_t i) {
         const auto rv = ldp<T, PK, NT>(r, i);
 #pragma unroll
         for (int e = 0; e < PK; ++e)
             if (L.template row_of<PK>(i, e, lg) < n) L.accN[e] = L.accN[e] + ssq(rv.v[e]);
     }
-    template <int PK> __device__ __forceinline__ void epilogue() { L.template hand_over<PK, false>(kp, partN, nullptr); }
+    __device__ __forceinline__ void epilogue() { L.template hand_over<false>(kp, partN, nullptr); }
 };
 
 // S1: rhs_norm_c ; zero right-hand side (x_c = 0, done) ; tol2_c = tol rhs_norm_c ; r = rhs*1 + (A x)*(-1) ; z = M^-1 r ;
@@ -176,11 +177,12 @@ struct CgManyS1 {
     const T *q; T *x; T *r; T *p; const V *dinv; T *z; Real<T> *partN; T *partRZ; int kp, lg; int64_t n;
     CgManyLane<T> L;
     bool zero[CgManyLane<T>::PKW];
-    template <int PK> __device__ __forceinline__ bool prologue() {
+    static constexpr bool whole_packs = true;
+    __device__ __forceinline__ bool prologue() {
         __shared__ Real<T> smD[CGM_MAXK * NWAVE];
         Real<T> sN[CGM_MAXK], dummy[CGM_MAXK];
         cgm_reduce<Real<T>, Real<T>, false>(partRhs, partRhs, P, P, kp, sN, dummy, smD, smD);
-        L.template init<PK>(kp);
+        L.init(kp);
         bool zc[CGM_MAXK];
 #pragma unroll
         for (int c = 0; c < CGM_MAXK; ++c) {
@@ -192,7 +194,7 @@ struct CgManyS1 {
             }
         }
 #pragma unroll
-        for (int e = 0; e < PK; ++e) { zero[e] = cgm_pick(zc, L.col[e]); L.act[e] = !zero[e]; }
+        for (int e = 0; e < CgManyLane<T>::PKW; ++e) { zero[e] = cgm_pick(zc, L.col[e]); L.act[e] = !zero[e]; }
         return true;
     }
     template <int PK, bool NT> __device__ __forceinline__ void run(int64_t i) {
@@ -220,14 +222,15 @@ struct CgManyS1 {
         if (PC) stp<T, PK, NT>(z, i, zv);
         if (any_zero) stp<T, PK, NT>(x, i, xv);
     }
-    template <int PK> __device__ __forceinline__ void epilogue() { L.template hand_over<PK, true>(kp, partN, partRZ); }
+    __device__ __forceinline__ void epilogue() { L.template hand_over<true>(kp, partN, partRZ); }
 };
 
 // S2 (one workgroup, no vector work): converged at the start? ; rho_c = conj(r_c).z_c ; running = the columns that iterate
 template <class T>
 struct CgManyS2 {
     CgManyState<T> *S; const Real<T> *partN; const T *partRZ; int P; int kp;
-    template <int PK> __device__ __forceinline__ bool prologue() {
+    static constexpr bool whole_packs = true;
+    __device__ __forceinline__ bool prologue() {
         __shared__ Real<T> smD[CGM_MAXK * NWAVE];
         __shared__ T smT[CGM_MAXK * NWAVE];
         int status[CGM_MAXK]; Real<T> tol2[CGM_MAXK];
@@ -253,7 +256,7 @@ struct CgManyS2 {
         return false;
     }
     template <int PK, bool NT> __device__ __forceinline__ void run(int64_t) {}
-    template <int PK> __device__ __forceinline__ void epilogue() {}
+    __device__ __forceinline__ void epilogue() {}
 };
 
 // KB (CgKB per column).  Reads x, p, r, q (+ dinv), writes x, r (+ z).
@@ -263,7 +266,8 @@ struct CgManyKB {
     const T *p; const T *q; T *x; T *r; const V *dinv; T *z; Real<T> *partN; T *partRZ; int kp, lg; int64_t n;
     CgManyLane<T> L;
     T alpha[CgManyLane<T>::PKW], na[CgManyLane<T>::PKW];
-    template <int PK> __device__ __forceinline__ bool prologue() {
+    static constexpr bool whole_packs = true;
+    __device__ __forceinline__ bool prologue() {
         const int running = S->running;
         if (running == 0) return false;
         __shared__ T smT[CGM_MAXK * NWAVE];
@@ -275,7 +279,7 @@ struct CgManyKB {
         }
         T pq[CGM_MAXK], dummy[CGM_MAXK];
         cgm_reduce<T, T, false>(partPQ, partPQ, strideQ, P, kp, pq, dummy, smT, smT);
-        L.template init<PK>(kp);
+        L.init(kp);
         // (every column's quotient is formed, used or not: branch-free values stay in registers)
         T al[CGM_MAXK]; bool on[CGM_MAXK];
         int stopped = 0, live = 0;
@@ -294,7 +298,7 @@ struct CgManyKB {
         if (stopped && first_thread()) S->running = running - stopped;
         if (live == 0) return false;
 #pragma unroll
-        for (int e = 0; e < PK; ++e) { L.act[e] = cgm_pick(on, L.col[e]); alpha[e] = cgm_pick(al, L.col[e]); na[e] = sneg(alpha[e]); }
+        for (int e = 0; e < CgManyLane<T>::PKW; ++e) { L.act[e] = cgm_pick(on, L.col[e]); alpha[e] = cgm_pick(al, L.col[e]); na[e] = sneg(alpha[e]); }
         return true;
     }
     template <int PK, bool NT> __device__ __forceinline__ void run(int64_t i) {
@@ -321,7 +325,7 @@ struct CgManyKB {
         stp<T, PK, NT>(r, i, rv);
         if (PC) stp<T, PK, NT>(z, i, zv);
     }
-    template <int PK> __device__ __forceinline__ void epilogue() { L.template hand_over<PK, true>(kp, partN, partRZ); }
+    __device__ __forceinline__ void epilogue() { L.template hand_over<true>(kp, partN, partRZ); }
 };
 
 // KC (CgKC per column).  Reads z (= r without a preconditioner) and p, writes p.
@@ -331,7 +335,8 @@ struct CgManyKC {
     const T *z; T *p; int kp, lg; int64_t n;
     CgManyLane<T> L;
     T beta[CgManyLane<T>::PKW];
-    template <int PK> __device__ __forceinline__ bool prologue() {
+    static constexpr bool whole_packs = true;
+    __device__ __forceinline__ bool prologue() {
         const int running = S->running;
         if (running == 0) return false;
         __shared__ Real<T> smD[CGM_MAXK * NWAVE];
@@ -345,7 +350,7 @@ struct CgManyKC {
         }
         Real<T> sN[CGM_MAXK]; T sR[CGM_MAXK];
         cgm_reduce<Real<T>, T, true>(partN, partRZ, P, P, kp, sN, sR, smD, smT);
-        L.template init<PK>(kp);
+        L.init(kp);
         T be[CGM_MAXK]; bool on[CGM_MAXK];
         int stopped = 0, live = 0;
 #pragma unroll
@@ -367,7 +372,7 @@ struct CgManyKC {
         if (stopped && first_thread()) S->running = running - stopped;
         if (live == 0) return false;
 #pragma unroll
-        for (int e = 0; e < PK; ++e) { L.act[e] = cgm_pick(on, L.col[e]); beta[e] = cgm_pick(be, L.col[e]); }
+        for (int e = 0; e < CgManyLane<T>::PKW; ++e) { L.act[e] = cgm_pick(on, L.col[e]); beta[e] = cgm_pick(be, L.col[e]); }
         return true;
     }
     template <int PK, bool NT> __device__ __forceinline__ void run(int64_t i) {
@@ -383,23 +388,8 @@ struct CgManyKC {
         }
         stp<T, PK, NT>(p, i, pv);
     }
-    template <int PK> __device__ __forceinline__ void epilogue() {}
+    __device__ __forceinline__ void epilogue() {}
 };
-
-// fused_kernel's structure (krylov.hip) for the functors above: `np` packs, no tail (the blocks are whole packs)
-template <int PK, bool NT, class F>
-__global__ __launch_bounds__(BLOCK) void cg_many_kernel(int64_t np, F f, int chunked) {
-    if (!f.template prologue<PK>()) return;
-    if (chunked) {
-        const int64_t chunk = ((np + 7) / 8 + BLOCK - 1) / BLOCK * BLOCK;
-        const int xcd = blockIdx.x & 7;
-        const int64_t end = min(np, (int64_t)(xcd + 1) * chunk), st = (int64_t)(gridDim.x >> 3) * BLOCK;
-        for (int64_t i = xcd * chunk + (int64_t)(blockIdx.x >> 3) * BLOCK + threadIdx.x; i < end; i += st) f.template run<PK, NT>(i);
-    } else {
-        for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x, st = (int64_t)gridDim.x * BLOCK; i < np; i += st) f.template run<PK, NT>(i);
-    }
-    f.template epilogue<PK>();
-}
 
 // rows x k (leading dimension k) <-> rows_pad x KP blocks; the padding of `dst` is zeroed by to_block
 template <class T>

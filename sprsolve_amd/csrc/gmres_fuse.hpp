@@ -1,4 +1,4 @@
-// Restarted GMRES' vector kernels and its single-workgroup scalar kernel (the solver itself: Gmres<T> in krylov.hip).  No
+// Restarted GMRES' vector kernels and its single-workgroup scalar kernel (the solver itself: Gmres<T> in gmres.hip).  No
 // reference analogue — the recurrence is the one stated in the header (sprs_gmres_*).  One Arnoldi step j of a fused cycle:
 //   [GmPrec   z = M^-1 v_j]                                              (Jacobi only)
 //   SpMV      w = A z                                                    (KrylovBase::spmv, any route)
@@ -19,7 +19,7 @@
 // cleared by the next cycle's GmStart).  The x update is keyed on the cycle number its GmStep recorded, so it runs exactly
 // once per cycle that made a step, the event's cycle included.
 #pragma once
-#include "bicg_fuse.hpp"
+#include "fused_launch.hpp"
 
 namespace sprs {
 

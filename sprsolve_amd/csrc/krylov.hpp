@@ -1,4 +1,25 @@
-// Solver objects behind sprs_bicgstab / sprs_minres / sprs_csminres / sprs_cg / sprs_gmres.
+// Krylov recurrences (host side, C++) over device-resident vectors and scalars: the solver objects behind sprs_bicgstab,
+// sprs_minres / sprs_csminres, sprs_cg, sprs_gmres and sprs_cg_many.  One translation unit per solver (bicgstab.hip, minres.hip,
+// cg.hip, gmres.hip, cg_many.hip), each with its recurrence comment; its kernels are the functors of its *_fuse.hpp, all run by
+// fused_kernel (fused_launch.hpp).  BiCGStab and MINRES / CSMINRES follow the reference (src/bicg_stab.rs, src/minres.rs,
+// src/cs_minres.rs); CG, GMRES and the batched CG have no reference analogue: include/sprsolve_hip.h states their recurrences.
+//
+// Two execution modes per solver (sprs_solver_set_mode; the batched CG is fused only):
+//  * fused (default): the full-vector passes of an iteration are regrouped into a few kernels (BiCGStab 13 passes -> 5 kernels,
+//    MINRES 11 -> 3, CG and GMRES: cg_fuse.hpp, gmres_fuse.hpp).  Every scalar of the recurrence lives in HBM: a kernel that
+//    needs the result of a dot product re-reduces that product's per-workgroup partials in its prologue (same partials, same
+//    order in every workgroup => bit-identical scalars everywhere) and workgroup 0 records the scalar for later kernels.  The
+//    host never waits for a scalar; it polls a status word every `poll` iterations.  After convergence / breakdown / restart
+//    request every later kernel returns at its first instruction, so x, r and the iteration number are exactly those at the
+//    moment of the event.  The arithmetic of every element keeps the reference's rounding sequence (e.g.
+//    y = (v*(-beta*w) + y*beta) + r*1, bicg_stab.rs:155-156); only the summation order of the dot products / norms differs.
+//  * literal: one kernel per reference op, scalars consumed on the host where the reference consumes them.  Slow (5 host syncs
+//    per iteration); kept as the on-GPU cross-check.
+//
+// What the hosts share is written once: KrylovBase (below; krylov_base.hip) with solve(), handoff() (a producer's partials to
+// their consumer: single GPU / mailbox / all-reduce), zero_rhs(), poll_interval(), comm_timeout(); StateBlock (the device +
+// pinned-host pair of the scalar state); with_dinv() (the preconditioner's checks and element type).  The main loops stay
+// apart: BiCGStab's restart, MINRES's deferred M3, CG's accounting of idle launches and GMRES's cycles have nothing in common.
 #pragma once
 #include "internal.hpp"
 
@@ -79,6 +100,9 @@ struct EvPair {
     bool noop = false;          // launched after a restart request, i.e. returned at once — not a measurement
 };
 
+// iterations between two reads of the status word (knob "poll")
+inline size_t poll_interval(const sprs_ctx *c) { return (size_t)(c->poll < 1 ? 1 : c->poll); }
+
 template <class T>
 class KrylovBase {
    public:
@@ -94,7 +118,7 @@ class KrylovBase {
     double *trace = nullptr;
     size_t trace_cap = 0, trace_rows = 0;
     int profile = 0;             // 0 off; 1: every SpMV launch between HIP events; k >= 2: one pair of consecutive launches in k (a sample:
-                                 // the events cost ~6 us per launch, krylov.hip profiled())
+                                 // the events cost ~6 us per launch, profiled() below)
     size_t prof_calls = 0;       // SpMV-class steps of this solve so far (sampled or not)
     std::vector<hipEvent_t> ev;
     size_t ev_used = 0;
@@ -127,7 +151,7 @@ class KrylovBase {
                      Real<T> tol, size_t *its_out, Real<T> *res_out);
     // |rhs|; a zero right-hand side answers x = 0 (*zero = true: the solve is over, *res_out holds the norm)
     int zero_rhs(const T *rhs, T *x, Real<T> *rhs_norm, Real<T> *res_out, bool *zero);
-    size_t poll_interval() const { return trace ? 1 : (size_t)(ctx->poll < 1 ? 1 : ctx->poll); }   // iterations between two reads of the status word
+    size_t poll_interval() const { return trace ? 1 : sprs::poll_interval(ctx); }   // a trace reads the state every iteration
     int comm_timeout();          // ST_COMM_TIMEOUT as the caller sees it: the error text and SPRS_ERR_RCCL
     int ew_grid() const;  // workgroups used by the fused element-wise kernels for this n
     sprs_comm *comm() const { return A->dist ? A->dist->comm : nullptr; }
@@ -254,6 +278,97 @@ class CgMany {
     template <class V>
     int run(const V *dinv, const T *rhs, T *x, int k, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out, int *status_out);
 };
+
+// ======================================================================= KrylovBase's member templates
+template <class T>
+template <class U, class W>
+int KrylovBase<T>::handoff(int slot, int P, const U *a, Part<U> *oa, const W *b, Part<W> *ob) {
+    if (!A->dist) {
+        *oa = Part<U>{a, P};
+        if (ob) *ob = Part<W>{b, P};
+        return SPRS_OK;
+    }
+    if (use_p2p()) {    // both values are in the same mailbox entries
+        *oa = Part<U>{reinterpret_cast<const U *>(mbox_entries(slot)), comm()->world, comm()->seq[slot]};
+        if (ob) *ob = Part<W>{reinterpret_cast<const W *>(mbox_entries(slot)), comm()->world, comm()->seq[slot]};
+        return SPRS_OK;
+    }
+    double *ra = red + 2 * slot, *rb = red + 2 * slot + 2;
+    SPRS_TRY(allreduce_sum(comm(), ra, (ob ? 32 : 16) / sizeof(Real<T>), sizeof(Real<T>) == 4));
+    *oa = Part<U>{reinterpret_cast<const U *>(ra), 1};
+    if (ob) *ob = Part<W>{reinterpret_cast<const W *>(rb), 1};
+    return SPRS_OK;
+}
+
+template <class T>
+template <class F>
+int KrylovBase<T>::profiled(F &&run, bool one_kernel) {
+    if (!profile) return run();
+    // The events are not free: a launch that carries them costs ~6 us more (completion signal + timestamps; measured on the
+    // 30-50 us iterations of cfg 2 / 3 / 4, and 11-13 us per cfg-5 iteration = 1 %).  profile = k >= 2 brackets one PAIR of
+    // consecutive SpMV-class steps in k (a pair: BiCGStab's K2 and K4 are sampled equally often).
+    const size_t call = prof_calls++;
+    last_pair = -1;
+    if (profile >= 2 && (call >> 1) % (size_t)profile != 0) return run();
+    if (ev_used + 2 > ev.size()) {
+        for (int k = 0; k < 2; ++k) {
+            hipEvent_t e;
+            SPRS_HIP_TRY(ctx, hipEventCreate(&e));
+            ev.push_back(e);
+        }
+    }
+    int st;
+    if (one_kernel) {
+        // one kernel per SpMV: the launch records its own begin / end (what rocprofv3 reports as the kernel's duration)
+        ctx->prof_start = ev[ev_used]; ctx->prof_stop = ev[ev_used + 1];
+        st = run();
+        ctx->prof_start = nullptr; ctx->prof_stop = nullptr;
+    } else {
+        // exchange + two launches: bracket the whole thing (includes the wait for the halo)
+        SPRS_HIP_TRY(ctx, hipEventRecord(ev[ev_used], ctx->stream));
+        st = run();
+        SPRS_HIP_TRY(ctx, hipEventRecord(ev[ev_used + 1], ctx->stream));
+    }
+    ev_pair.resize(ev_used / 2);
+    ev_pair.push_back(EvPair{call});
+    last_pair = (long)(ev_used / 2);
+    ev_used += 2;
+    return st;
+}
+
+// The preconditioner as a solve takes it: P's size and scalar type are checked, then run(dinv) is called with dinv typed
+// const T * (a complex M^-1: complex T only) or const Real<T> * (null: no preconditioner).
+template <class T, class F>
+int with_dinv(const sprs_diag *P, size_t n, F &&run) {
+    if (P && P->n != n) return SPRS_DIM_MISMATCH;
+    if (P && P->t_dtype != dtype_of<T>::value) return SPRS_INVALID_ARGUMENT;
+    if (P && P->v_complex) {
+        if constexpr (is_complex<T>::value) return run((const T *)P->dinv);
+        else return SPRS_INVALID_ARGUMENT;
+    }
+    return run(P ? (const Real<T> *)P->dinv : (const Real<T> *)nullptr);
+}
+
+template <class T>
+template <class S>
+int KrylovBase<T>::solve(S &s, bool no_precond, const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter,
+                         Real<T> tol, size_t *its_out, Real<T> *res_out) {
+    size_t its_dummy; Real<T> res_dummy;
+    if (!its_out) its_out = &its_dummy;
+    if (!res_out) res_out = &res_dummy;
+    if (rhs_len != s.n) return SPRS_INCOMPATIBLE_RHS_SIZE;                  // bicg_stab.rs:44-48, minres.rs:40-44
+    if (x_len != s.n) return SPRS_INCOMPATIBLE_X_SIZE;                      // bicg_stab.rs:49-53, minres.rs:45-49
+    if (no_precond && P) return SPRS_INVALID_ARGUMENT;                      // CSMinRes has no precond_solve
+    return with_dinv<T>(P, s.n, [&](const auto *d) -> int {
+        using V = std::remove_cv_t<std::remove_pointer_t<decltype(d)>>;
+        SPRS_TRY(s.begin_solve());
+        const int st = s.mode == 1 ? s.template run_literal<V>(d, rhs, x, max_iter, tol, its_out, res_out)
+                                   : s.template run<V>(d, rhs, x, max_iter, tol, its_out, res_out);
+        if (st >= SPRS_ERR_HIP) return st;
+        SPRS_TRY(s.end_solve());
+        return st;
+    });
+}
 
 }  // namespace sprs
 

@@ -1,13 +1,79 @@
-// MINRES' third kernel (krylov.hip) as a structure other translation units can run, and the DEFERRED form of it ("M3 deferred",
-// krylov.hip): M3 of iteration k — beta_new, the normalisation of v_new, the Givens rotation, p, x, the convergence test — is not
+// MINRES' kernels M2 and M3 (host: minres.hip); M3 as a structure other translation units can run, and the DEFERRED form of
+// it ("M3 deferred", minres.hip): M3 of iteration k — beta_new, the normalisation of v_new, the Givens rotation, p, x, the convergence test — is not
 // launched.  The SpMV of iteration k + 1 (spmv_dict.hip, the lane-per-row kernels of the compressed streams) runs M3's PROLOGUE to
 // get 1 / beta_new and multiplies by v_new[c] * (1 / beta_new) formed in its gathers; the normalised vector is never stored.
 // M3's element-wise work then rides in the same launch as M2 of iteration k + 1 (MinresM23 below), which reads v_new(k) and
 // v(k) anyway: 9 vector passes instead of M3's 8 + M2's 4, two launches per iteration instead of three.
 #pragma once
-#include "bicg_fuse.hpp"
+#include "fused_launch.hpp"
+#include "krylov.hpp"
 
 namespace sprs {
+
+// M2  minres.rs:117-120 (+ :276-278):  v_new -= beta*v_old ; v_new -= alpha*v ;
+//     partials of |v_new|^2   or, preconditioned,  w_new = M^-1 v_new and conj(v_new).w_new
+template <class T, class V, bool PC>
+struct MinresM2 {
+    MinresDev<T> *D; int par; const T *partAlpha; int P;
+    const T *v_old; const T *v; T *v_new; const V *dinv; T *w_new; Real<T> *partBeta; T *partBeta2;
+    Fin fin;                    // distributed: the last workgroup reduces partBeta / partBeta2 for the all-reduce
+    T nb, na; Real<T> accD; T accT;
+    unsigned int tag = 0; unsigned long long mb_timeout = 0;     // peer-to-peer hand-off (see BicgK1): partAlpha = this rank's mailbox entries
+    __device__ __forceinline__ bool prologue() {
+        __shared__ T smT[NWAVE];
+        const int status = D->status;                               // requested together with the partials
+        const Real<T> beta = D->st[par].beta;
+        T alpha;
+        if (tag != 0) {
+            if (status != ST_RUNNING) { fin_idle(fin, false); return false; }
+            if (!mbox_sum1(MboxSrc{reinterpret_cast<const unsigned long long *>(partAlpha), P, tag, mb_timeout}, alpha)) {
+                if (first_thread()) D->status = ST_COMM_TIMEOUT;
+                return false;
+            }
+        } else {
+            alpha = reduce_partials(partAlpha, P, smT);             // :116
+        }
+        if (status != ST_RUNNING) { fin_idle(fin, false); return false; }
+        nb = sfromr<T>(-beta);                                      // :117 T::from_real(-beta)
+        na = sneg(alpha);                                           // :118
+        accD = 0.0; accT = szero<T>();
+        if (first_thread()) D->st[par].alpha = alpha;
+        return true;
+    }
+    template <int PK, bool NT> __device__ __forceinline__ void run(int64_t i) {
+        auto nv = ldp<T, PK, NT>(v_new, i); auto ov = ldp<T, PK, NT>(v_old, i); auto cv = ldp<T, PK, NT>(v, i);
+        Pack<T, PK> wv;
+        [[maybe_unused]] Pack<V, PK> dv;
+        if (PC) dv = ldp<V, PK, NT>(dinv, i);
+#pragma unroll
+        for (int e = 0; e < PK; ++e) {
+            T t = sadd(nv.v[e], smul(ov.v[e], nb));                 // :117
+            t = sadd(t, smul(cv.v[e], na));                         // :118
+            nv.v[e] = t;
+            if (PC) {
+                wv.v[e] = smulv(t, dv.v[e]);                        // :276
+                accT = sadd(accT, smul(sconj(t), wv.v[e]));         // :278
+            } else {
+                accD = accD + ssq(t);                               // :120
+            }
+        }
+        stp<T, PK, NT>(v_new, i, nv);
+        if (PC) stp<T, PK, NT>(w_new, i, wv);
+    }
+    __device__ __forceinline__ void epilogue() {
+        __shared__ Real<T> smD[NWAVE];
+        __shared__ T smT[NWAVE];
+        if (PC) {
+            const T s = block_sum(accT, smT);
+            if (threadIdx.x == 0) st_partial(fin, partBeta2 + blockIdx.x, s);
+            if (fin.counter) finalize_last_block<T, T>(fin, false, smT, smT);
+        } else {
+            const Real<T> s = block_sum(accD, smD);
+            if (threadIdx.x == 0) st_partial(fin, partBeta + blockIdx.x, s);
+            if (fin.counter) finalize_last_block<Real<T>, Real<T>>(fin, false, smD, smD);
+        }
+    }
+};
 
 // M3  minres.rs:120-168 (cs_minres.rs:106-154 with SAUNDERS):  beta_new, normalise v_new
 //     [and w_new], Givens rotation, p = q - r2*p_old - r3*p_oold, p *= 1/r1, x += c*eta*beta_1*p,

@@ -27,7 +27,7 @@ constexpr int CH_WL = CH_ROWS + 2 * CH_W;         // 3072 doubles per window, th
 // UX: the dot operand is the input vector itself (taken from the window).  TRI: the near slots are (.., c - 1, c, c + 1, ..)
 // around an even centre offset and all other near offsets are even (every stencil with sorted columns on a grid of even line
 // length): 16-byte LDS reads, the centre's pair serves the +-1 columns' inner halves.
-// FUSE (krylov.hip, "fused SpMV input"): 0 = x is a vector in memory.  2 = x is BiCGStab's s = r + v * (-alpha) (K3 into K4:
+// FUSE (bicgstab.hip, "fused SpMV input"): 0 = x is a vector in memory.  2 = x is BiCGStab's s = r + v * (-alpha) (K3 into K4:
 // x = r, in1 = v), 3 = its p' = (v * (-beta w) + p * beta) + r (K1 into K2: x = v, in1 = p, in2 = r): `pro` is that update's kernel
 // structure — its prologue (the scalars of the recurrence and its convergence / restart / breakdown decisions, taken identically by
 // every workgroup from the same partials) runs at the top of this launch, the update itself while a window is staged, with the
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(BLOCK) void spmv_chain_kernel(const int4 *__restric
                 u4v qv;
                 __builtin_memcpy(&qv, &yy, 16);
                 __builtin_nontemporal_store(qv, reinterpret_cast<u4v *>(y + (ts + ((q * NWAVE + wv) << 7) + 2 * lane)));
-                if constexpr (FUSE == 3) {          // (K3 in K4 stores nothing: K5 forms s again, krylov.hip BicgK5<SV>)
+                if constexpr (FUSE == 3) {          // (K3 in K4 stores nothing: K5 forms s again, bicg_fuse.hpp BicgK5<SV>)
                     u4v ov;
                     __builtin_memcpy(&ov, &mine, 16);
                     __builtin_nontemporal_store(ov, reinterpret_cast<u4v *>(own + (ts + ((q * NWAVE + wv) << 7) + 2 * lane)));

@@ -404,7 +404,7 @@ __global__ __launch_bounds__(BLOCK) void spmv_dict_kernel(int n_rowblk, int xcd_
     if (DOT >= 1 && fin.counter) finalize_last_block<T, T>(fin, DOT == 2, red, red);
 }
 
-// M1 of MINRES' iteration k + 1 on the UN-NORMALISED v_new of iteration k (minres_fuse.hpp; krylov.hip "M3 deferred"): the launch runs
+// M1 of MINRES' iteration k + 1 on the UN-NORMALISED v_new of iteration k (minres_fuse.hpp; minres.hip "M3 deferred"): the launch runs
 // M3's prologue for beta_new and multiplies A by x * (1 / beta_new) formed in the gathers (ScaleEw); the dot operand is the scaled
 // row value.  x is not modified and nothing of the solver's state is written.  The stopping rule is M3's: a launch of a stopped
 // solve returns at once.

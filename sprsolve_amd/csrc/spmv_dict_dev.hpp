@@ -42,7 +42,7 @@ struct BlkLoads {
     T vv[PAIR ? 1 : ITEMS];  // values (offset-code stream only)
 };
 
-// A scaled operand for the lane-per-row walk ("M3 deferred", minres_fuse.hpp / krylov.hip): the SpMV multiplies by x[c] * scale —
+// A scaled operand for the lane-per-row walk ("M3 deferred", minres_fuse.hpp / minres.hip): the SpMV multiplies by x[c] * scale —
 // MINRES' v_new / beta_new, which is then never stored — with the product M3 would have stored (smulr), in the gathers and for the
 // dot operand of the lane's own row.
 struct NoScale { static constexpr bool ON = false; };
@@ -296,7 +296,7 @@ constexpr int UNI2_MAXLEN = 8;              // ... of at most this many codes; t
 
 // Where the two-rows-per-lane kernels take x from.  XPlain: a vector in memory.  XFused<NV>: x is the RESULT of the vector update
 // that precedes the SpMV in BiCGStab's recurrence, formed on the fly from that update's operands with the update's own rounding
-// sequence (krylov.hip, "fused SpMV input": K3 into K4, s = r + v * (-alpha), bicg_stab.rs:172; K1 into K2,
+// sequence (bicgstab.hip, "fused SpMV input": K3 into K4, s = r + v * (-alpha), bicg_stab.rs:172; K1 into K2,
 // p = (v * (-beta w) + p * beta) + r * 1, bicg_stab.rs:155-156) — the updated vector is never read back from memory.
 // ld2(soff, voff): the pair at byte offset soff (wave-uniform) + voff (per lane); ld1: one element; lds: one element at a
 // wave-uniform offset (a scalar load where the compiler can prove it).

@@ -6,7 +6,7 @@ from ._solver import _SolverBase
 class GMRES(_SolverBase):
     """`GMRES.new(A, size, restart=30)`: GMRES(restart), right-preconditioned, classical Gram-Schmidt applied twice, Givens
     rotations; restart is at most 64 (0 means 30).  The recurrence is stated in include/sprsolve_hip.h (sprs_gmres_*) and runs in
-    C++ on device-resident vectors and scalars (sprsolve_amd/csrc/krylov.hip, gmres_fuse.hpp); the handle holds restart + 4
+    C++ on device-resident vectors and scalars (sprsolve_amd/csrc/gmres.hip, gmres_fuse.hpp); the handle holds restart + 4
     work vectors.  Conventions as BiCGStab's: relative residual against |rhs|, x in/out; `iters` counts Arnoldi steps."""
     KIND = _lib.SOLVER_GMRES
     NAME = "gmres"

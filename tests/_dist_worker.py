@@ -39,7 +39,7 @@ def build_global(kind):
 
 
 class DistEmu:
-    """numpy twin of csrc/dist.hip + the distributed branches of csrc/krylov.hip."""
+    """numpy twin of csrc/dist.hip + the distributed branches of csrc/krylov_base.hip and the solvers' hosts."""
 
     def __init__(self, dist, rank, world, plan, ip_loc, data_loc, orc):
         self.dist, self.rank, self.world, self.plan, self.orc = dist, rank, world, plan, orc

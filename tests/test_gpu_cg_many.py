@@ -99,6 +99,25 @@ def _true_res(ip, ix, d, b, x):
     return np.linalg.norm(b.astype(wide) - M @ x.astype(wide)) / np.linalg.norm(b.astype(wide))
 
 
+def _assert_columns(dt, pc, k, sel, system, got, checker):
+    """Every column of one solve against the checker's: status, iteration count, residuals, solution."""
+    (ip, ix, d, B), (its, res, st, X), (cits, cres, cX) = system, got, checker
+    tol = _tol(dt)
+    for j, c in enumerate(sel):
+        err = np.max(np.abs(X[:, j] - cX[:, c])); true = _true_res(ip, ix, d, B[:, j], X[:, j])
+        print("%s pc=%d k=%d col %d: its %d (checker %d) res %.3e (checker %.3e) true %.3e max|x - checker| %.3e"
+              % (np.dtype(dt).name, pc, k, c, its[j], cits[c], res[j], cres[c], true, err))
+        assert st[j] == ref.OK
+        assert abs(int(its[j]) - int(cits[c])) <= max(5, int(cits[c]) // 4)
+        assert res[j] <= tol and true <= 10 * tol                # test_gpu_cg.py's margin on the true residual
+        if _is_single(dt):
+            assert err < (5e-3 if np.dtype(dt).kind == "c" else 2e-3)
+        else:
+            assert err <= 1e-7 * max(1.0, np.max(np.abs(cX[:, c])))
+            if its[j] == cits[c]:                                # the same iteration: the same residual but for the sums' order
+                assert np.isclose(res[j], cres[c], rtol=1e-9, atol=1e-12)
+
+
 # ------------------------------------------------------------------------------------------------ 1. against the checker
 @pytest.mark.parametrize("k", [1, 3, 4, 8])
 @pytest.mark.parametrize("pc", [False, True], ids=["none", "jacobi"])
@@ -115,20 +134,7 @@ def test_every_column_follows_the_checker(sa, dt, pc, k):
     s = sa.CGMany.new(A, n, k)
     X = np.zeros((n, k), dt)
     its, res, st = _solve(s, P, B, X, MAX_ITER, _tol(dt))       # checker: at most 26 iterations
-    tol = _tol(dt)
-    for j, c in enumerate(sel):
-        err = np.max(np.abs(X[:, j] - cX[:, c])); true = _true_res(ip, ix, d, B[:, j], X[:, j])
-        print("%s pc=%d k=%d col %d: its %d (checker %d) res %.3e (checker %.3e) true %.3e max|x - checker| %.3e"
-              % (np.dtype(dt).name, pc, k, c, its[j], cits[c], res[j], cres[c], true, err))
-        assert st[j] == ref.OK
-        assert abs(int(its[j]) - int(cits[c])) <= max(5, int(cits[c]) // 4)
-        assert res[j] <= tol and true <= 10 * tol                # test_gpu_cg.py's margin on the true residual
-        if _is_single(dt):
-            assert err < (5e-3 if np.dtype(dt).kind == "c" else 2e-3)
-        else:
-            assert err <= 1e-7 * max(1.0, np.max(np.abs(cX[:, c])))
-            if its[j] == cits[c]:                                # the same iteration: the same residual but for the sums' order
-                assert np.isclose(res[j], cres[c], rtol=1e-9, atol=1e-12)
+    _assert_columns(dt, pc, k, sel, (ip, ix, d, B), (its, res, st, X), (cits, cres, cX))
     assert s.last_status == 0
 
 
@@ -233,3 +239,38 @@ def test_entry_points(sa, dt):
     for k in (0, 9):
         with pytest.raises(ValueError):
             sa.CGMany.new(A, n, k)
+
+
+# ------------------------------------------------------------------------------------------------ 5. the grid walk's knobs
+@pytest.mark.parametrize("dt,pc,k", [(F64, False, 8), (C64, True, 3), (F32, False, 3)], ids=["float64-k8", "complex128-k3-jacobi", "float32-k3"])
+def test_walk_knobs_change_nothing_but_the_sums_order(sa, dt, pc, k):
+    """The batched functors under fused_kernel's two walks (knob ew_chunk) and two cache policies (stream_nt), on every pack width:
+    f64 k = 8: 2-wide packs, 8 000 of them, so the eighth XCD's chunk of 1 024 is cut short; c64 k = 3 with Jacobi: 1-wide packs,
+    kp = 4 with a padding column, 6 000 packs; f32 k = 3: 4-wide packs, one pack is one padded row.  stream_nt changes the cache
+    policy alone: bit-identical results.  ew_chunk regroups the partials: each run meets the checker as in section 1."""
+    ip, ix, d, Ball = _system(dt)
+    n = Ball.shape[0]
+    sel = _pick(k)
+    B = np.ascontiguousarray(Ball[:, sel])
+    cits, cres, cst, cX = _checker(dt, pc)
+    assert np.all(cst == ref.OK)
+    A = sa.HipCsr.new((n, n), ip, ix, d)
+    P = sa.DiagPrecond.new(_diag(ip, ix, d), t_dtype=d.dtype) if pc else None
+    s = sa.CGMany.new(A, n, k)
+    ctx = sa.default_ctx(0)
+    knobs = {name: ctx.get(name) for name in ("ew_chunk", "stream_nt")}
+    try:
+        for chunk in (0, 1):
+            runs = []
+            for nt in (0, 1):
+                ctx.set("ew_chunk", chunk); ctx.set("stream_nt", nt)
+                X = np.zeros((n, k), dt)
+                its, res, st = _solve(s, P, B, X, MAX_ITER, _tol(dt))
+                print("ew_chunk=%d stream_nt=%d" % (chunk, nt))
+                _assert_columns(dt, pc, k, sel, (ip, ix, d, B), (its, res, st, X), (cits, cres, cX))
+                assert s.last_status == 0
+                runs.append((np.asarray(its).tobytes(), np.asarray(res).tobytes(), np.asarray(st).tobytes(), X.tobytes()))
+            assert runs[0] == runs[1]
+    finally:
+        for name, value in knobs.items():
+            ctx.set(name, value)

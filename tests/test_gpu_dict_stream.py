@@ -890,7 +890,7 @@ def _fused_against_five_launches(sa, ctx, A, n, rhs, rhs2, x0, exact, exact_tol=
 
 @pytest.mark.parametrize("name", [k for k in _chain_cases() if k.startswith("p3_")])
 def test_fused_spmv_input_is_bit_identical(sa, oracle, name):
-    """Knob spmv_fuse (csrc/krylov.hip "fused SpMV input", csrc/spmv_chain.hip FUSE): on a handle whose SpMV runs through chains
+    """Knob spmv_fuse (csrc/bicgstab.hip "fused SpMV input", csrc/spmv_chain.hip FUSE): on a handle whose SpMV runs through chains
     BiCGStab forms K3's r -= alpha v inside K4 and K1's p = (v (-beta w) + p beta) + r inside K2 (bicg_stab.rs:155-156,172) — the
     same prologues, the same rounding sequence per element, the same dot partials.  So the three-launch iteration must reproduce
     the five-launch one BIT FOR BIT: iteration count, residual, every traced scalar, x — to convergence and for a fixed number
@@ -936,7 +936,7 @@ def _m3_cases():
 
 @pytest.mark.parametrize("name", list(_m3_cases()))
 def test_minres_m3_inside_m1_is_bit_identical(sa, oracle, name):
-    """Knob spmv_fuse for MINRES / CSMINRES (csrc/krylov.hip "M3 deferred", csrc/minres_fuse.hpp MinresM23, csrc/spmv_dict.hip
+    """Knob spmv_fuse for MINRES / CSMINRES (csrc/minres.hip "M3 deferred", csrc/minres_fuse.hpp MinresM23, csrc/spmv_dict.hip
     spmv_dict_scaled_kernel): M3 of iteration k — beta_new, the normalisation, the Givens rotation, p, x, the convergence test
     (minres.rs:120-168) — is not launched; the SpMV of iteration k + 1 multiplies by the un-normalised v_new scaled in its gathers
     and M3's element-wise work rides with M2 of iteration k + 1.  Two launches per iteration instead of three, and everything the

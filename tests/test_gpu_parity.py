@@ -892,7 +892,7 @@ def test_malformed_host_matrix_is_refused(sa):
 
 def test_sampled_spmv_profile_counts(sa, oracle):
     """sprs_solver_set_profile(k): 1 = HIP events around every SpMV launch, k >= 2 = around one pair of consecutive launches in k
-    (csrc/krylov.hip profiled(): a launch that carries events costs ~6 us).  The profile says how many launches it timed, how many
+    (csrc/krylov.hpp profiled(): a launch that carries events costs ~6 us).  The profile says how many launches it timed, how many
     of those read a dot operand that is not their input (BiCGStab's K2: r0) and how many launches the solve had; the iterates do
     not depend on it."""
     from sprsolve_amd import gen
