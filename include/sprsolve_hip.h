@@ -425,6 +425,50 @@ int sprs_gmres_precond_solve_z(sprs_gmres *S, const sprs_diag *P, const sprs_c64
 int sprs_gmres_solve_dev_d(sprs_gmres *S, const sprs_diag *P_or_null, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
 int sprs_gmres_solve_dev_z(sprs_gmres *S, const sprs_diag *P_or_null, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
 
+/* ---------------------------------------------------------------- mixed-precision iterative refinement
+ * An answer of H precision (H = f64 for _d, Complex<f64> for _z) at the byte cost of L iterations (L = f32 / Complex<f32>):
+ * the residual and the solution stay in H, every correction comes from an inner Krylov solve in L on a copy of A whose values
+ * were rounded to L once, at creation.  The reference has no such solver; conventions are the other solvers'.  Single GPU: a
+ * distributed A is refused with SPRS_INVALID_ARGUMENT (text in sprs_last_error).  Every line is one library operation per
+ * element, each arithmetic operation rounded once; fl_L rounds an H value to L (to nearest, per component), fl_H is exact:
+ *     the sums of |b|^2 and of the first |r|^2 are formed in one pass;  if norm2(b) <= eps(H::Real): x = 0, SPRS_OK,
+ *                                                                   *outer_out = 0, *res_out = norm2(b)
+ *     for k = 0, 1, ...:
+ *         r = b*1 + (A x)*(-1)                in H, the SpMV of the handle A (any route)
+ *         res = norm2(r) / norm2(b);  if res <= tol: SPRS_OK, *outer_out = k, *res_out = res
+ *         unless norm2(r) is finite: SPRS_BREAKDOWN, *outer_out = k
+ *         if k == max_outer: SPRS_INSUFFICIENT_ITER, *outer_out = max_outer, *res_out = res  (x is the last iterate)
+ *         s = norm2(r);  rl_i = fl_L(r_i * (1 / s))       1 / s rounded once in H::Real; a real scale (mul_real)
+ *         e = 0;  inner solve of A_L e = rl in L: sprs_cg_* or sprs_gmres_* as stated above with max_iter = inner_max_iter,
+ *                 tol = fl(inner_tol), P_L (P's stored 1 / diag rounded to L) or no preconditioner
+ *             SPRS_OK or SPRS_INSUFFICIENT_ITER: the correction is used
+ *             any other status is returned as this solve's, *outer_out = k, x unchanged by this step
+ *         x_i = x_i + fl_H(e_i) * s                       the product rounded (a real scale), then the sum
+ * Every inner right-hand side has norm 1, so no residual underflows in L and inner_tol means the same at every step.
+ * *inner_its_out is the sum of the inner solves' *its_out; x is in/out and is left modified on error.
+ * create: `inner` picks the inner solver, `restart` is GMRES' m (0 = 30; ignored by CG).  SPRS_INVALID_ARGUMENT (with a text)
+ * if a finite value of A leaves L's range; P's size / scalar type are checked as for the other solvers.  The handle borrows A
+ * (A's row_ptr / col_idx are shared with the L operator) and copies P; it owns the L operator (sprs_refine_low_csr returns it,
+ * borrowed: any sprs_mul_vec_*_s / _c call applies), the inner solver, one H vector, two L vectors, and two more H vectors once a
+ * solve was given host slices.  An outer step costs one SpMV in H and three launches besides its inner iterations. */
+typedef struct sprs_refine sprs_refine;
+enum { SPRS_INNER_CG = 0, SPRS_INNER_GMRES = 1 };
+int sprs_refine_create_d(const sprs_csr *A, size_t size, const sprs_diag *P_or_null, int inner, size_t restart, sprs_refine **out);
+int sprs_refine_create_z(const sprs_csr *A, size_t size, const sprs_diag *P_or_null, int inner, size_t restart, sprs_refine **out);
+int sprs_refine_destroy(sprs_refine *R);       /* NULL is a no-op */
+const sprs_csr *sprs_refine_low_csr(const sprs_refine *R);
+int sprs_refine_solve_d(sprs_refine *R, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_outer, double tol, size_t inner_max_iter, double inner_tol, size_t *outer_out, size_t *inner_its_out, double *res_out);
+int sprs_refine_solve_z(sprs_refine *R, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_outer, double tol, size_t inner_max_iter, double inner_tol, size_t *outer_out, size_t *inner_its_out, double *res_out);
+/* the same on device vectors (16-byte aligned ones are used in place) */
+int sprs_refine_solve_dev_d(sprs_refine *R, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_outer, double tol, size_t inner_max_iter, double inner_tol, size_t *outer_out, size_t *inner_its_out, double *res_out);
+int sprs_refine_solve_dev_z(sprs_refine *R, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_outer, double tol, size_t inner_max_iter, double inner_tol, size_t *outer_out, size_t *inner_its_out, double *res_out);
+/* The two mixed-precision vector operations of the recurrence on device vectors, asynchronous on the context's stream like the
+ * vecalg entry points; the scalars are real (H::Real):  out_i = fl_L(in_i * scale)  and  x_i = x_i + fl_H(in_i) * alpha. */
+int sprs_demote_scaled_dev_d(sprs_ctx *ctx, size_t n, const double *in_dev, double scale, float *out_dev);
+int sprs_demote_scaled_dev_z(sprs_ctx *ctx, size_t n, const sprs_c64 *in_dev, double scale, sprs_c32 *out_dev);
+int sprs_axpy_promoted_dev_d(sprs_ctx *ctx, size_t n, double alpha, const float *in_dev, double *x_dev);
+int sprs_axpy_promoted_dev_z(sprs_ctx *ctx, size_t n, double alpha, const sprs_c32 *in_dev, sprs_c64 *x_dev);
+
 /* ---------------------------------------------------------------- f32 / Complex<f32>
  * The reference is generic over cauchy::Scalar = {f32, f64, c32, c64} and its unit tests exercise f32 / c32
  * BLAS-1 (src/vecalg.rs:647-658,669-677,771-798,816-830).  Every typed entry point above exists again with

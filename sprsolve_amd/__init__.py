@@ -16,5 +16,6 @@ from .device import Context, DevVec, default_ctx  # noqa: F401
 from .mat import HipCsr, MatVecMul  # noqa: F401
 from .minres import MinRes  # noqa: F401
 from .precond import DiagPrecond  # noqa: F401
+from .refine import Refine  # noqa: F401
 
 __version__ = "0.1.0"

@@ -17,6 +17,7 @@ ZERO_DIAGONAL, NOT_SQUARE, NOT_CSR = 8, 9, 10
 ERR_HIP, ERR_RCCL, ERR_NO_DEVICE = 100, 101, 102
 SOLVER_BICGSTAB, SOLVER_MINRES, SOLVER_CSMINRES, SOLVER_CG, SOLVER_GMRES = 1, 2, 3, 4, 5
 GMRES_MAX_RESTART = 64
+INNER_CG, INNER_GMRES = 0, 1
 
 
 class c64(C.Structure):
@@ -110,6 +111,13 @@ def _protos():
             P["sprs_%s_precond_solve_%s" % (k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
             P["sprs_%s_solve_dev_%s" % (k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
         P["sprs_csminres_solve_dev_" + s] = [_vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
+    for s in ("d", "z"):          # mixed-precision refinement: H = f64 / c64 over L = f32 / c32; every real scalar is a double
+        P["sprs_refine_create_" + s] = [_vp, _sz, _vp, _int, _sz, _pp]
+        for k in ("solve", "solve_dev"):
+            P["sprs_refine_%s_%s" % (k, s)] = [_vp, _vp, _sz, _vp, _sz, _sz, _dbl, _sz, _dbl, _psz, _psz, _pd]
+        P["sprs_demote_scaled_dev_" + s] = [_vp, _sz, _vp, _dbl, _vp]
+        P["sprs_axpy_promoted_dev_" + s] = [_vp, _sz, _dbl, _vp, _vp]
+    P["sprs_refine_destroy"] = [_vp]
     P["sprs_axpy_zd"] = [_vp, _sz, _dbl, _vp, _vp]
     P["sprs_axpy_cs"] = [_vp, _sz, C.c_float, _vp, _vp]
     P["sprs_csr_destroy"] = [_vp]
@@ -156,7 +164,8 @@ def _protos():
 PROTOTYPES = _protos()
 # entry points declared in include/sprsolve_hip.h that return something other than int
 _SPECIAL_RET = {"sprs_last_error": C.c_char_p, "sprs_status_str": C.c_char_p, "sprs_ctx_get": _i64,
-                "sprs_gauss_seidel_levels": _i64, "sprs_csr_rows": _i64, "sprs_csr_cols": _i64, "sprs_csr_nnz": _i64, "sprs_version": _int}
+                "sprs_gauss_seidel_levels": _i64, "sprs_csr_rows": _i64, "sprs_csr_cols": _i64, "sprs_csr_nnz": _i64, "sprs_version": _int,
+                "sprs_refine_low_csr": _vp}
 
 
 def lib():
@@ -186,6 +195,7 @@ def lib():
             f = getattr(L, "sprs_csr_" + n); f.argtypes = [_vp]; f.restype = _i64
         L.sprs_version.argtypes = []; L.sprs_version.restype = _int
         L.sprs_gauss_seidel_levels.argtypes = [_vp]; L.sprs_gauss_seidel_levels.restype = _i64
+        L.sprs_refine_low_csr.argtypes = [_vp]; L.sprs_refine_low_csr.restype = _vp
         _lib = L
     return _lib
 

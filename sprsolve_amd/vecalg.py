@@ -132,3 +132,29 @@ def axpby(a, vec1, b, vec2, ctx=None):
         n = _same_len(x, y)
         check(getattr(_lib.lib(), "sprs_axpby_" + s)(ctx.h, n, _scalar(a, s), dev_ptr(x), _scalar(b, s), dev_ptr(y)), ctx.h)
         ctx.sync()
+
+
+def demote_scaled(vec_in, scale, vec_out, ctx=None):
+    """vec_out = fl_L(vec_in * scale): an f64 / c64 vector times a real scale (the product rounded in f64), then rounded once to
+    f32 / c32 — the demotion of mixed-precision refinement (sprs_demote_scaled_dev_*; no reference analogue)."""
+    ctx = _ctx(ctx)
+    with _Staged(vec_in, ctx=ctx) as x, _Staged(vec_out, out=True, ctx=ctx) as y:
+        s = dev_sfx(x)
+        n = _same_len(x, y)
+        if (s, dev_sfx(y)) not in (("d", "s"), ("z", "c")):
+            raise TypeError("demote_scaled takes f64 -> f32 or c64 -> c32 vectors")
+        check(getattr(_lib.lib(), "sprs_demote_scaled_dev_" + s)(ctx.h, n, dev_ptr(x), float(scale), dev_ptr(y)), ctx.h)
+        ctx.sync()
+
+
+def axpy_promoted(alpha, vec_in, vec, ctx=None):
+    """vec += fl_H(vec_in) * alpha: an f32 / c32 vector promoted (exactly) to f64 / c64, times a real alpha (the product
+    rounded), then the sum — the update of mixed-precision refinement (sprs_axpy_promoted_dev_*; no reference analogue)."""
+    ctx = _ctx(ctx)
+    with _Staged(vec_in, ctx=ctx) as x, _Staged(vec, out=True, ctx=ctx) as y:
+        s = dev_sfx(y)
+        n = _same_len(x, y)
+        if (s, dev_sfx(x)) not in (("d", "s"), ("z", "c")):
+            raise TypeError("axpy_promoted takes f32 -> f64 or c32 -> c64 vectors")
+        check(getattr(_lib.lib(), "sprs_axpy_promoted_dev_" + s)(ctx.h, n, float(alpha), dev_ptr(x), dev_ptr(y)), ctx.h)
+        ctx.sync()
