@@ -54,6 +54,7 @@ typedef struct sprs_bicgstab sprs_bicgstab; /* BiCGStab<T,M>                 (bi
 typedef struct sprs_minres sprs_minres;     /* MinRes<T,M>                   (minres.rs:13-27)    */
 typedef struct sprs_csminres sprs_csminres; /* CSMinRes<T,M>                 (cs_minres.rs:11-25) */
 typedef struct sprs_cg sprs_cg;             /* conjugate gradients (no reference analogue; "conjugate gradients" below) */
+typedef struct sprs_lsmr sprs_lsmr;         /* LSMR least squares on any A, rectangular included ("LSMR" below) */
 typedef struct sprs_cg_many sprs_cg_many;   /* conjugate gradients on several right-hand sides at once ("several right-hand sides" below) */
 typedef struct sprs_gmres sprs_gmres;       /* restarted GMRES (no reference analogue; "restarted GMRES" below) */
 typedef struct sprs_comm sprs_comm;         /* RCCL communicator of this rank (multi-GPU section)  */
@@ -341,6 +342,77 @@ int sprs_cg_precond_solve_z(sprs_cg *S, const sprs_diag *P, const sprs_c64 *rhs,
 int sprs_cg_solve_dev_d(sprs_cg *S, const sprs_diag *P_or_null, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
 int sprs_cg_solve_dev_z(sprs_cg *S, const sprs_diag *P_or_null, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
 
+/* ---------------------------------------------------------------- the adjoint of an operator
+ * sprs_csr_adjoint builds A^T (conjugate = 0) or A^H (conjugate != 0; the flag is ignored for real scalars) as an ordinary,
+ * independent handle of shape ncols x nrows: it owns its arrays, outlives A, and every sprs_mul_vec_* / sprs_mul_mat_* / solver
+ * entry point takes it like any other handle (it gets its row blocks, dictionary streams, tile and chain plans at creation).
+ * Row j of the result holds the entries of column j of A in ascending original row; the entries of one row of A keep their
+ * stored order, duplicates included; conjugation flips the sign of the imaginary part and nothing else.  These are exactly the
+ * arrays sprs_csr_create_* builds from A's (row_ptr, col_idx, conjugated val) passed with storage_csc = 1 and the dimensions
+ * swapped, so an SpMV through either handle has the same bits on every route.  The construction runs on the device only (count,
+ * scan, stable key sort + gather: csrc/transpose.hip), so a matrix adopted in HBM never crosses PCIe; temporary device memory:
+ * 16 bytes per entry + the result.  A distributed A: SPRS_INVALID_ARGUMENT (text in sprs_last_error). */
+int sprs_csr_adjoint(const sprs_csr *A, int conjugate, sprs_csr **out);
+/* The handle's CSR arrays copied to host memory (any pointer may be NULL): row_ptr nrows + 1 and col_idx nnz entries of int32_t,
+ * val nnz entries of the handle's scalar type. */
+int sprs_csr_read(const sprs_csr *A, int32_t *row_ptr_host, int32_t *col_idx_host, void *val_host);
+
+/* ---------------------------------------------------------------- LSMR
+ * Fong & Saunders' LSMR: x minimises |rhs - A x|_2, or with damp > 0 |[A; damp I] x - [rhs; 0]|_2, for A of ANY shape (m rows,
+ * n columns; rank-deficient and inconsistent systems included; on an under-determined system started from x = 0 the minimum-norm
+ * solution).  It runs on the Golub-Kahan bidiagonalisation and is MINRES on the normal equations in exact arithmetic.  Two SpMVs
+ * per iteration, one by A and one by its adjoint handle AH (shape n x m, the same scalar type and context; sprs_csr_adjoint(A, 1)):
+ * create borrows the caller's AH (SPRS_DIM_MISMATCH / SPRS_INVALID_ARGUMENT where shape / type do not fit) or, given NULL, builds
+ * and owns one.  The handle holds 2m + 4n of workspace.  A distributed A: SPRS_INVALID_ARGUMENT (text in sprs_last_error).
+ * x is in/out (n entries): a non-zero x is an initial guess, the recurrence runs on the correction; rhs has m entries.  Wrong
+ * lengths: SPRS_DIM_MISMATCH; damp < 0 (or NaN): SPRS_INVALID_ARGUMENT.
+ * EVERY recurrence scalar is of type T::Real, also for complex T (norms and plane rotations); only the vectors are complex.
+ * In the vector updates below a*s is the element times the real s, one rounding per real operation, and + is one addition:
+ * axpby(a, p, b, q) is q = sadd(smul(p, a), smul(q, b)).  u is kept UN-NORMALISED: in memory u = beta u_k, readers apply 1/beta.
+ * symortho(a, b) -> (c, s, r) with c a + s b = r, -s a + c b = 0:   b == 0: (sign a, 0, |a|);   a == 0: (0, sign b, |b|);
+ *     |b| > |a|: tau = a / b, s = sign(b) / sqrt(1 + tau tau), c = s tau, r = b / s;   else: tau = b / a, c = sign(a) / sqrt(1 + tau tau),
+ *     s = c tau, r = a / c        (sign 0 = 0)
+ *     normb = norm2(rhs);  if normb <= eps: x = 0, return SPRS_OK with *its_out = 0, *res_out = normb, *ares_out = 0
+ *     u = rhs*1 + (A x)*(-1);  beta = norm2(u);  not finite: SPRS_BREAKDOWN (its 0);  beta == 0: SPRS_OK, its 0, res 0, ares 0
+ *     v = AH u;  v = v*(1/beta);  alpha = norm2(v);  not finite: SPRS_BREAKDOWN;  alpha == 0: SPRS_OK, its 0, res = beta / normb, ares 0
+ *     v = v*(1/alpha);  h = v;  hbar = 0
+ *     alphabar = alpha; zetabar = alpha beta; rho = rhobar = cbar = 1; sbar = 0; betadd = beta; betad = 0; rhodold = 1;
+ *     tautildeold = thetatilde = zeta = d = 0; normA2 = alpha alpha
+ *     for its = 0 .. max_iter - 1:
+ *         V1  w = A v;  u = w*1 + u*f with f = -(alpha (1/beta))             [axpby(1, w, f, u)]
+ *         V2  beta = norm2(u);  not finite: SPRS_BREAKDOWN, *its_out = its
+ *         V3  if beta > 0:  w' = AH u;  v = w'*(1/beta) + v*(-beta)  [axpby(1/beta, w', -beta, v)];  alpha = norm2(v);  not finite:
+ *             SPRS_BREAKDOWN;   if beta == 0:  alpha = 0 and v is left alone
+ *         S1  (chat, shat, alphahat) = symortho(alphabar, damp);  rhoold = rho;  (c, s, rho) = symortho(alphahat, beta)
+ *         S2  thetanew = s alpha;  alphabar = c alpha;  rhobarold = rhobar;  zetaold = zeta;  thetabar = sbar rho
+ *         S3  (cbar, sbar, rhobar) = symortho(cbar rho, thetanew)  [the old cbar];  zeta = cbar zetabar;  zetabar = -sbar zetabar
+ *         S4  g1 = -(thetabar rho / (rhoold rhobarold));  g2 = zeta / (rho rhobar);  g3 = -(thetanew / rho)
+ *         S5  betaacute = chat betadd;  betacheck = -shat betadd;  betahat = c betaacute;  betadd = -s betaacute
+ *         S6  thetatildeold = thetatilde;  (ct, st, rt) = symortho(rhodold, thetabar);  thetatilde = st rhobar;  rhodold = ct rhobar;
+ *             betad = -st betad + ct betahat;  tautildeold = (zetaold - thetatildeold tautildeold) / rt;
+ *             taud = (zeta - thetatilde tautildeold) / rhodold;  d = d + betacheck betacheck
+ *         S7  normr = sqrt(d + (betad - taud)^2 + betadd betadd);  normA2 += beta beta;  normA = sqrt(normA2);  normA2 += alpha alpha;
+ *             normar = |zetabar|
+ *         S8  unless g1, g2, g3, normr, normA, normar are all finite: SPRS_BREAKDOWN, *its_out = its  (x as after its iterations)
+ *         V4  hbar = h*1 + hbar*g1  [axpby(1, h, g1, hbar)];  x = x + hbar*g2  [axpy(g2, hbar, x)];  if alpha > 0: v = v*(1/alpha);
+ *             h = v*1 + h*g3  [axpby(1, v, g3, h)]
+ *         T   normx = norm2(x);  SPRS_OK with *its_out = its + 1 if beta == 0 or alpha == 0 (the exact solution has been reached),
+ *             or normr <= tol normb + tol normA normx   (test 1),   or normar <= tol normA normr   (test 2)
+ *     SPRS_INSUFFICIENT_ITER, *its_out = max_iter
+ * On SPRS_OK from the loop *res_out = normr / normb and *ares_out = normar / (normA normr) (0 where that product is 0): the
+ * recurrence's estimates of |r| / |rhs| and |A^H r| / (|A|_F |r|), r = rhs - A x; no extra pass is made for them.  No condition-
+ * number limit is applied.  The fused mode (default; five launches per iteration, csrc/lsmr_fuse.hpp) evaluates T in the launch
+ * after V4 — same values, same event, whatever the context's `poll`; the literal mode runs the steps one kernel per operation.
+ * Solver kind SPRS_SOLVER_LSMR for sprs_solver_set_mode / set_trace / the profile getters.  Trace row, one per iteration that
+ * reached T: [its, normr, normar, 0, alpha, 0, beta, 0]. */
+int sprs_lsmr_destroy(sprs_lsmr *S);           /* NULL is a no-op */
+int sprs_lsmr_create_d(const sprs_csr *A, const sprs_csr *AH_or_null, sprs_lsmr **out);
+int sprs_lsmr_solve_d(sprs_lsmr *S, const double *rhs, size_t rhs_len, double *x, size_t x_len, double damp, size_t max_iter, double tol, size_t *its_out, double *res_out, double *ares_out);
+int sprs_lsmr_solve_dev_d(sprs_lsmr *S, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, double damp, size_t max_iter, double tol, size_t *its_out, double *res_out, double *ares_out);
+int sprs_lsmr_create_z(const sprs_csr *A, const sprs_csr *AH_or_null, sprs_lsmr **out);
+int sprs_lsmr_solve_z(sprs_lsmr *S, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, double damp, size_t max_iter, double tol, size_t *its_out, double *res_out, double *ares_out);
+int sprs_lsmr_solve_dev_z(sprs_lsmr *S, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, double damp, size_t max_iter, double tol, size_t *its_out, double *res_out, double *ares_out);
+
 /* ---------------------------------------------------------------- several right-hand sides at once: SpMM and batched CG
  * A block of k vectors (1 <= k <= 8) is an n x k ROW-MAJOR array: the k values of row i are contiguous (numpy's C order
  * of an (n, k) array).  Single GPU: a distributed operator is refused with SPRS_INVALID_ARGUMENT (text in sprs_last_error).
@@ -554,6 +626,12 @@ int sprs_mul_mat_dev_c(const sprs_csr *A, const sprs_c32 *x_dev, sprs_c32 *y_dev
 int sprs_cgmany_create_c(const sprs_csr *A, size_t size, size_t k, sprs_cg_many **out);
 int sprs_cgmany_solve_c(sprs_cg_many *S, const sprs_diag *P_or_null, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t k, size_t max_iter, float tol, size_t *its_out, float *res_out, int *status_out);
 int sprs_cgmany_solve_dev_c(sprs_cg_many *S, const sprs_diag *P_or_null, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t k, size_t max_iter, float tol, size_t *its_out, float *res_out, int *status_out);
+int sprs_lsmr_create_s(const sprs_csr *A, const sprs_csr *AH_or_null, sprs_lsmr **out);
+int sprs_lsmr_solve_s(sprs_lsmr *S, const float *rhs, size_t rhs_len, float *x, size_t x_len, float damp, size_t max_iter, float tol, size_t *its_out, float *res_out, float *ares_out);
+int sprs_lsmr_solve_dev_s(sprs_lsmr *S, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, float damp, size_t max_iter, float tol, size_t *its_out, float *res_out, float *ares_out);
+int sprs_lsmr_create_c(const sprs_csr *A, const sprs_csr *AH_or_null, sprs_lsmr **out);
+int sprs_lsmr_solve_c(sprs_lsmr *S, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, float damp, size_t max_iter, float tol, size_t *its_out, float *res_out, float *ares_out);
+int sprs_lsmr_solve_dev_c(sprs_lsmr *S, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, float damp, size_t max_iter, float tol, size_t *its_out, float *res_out, float *ares_out);
 int sprs_gmres_create_s(const sprs_csr *A, size_t size, size_t restart, sprs_gmres **out);
 int sprs_gmres_create_c(const sprs_csr *A, size_t size, size_t restart, sprs_gmres **out);
 int sprs_gmres_solve_s(sprs_gmres *S, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
@@ -629,14 +707,15 @@ int sprs_dist_mul_vec_dev_d(const sprs_csr *A, double *x_ext_dev, double *y_loca
 int sprs_dist_mul_vec_dev_z(const sprs_csr *A, sprs_c64 *x_ext_dev, sprs_c64 *y_local_dev);
 
 /* ---------------------------------------------------------------- solver options / instrumentation
- * `solver` is any of the four solver handle types. */
-enum { SPRS_SOLVER_BICGSTAB = 1, SPRS_SOLVER_MINRES = 2, SPRS_SOLVER_CSMINRES = 3, SPRS_SOLVER_CG = 4, SPRS_SOLVER_GMRES = 5 };
+ * `solver` is a handle of any of the solver types below, `kind` says which. */
+enum { SPRS_SOLVER_BICGSTAB = 1, SPRS_SOLVER_MINRES = 2, SPRS_SOLVER_CSMINRES = 3, SPRS_SOLVER_CG = 4, SPRS_SOLVER_GMRES = 5, SPRS_SOLVER_LSMR = 6 };
 /* mode 0 (default): fused kernels, device-resident scalars, lazy host polling.
  * mode 1: "literal" — the reference's op list one kernel per op, every scalar consumed on the
  *         host exactly where the reference consumes it (bicg_stab.rs:122-197). */
 int sprs_solver_set_mode(void *solver, int kind, int mode);
 /* Per-iteration scalar trace (8 doubles per row: BiCGStab [its, r_norm, rho, alpha, w]; MINRES [its, beta, alpha, c, s, res_norm];
- * CG [its, r_norm, rho, alpha, beta]): the solver
+ * CG [its, r_norm, rho, alpha, beta]; LSMR [its, normr, normar, alpha, beta], each scalar in a (re, im) pair — LSMR's scalars
+ * are real, so its imaginary slots hold 0, as the sprs_lsmr_* section says): the solver
  * synchronises every iteration while a trace buffer is set.  rows_out: rows written by the last solve. */
 int sprs_solver_set_trace(void *solver, int kind, double *trace_host, size_t capacity_rows);
 int sprs_solver_trace_rows(const void *solver, int kind, size_t *rows_out);

@@ -15,7 +15,7 @@ CSRC = os.path.join(_HERE, "csrc")
  INVALID_ARGUMENT) = range(8)
 ZERO_DIAGONAL, NOT_SQUARE, NOT_CSR = 8, 9, 10
 ERR_HIP, ERR_RCCL, ERR_NO_DEVICE = 100, 101, 102
-SOLVER_BICGSTAB, SOLVER_MINRES, SOLVER_CSMINRES, SOLVER_CG, SOLVER_GMRES = 1, 2, 3, 4, 5
+SOLVER_BICGSTAB, SOLVER_MINRES, SOLVER_CSMINRES, SOLVER_CG, SOLVER_GMRES, SOLVER_LSMR = 1, 2, 3, 4, 5, 6
 GMRES_MAX_RESTART = 64
 INNER_CG, INNER_GMRES = 0, 1
 
@@ -92,6 +92,9 @@ def _protos():
         P["sprs_cgmany_create_" + s] = [_vp, _sz, _sz, _pp]
         for k in ("solve", "solve_dev"):
             P["sprs_cgmany_%s_%s" % (k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, _sz, re_, _psz, pre, C.POINTER(_int)]
+        P["sprs_lsmr_create_" + s] = [_vp, _vp, _pp]
+        for k in ("solve", "solve_dev"):
+            P["sprs_lsmr_%s_%s" % (k, s)] = [_vp, _vp, _sz, _vp, _sz, re_, _sz, re_, _psz, pre, pre]
         P["sprs_dot_" + s] = [_vp, _sz, _vp, _vp, _vp]
         P["sprs_conj_dot_" + s] = [_vp, _sz, _vp, _vp, _vp]
         P["sprs_norm2_" + s] = [_vp, _sz, _vp, pre]
@@ -121,7 +124,9 @@ def _protos():
     P["sprs_axpy_zd"] = [_vp, _sz, _dbl, _vp, _vp]
     P["sprs_axpy_cs"] = [_vp, _sz, C.c_float, _vp, _vp]
     P["sprs_csr_destroy"] = [_vp]
-    for k in ("bicgstab", "minres", "csminres", "cg", "gmres", "cgmany"):
+    P["sprs_csr_adjoint"] = [_vp, _int, _pp]
+    P["sprs_csr_read"] = [_vp, _vp, _vp, _vp]
+    for k in ("bicgstab", "minres", "csminres", "cg", "gmres", "cgmany", "lsmr"):
         P["sprs_%s_destroy" % k] = [_vp]
     for s in ("d", "zd", "z", "s", "cs", "c"):
         P["sprs_diag_precond_create_" + s] = [_vp, _sz, _vp, _pp]

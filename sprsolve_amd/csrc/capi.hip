@@ -557,6 +557,54 @@ int solve_many(CgMany<T> *s, bool host, const sprs_diag *P, const T *rhs, size_t
     return st;
 }
 
+// LSMR's handle: A of any shape, its adjoint handle borrowed (checked here) or built by the solver
+template <class T>
+int lsmr_create(const sprs_csr *A, const sprs_csr *AH, sprs_lsmr **out) {
+    if (!A || !out) return SPRS_INVALID_ARGUMENT;
+    *out = nullptr;
+    if (A->dtype != dtype_of<T>::value) return SPRS_INVALID_ARGUMENT;
+    if (A->dist || (AH && AH->dist)) {
+        snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_lsmr: distributed operators are not supported (single GPU only)");
+        return SPRS_INVALID_ARGUMENT;
+    }
+    if (AH && (AH->dtype != A->dtype || AH->ctx != A->ctx)) return SPRS_INVALID_ARGUMENT;
+    if (AH && (AH->nrows != A->ncols || AH->ncols != A->nrows)) return SPRS_DIM_MISMATCH;
+    CtxLock lock(A->ctx);
+    sprs_lsmr *h = new sprs_lsmr();
+    h->dtype = dtype_of<T>::value;
+    auto *s = new Lsmr<T>();
+    h->impl = s;
+    const int st = s->create(A, AH);
+    if (st != SPRS_OK) { s->destroy(); delete s; delete h; return st; }
+    *out = h;
+    return SPRS_OK;
+}
+
+// One LSMR solve: rhs of nrows, x of ncols entries.  Host slices, and device vectors that are not 16-byte aligned, go through the
+// solver's staging buffers.
+template <class T>
+int lsmr_solve(Lsmr<T> *s, bool host, const T *rhs, size_t rl, T *x, size_t xl, Real<T> damp, size_t max_iter, Real<T> tol, size_t *its,
+               Real<T> *res, Real<T> *ares) {
+    if (!s || !rhs || !x) return SPRS_INVALID_ARGUMENT;
+    if (rl != s->m || xl != s->nc) return SPRS_DIM_MISMATCH;                 // nothing is copied on a mismatch
+    if (!(damp >= (Real<T>)0)) return SPRS_INVALID_ARGUMENT;
+    sprs_ctx *c = s->ctx;
+    CtxLock lock(c);
+    if (!host && ((reinterpret_cast<uintptr_t>(rhs) | reinterpret_cast<uintptr_t>(x)) & 15) == 0)
+        return s->solve_dev(rhs, rl, x, xl, damp, max_iter, tol, its, res, ares);
+    const hipMemcpyKind in = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, out = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    SPRS_HIP_TRY(c, hipSetDevice(c->device));
+    if (!s->rhs_buf) SPRS_HIP_TRY(c, hipMalloc((void **)&s->rhs_buf, sizeof(T) * s->stride));
+    if (!s->x_buf) SPRS_HIP_TRY(c, hipMalloc((void **)&s->x_buf, sizeof(T) * s->stride_n));
+    SPRS_HIP_TRY(c, hipMemcpyAsync(s->rhs_buf, rhs, sizeof(T) * rl, in, c->stream));
+    SPRS_HIP_TRY(c, hipMemcpyAsync(s->x_buf, x, sizeof(T) * xl, in, c->stream));
+    const int st = s->solve_dev(s->rhs_buf, rl, s->x_buf, xl, damp, max_iter, tol, its, res, ares);
+    if (st >= SPRS_ERR_HIP) return st;
+    SPRS_HIP_TRY(c, hipMemcpyAsync(x, s->x_buf, sizeof(T) * xl, out, c->stream));   // x is in/out and is left modified on an error too
+    SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return st;
+}
+
 // the S<T> behind a handle, or null where the handle holds another scalar type
 template <template <class> class S, class T>
 S<T> *impl_of(sprs_solver_handle *h) { return (h && h->dtype == dtype_of<T>::value) ? (S<T> *)h->impl : nullptr; }
@@ -572,6 +620,7 @@ static int with_base(void *solver, int kind, F &&f) {
         case SPRS_SOLVER_BICGSTAB: return with_solver<BicgStab>(h->dtype, h->impl, f);
         case SPRS_SOLVER_CG: return with_solver<Cg>(h->dtype, h->impl, f);
         case SPRS_SOLVER_GMRES: return with_solver<Gmres>(h->dtype, h->impl, f);
+        case SPRS_SOLVER_LSMR: return with_solver<Lsmr>(h->dtype, h->impl, f);
         case SPRS_SOLVER_MINRES:
         case SPRS_SOLVER_CSMINRES: return with_solver<MinRes>(h->dtype, h->impl, f);
     }
@@ -620,6 +669,19 @@ int sprs_csr_destroy(sprs_csr *A) {
 int64_t sprs_csr_rows(const sprs_csr *A) { return A ? A->nrows : -1; }
 int64_t sprs_csr_cols(const sprs_csr *A) { return A ? A->ncols : -1; }
 int64_t sprs_csr_nnz(const sprs_csr *A) { return A ? A->nnz : -1; }
+// The handle's CSR arrays copied to the host (any pointer may be NULL): row_ptr nrows + 1 and col_idx nnz entries of i32, val nnz
+// entries of the handle's scalar type.
+int sprs_csr_read(const sprs_csr *A, int32_t *row_ptr_host, int32_t *col_idx_host, void *val_host) {
+    if (!A) return SPRS_INVALID_ARGUMENT;
+    sprs_ctx *c = A->ctx;
+    CtxLock lock(c);
+    SPRS_HIP_TRY(c, hipSetDevice(c->device));
+    if (row_ptr_host) SPRS_HIP_TRY(c, hipMemcpyAsync(row_ptr_host, A->row_ptr, sizeof(int32_t) * ((size_t)A->nrows + 1), hipMemcpyDeviceToHost, c->stream));
+    if (col_idx_host && A->nnz) SPRS_HIP_TRY(c, hipMemcpyAsync(col_idx_host, A->col_idx, sizeof(int32_t) * (size_t)A->nnz, hipMemcpyDeviceToHost, c->stream));
+    if (val_host && A->nnz) SPRS_HIP_TRY(c, hipMemcpyAsync(val_host, A->val, dtype_size(A->dtype) * (size_t)A->nnz, hipMemcpyDeviceToHost, c->stream));
+    SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SPRS_OK;
+}
 int sprs_csr_wide_blocks(const sprs_csr *A, int64_t *n_blocks, int64_t *n_uniform) {
     if (!A || !n_blocks || !n_uniform) return SPRS_INVALID_ARGUMENT;
     *n_blocks = 0; *n_uniform = 0;
@@ -700,6 +762,7 @@ int sprs_csminres_destroy(sprs_csminres *S) { return solver_destroy<MinRes>(S); 
 int sprs_cg_destroy(sprs_cg *S) { return solver_destroy<Cg>(S); }
 int sprs_gmres_destroy(sprs_gmres *S) { return solver_destroy<Gmres>(S); }
 int sprs_cgmany_destroy(sprs_cg_many *S) { return solver_destroy<CgMany>(S); }
+int sprs_lsmr_destroy(sprs_lsmr *S) { return solver_destroy<Lsmr>(S); }
 
 // ---- a solver's entry points per scalar type.  NAME = the handle is sprs_NAME, S = its class, CREATE = the arguments of S<T>::create
 #define SPRS_SOLVER_SOLVES(X, T, CT, R, NAME, S)                                                                       \
@@ -763,6 +826,14 @@ int sprs_cgmany_destroy(sprs_cg_many *S) { return solver_destroy<CgMany>(S); }
     int sprs_cgmany_solve_dev_##X(sprs_cg_many *h, const sprs_diag *P, const CT *rhs, size_t rl, CT *x, size_t xl, size_t k, size_t mi, R tol, \
                                    size_t *its, R *res, int *status) {                                                 \
         SPRS_G(return solve_many<T>(impl_of<CgMany, T>(h), false, P, (const T *)rhs, rl, (T *)x, xl, k, mi, tol, its, res, status);) \
+    }                                                                                                                  \
+    /* LSMR: A of any shape and its adjoint handle (NULL: built and owned by the solver) */                            \
+    int sprs_lsmr_create_##X(const sprs_csr *A, const sprs_csr *AH, sprs_lsmr **out) { SPRS_G(return lsmr_create<T>(A, AH, out);) } \
+    int sprs_lsmr_solve_##X(sprs_lsmr *h, const CT *rhs, size_t rl, CT *x, size_t xl, R damp, size_t mi, R tol, size_t *its, R *res, R *ares) { \
+        SPRS_G(return lsmr_solve<T>(impl_of<Lsmr, T>(h), true, (const T *)rhs, rl, (T *)x, xl, damp, mi, tol, its, res, ares);) \
+    }                                                                                                                  \
+    int sprs_lsmr_solve_dev_##X(sprs_lsmr *h, const CT *rhs, size_t rl, CT *x, size_t xl, R damp, size_t mi, R tol, size_t *its, R *res, R *ares) { \
+        SPRS_G(return lsmr_solve<T>(impl_of<Lsmr, T>(h), false, (const T *)rhs, rl, (T *)x, xl, damp, mi, tol, its, res, ares);) \
     }                                                                                                                  \
     int sprs_dot_##X(sprs_ctx *c, size_t n, const CT *x, const CT *y, CT *o) { SPRS_CHK(c && o); return dot_host<T>(c, n, (const T *)x, (const T *)y, false, (T *)o); } \
     int sprs_conj_dot_##X(sprs_ctx *c, size_t n, const CT *x, const CT *y, CT *o) { SPRS_CHK(c && o); return dot_host<T>(c, n, (const T *)x, (const T *)y, true, (T *)o); } \

@@ -1,8 +1,8 @@
 // Krylov recurrences (host side, C++) over device-resident vectors and scalars: the solver objects behind sprs_bicgstab,
-// sprs_minres / sprs_csminres, sprs_cg, sprs_gmres and sprs_cg_many.  One translation unit per solver (bicgstab.hip, minres.hip,
-// cg.hip, gmres.hip, cg_many.hip), each with its recurrence comment; its kernels are the functors of its *_fuse.hpp, all run by
+// sprs_minres / sprs_csminres, sprs_cg, sprs_gmres, sprs_cg_many and sprs_lsmr.  One translation unit per solver (bicgstab.hip, minres.hip,
+// cg.hip, gmres.hip, cg_many.hip, lsmr.hip), each with its recurrence comment; its kernels are the functors of its *_fuse.hpp, all run by
 // fused_kernel (fused_launch.hpp).  BiCGStab and MINRES / CSMINRES follow the reference (src/bicg_stab.rs, src/minres.rs,
-// src/cs_minres.rs); CG, GMRES and the batched CG have no reference analogue: include/sprsolve_hip.h states their recurrences.
+// src/cs_minres.rs); CG, GMRES, the batched CG and LSMR have no reference analogue: include/sprsolve_hip.h states their recurrences.
 //
 // Two execution modes per solver (sprs_solver_set_mode; the batched CG is fused only):
 //  * fused (default): the full-vector passes of an iteration are regrouped into a few kernels (BiCGStab 13 passes -> 5 kernels,
@@ -51,6 +51,8 @@ struct MinresDev {
 
 template <class T> struct CgState;   // cg_fuse.hpp
 template <class T> struct GmresState;   // gmres_fuse.hpp
+template <class R> struct LsDev;       // lsmr_fuse.hpp
+template <class R> struct LsIter;
 
 struct SolverStats {
     double spmv_ms = 0.0, solve_ms = 0.0;
@@ -252,6 +254,33 @@ class Gmres : public KrylovBase<T> {
     int run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
 };
 
+// LSMR for min |rhs - A x|_2 (+ damping) on any A, rectangular included (recurrence: include/sprsolve_hip.h, sprs_lsmr_*; kernels:
+// lsmr_fuse.hpp).  Two operators and two vector lengths: KrylovBase carries A, the m = rows side (u, w) and everything that
+// is not tied to a length (context, poll, trace, profile, partial slots); the n = cols side (v, w', h, hbar) is held here.
+template <class T>
+class Lsmr : public KrylovBase<T> {
+   public:
+    using R = Real<T>;
+    StateBlock<LsDev<R>> state;
+    const sprs_csr *AH = nullptr;   // the adjoint handle: the caller's, or built here (own_AH)
+    sprs_csr *own_AH = nullptr;
+    size_t m = 0, nc = 0, stride_n = 0;
+    T *work_n = nullptr;         // 4 * stride_n
+    int create(const sprs_csr *A, const sprs_csr *AH_or_null);
+    void destroy();
+    // rhs: m entries, x: nc entries, both on the device and 16-byte aligned
+    int solve_dev(const T *rhs, size_t rhs_len, T *x, size_t x_len, R damp, size_t max_iter, R tol, size_t *its_out, R *res_out, R *ares_out);
+
+   private:
+    T *nvec_(int i) { return work_n + (size_t)i * stride_n; }
+    int mul(const sprs_csr *M, const T *x, T *y, const int *status);          // y = M x, profiled like KrylovBase::spmv
+    int grid_of(size_t len) const;
+    // what both modes share: |rhs|, u = rhs - A x, beta, v = A^H u / beta, alpha, h = v, hbar = 0; done: answered already
+    int start(const T *rhs, T *x, R damp, LsIter<R> *s0, R *normb, bool *done, R *res_out, R *ares_out);
+    int run(const T *rhs, T *x, R damp, size_t max_iter, R tol, size_t *its_out, R *res_out, R *ares_out);
+    int run_literal(const T *rhs, T *x, R damp, size_t max_iter, R tol, size_t *its_out, R *res_out, R *ares_out);
+};
+
 // Conjugate gradients on a block of up to kmax <= 8 right-hand sides at once (cg_many.hip; kernels: spmm.hip, cg_many_fuse.hpp).
 // Every column runs Cg<T>'s recurrence on its own scalars and stops on its own events.  Single GPU, fused mode only.
 template <class T> struct CgManyState;   // cg_many_fuse.hpp
@@ -383,3 +412,4 @@ struct sprs_csminres : sprs_solver_handle {};
 struct sprs_cg : sprs_solver_handle {};
 struct sprs_gmres : sprs_solver_handle {};
 struct sprs_cg_many : sprs_solver_handle {};
+struct sprs_lsmr : sprs_solver_handle {};

@@ -82,6 +82,22 @@ class HipCsr(MatVecMul):
         from .device import NP_OF
         return cls(h, ctx, NP_OF[s], shape, keepalive=(indptr_dev, indices_dev, data_dev) if adopt else None)
 
+    def adjoint(self, conjugate=True):
+        """A^H (conjugate=True) or A^T as an independent handle of shape (cols, rows), built on the device from this handle's
+        arrays (csrc/transpose.hip): the arrays `new(..., storage="CSC")` builds from them, so SpMV through either has the same
+        bits.  The flag is ignored for real dtypes."""
+        h = C.c_void_p()
+        check(_lib.lib().sprs_csr_adjoint(self.h, 1 if conjugate else 0, C.byref(h)), self.ctx.h)
+        return HipCsr(h, self.ctx, self.dtype, (self.shape[1], self.shape[0]))     # owning, whatever view `self` is
+
+    def to_host(self):
+        """(indptr, indices, data) of the handle's CSR arrays, copied from the device."""
+        nnz = self.nnz()
+        ip = np.empty(self.shape[0] + 1, np.int32); ix = np.empty(nnz, np.int32); d = np.empty(nnz, self.dtype)
+        check(_lib.lib().sprs_csr_read(self.h, ip.ctypes.data_as(C.c_void_p), ix.ctypes.data_as(C.c_void_p),
+                                       d.ctypes.data_as(C.c_void_p)), self.ctx.h)
+        return ip, ix, d
+
     # -------------------------------------------------------------- accessors
     def rows(self):
         return self.shape[0]
