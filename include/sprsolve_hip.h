@@ -59,6 +59,7 @@ typedef struct sprs_cg_many sprs_cg_many;   /* conjugate gradients on several ri
 typedef struct sprs_gmres sprs_gmres;       /* restarted GMRES (no reference analogue; "restarted GMRES" below) */
 typedef struct sprs_comm sprs_comm;         /* RCCL communicator of this rank (multi-GPU section)  */
 typedef struct sprs_gauss_seidel sprs_gauss_seidel; /* GaussSeidel<T>        (gauss_seidel.rs:8-31) */
+/* sprs_ilu0, the ILU(0) preconditioner handle, is declared with its section ("ILU(0) preconditioner" below) */
 
 /* ---------------------------------------------------------------- context */
 /* device: HIP device ordinal.  stream: an existing hipStream_t to run on (e.g. the caller's
@@ -644,6 +645,67 @@ int sprs_dist_csr_create_dev_s(sprs_comm *comm, int64_t n_local, int64_t n_ext, 
 int sprs_dist_csr_create_dev_c(sprs_comm *comm, int64_t n_local, int64_t n_ext, int64_t nnz, const int32_t *dev_row_ptr, const int32_t *dev_col_idx_ext, const sprs_c32 *dev_val, int adopt, int n_peers, const int32_t *peer_rank, const int64_t *send_off, const int32_t *send_idx_dev, const int64_t *recv_off, sprs_csr **out);
 int sprs_dist_mul_vec_dev_s(const sprs_csr *A, float *x_ext_dev, float *y_local_dev);
 int sprs_dist_mul_vec_dev_c(const sprs_csr *A, sprs_c32 *x_ext_dev, sprs_c32 *y_local_dev);
+
+/* ---------------------------------------------------------------- ILU(0) preconditioner
+ * The incomplete LU factorisation of a square, single-GPU CSR handle on A's own pattern (any of the four scalar types, taken
+ * from A), and the two triangular solves that apply it: z = U^-1 (L^-1 r), L unit lower.  The reference has no such
+ * preconditioner.  The handle owns everything it derives and borrows nothing from A after creation.
+ * create:  SPRS_NOT_SQUARE;  SPRS_INVALID_ARGUMENT (text in sprs_last_error) for a distributed A and for a row whose column
+ * indices are not strictly ascending (unsorted or duplicate);  SPRS_ZERO_DIAGONAL with *row_out = the smallest row that stores
+ * no diagonal entry.  A handle created from CSC arrays is accepted (it is CSR by then).  *row_out is -1 otherwise.
+ * The factorisation, in place on a copy of A's values (sdiv, ssub, smul: one scalar operation each, rounded once, complex
+ * ones by the naive formulas; nothing is fused):
+ *     for i = 0 .. n - 1 in order:
+ *         for each stored entry of row i with column k < i, ascending:
+ *             l = a_ik / u_kk;  a_ik = l
+ *             for each stored entry of row i with column j > k, ascending:  if row k stores column j:  a_ij = a_ij - l*u_kj
+ * After all rows: if a pivot u_ii is exactly zero or not finite, SPRS_ZERO_DIAGONAL with *row_out = the smallest such row and
+ * no handle (rows downstream of that row simply carry the inf or NaN).
+ * Levels: level(i) = 1 + max level(k) over the stored k < i (0 without one); for the upper solve ulevel(i) = 1 + max ulevel(j)
+ * over the stored j > i, from the last row down.  The rows of one level are independent in the factorisation and in the
+ * solves; the device runs level after level, one lane per row, so factors and solves have the bits of the serial loops.
+ * The solves (which = 1: out = L^-1 in, 2: out = U^-1 in, 0: out = U^-1 (L^-1 in); another value is SPRS_INVALID_ARGUMENT):
+ *     forward,  i = 0 .. n - 1:  sigma = 0;  for stored k < i ascending: sigma = sigma + l_ik*y_k;  y_i = r_i - sigma
+ *     backward, i = n - 1 .. 0:  sigma = 0;  for stored j > i ascending: sigma = sigma + u_ij*z_j;  z_i = (y_i - sigma) / u_ii
+ * (a division, not a stored reciprocal).  The factors are kept level by level in 64-row slices, slice-column-major, so a
+ * wavefront's loads are coalesced; a run of consecutive levels of at most 256 rows each (at most 128 levels) is one launch of
+ * one workgroup, a larger level one launch: sprs_ilu0_levels reports the levels and the launches of one solve of each kind.
+ * The _dev solves are asynchronous on the context's stream; in == out is allowed; the handle owns the intermediate y of a
+ * which = 0 solve, so calls on one context serialise.  Host slices of the wrong length: SPRS_DIM_MISMATCH.
+ * sprs_ilu0_read: the nnz factor values at A's CSR positions, l_ik below the diagonal, u_ij on and above it.
+ * Solvers: a handle of another scalar type or context than the solver's A, a distributed A, or a NULL P is
+ * SPRS_INVALID_ARGUMENT; another size is SPRS_DIM_MISMATCH.  z = P r, z = P v_j and u = P u of the recurrences are the
+ * which = 0 solve; everything else (events, *its_out / *res_out, trace rows, both modes) is as stated for the solvers. */
+typedef struct sprs_ilu0 sprs_ilu0;
+int sprs_ilu0_create(const sprs_csr *A, sprs_ilu0 **out, int64_t *row_out);   /* row_out may be NULL */
+int sprs_ilu0_destroy(sprs_ilu0 *P);           /* NULL is a no-op */
+int sprs_ilu0_levels(const sprs_ilu0 *P, int64_t *lower_levels, int64_t *upper_levels, int64_t *lower_launches, int64_t *upper_launches);   /* any pointer may be NULL */
+int sprs_ilu0_read(const sprs_ilu0 *P, void *val_host);
+int sprs_ilu0_solve_dev_d(const sprs_ilu0 *P, int which, const double *in_dev, double *out_dev);
+int sprs_ilu0_solve_dev_z(const sprs_ilu0 *P, int which, const sprs_c64 *in_dev, sprs_c64 *out_dev);
+int sprs_ilu0_solve_dev_s(const sprs_ilu0 *P, int which, const float *in_dev, float *out_dev);
+int sprs_ilu0_solve_dev_c(const sprs_ilu0 *P, int which, const sprs_c32 *in_dev, sprs_c32 *out_dev);
+int sprs_ilu0_solve_d(const sprs_ilu0 *P, int which, const double *in_host, size_t in_len, double *out_host, size_t out_len);
+int sprs_ilu0_solve_z(const sprs_ilu0 *P, int which, const sprs_c64 *in_host, size_t in_len, sprs_c64 *out_host, size_t out_len);
+int sprs_ilu0_solve_s(const sprs_ilu0 *P, int which, const float *in_host, size_t in_len, float *out_host, size_t out_len);
+int sprs_ilu0_solve_c(const sprs_ilu0 *P, int which, const sprs_c32 *in_host, size_t in_len, sprs_c32 *out_host, size_t out_len);
+/* CG and GMRES preconditioned by ILU(0): the recurrences of sprs_cg_* and sprs_gmres_* with P = the which = 0 solve */
+int sprs_ilu0_cg_solve_d(sprs_cg *S, const sprs_ilu0 *P, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_ilu0_cg_solve_z(sprs_cg *S, const sprs_ilu0 *P, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_ilu0_cg_solve_s(sprs_cg *S, const sprs_ilu0 *P, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_ilu0_cg_solve_c(sprs_cg *S, const sprs_ilu0 *P, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_ilu0_cg_solve_dev_d(sprs_cg *S, const sprs_ilu0 *P, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_ilu0_cg_solve_dev_z(sprs_cg *S, const sprs_ilu0 *P, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_ilu0_cg_solve_dev_s(sprs_cg *S, const sprs_ilu0 *P, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_ilu0_cg_solve_dev_c(sprs_cg *S, const sprs_ilu0 *P, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_ilu0_gmres_solve_d(sprs_gmres *S, const sprs_ilu0 *P, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_ilu0_gmres_solve_z(sprs_gmres *S, const sprs_ilu0 *P, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_ilu0_gmres_solve_s(sprs_gmres *S, const sprs_ilu0 *P, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_ilu0_gmres_solve_c(sprs_gmres *S, const sprs_ilu0 *P, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_ilu0_gmres_solve_dev_d(sprs_gmres *S, const sprs_ilu0 *P, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_ilu0_gmres_solve_dev_z(sprs_gmres *S, const sprs_ilu0 *P, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_ilu0_gmres_solve_dev_s(sprs_gmres *S, const sprs_ilu0 *P, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_ilu0_gmres_solve_dev_c(sprs_gmres *S, const sprs_ilu0 *P, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
 
 /* ---------------------------------------------------------------- multi-GPU (one process per GPU)
  * No reference analogue: the reference is single-process (rayon).  The matrix is row-partitioned;

@@ -114,6 +114,11 @@ def _protos():
             P["sprs_%s_precond_solve_%s" % (k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
             P["sprs_%s_solve_dev_%s" % (k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
         P["sprs_csminres_solve_dev_" + s] = [_vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
+        P["sprs_ilu0_solve_dev_" + s] = [_vp, _int, _vp, _vp]
+        P["sprs_ilu0_solve_" + s] = [_vp, _int, _vp, _sz, _vp, _sz]
+        for k in ("cg", "gmres"):
+            P["sprs_ilu0_%s_solve_%s" % (k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
+            P["sprs_ilu0_%s_solve_dev_%s" % (k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
     for s in ("d", "z"):          # mixed-precision refinement: H = f64 / c64 over L = f32 / c32; every real scalar is a double
         P["sprs_refine_create_" + s] = [_vp, _sz, _vp, _int, _sz, _pp]
         for k in ("solve", "solve_dev"):
@@ -151,6 +156,10 @@ def _protos():
     P["sprs_csr_tile_plan"] = [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]
     P["sprs_csr_chain_plan"] = [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]
     P["sprs_csr_spmv_route"] = [_vp, _int, _int, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int), C.POINTER(_i64), C.POINTER(_int), C.POINTER(_int)]
+    P["sprs_ilu0_create"] = [_vp, _pp, C.POINTER(_i64)]
+    P["sprs_ilu0_destroy"] = [_vp]
+    P["sprs_ilu0_levels"] = [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]
+    P["sprs_ilu0_read"] = [_vp, _vp]
     P["sprs_gauss_seidel_create"] = [_vp, _pp]
     P["sprs_gauss_seidel_destroy"] = [_vp]
     for s in ("d", "s"):

@@ -1,6 +1,7 @@
 """Conjugate gradients for Hermitian positive-definite operators (no reference analogue)."""
 from . import _lib
 from ._solver import _SolverBase
+from .ilu import ILU0
 
 
 class CG(_SolverBase):
@@ -15,5 +16,7 @@ class CG(_SolverBase):
         return self._solve(None, rhs, x, max_iter, tol, False)
 
     def precond_solve(self, precond, rhs, x, max_iter, tol):
-        """Jacobi-preconditioned; InvalidPreconditioner where conj(r).M^-1 r is not positive."""
+        """Preconditioned by a `DiagPrecond` (Jacobi) or an `ILU0`; InvalidPreconditioner where conj(r).M^-1 r is not positive."""
+        if isinstance(precond, ILU0):
+            return self._solve_ilu(precond, rhs, x, max_iter, tol)
         return self._solve(precond, rhs, x, max_iter, tol, True)

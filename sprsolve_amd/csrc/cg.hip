@@ -166,6 +166,141 @@ int Cg<T>::solve_dev(const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, siz
     return KrylovBase<T>::solve(*this, false, P, rhs, rhs_len, x, x_len, max_iter, tol, its_out, res_out);
 }
 
+// ---------------------------------------------------------------------------------------------- ILU(0)-preconditioned
+// The same recurrence with z = P r = U^-1 (L^-1 r) (ilu0.hip).  Fused: CA, CgKB without a preconditioner, the solves into z,
+// CgRZ (the partials of conj(r).z), CgKC — no host wait inside an iteration.  Once the status word has left ST_RUNNING the
+// solves still run: they read r and write only z and the handle's scratch, never x, r or p.
+template <class T>
+int Cg<T>::start_ilu(const sprs_ilu0 *P, const T *rhs, T *x, Real<T> tol, Real<T> *rhs_norm, Real<T> *tol2, T *rho, bool *done, Real<T> *res_out) {
+    sprs_ctx *c = this->ctx;
+    const size_t n = this->n;
+    T *r = this->vec(0), *p = this->vec(1), *z = this->vec(3);
+    SPRS_TRY(this->zero_rhs(rhs, x, rhs_norm, res_out, done));
+    if (*done) return SPRS_OK;
+    *done = true;
+    *tol2 = tol * *rhs_norm;
+    SPRS_TRY(this->spmv(x, r, 0, nullptr, nullptr, nullptr, nullptr));      // r = A x
+    SPRS_TRY(launch_axpby<T>(c, n, sone<T>(), rhs, sneg(sone<T>()), r));    // r = rhs*1 + r*(-1)
+    Real<T> r_norm = 0.0;
+    SPRS_TRY(this->norm2(r, &r_norm));
+    if (r_norm <= *tol2) { *res_out = r_norm / *rhs_norm; return SPRS_OK; }
+    SPRS_TRY(ilu0_apply<T>(P, 0, r, z));                                    // z = P r
+    SPRS_TRY(dcopy(c, p, z, n));                                            // p = z
+    SPRS_TRY(this->cdot(r, z, rho));                                        // rho = conj(r).z
+    *done = false;
+    return SPRS_OK;
+}
+
+template <class T>
+int Cg<T>::run_ilu(const sprs_ilu0 *P, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out) {
+    sprs_ctx *c = this->ctx;
+    const size_t n = this->n;
+    *its_out = 0; *res_out = 0.0;
+    T *r = this->vec(0), *p = this->vec(1), *q = this->vec(2), *z = this->vec(3);
+
+    Real<T> rhs_norm = 0.0, tol2 = 0.0;
+    T rho = szero<T>();
+    bool done;
+    SPRS_TRY(start_ilu(P, rhs, x, tol, &rhs_norm, &tol2, &rho, &done, res_out));
+    if (done) return SPRS_OK;
+
+    CgState<T> &H = *state.host;
+    CgState<T> *const d_state = state.dev;
+    memset(&H, 0, sizeof(H));
+    H.rho = rho; H.rho_prev = rho; H.tol2 = tol2;
+    H.its = 0; H.status = ST_RUNNING;
+    SPRS_TRY(state.push());
+    const int *d_status = &d_state->status;
+
+    const int G = this->ew_grid();
+    const int cw = fused_chunked(this->A) ? 1 : 0;
+    const int GS = spmv_num_partials(this->A);
+    Real<T> *partN = this->dslot(0);
+    T *partRZ = this->pslot(0), *partPQ = this->pslot(1);
+    using V = Real<T>;
+
+    auto iteration = [&]() -> int {
+        SPRS_TRY(this->spmv(p, q, 1, p, partPQ, nullptr, d_status, false, nullptr));                 // q = A p ; conj(p).q
+        SPRS_TRY(launch_fused<T>(c, n, G, cw, CgKB<T, V, false>{d_state, partPQ, GS, p, q, x, r, (const V *)nullptr, r, partN, partRZ, Fin{}, T(), T(), 0.0, T()}));
+        SPRS_TRY(ilu0_apply<T>(P, 0, r, z));                                                         // z = P r
+        SPRS_TRY(launch_fused<T>(c, n, G, cw, CgRZ<T>{d_state, r, z, partRZ, T()}));
+        return launch_fused<T>(c, n, G, cw, CgKC<T, true>{d_state, partN, partRZ, G, z, p, T(), T()});
+    };
+
+    const bool tracing = this->trace != nullptr;
+    const size_t poll = this->poll_interval();
+    size_t its = 0, since_poll = 0;
+    while (true) {
+        const bool done_enqueue = its >= max_iter;
+        if (!done_enqueue) {
+            SPRS_TRY(iteration());
+            ++its; ++since_poll;
+        }
+        if (done_enqueue || since_poll >= poll) {
+            since_poll = 0;
+            SPRS_TRY(state.fetch());
+            if (H.status != ST_RUNNING && its > (size_t)H.its) this->profile_discard_last(its - (size_t)H.its - (H.status == ST_CONVERGED ? 0 : 1));
+            if (H.status == ST_CONVERGED) {
+                *its_out = (size_t)H.its; *res_out = H.r_norm / rhs_norm;
+                return SPRS_OK;
+            }
+            if (H.status == ST_BREAKDOWN) {
+                *its_out = (size_t)H.its;
+                return SPRS_BREAKDOWN;
+            }
+            if (H.status == ST_INVALID_PC) {
+                *its_out = (size_t)H.its; *res_out = H.pc_re;
+                return SPRS_INVALID_PRECOND;
+            }
+            if (tracing && !done_enqueue) this->trace_row((double)(H.its - 1), H.r_norm, H.rho, H.alpha, H.beta);
+            if (done_enqueue) break;
+        }
+    }
+    *its_out = max_iter;
+    return SPRS_INSUFFICIENT_ITER;
+}
+
+template <class T>
+int Cg<T>::run_literal_ilu(const sprs_ilu0 *P, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out) {
+    sprs_ctx *c = this->ctx;
+    const size_t n = this->n;
+    *its_out = 0; *res_out = 0.0;
+    T *r = this->vec(0), *p = this->vec(1), *q = this->vec(2), *z = this->vec(3);
+    Real<T> rhs_norm = 0.0, tol2 = 0.0;
+    T rho = szero<T>();
+    bool done;
+    SPRS_TRY(start_ilu(P, rhs, x, tol, &rhs_norm, &tol2, &rho, &done, res_out));
+    if (done) return SPRS_OK;
+    for (size_t its = 0; its < max_iter; ++its) {
+        SPRS_TRY(this->spmv(p, q, 0, nullptr, nullptr, nullptr, nullptr));
+        T pq;
+        SPRS_TRY(this->cdot(p, q, &pq));
+        if (!(sre(pq) > 0.0)) { *its_out = its; return SPRS_BREAKDOWN; }
+        const T alpha = sdiv(rho, pq);
+        SPRS_TRY((launch_axpy<T, T>(c, n, alpha, p, x)));
+        SPRS_TRY((launch_axpy<T, T>(c, n, sneg(alpha), q, r)));
+        Real<T> r_norm = 0.0;
+        SPRS_TRY(this->norm2(r, &r_norm));
+        if (r_norm <= tol2) { *its_out = its + 1; *res_out = r_norm / rhs_norm; return SPRS_OK; }
+        SPRS_TRY(ilu0_apply<T>(P, 0, r, z));
+        T rho_new;
+        SPRS_TRY(this->cdot(r, z, &rho_new));
+        if (!(sre(rho_new) > 0.0)) { *its_out = its; *res_out = sre(rho_new); return SPRS_INVALID_PRECOND; }
+        const T beta = sdiv(rho_new, rho);
+        rho = rho_new;
+        SPRS_TRY(launch_axpby<T>(c, n, sone<T>(), z, beta, p));
+        this->trace_row((double)its, r_norm, rho, alpha, beta);
+    }
+    *its_out = max_iter;
+    return SPRS_INSUFFICIENT_ITER;
+}
+
+template <class T>
+int Cg<T>::solve_dev_ilu(const sprs_ilu0 *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
+                         size_t *its_out, Real<T> *res_out) {
+    return KrylovBase<T>::solve_ilu(*this, P, rhs, rhs_len, x, x_len, max_iter, tol, its_out, res_out);
+}
+
 template class Cg<double>;
 template class Cg<float>;
 template class Cg<cplxf>;

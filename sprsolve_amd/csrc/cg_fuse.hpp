@@ -116,4 +116,27 @@ struct CgKC {
     __device__ __forceinline__ void epilogue() const {}
 };
 
+// RZ (ILU(0) only): z = P r is a chain of launches of its own between KB and KC (the triangular solves, ilu0.hip), so KB runs
+//      without a preconditioner and this pass forms the partials of conj(r).z that KC expects.  Reads r and z.
+template <class T>
+struct CgRZ {
+    const CgState<T> *S; const T *r; const T *z; T *partRZ;
+    T accR;
+    __device__ __forceinline__ bool prologue() {
+        if (S->status != ST_RUNNING) return false;
+        accR = szero<T>();
+        return true;
+    }
+    template <int PK, bool NT> __device__ __forceinline__ void run(int64_t i) {
+        const auto rv = ldp<T, PK, NT>(r, i); const auto zv = ldp<T, PK, NT>(z, i);
+#pragma unroll
+        for (int e = 0; e < PK; ++e) accR = sadd(accR, smul(sconj(rv.v[e]), zv.v[e]));          // conj_dot(r, z)
+    }
+    __device__ __forceinline__ void epilogue() {
+        __shared__ T smT[NWAVE];
+        const T sR = block_sum(accR, smT);
+        if (threadIdx.x == 0) partRZ[blockIdx.x] = sR;
+    }
+};
+
 }  // namespace sprs

@@ -267,6 +267,48 @@ struct GmXUpdate {
     __device__ __forceinline__ void epilogue() const {}
 };
 
+// ---- GmUForm / GmXAdd (ILU(0) only): GmXUpdate in two halves around the triangular solves u = P u (ilu0.hip), both keyed on the
+// cycle GmStep recorded.  GmUForm: u = sum_{i < k} v_i y_i (from zero, i ascending).  GmXAdd: x += u*1.
+template <class T>
+struct GmUForm {
+    const GmresState<T> *S; long long cycle; const T *Vb; int64_t vstride; T *u;
+    const T *yv; int k;
+    __device__ __forceinline__ bool prologue() {
+        __shared__ T ys[GM_MAXM];
+        const long long xc = S->hd.x_cycle;
+        k = S->hd.kx;
+        if (threadIdx.x < GM_MAXM) ys[threadIdx.x] = S->y[threadIdx.x];
+        __syncthreads();
+        yv = ys;
+        return xc == cycle && k > 0;
+    }
+    template <int PK, bool NT> __device__ __forceinline__ void run(int64_t i) const {
+        Pack<T, PK> uv;
+#pragma unroll
+        for (int e = 0; e < PK; ++e) uv.v[e] = szero<T>();
+        for (int c = 0; c < k; ++c) {
+            const auto vv = ldp<T, PK, NT>(Vb + (int64_t)c * vstride, i);
+            const T yy = yv[c];
+#pragma unroll
+            for (int e = 0; e < PK; ++e) uv.v[e] = sadd(uv.v[e], smul(vv.v[e], yy));             // axpy(y_i, v_i, u)
+        }
+        stp<T, PK, NT>(u, i, uv);
+    }
+    __device__ __forceinline__ void epilogue() const {}
+};
+template <class T>
+struct GmXAdd {
+    const GmresState<T> *S; long long cycle; const T *u; T *x;
+    __device__ __forceinline__ bool prologue() const { return S->hd.x_cycle == cycle && S->hd.kx > 0; }
+    template <int PK, bool NT> __device__ __forceinline__ void run(int64_t i) const {
+        auto xv = ldp<T, PK, NT>(x, i); const auto uv = ldp<T, PK, NT>(u, i);
+#pragma unroll
+        for (int e = 0; e < PK; ++e) xv.v[e] = sadd(xv.v[e], smul(uv.v[e], sone<T>()));          // axpy(1, u, x)
+        stp<T, PK, NT>(x, i, xv);
+    }
+    __device__ __forceinline__ void epilogue() const {}
+};
+
 // ======================================================================= the O(m) scalar work: one workgroup, thread 0
 // The header's scalar lines, shared by the kernel and the literal mode's host loop (same operations, same order).
 // Rotations 0 .. j-1 on the column h[0 .. j], rotation j from (h[j], hn), g; R's column j.  Returns |g_{j+1}|.

@@ -1,0 +1,465 @@
+// ILU(0): the incomplete LU factorisation on A's own pattern, and the two triangular solves that apply it as a preconditioner
+// (z = U^-1 (L^-1 r), L unit lower).  No reference analogue; the arithmetic is the serial loop stated in the header (sprs_ilu0_*).
+//
+// gs.hip's idea carries the whole file: rows are grouped into dependency levels (level(i) = 1 + max level(k) over the stored
+// k < i; for the upper solve the same from the last row down), the rows of one level are independent, and ONE LANE folds ONE
+// ROW left to right — so factors and solves are bit-identical to the serial loop for all four scalar types.  What gs.hip does
+// not have:
+//  * Level-major storage.  L's strictly-lower entries and U's strictly-upper entries (the pivots apart) are re-laid level by
+//    level at creation: the rows of a level in ascending order, in slices of 64 rows, each slice stored slice-column-major —
+//    lane t of a wavefront reads entry e of its row at base + e * 64 + t, so every value and column load is one coalesced
+//    wavefront load instead of a walk through 64 scattered CSR rows.  Row lengths are kept per row and the padded slots are
+//    SKIPPED, never multiplied by zero (0 * inf and -0.0 would change bits).  A slice never spans two levels.
+//  * Small levels are batched.  A maximal run of consecutive levels of at most BLOCK rows each (at most ILU_MAX_BATCH_LEVELS of
+//    them) is ONE launch of ONE workgroup that loops over the levels with __syncthreads() between them: the head and the tail
+//    of a 3-D wavefront, every level of a 2-D grid, a tridiagonal matrix.  The vector being solved for is read and written
+//    through plain pointers there, and the barrier orders one level's stores before the next level's loads (all wavefronts of
+//    a workgroup share one CU and its L1).  A level of more than BLOCK rows is one launch of its own.  No kernel ever waits for
+//    another workgroup: stream order between launches is the only inter-workgroup synchronisation.
+// The factorisation runs on the same plan over a copy of A's values in CSR order (one lane per row, the row-k match by a
+// two-pointer merge); the level-major copies are laid out from its result.
+#include <algorithm>
+
+#include "device.hpp"
+
+using namespace sprs;
+
+namespace sprs {
+constexpr int ILU_SLICE = WAVE;              // rows per slice = lanes of a wavefront
+// Levels per batched launch: bounds the run time of one kernel on a chain-like matrix (a level costs the one workgroup a few
+// dependent memory round trips, some microseconds; 128 of them stay well below a millisecond).
+constexpr int ILU_MAX_BATCH_LEVELS = 128;
+}  // namespace sprs
+
+namespace {
+
+struct IluLaunch { int32_t l0, l1; bool batch; };   // levels [l0, l1): one workgroup looping over them, or (l1 == l0 + 1) one level
+
+// runs of small levels -> one launch each, every larger level -> its own
+std::vector<IluLaunch> make_plan(const std::vector<int32_t> &lvl_ptr) {
+    std::vector<IluLaunch> plan;
+    const int32_t nlev = (int32_t)lvl_ptr.size() - 1;
+    for (int32_t l = 0; l < nlev; ++l) {
+        const bool small = lvl_ptr[l + 1] - lvl_ptr[l] <= BLOCK;
+        if (small && !plan.empty() && plan.back().batch && plan.back().l1 == l && l - plan.back().l0 < ILU_MAX_BATCH_LEVELS) plan.back().l1 = l + 1;
+        else plan.push_back(IluLaunch{l, l + 1, small});
+    }
+    return plan;
+}
+
+// One triangular factor in level-major storage.
+struct IluTri {
+    int32_t nlev = 0, nslice = 0;
+    std::vector<int32_t> h_lvl_slice;    // host: level l owns slices [h_lvl_slice[l], h_lvl_slice[l + 1])
+    std::vector<IluLaunch> plan;
+    int32_t *lvl_slice = nullptr;        // device copy
+    int32_t *prow = nullptr;             // device, nslice * 64: the row of (slice, lane), -1 = no row
+    int32_t *plen = nullptr;             // device, nslice * 64: its number of entries
+    int64_t *sbase = nullptr;            // device, nslice: first slot of the slice in col / val
+    int32_t *col = nullptr;              // device, slots
+    void *val = nullptr;                 // device, slots of T
+    void *piv = nullptr;                 // device, nslice * 64 of T: u_ii (upper factor only)
+    void release() {
+        for (void *p : {(void *)lvl_slice, (void *)prow, (void *)plen, (void *)sbase, (void *)col, val, piv}) if (p) (void)hipFree(p);
+        lvl_slice = prow = plen = col = nullptr; sbase = nullptr; val = piv = nullptr;
+    }
+};
+
+template <class T>
+struct TriDev {
+    const int32_t *lvl_slice, *prow, *plen;
+    const int64_t *sbase;
+    const int32_t *col;
+    const T *val, *piv;
+};
+
+// One row by one lane: sigma over the row's entries in ascending column order, then the row's own element.  `in` and `out` may
+// be the same vector; out[c] of an entry was written by an earlier level.
+template <class T, bool UPPER>
+__device__ __forceinline__ void tri_row(const TriDev<T> &F, int s, int t, const T *in, T *out) {
+    const int p = s * ILU_SLICE + t;
+    const int row = F.prow[p];
+    if (row < 0) return;
+    const int len = F.plen[p];
+    const int64_t b = F.sbase[s] + t;
+    T sigma = szero<T>();
+    int e = 0;
+    for (; e + 4 <= len; e += 4) {                                   // four gathers in flight, folded in order
+        int c[4]; T v[4], x[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { c[u] = F.col[b + (int64_t)(e + u) * ILU_SLICE]; v[u] = F.val[b + (int64_t)(e + u) * ILU_SLICE]; }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) x[u] = out[c[u]];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) sigma = sadd(sigma, smul(v[u], x[u]));
+    }
+    for (; e < len; ++e) sigma = sadd(sigma, smul(F.val[b + (int64_t)e * ILU_SLICE], out[F.col[b + (int64_t)e * ILU_SLICE]]));
+    const T d = ssub(in[row], sigma);
+    if (UPPER) out[row] = sdiv(d, F.piv[p]);
+    else out[row] = d;
+}
+
+// a level of more than BLOCK rows: one wavefront per slice
+template <class T, bool UPPER>
+__global__ __launch_bounds__(BLOCK) void tri_level_kernel(TriDev<T> F, int s0, int s1, const T *in, T *out) {
+    const int s = s0 + (int)blockIdx.x * NWAVE + (int)(threadIdx.x >> 6);
+    if (s < s1) tri_row<T, UPPER>(F, s, threadIdx.x & (WAVE - 1), in, out);
+}
+
+// levels [l0, l1) of at most BLOCK rows (NWAVE slices) each: one workgroup, a barrier between two levels
+template <class T, bool UPPER>
+__global__ __launch_bounds__(BLOCK) void tri_batch_kernel(TriDev<T> F, int l0, int l1, const T *in, T *out) {
+    const int w = threadIdx.x >> 6, t = threadIdx.x & (WAVE - 1);
+    for (int l = l0; l < l1; ++l) {
+        const int s = F.lvl_slice[l] + w;
+        if (s < F.lvl_slice[l + 1]) tri_row<T, UPPER>(F, s, t, in, out);
+        __syncthreads();
+    }
+}
+
+// ---- the factorisation, in place on `a` (CSR order): row i by one lane
+template <class T>
+__device__ __forceinline__ void ilu_row(int i, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                        const int32_t *__restrict__ dpos, T *a) {
+    const int end = rp[i + 1];
+    for (int pk = rp[i]; pk < end; ++pk) {
+        const int k = ci[pk];
+        if (k >= i) break;
+        const int dk = dpos[k];
+        const T l = sdiv(a[pk], a[dk]);
+        a[pk] = l;
+        int q = dk + 1;
+        const int qe = rp[k + 1];
+        for (int pj = pk + 1; pj < end && q < qe;) {                 // columns j > k that rows i and k both store
+            const int cj = ci[pj], cq = ci[q];
+            if (cj == cq) { a[pj] = ssub(a[pj], smul(l, a[q])); ++pj; ++q; }
+            else if (cj < cq) ++pj;
+            else ++q;
+        }
+    }
+}
+
+template <class T>
+__global__ __launch_bounds__(BLOCK) void ilu_level_kernel(int count, const int32_t *__restrict__ rows, const int32_t *__restrict__ rp,
+                                                          const int32_t *__restrict__ ci, const int32_t *__restrict__ dpos, T *a) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i < count) ilu_row<T>(rows[i], rp, ci, dpos, a);
+}
+
+template <class T>
+__global__ __launch_bounds__(BLOCK) void ilu_batch_kernel(const int32_t *__restrict__ lvl_ptr, int l0, int l1, const int32_t *__restrict__ rows,
+                                                          const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
+                                                          const int32_t *__restrict__ dpos, T *a) {
+    for (int l = l0; l < l1; ++l) {
+        const int i = lvl_ptr[l] + (int)threadIdx.x;
+        if (i < lvl_ptr[l + 1]) ilu_row<T>(rows[i], rp, ci, dpos, a);
+        __syncthreads();
+    }
+}
+
+// smallest row whose pivot is exactly zero or not finite
+template <class T>
+__global__ __launch_bounds__(BLOCK) void ilu_pivot_check_kernel(int n, const int32_t *__restrict__ dpos, const T *__restrict__ a, int *__restrict__ bad) {
+    for (int row = blockIdx.x * BLOCK + threadIdx.x; row < n; row += gridDim.x * BLOCK) {
+        const T u = a[dpos[row]];
+        const Real<T> re = sre(u), im = sim(u);
+        if (!isfinite(re) || !isfinite(im) || (re == Real<T>(0) && im == Real<T>(0))) atomicMin(bad, row);
+    }
+}
+
+}  // namespace
+
+struct sprs_ilu0 {
+    sprs_ctx *ctx = nullptr;
+    int dtype = 0;
+    int64_t n = 0, nnz = 0;
+    void *fval = nullptr;                // device, nnz of T: the factors at A's CSR positions (sprs_ilu0_read)
+    IluTri L, U;
+    void *ybuf = nullptr;                // device, n of T: y = L^-1 in of a which = 0 solve
+    void *in_tmp = nullptr, *out_tmp = nullptr;   // staging of the host entry points (lazily allocated)
+};
+
+namespace {
+
+template <class T>
+TriDev<T> tri_dev(const IluTri &F) {
+    return TriDev<T>{F.lvl_slice, F.prow, F.plen, F.sbase, F.col, (const T *)F.val, (const T *)F.piv};
+}
+
+// out = F^-1 in: the launches of the factor's plan, asynchronous on the context's stream
+template <class T, bool UPPER>
+int tri_solve(sprs_ctx *c, const IluTri &F, const T *in, T *out) {
+    const TriDev<T> D = tri_dev<T>(F);
+    for (const IluLaunch &p : F.plan) {
+        if (p.batch) {
+            hipLaunchKernelGGL((tri_batch_kernel<T, UPPER>), dim3(1), dim3(BLOCK), 0, c->stream, D, p.l0, p.l1, in, out);
+        } else {
+            const int s0 = F.h_lvl_slice[p.l0], s1 = F.h_lvl_slice[p.l1];
+            hipLaunchKernelGGL((tri_level_kernel<T, UPPER>), dim3((s1 - s0 + NWAVE - 1) / NWAVE), dim3(BLOCK), 0, c->stream, D, s0, s1, in, out);
+        }
+    }
+    SPRS_HIP_TRY(c, hipGetLastError());
+    return SPRS_OK;
+}
+
+template <class U>
+bool upload(U **dst, const std::vector<U> &src, size_t pad = 1) {
+    if (hipMalloc((void **)dst, sizeof(U) * (src.size() + pad)) != hipSuccess) return false;
+    return src.empty() || hipMemcpy(*dst, src.data(), sizeof(U) * src.size(), hipMemcpyHostToDevice) == hipSuccess;
+}
+
+// rows in level order (ascending inside a level) and the levels' extents
+void group_by_level(const std::vector<int32_t> &level, int32_t nlev, std::vector<int32_t> &lvl_ptr, std::vector<int32_t> &rows) {
+    const size_t n = level.size();
+    lvl_ptr.assign((size_t)nlev + 1, 0);
+    for (size_t i = 0; i < n; ++i) lvl_ptr[(size_t)level[i] + 1]++;
+    for (int32_t l = 0; l < nlev; ++l) lvl_ptr[l + 1] += lvl_ptr[l];
+    std::vector<int32_t> fill(lvl_ptr.begin(), lvl_ptr.end() - 1);
+    rows.resize(n);
+    for (size_t i = 0; i < n; ++i) rows[(size_t)fill[level[i]]++] = (int32_t)i;
+}
+
+// Level-major layout of one factor.  Row i's entries are the CSR positions [eb(i), ee(i)); fv holds the factorised values.
+template <class T, class EB, class EE>
+int build_tri(IluTri &F, const std::vector<int32_t> &lvl_ptr, const std::vector<int32_t> &rows, const std::vector<int32_t> &ci,
+              const std::vector<T> &fv, EB eb, EE ee, const std::vector<int32_t> *dpos) {
+    const int32_t nlev = (int32_t)lvl_ptr.size() - 1;
+    F.nlev = nlev;
+    F.h_lvl_slice.assign((size_t)nlev + 1, 0);
+    for (int32_t l = 0; l < nlev; ++l) F.h_lvl_slice[l + 1] = F.h_lvl_slice[l] + (lvl_ptr[l + 1] - lvl_ptr[l] + ILU_SLICE - 1) / ILU_SLICE;
+    F.nslice = F.h_lvl_slice[nlev];
+    F.plan = make_plan(lvl_ptr);
+    const size_t np = (size_t)F.nslice * ILU_SLICE;
+    std::vector<int32_t> prow(np, -1), plen(np, 0);
+    std::vector<int64_t> sbase((size_t)F.nslice, 0);
+    std::vector<T> piv(dpos ? np : 0, sone<T>());
+    int64_t slots = 0;
+    for (int32_t l = 0; l < nlev; ++l)
+        for (int32_t s = F.h_lvl_slice[l]; s < F.h_lvl_slice[l + 1]; ++s) {
+            const int32_t r0 = lvl_ptr[l] + (s - F.h_lvl_slice[l]) * ILU_SLICE, r1 = std::min(r0 + ILU_SLICE, lvl_ptr[l + 1]);
+            int32_t width = 0;
+            for (int32_t r = r0; r < r1; ++r) {
+                const int32_t i = rows[r], len = ee(i) - eb(i);
+                const size_t p = (size_t)s * ILU_SLICE + (size_t)(r - r0);
+                prow[p] = i; plen[p] = len;
+                if (dpos) piv[p] = fv[(size_t)(*dpos)[i]];
+                width = std::max(width, len);
+            }
+            sbase[s] = slots;
+            slots += (int64_t)width * ILU_SLICE;
+        }
+    std::vector<int32_t> col((size_t)slots, 0);
+    std::vector<T> val((size_t)slots, szero<T>());
+    for (int32_t s = 0; s < F.nslice; ++s)
+        for (int t = 0; t < ILU_SLICE; ++t) {
+            const size_t p = (size_t)s * ILU_SLICE + t;
+            if (prow[p] < 0) continue;
+            const int32_t b = eb(prow[p]);
+            for (int32_t e = 0; e < plen[p]; ++e) {
+                const size_t d = (size_t)sbase[s] + (size_t)e * ILU_SLICE + t;
+                col[d] = ci[(size_t)b + e]; val[d] = fv[(size_t)b + e];
+            }
+        }
+    T *dval = nullptr, *dpiv = nullptr;
+    bool ok = upload(&F.lvl_slice, F.h_lvl_slice) && upload(&F.prow, prow) && upload(&F.plen, plen) && upload(&F.sbase, sbase) &&
+              upload(&F.col, col) && upload(&dval, val);
+    F.val = dval;
+    if (ok && dpos) { ok = upload(&dpiv, piv); F.piv = dpiv; }
+    return ok ? SPRS_OK : SPRS_ERR_HIP;
+}
+
+template <class T>
+int ilu0_create(const sprs_csr *A, sprs_ilu0 **out, int64_t *row_out) {
+    sprs_ctx *c = A->ctx;
+    CtxLock lock(c);
+    const int64_t n = A->nrows, nnz = A->nnz;
+    SPRS_HIP_TRY(c, hipSetDevice(c->device));
+    // the pattern on the host: its checks, the diagonal positions and both level rules
+    std::vector<int32_t> rp((size_t)n + 1, 0), ci((size_t)nnz);
+    SPRS_HIP_TRY(c, hipMemcpyAsync(rp.data(), A->row_ptr, sizeof(int32_t) * rp.size(), hipMemcpyDeviceToHost, c->stream));
+    if (nnz) SPRS_HIP_TRY(c, hipMemcpyAsync(ci.data(), A->col_idx, sizeof(int32_t) * ci.size(), hipMemcpyDeviceToHost, c->stream));
+    SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int64_t i = 0; i < n; ++i)
+        for (int32_t k = rp[i] + 1; k < rp[i + 1]; ++k)
+            if (ci[k] <= ci[k - 1]) {
+                snprintf(c->err, sizeof(c->err), "sprs_ilu0: the column indices of row %lld are not strictly ascending", (long long)i);
+                return SPRS_INVALID_ARGUMENT;
+            }
+    std::vector<int32_t> dpos((size_t)n, -1);
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t *b = ci.data() + rp[i], *e = ci.data() + rp[i + 1];
+        const int32_t *d = std::lower_bound(b, e, (int32_t)i);
+        if (d == e || *d != (int32_t)i) { if (row_out) *row_out = i; return SPRS_ZERO_DIAGONAL; }
+        dpos[i] = (int32_t)(d - ci.data());
+    }
+    std::vector<int32_t> level((size_t)n, 0), ulevel((size_t)n, 0);
+    int32_t nlev = n ? 1 : 0, nulev = n ? 1 : 0;
+    for (int64_t i = 0; i < n; ++i) {
+        int32_t l = 0;
+        for (int32_t k = rp[i]; k < dpos[i]; ++k) l = std::max(l, level[ci[k]] + 1);
+        level[i] = l; nlev = std::max(nlev, l + 1);
+    }
+    for (int64_t i = n - 1; i >= 0; --i) {
+        int32_t l = 0;
+        for (int32_t k = dpos[i] + 1; k < rp[i + 1]; ++k) l = std::max(l, ulevel[ci[k]] + 1);
+        ulevel[i] = l; nulev = std::max(nulev, l + 1);
+    }
+    std::vector<int32_t> lptr, lrows, uptr, urows;
+    group_by_level(level, nlev, lptr, lrows);
+    group_by_level(ulevel, nulev, uptr, urows);
+
+    auto *P = new sprs_ilu0();
+    P->ctx = c; P->dtype = A->dtype; P->n = n; P->nnz = nnz;
+    int32_t *d_dpos = nullptr, *d_rows = nullptr, *d_lptr = nullptr;
+    int *d_bad = nullptr;
+    auto fail = [&](int st) {
+        for (void *p : {(void *)d_dpos, (void *)d_rows, (void *)d_lptr, (void *)d_bad}) if (p) (void)hipFree(p);
+        sprs_ilu0_destroy(P);
+        return st;
+    };
+    T *a = nullptr;
+    if (hipMalloc((void **)&a, sizeof(T) * ((size_t)nnz + 2)) != hipSuccess) return fail(SPRS_ERR_HIP);
+    P->fval = a;
+    if (hipMalloc(&P->ybuf, sizeof(T) * ((size_t)n + 2)) != hipSuccess) return fail(SPRS_ERR_HIP);
+    if (!upload(&d_dpos, dpos) || !upload(&d_rows, lrows) || !upload(&d_lptr, lptr) || hipMalloc((void **)&d_bad, sizeof(int)) != hipSuccess)
+        return fail(SPRS_ERR_HIP);
+    int bad = INT32_MAX;
+    if ((nnz && hipMemcpyAsync(a, A->val, sizeof(T) * (size_t)nnz, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) ||
+        hipMemcpyAsync(d_bad, &bad, sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess) return fail(SPRS_ERR_HIP);
+    // the factorisation: level by level, on the lower solve's plan
+    for (const IluLaunch &p : make_plan(lptr)) {
+        if (p.batch) hipLaunchKernelGGL((ilu_batch_kernel<T>), dim3(1), dim3(BLOCK), 0, c->stream, d_lptr, p.l0, p.l1, d_rows, A->row_ptr, A->col_idx, d_dpos, a);
+        else {
+            const int cnt = lptr[p.l1] - lptr[p.l0];
+            hipLaunchKernelGGL((ilu_level_kernel<T>), dim3((cnt + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, cnt, d_rows + lptr[p.l0], A->row_ptr, A->col_idx, d_dpos, a);
+        }
+    }
+    if (n) hipLaunchKernelGGL((ilu_pivot_check_kernel<T>), dim3((int)std::min<int64_t>((n + BLOCK - 1) / BLOCK, 2048)), dim3(BLOCK), 0, c->stream,
+                              (int)n, d_dpos, a, d_bad);
+    std::vector<T> fv((size_t)nnz);
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        (nnz && hipMemcpyAsync(fv.data(), a, sizeof(T) * (size_t)nnz, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+        hipStreamSynchronize(c->stream) != hipSuccess) {
+        snprintf(c->err, sizeof(c->err), "sprs_ilu0: the factorisation failed on the device (%s)", hipGetErrorString(hipGetLastError()));
+        return fail(SPRS_ERR_HIP);
+    }
+    if (bad != INT32_MAX) { if (row_out) *row_out = bad; return fail(SPRS_ZERO_DIAGONAL); }
+    // the level-major copies of both factors
+    int st = build_tri<T>(P->L, lptr, lrows, ci, fv, [&](int32_t i) { return rp[i]; }, [&](int32_t i) { return dpos[i]; }, nullptr);
+    if (st == SPRS_OK)
+        st = build_tri<T>(P->U, uptr, urows, ci, fv, [&](int32_t i) { return dpos[i] + 1; }, [&](int32_t i) { return rp[i + 1]; }, &dpos);
+    if (st != SPRS_OK) return fail(st);
+    for (void *p : {(void *)d_dpos, (void *)d_rows, (void *)d_lptr, (void *)d_bad}) (void)hipFree(p);
+    *out = P;
+    return SPRS_OK;
+}
+
+template <class T>
+int ilu0_solve_host(const sprs_ilu0 *Pc, int which, const T *in, size_t in_len, T *out, size_t out_len) {
+    if (!Pc || !in || !out || Pc->dtype != dtype_of<T>::value || which < 0 || which > 2) return SPRS_INVALID_ARGUMENT;
+    if (in_len != (size_t)Pc->n || out_len != (size_t)Pc->n) return SPRS_DIM_MISMATCH;
+    sprs_ilu0 *P = const_cast<sprs_ilu0 *>(Pc);
+    sprs_ctx *c = P->ctx;
+    CtxLock lock(c);   // in_tmp / out_tmp are per-handle staging
+    SPRS_HIP_TRY(c, hipSetDevice(c->device));
+    if (!P->in_tmp) SPRS_HIP_TRY(c, hipMalloc(&P->in_tmp, sizeof(T) * ((size_t)P->n + 2)));
+    if (!P->out_tmp) SPRS_HIP_TRY(c, hipMalloc(&P->out_tmp, sizeof(T) * ((size_t)P->n + 2)));
+    SPRS_HIP_TRY(c, hipMemcpyAsync(P->in_tmp, in, sizeof(T) * in_len, hipMemcpyHostToDevice, c->stream));
+    SPRS_TRY(ilu0_apply<T>(P, which, (const T *)P->in_tmp, (T *)P->out_tmp));
+    SPRS_HIP_TRY(c, hipMemcpyAsync(out, P->out_tmp, sizeof(T) * out_len, hipMemcpyDeviceToHost, c->stream));
+    SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SPRS_OK;
+}
+
+}  // namespace
+
+namespace sprs {
+
+int ilu0_check(const sprs_ilu0 *P, const sprs_csr *A, int dtype, size_t n) {
+    if (!P || !A || P->dtype != dtype || P->ctx != A->ctx || A->dist) return SPRS_INVALID_ARGUMENT;
+    if ((size_t)P->n != n) return SPRS_DIM_MISMATCH;
+    return SPRS_OK;
+}
+
+template <class T>
+int ilu0_apply(const sprs_ilu0 *P, int which, const T *in, T *out) {
+    if (!P || !in || !out || P->dtype != dtype_of<T>::value || which < 0 || which > 2) return SPRS_INVALID_ARGUMENT;
+    sprs_ctx *c = P->ctx;
+    CtxLock lock(c);   // ybuf is per-handle scratch
+    SPRS_HIP_TRY(c, hipSetDevice(c->device));
+    if (which == 1) return tri_solve<T, false>(c, P->L, in, out);
+    if (which == 2) return tri_solve<T, true>(c, P->U, in, out);
+    SPRS_TRY((tri_solve<T, false>(c, P->L, in, (T *)P->ybuf)));
+    return tri_solve<T, true>(c, P->U, (const T *)P->ybuf, out);
+}
+template int ilu0_apply<double>(const sprs_ilu0 *, int, const double *, double *);
+template int ilu0_apply<cplx>(const sprs_ilu0 *, int, const cplx *, cplx *);
+template int ilu0_apply<float>(const sprs_ilu0 *, int, const float *, float *);
+template int ilu0_apply<cplxf>(const sprs_ilu0 *, int, const cplxf *, cplxf *);
+
+}  // namespace sprs
+
+#define SPRS_G(...) try { __VA_ARGS__ } catch (...) { return SPRS_ERR_HIP; }
+
+extern "C" {
+
+int sprs_ilu0_create(const sprs_csr *A, sprs_ilu0 **out, int64_t *row_out) {
+    SPRS_G(
+        if (!A || !out) return SPRS_INVALID_ARGUMENT;
+        *out = nullptr;
+        if (row_out) *row_out = -1;
+        if (A->dist) {                   // (before the shape: a row block with a halo has more columns than rows)
+            snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_ilu0: distributed operators are not supported (single GPU only)");
+            return SPRS_INVALID_ARGUMENT;
+        }
+        if (A->nrows != A->ncols) return SPRS_NOT_SQUARE;
+        switch (A->dtype) {
+            case DT_D: return ilu0_create<double>(A, out, row_out);
+            case DT_Z: return ilu0_create<cplx>(A, out, row_out);
+            case DT_S: return ilu0_create<float>(A, out, row_out);
+            case DT_C: return ilu0_create<cplxf>(A, out, row_out);
+        }
+        return SPRS_INVALID_ARGUMENT;)
+}
+
+int sprs_ilu0_destroy(sprs_ilu0 *P) {
+    if (!P) return SPRS_OK;
+    if (P->ctx) { (void)hipSetDevice(P->ctx->device); (void)hipStreamSynchronize(P->ctx->stream); }
+    P->L.release(); P->U.release();
+    for (void *p : {P->fval, P->ybuf, P->in_tmp, P->out_tmp}) if (p) (void)hipFree(p);
+    delete P;
+    return SPRS_OK;
+}
+
+int sprs_ilu0_levels(const sprs_ilu0 *P, int64_t *lower_levels, int64_t *upper_levels, int64_t *lower_launches, int64_t *upper_launches) {
+    if (!P) return SPRS_INVALID_ARGUMENT;
+    if (lower_levels) *lower_levels = P->L.nlev;
+    if (upper_levels) *upper_levels = P->U.nlev;
+    if (lower_launches) *lower_launches = (int64_t)P->L.plan.size();
+    if (upper_launches) *upper_launches = (int64_t)P->U.plan.size();
+    return SPRS_OK;
+}
+
+int sprs_ilu0_read(const sprs_ilu0 *P, void *val_host) {
+    if (!P || (!val_host && P->nnz)) return SPRS_INVALID_ARGUMENT;
+    sprs_ctx *c = P->ctx;
+    CtxLock lock(c);
+    SPRS_HIP_TRY(c, hipSetDevice(c->device));
+    if (P->nnz) SPRS_HIP_TRY(c, hipMemcpyAsync(val_host, P->fval, dtype_size(P->dtype) * (size_t)P->nnz, hipMemcpyDeviceToHost, c->stream));
+    SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SPRS_OK;
+}
+
+#define SPRS_ILU_API(X, T, CT)                                                                                          \
+    int sprs_ilu0_solve_dev_##X(const sprs_ilu0 *P, int which, const CT *in, CT *out) {                                 \
+        SPRS_G(return ilu0_apply<T>(P, which, (const T *)in, (T *)out);)                                                \
+    }                                                                                                                   \
+    int sprs_ilu0_solve_##X(const sprs_ilu0 *P, int which, const CT *in, size_t il, CT *out, size_t ol) {               \
+        SPRS_G(return ilu0_solve_host<T>(P, which, (const T *)in, il, (T *)out, ol);)                                   \
+    }
+SPRS_ILU_API(d, double, double)
+SPRS_ILU_API(z, cplx, sprs_c64)
+SPRS_ILU_API(s, float, float)
+SPRS_ILU_API(c, cplxf, sprs_c32)
+
+}  // extern "C"

@@ -368,6 +368,13 @@ template <class T> int norm2_host(sprs_ctx *c, size_t n, const T *x, Real<T> *ou
 // reduce `P` partials of T (or of double when T_is_real_partials) with the library's fixed order; blocking
 template <class T> int reduce_partials_host(sprs_ctx *c, const T *part, int P, T *out, sprs_comm *comm = nullptr);
 
+// ---- ilu0.hip
+// The solvers' view of an ILU(0) handle.  ilu0_check: SPRS_INVALID_ARGUMENT unless P has the scalar type `dtype` and lives on A's
+// context and A is on one GPU, SPRS_DIM_MISMATCH unless it has n rows.  ilu0_apply: out = U^-1 L^-1 in (which = 0), L^-1 in (1) or
+// U^-1 in (2) on device vectors, asynchronous on the context's stream; in == out is allowed.
+int ilu0_check(const sprs_ilu0 *P, const sprs_csr *A, int dtype, size_t n);
+template <class T> int ilu0_apply(const sprs_ilu0 *P, int which, const T *in, T *out);
+
 // ---- dist.hip
 // exchange the halo entries of the extended vector x (local part [0,n_local) already in place)
 template <class T> int halo_exchange(const sprs_csr *A, T *x_ext);

@@ -1,6 +1,7 @@
 """Restarted GMRES for general (non-symmetric) operators (no reference analogue)."""
 from . import _lib
 from ._solver import _SolverBase
+from .ilu import ILU0
 
 
 class GMRES(_SolverBase):
@@ -27,5 +28,7 @@ class GMRES(_SolverBase):
         return self._solve(None, rhs, x, max_iter, tol, False)
 
     def precond_solve(self, precond, rhs, x, max_iter, tol):
-        """Jacobi-preconditioned from the right: the residual it reports is the true one's estimate."""
+        """Preconditioned from the right by a `DiagPrecond` (Jacobi) or an `ILU0`: the residual it reports is the true one's estimate."""
+        if isinstance(precond, ILU0):
+            return self._solve_ilu(precond, rhs, x, max_iter, tol)
         return self._solve(precond, rhs, x, max_iter, tol, True)
