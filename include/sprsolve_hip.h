@@ -707,6 +707,85 @@ int sprs_ilu0_gmres_solve_dev_z(sprs_gmres *S, const sprs_ilu0 *P, const sprs_c6
 int sprs_ilu0_gmres_solve_dev_s(sprs_gmres *S, const sprs_ilu0 *P, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
 int sprs_ilu0_gmres_solve_dev_c(sprs_gmres *S, const sprs_ilu0 *P, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
 
+/* ---------------------------------------------------------------- smoothed-aggregation AMG preconditioner
+ * An algebraic multigrid hierarchy of a square, single-GPU CSR handle (any of the four scalar types, taken from A) and the
+ * V(1,1) cycle that applies it.  The reference has no such preconditioner.  The handle owns everything it derives (host copies
+ * of every level included) and borrows nothing from A after creation.
+ * create(A, theta, coarse_max, max_levels):  SPRS_NOT_SQUARE;  SPRS_INVALID_ARGUMENT (text in sprs_last_error) for a distributed
+ * A, a row whose column indices are not strictly ascending, theta < 0 or NaN, coarse_max outside 1 .. 1024, max_levels outside
+ * 1 .. 32;  SPRS_ZERO_DIAGONAL with *row_out = the smallest row OF THE LEVEL BEING BUILT that stores no diagonal entry or whose
+ * diagonal is exactly zero or not finite, or the row of a zero or non-finite pivot of the coarse LU.  *row_out is -1 otherwise.
+ * The hierarchy is built on the host, serially, from one copy of A; every scalar operation is rounded once, complex ones by
+ * the naive formulas, nothing is fused.  |a| is fabs(a), for a complex a sqrt(re*re + im*im); |a|^2 is a*a or re*re + im*im.
+ * Level l (A_0 = A), with d_i its diagonal:
+ *   omega_l = 4 / (3 * rho),  rho = max_i (s_i / |d_i|),  s_i = sum over the stored j of |a_ij|, left to right from zero.
+ *   It is the coarsest level when it has at most coarse_max rows or l + 1 == max_levels.
+ *   Strength, theta_l = theta * 2^-l:  a stored j != i is strong for row i when |a_ij|^2 >= (theta_l*theta_l) * (|d_i| * |d_j|).
+ *   Aggregation, three passes over the rows in ascending order:
+ *     1. an unaggregated row none of whose strong neighbours is aggregated founds the next aggregate with them (a row without
+ *        strong neighbours founds a singleton);
+ *     2. a row left over joins the aggregate that its strong neighbour of largest |a_ij|^2 had AFTER PASS 1 (pass 2 reads a
+ *        snapshot; the first of equal neighbours wins; neighbours unaggregated in the snapshot do not count);
+ *     3. a row still left founds the next aggregate with its strong neighbours that are still unaggregated.
+ *        (A row is left by pass 1 only because a strong neighbour of its was aggregated by then, and pass 2 places it with one
+ *        of those: as the rules stand pass 3 finds no row.  It is kept as the guard that every row ends in an aggregate.)
+ *   If the aggregates number more than half the rows, level l is the coarsest after all (the half-rows stop).
+ *   Products run row by row in Gustavson order: for a_ik with k ascending, for b_kj with j ascending, acc_j = acc_j + a_ik*b_kj,
+ *   acc from zero; the stored pattern is the structural one (exact zeros are kept), columns ascending.
+ *   T has a 1 at (i, agg(i)).  P = T - omega D^-1 A T entry by entry on the pattern of the product A T:
+ *   p_ic = t_ic - ((A T)_ic * omega_l) / d_i.   R = P^H.   A_{l+1} = R (A P), the inner product first.
+ *   (theta_l halves per level, Vanek's rule: DESIGN.md §4h has the level sizes it gives.)
+ * Coarse solve.  At most coarse_max rows: the dense no-pivot LU of the coarsest A in the k-i-j order (l_ik = a_ik / a_kk, then
+ * a_ij = a_ij - l_ik*a_kj), applied as  w = b;  for j ascending: w_i = w_i - l_ij*w_j (i > j);  then for j descending:
+ * x_j = w_j / u_jj, w_i = w_i - u_ij*x_j (i < j).  More rows (the half-rows stop or max_levels ended the coarsening early):
+ * eight damped-Jacobi sweeps from zero, i.e. the pre-smoothing formula followed by seven sweeps of the post-smoothing one.
+ * The cycle on level l, right-hand side b (sigma = sum over a row's stored entries, left to right from zero):
+ *     x_i = (b_i*omega_l) / d_i;   r_i = b_i - sigma_i(A x);   b' = R r (b'_c = sigma_c);   e = cycle(l + 1, b');
+ *     x_i = x_i + sigma_i(P e);    result_i = x_i + ((b_i - sigma_i(A x))*omega_l) / d_i.
+ * One lane folds one row, so an application has the bits of these loops.  Every operator is kept in 64-row slices,
+ * slice-column-major; the levels of at most 1024 rows (AMG_TAIL_ROWS) run in ONE launch of ONE workgroup, down, coarse solve and
+ * up; each larger level takes five launches.  sprs_amg_info: the levels, the launches of one application, the first level of
+ * the tail (== levels when there is none) and the rows of the coarse LU (0: Jacobi sweeps).  sprs_amg_level_info: rows, nnz(A_l),
+ * nnz(P_l) (0 on the coarsest level) and omega_l.  sprs_amg_level_read: the CSR arrays of A_l (which = 0), P_l (1) or R_l (2) and
+ * the aggregate of every row of level l, into host arrays; any pointer may be NULL; P, R and aggregates of the coarsest level
+ * are SPRS_INVALID_ARGUMENT.
+ * mul_vec: out = one cycle on in.  The _dev form is asynchronous on the context's stream; in == out is allowed; the handle
+ * owns the level vectors, so calls on one context serialise.  Host slices of the wrong length: SPRS_DIM_MISMATCH.
+ * Solvers: as for ILU(0) (same errors); z = P r, z = P v_j and u = P u of the recurrences are one cycle.  The cycle is
+ * Hermitian positive definite when A is, so it is a valid CG preconditioner; on an indefinite A, CG ends in
+ * SPRS_INVALID_PRECOND as with any preconditioner that is not positive definite. */
+typedef struct sprs_amg sprs_amg;
+int sprs_amg_create(const sprs_csr *A, double theta, int64_t coarse_max, int64_t max_levels, sprs_amg **out, int64_t *row_out);   /* row_out may be NULL */
+int sprs_amg_destroy(sprs_amg *P);             /* NULL is a no-op */
+int sprs_amg_info(const sprs_amg *P, int64_t *levels, int64_t *launches, int64_t *tail_level, int64_t *lu_rows);   /* any pointer may be NULL */
+int sprs_amg_level_info(const sprs_amg *P, int64_t level, int64_t *rows, int64_t *nnz, int64_t *p_nnz, double *omega);
+int sprs_amg_level_read(const sprs_amg *P, int64_t level, int which, int32_t *row_ptr_host, int32_t *col_idx_host, void *val_host, int32_t *agg_host);
+int sprs_amg_mul_vec_dev_d(const sprs_amg *P, const double *in_dev, double *out_dev);
+int sprs_amg_mul_vec_dev_z(const sprs_amg *P, const sprs_c64 *in_dev, sprs_c64 *out_dev);
+int sprs_amg_mul_vec_dev_s(const sprs_amg *P, const float *in_dev, float *out_dev);
+int sprs_amg_mul_vec_dev_c(const sprs_amg *P, const sprs_c32 *in_dev, sprs_c32 *out_dev);
+int sprs_amg_mul_vec_d(const sprs_amg *P, const double *in_host, size_t in_len, double *out_host, size_t out_len);
+int sprs_amg_mul_vec_z(const sprs_amg *P, const sprs_c64 *in_host, size_t in_len, sprs_c64 *out_host, size_t out_len);
+int sprs_amg_mul_vec_s(const sprs_amg *P, const float *in_host, size_t in_len, float *out_host, size_t out_len);
+int sprs_amg_mul_vec_c(const sprs_amg *P, const sprs_c32 *in_host, size_t in_len, sprs_c32 *out_host, size_t out_len);
+/* CG and GMRES preconditioned by AMG: the recurrences of sprs_cg_* and sprs_gmres_* with P = one cycle */
+int sprs_amg_cg_solve_d(sprs_cg *S, const sprs_amg *P, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_amg_cg_solve_z(sprs_cg *S, const sprs_amg *P, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_amg_cg_solve_s(sprs_cg *S, const sprs_amg *P, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_amg_cg_solve_c(sprs_cg *S, const sprs_amg *P, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_amg_cg_solve_dev_d(sprs_cg *S, const sprs_amg *P, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_amg_cg_solve_dev_z(sprs_cg *S, const sprs_amg *P, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_amg_cg_solve_dev_s(sprs_cg *S, const sprs_amg *P, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_amg_cg_solve_dev_c(sprs_cg *S, const sprs_amg *P, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_amg_gmres_solve_d(sprs_gmres *S, const sprs_amg *P, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_amg_gmres_solve_z(sprs_gmres *S, const sprs_amg *P, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_amg_gmres_solve_s(sprs_gmres *S, const sprs_amg *P, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_amg_gmres_solve_c(sprs_gmres *S, const sprs_amg *P, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_amg_gmres_solve_dev_d(sprs_gmres *S, const sprs_amg *P, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_amg_gmres_solve_dev_z(sprs_gmres *S, const sprs_amg *P, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_amg_gmres_solve_dev_s(sprs_gmres *S, const sprs_amg *P, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_amg_gmres_solve_dev_c(sprs_gmres *S, const sprs_amg *P, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+
 /* ---------------------------------------------------------------- multi-GPU (one process per GPU)
  * No reference analogue: the reference is single-process (rayon).  The matrix is row-partitioned;
  * rank r owns rows [r0, r1) and the matching slices of every vector.  A distributed operator is the

@@ -116,9 +116,12 @@ def _protos():
         P["sprs_csminres_solve_dev_" + s] = [_vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
         P["sprs_ilu0_solve_dev_" + s] = [_vp, _int, _vp, _vp]
         P["sprs_ilu0_solve_" + s] = [_vp, _int, _vp, _sz, _vp, _sz]
+        P["sprs_amg_mul_vec_dev_" + s] = [_vp, _vp, _vp]
+        P["sprs_amg_mul_vec_" + s] = [_vp, _vp, _sz, _vp, _sz]
         for k in ("cg", "gmres"):
-            P["sprs_ilu0_%s_solve_%s" % (k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
-            P["sprs_ilu0_%s_solve_dev_%s" % (k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
+            for pc in ("ilu0", "amg"):
+                P["sprs_%s_%s_solve_%s" % (pc, k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
+                P["sprs_%s_%s_solve_dev_%s" % (pc, k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
     for s in ("d", "z"):          # mixed-precision refinement: H = f64 / c64 over L = f32 / c32; every real scalar is a double
         P["sprs_refine_create_" + s] = [_vp, _sz, _vp, _int, _sz, _pp]
         for k in ("solve", "solve_dev"):
@@ -160,6 +163,11 @@ def _protos():
     P["sprs_ilu0_destroy"] = [_vp]
     P["sprs_ilu0_levels"] = [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]
     P["sprs_ilu0_read"] = [_vp, _vp]
+    P["sprs_amg_create"] = [_vp, _dbl, _i64, _i64, _pp, C.POINTER(_i64)]
+    P["sprs_amg_destroy"] = [_vp]
+    P["sprs_amg_info"] = [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]
+    P["sprs_amg_level_info"] = [_vp, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), _pd]
+    P["sprs_amg_level_read"] = [_vp, _i64, _int, _vp, _vp, _vp, _vp]
     P["sprs_gauss_seidel_create"] = [_vp, _pp]
     P["sprs_gauss_seidel_destroy"] = [_vp]
     for s in ("d", "s"):

@@ -92,8 +92,8 @@ class _SolverBase:
                     self.h, rp, rhs_a.size, xp, x.size, int(max_iter), float(tol), C.byref(its), C.byref(res))
         return solve_result(st, its.value, res.value, self.A.ctx.h)
 
-    def _solve_ilu(self, P, rhs, x, max_iter, tol):
-        """CG / GMRES with an ILU0 handle for the preconditioner (sprs_ilu0_*_solve_*)."""
+    def _solve_applied(self, prefix, P, rhs, x, max_iter, tol):
+        """CG / GMRES with an ILU0 (prefix "ilu0") or AMG ("amg") handle for the preconditioner (sprs_<prefix>_*_solve_*)."""
         L = _lib.lib()
         its = C.c_size_t(0); res = _lib.REAL[self.s](0.0)
         dev = is_device_array(rhs)
@@ -101,13 +101,13 @@ class _SolverBase:
             raise TypeError("rhs and x must both be host arrays or both be device vectors")
         if dev:
             pre_sync(rhs, x)
-            st = getattr(L, "sprs_ilu0_%s_solve_dev_%s" % (self.NAME, self.s))(
+            st = getattr(L, "sprs_%s_%s_solve_dev_%s" % (prefix, self.NAME, self.s))(
                 self.h, P.h, dev_ptr(rhs), dev_len(rhs), dev_ptr(x), dev_len(x), int(max_iter), float(tol), C.byref(its), C.byref(res))
         else:
             rhs_a = np.ascontiguousarray(rhs, dtype=self.dtype)
             if not (isinstance(x, np.ndarray) and x.dtype == self.dtype and x.flags.c_contiguous):
                 raise TypeError("x must be a contiguous %s ndarray (it is updated in place)" % self.dtype)
-            st = getattr(L, "sprs_ilu0_%s_solve_%s" % (self.NAME, self.s))(
+            st = getattr(L, "sprs_%s_%s_solve_%s" % (prefix, self.NAME, self.s))(
                 self.h, P.h, rhs_a.ctypes.data_as(C.c_void_p), rhs_a.size, x.ctypes.data_as(C.c_void_p), x.size, int(max_iter),
                 float(tol), C.byref(its), C.byref(res))
         return solve_result(st, its.value, res.value, self.A.ctx.h)

@@ -1,6 +1,7 @@
 """Conjugate gradients for Hermitian positive-definite operators (no reference analogue)."""
 from . import _lib
 from ._solver import _SolverBase
+from .amg import AMG
 from .ilu import ILU0
 
 
@@ -16,7 +17,9 @@ class CG(_SolverBase):
         return self._solve(None, rhs, x, max_iter, tol, False)
 
     def precond_solve(self, precond, rhs, x, max_iter, tol):
-        """Preconditioned by a `DiagPrecond` (Jacobi) or an `ILU0`; InvalidPreconditioner where conj(r).M^-1 r is not positive."""
+        """Preconditioned by a `DiagPrecond` (Jacobi), an `ILU0` or an `AMG`; InvalidPreconditioner where conj(r).M^-1 r is not positive."""
         if isinstance(precond, ILU0):
-            return self._solve_ilu(precond, rhs, x, max_iter, tol)
+            return self._solve_applied("ilu0", precond, rhs, x, max_iter, tol)
+        if isinstance(precond, AMG):
+            return self._solve_applied("amg", precond, rhs, x, max_iter, tol)
         return self._solve(precond, rhs, x, max_iter, tol, True)

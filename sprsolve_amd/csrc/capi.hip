@@ -532,25 +532,26 @@ int solve(SolverT *s, bool host, const sprs_diag *P, const T *rhs, size_t rl, T 
     return st;
 }
 
-// The same with an ILU(0) handle for P (sprs_ilu0_cg_*, sprs_ilu0_gmres_*): SolverT::solve_dev_ilu.
+// The same with an applied preconditioner for P (an ILU(0) or AMG handle's view: sprs_ilu0_cg_*, sprs_amg_gmres_*, ...):
+// SolverT::solve_dev_applied.
 template <class T, class SolverT>
-int solve_ilu(SolverT *s, bool host, const sprs_ilu0 *P, const T *rhs, size_t rl, T *x, size_t xl, size_t max_iter, Real<T> tol,
+int solve_applied(SolverT *s, bool host, const AppliedPrec<T> &P, const T *rhs, size_t rl, T *x, size_t xl, size_t max_iter, Real<T> tol,
               size_t *its, Real<T> *res) {
-    if (!s || !P || !rhs || !x) return SPRS_INVALID_ARGUMENT;
+    if (!s || !P.h || !rhs || !x) return SPRS_INVALID_ARGUMENT;
     if (rl != s->n) return SPRS_INCOMPATIBLE_RHS_SIZE;
     if (xl != s->n) return SPRS_INCOMPATIBLE_X_SIZE;
-    SPRS_TRY(ilu0_check(P, s->A, dtype_of<T>::value, s->n));       // nothing is copied on a mismatch
+    SPRS_TRY(P.check(s->A, s->n));       // nothing is copied on a mismatch
     sprs_ctx *c = s->ctx;
     CtxLock lock(c);
     if (!host && ((reinterpret_cast<uintptr_t>(rhs) | reinterpret_cast<uintptr_t>(x)) & 15) == 0)
-        return s->solve_dev_ilu(P, rhs, rl, x, xl, max_iter, tol, its, res);
+        return s->solve_dev_applied(P, rhs, rl, x, xl, max_iter, tol, its, res);
     const hipMemcpyKind in = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, out = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     SPRS_HIP_TRY(c, hipSetDevice(c->device));
     if (!s->rhs_buf) SPRS_HIP_TRY(c, hipMalloc((void **)&s->rhs_buf, sizeof(T) * s->stride));
     if (!s->x_buf) SPRS_HIP_TRY(c, hipMalloc((void **)&s->x_buf, sizeof(T) * s->stride));
     SPRS_HIP_TRY(c, hipMemcpyAsync(s->rhs_buf, rhs, sizeof(T) * rl, in, c->stream));
     SPRS_HIP_TRY(c, hipMemcpyAsync(s->x_buf, x, sizeof(T) * xl, in, c->stream));
-    int st = s->solve_dev_ilu(P, s->rhs_buf, rl, s->x_buf, xl, max_iter, tol, its, res);
+    int st = s->solve_dev_applied(P, s->rhs_buf, rl, s->x_buf, xl, max_iter, tol, its, res);
     if (st >= SPRS_ERR_HIP) return st;
     SPRS_HIP_TRY(c, hipMemcpyAsync(x, s->x_buf, sizeof(T) * xl, out, c->stream));
     SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -900,19 +901,21 @@ SPRS_API(z, cplx, sprs_c64, double)
 SPRS_API(s, float, float, float)
 SPRS_API(c, cplxf, sprs_c32, float)
 
-// CG and GMRES preconditioned by an ILU(0) handle (ilu0.hip)
-#define SPRS_ILU_SOLVES(X, T, CT, R, NAME, S)                                                                          \
-    int sprs_ilu0_##NAME##_solve_##X(sprs_##NAME *h, const sprs_ilu0 *P, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
-        SPRS_G(return solve_ilu<T>(impl_of<S, T>(h), true, P, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);)     \
+// CG and GMRES preconditioned by an ILU(0) handle (ilu0.hip) or an AMG handle (amg.hip): one path, the handle's AppliedPrec view
+#define SPRS_APPLIED_SOLVES(X, T, CT, R, NAME, S, PFX)                                                                 \
+    int sprs_##PFX##_##NAME##_solve_##X(sprs_##NAME *h, const sprs_##PFX *P, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
+        SPRS_G(return solve_applied<T>(impl_of<S, T>(h), true, PFX##_prec<T>(P), (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);)  \
     }                                                                                                                  \
-    int sprs_ilu0_##NAME##_solve_dev_##X(sprs_##NAME *h, const sprs_ilu0 *P, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
-        SPRS_G(return solve_ilu<T>(impl_of<S, T>(h), false, P, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);)    \
+    int sprs_##PFX##_##NAME##_solve_dev_##X(sprs_##NAME *h, const sprs_##PFX *P, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
+        SPRS_G(return solve_applied<T>(impl_of<S, T>(h), false, PFX##_prec<T>(P), (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);) \
     }
-#define SPRS_ILU_API(X, T, CT, R) SPRS_ILU_SOLVES(X, T, CT, R, cg, Cg) SPRS_ILU_SOLVES(X, T, CT, R, gmres, Gmres)
-SPRS_ILU_API(d, double, double, double)
-SPRS_ILU_API(z, cplx, sprs_c64, double)
-SPRS_ILU_API(s, float, float, float)
-SPRS_ILU_API(c, cplxf, sprs_c32, float)
+#define SPRS_APPLIED_API(X, T, CT, R)                                                                 \
+    SPRS_APPLIED_SOLVES(X, T, CT, R, cg, Cg, ilu0) SPRS_APPLIED_SOLVES(X, T, CT, R, gmres, Gmres, ilu0) \
+    SPRS_APPLIED_SOLVES(X, T, CT, R, cg, Cg, amg) SPRS_APPLIED_SOLVES(X, T, CT, R, gmres, Gmres, amg)
+SPRS_APPLIED_API(d, double, double, double)
+SPRS_APPLIED_API(z, cplx, sprs_c64, double)
+SPRS_APPLIED_API(s, float, float, float)
+SPRS_APPLIED_API(c, cplxf, sprs_c32, float)
 
 // complex vector, real scalar (S = Real, T = Complex; vecalg.rs:746-757)
 int sprs_axpy_zd(sprs_ctx *c, size_t n, double a, const sprs_c64 *x, sprs_c64 *y) { SPRS_CHK(c); return launch_axpy<cplx, double>(c, n, a, (const cplx *)x, (cplx *)y); }

@@ -166,12 +166,13 @@ int Cg<T>::solve_dev(const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, siz
     return KrylovBase<T>::solve(*this, false, P, rhs, rhs_len, x, x_len, max_iter, tol, its_out, res_out);
 }
 
-// ---------------------------------------------------------------------------------------------- ILU(0)-preconditioned
-// The same recurrence with z = P r = U^-1 (L^-1 r) (ilu0.hip).  Fused: CA, CgKB without a preconditioner, the solves into z,
+// ---------------------------------------------------------------------------------------------- applied preconditioner
+// The same recurrence with z = P r a chain of launches of the handle's own (internal.hpp, AppliedPrec: ILU(0)'s two triangular
+// solves, AMG's cycle).  Fused: CA, CgKB without a preconditioner, the application into z,
 // CgRZ (the partials of conj(r).z), CgKC — no host wait inside an iteration.  Once the status word has left ST_RUNNING the
 // solves still run: they read r and write only z and the handle's scratch, never x, r or p.
 template <class T>
-int Cg<T>::start_ilu(const sprs_ilu0 *P, const T *rhs, T *x, Real<T> tol, Real<T> *rhs_norm, Real<T> *tol2, T *rho, bool *done, Real<T> *res_out) {
+int Cg<T>::start_applied(const AppliedPrec<T> &P, const T *rhs, T *x, Real<T> tol, Real<T> *rhs_norm, Real<T> *tol2, T *rho, bool *done, Real<T> *res_out) {
     sprs_ctx *c = this->ctx;
     const size_t n = this->n;
     T *r = this->vec(0), *p = this->vec(1), *z = this->vec(3);
@@ -184,7 +185,7 @@ int Cg<T>::start_ilu(const sprs_ilu0 *P, const T *rhs, T *x, Real<T> tol, Real<T
     Real<T> r_norm = 0.0;
     SPRS_TRY(this->norm2(r, &r_norm));
     if (r_norm <= *tol2) { *res_out = r_norm / *rhs_norm; return SPRS_OK; }
-    SPRS_TRY(ilu0_apply<T>(P, 0, r, z));                                    // z = P r
+    SPRS_TRY(P.apply(r, z));                                    // z = P r
     SPRS_TRY(dcopy(c, p, z, n));                                            // p = z
     SPRS_TRY(this->cdot(r, z, rho));                                        // rho = conj(r).z
     *done = false;
@@ -192,7 +193,7 @@ int Cg<T>::start_ilu(const sprs_ilu0 *P, const T *rhs, T *x, Real<T> tol, Real<T
 }
 
 template <class T>
-int Cg<T>::run_ilu(const sprs_ilu0 *P, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out) {
+int Cg<T>::run_applied(const AppliedPrec<T> &P, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out) {
     sprs_ctx *c = this->ctx;
     const size_t n = this->n;
     *its_out = 0; *res_out = 0.0;
@@ -201,7 +202,7 @@ int Cg<T>::run_ilu(const sprs_ilu0 *P, const T *rhs, T *x, size_t max_iter, Real
     Real<T> rhs_norm = 0.0, tol2 = 0.0;
     T rho = szero<T>();
     bool done;
-    SPRS_TRY(start_ilu(P, rhs, x, tol, &rhs_norm, &tol2, &rho, &done, res_out));
+    SPRS_TRY(start_applied(P, rhs, x, tol, &rhs_norm, &tol2, &rho, &done, res_out));
     if (done) return SPRS_OK;
 
     CgState<T> &H = *state.host;
@@ -222,7 +223,7 @@ int Cg<T>::run_ilu(const sprs_ilu0 *P, const T *rhs, T *x, size_t max_iter, Real
     auto iteration = [&]() -> int {
         SPRS_TRY(this->spmv(p, q, 1, p, partPQ, nullptr, d_status, false, nullptr));                 // q = A p ; conj(p).q
         SPRS_TRY(launch_fused<T>(c, n, G, cw, CgKB<T, V, false>{d_state, partPQ, GS, p, q, x, r, (const V *)nullptr, r, partN, partRZ, Fin{}, T(), T(), 0.0, T()}));
-        SPRS_TRY(ilu0_apply<T>(P, 0, r, z));                                                         // z = P r
+        SPRS_TRY(P.apply(r, z));                                                         // z = P r
         SPRS_TRY(launch_fused<T>(c, n, G, cw, CgRZ<T>{d_state, r, z, partRZ, T()}));
         return launch_fused<T>(c, n, G, cw, CgKC<T, true>{d_state, partN, partRZ, G, z, p, T(), T()});
     };
@@ -261,7 +262,7 @@ int Cg<T>::run_ilu(const sprs_ilu0 *P, const T *rhs, T *x, size_t max_iter, Real
 }
 
 template <class T>
-int Cg<T>::run_literal_ilu(const sprs_ilu0 *P, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out) {
+int Cg<T>::run_literal_applied(const AppliedPrec<T> &P, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out) {
     sprs_ctx *c = this->ctx;
     const size_t n = this->n;
     *its_out = 0; *res_out = 0.0;
@@ -269,7 +270,7 @@ int Cg<T>::run_literal_ilu(const sprs_ilu0 *P, const T *rhs, T *x, size_t max_it
     Real<T> rhs_norm = 0.0, tol2 = 0.0;
     T rho = szero<T>();
     bool done;
-    SPRS_TRY(start_ilu(P, rhs, x, tol, &rhs_norm, &tol2, &rho, &done, res_out));
+    SPRS_TRY(start_applied(P, rhs, x, tol, &rhs_norm, &tol2, &rho, &done, res_out));
     if (done) return SPRS_OK;
     for (size_t its = 0; its < max_iter; ++its) {
         SPRS_TRY(this->spmv(p, q, 0, nullptr, nullptr, nullptr, nullptr));
@@ -282,7 +283,7 @@ int Cg<T>::run_literal_ilu(const sprs_ilu0 *P, const T *rhs, T *x, size_t max_it
         Real<T> r_norm = 0.0;
         SPRS_TRY(this->norm2(r, &r_norm));
         if (r_norm <= tol2) { *its_out = its + 1; *res_out = r_norm / rhs_norm; return SPRS_OK; }
-        SPRS_TRY(ilu0_apply<T>(P, 0, r, z));
+        SPRS_TRY(P.apply(r, z));
         T rho_new;
         SPRS_TRY(this->cdot(r, z, &rho_new));
         if (!(sre(rho_new) > 0.0)) { *its_out = its; *res_out = sre(rho_new); return SPRS_INVALID_PRECOND; }
@@ -296,9 +297,9 @@ int Cg<T>::run_literal_ilu(const sprs_ilu0 *P, const T *rhs, T *x, size_t max_it
 }
 
 template <class T>
-int Cg<T>::solve_dev_ilu(const sprs_ilu0 *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
+int Cg<T>::solve_dev_applied(const AppliedPrec<T> &P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
                          size_t *its_out, Real<T> *res_out) {
-    return KrylovBase<T>::solve_ilu(*this, P, rhs, rhs_len, x, x_len, max_iter, tol, its_out, res_out);
+    return KrylovBase<T>::solve_applied(*this, P, rhs, rhs_len, x, x_len, max_iter, tol, its_out, res_out);
 }
 
 template class Cg<double>;

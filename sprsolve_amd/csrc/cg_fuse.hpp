@@ -116,7 +116,7 @@ struct CgKC {
     __device__ __forceinline__ void epilogue() const {}
 };
 
-// RZ (ILU(0) only): z = P r is a chain of launches of its own between KB and KC (the triangular solves, ilu0.hip), so KB runs
+// RZ (applied preconditioners only: ILU(0), AMG): z = P r is a chain of launches of its own between KB and KC, so KB runs
 //      without a preconditioner and this pass forms the partials of conj(r).z that KC expects.  Reads r and z.
 template <class T>
 struct CgRZ {

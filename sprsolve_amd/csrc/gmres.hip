@@ -240,12 +240,13 @@ int Gmres<T>::solve_dev(const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, 
     return KrylovBase<T>::solve(*this, false, P, rhs, rhs_len, x, x_len, max_iter, tol, its_out, res_out);
 }
 
-// ---------------------------------------------------------------------------------------------- ILU(0)-preconditioned
-// The same cycles with z = P v_j and u = P u the two triangular solves of an ILU(0) handle (ilu0.hip).  Fused: the solves stand
+// ---------------------------------------------------------------------------------------------- applied preconditioner
+// The same cycles with z = P v_j and u = P u a chain of launches of the handle's own (internal.hpp, AppliedPrec: ILU(0)'s two
+// triangular solves, AMG's cycle).  Fused: they stand
 // where GmPrec stood, and GmXUpdate becomes GmUForm, the solves in place on u, GmXAdd.  The solves are not keyed on `skip` or the
 // cycle: z and u are scratch, and neither x nor the basis is touched by them.
 template <class T>
-int Gmres<T>::run_ilu(const sprs_ilu0 *P, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out) {
+int Gmres<T>::run_applied(const AppliedPrec<T> &P, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out) {
     sprs_ctx *c = this->ctx;
     const size_t n = this->n;
     *its_out = 0; *res_out = 0.0;
@@ -311,7 +312,7 @@ int Gmres<T>::run_ilu(const sprs_ilu0 *P, const T *rhs, T *x, size_t max_iter, R
     };
     auto step = [&](int j, long long cycle) -> int {
         T *vj = Vb + (size_t)j * this->stride, *vn = Vb + (size_t)(j + 1) * this->stride;
-        SPRS_TRY(ilu0_apply<T>(P, 0, vj, z));                                                       // z = P v_j (z is scratch: it runs whatever `skip` says)
+        SPRS_TRY(P.apply(vj, z));                                                       // z = P v_j (z is scratch: it runs whatever `skip` says)
         SPRS_TRY(this->spmv(z, w, 0, nullptr, nullptr, nullptr, d_skip));                           // w = A z
         SPRS_TRY(multi_dot(j, w));
         SPRS_TRY(launch_fused<T>(c, n, G, cw, GmUpdate<T, false>{d_state, cpart, cstride, cP, j, Vb, vs, w, w, nullptr, Fin{}, nullptr, 0.0}));
@@ -325,7 +326,7 @@ int Gmres<T>::run_ilu(const sprs_ilu0 *P, const T *rhs, T *x, size_t max_iter, R
     };
     auto cycle_end = [&](long long cycle) -> int {
         SPRS_TRY(launch_fused<T>(c, n, G, cw, GmUForm<T>{d_state, cycle, Vb, vs, u, nullptr, 0}));          // u = sum v_i y_i
-        SPRS_TRY(ilu0_apply<T>(P, 0, u, u));                                                        // u = P u (u is scratch)
+        SPRS_TRY(P.apply(u, u));                                                        // u = P u (u is scratch)
         return launch_fused<T>(c, n, G, cw, GmXAdd<T>{d_state, cycle, u, x});                       // x += u*1
     };
 
@@ -371,7 +372,7 @@ int Gmres<T>::run_ilu(const sprs_ilu0 *P, const T *rhs, T *x, size_t max_iter, R
 }
 
 template <class T>
-int Gmres<T>::run_literal_ilu(const sprs_ilu0 *P, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out) {
+int Gmres<T>::run_literal_applied(const AppliedPrec<T> &P, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out) {
     sprs_ctx *c = this->ctx;
     const size_t n = this->n;
     *its_out = 0; *res_out = 0.0;
@@ -399,7 +400,7 @@ int Gmres<T>::run_literal_ilu(const sprs_ilu0 *P, const T *rhs, T *x, size_t max
         Real<T> gabs = 0.0;
         for (int j = 0; j < m; ++j) {
             T *vj = basis(j);
-            SPRS_TRY(ilu0_apply<T>(P, 0, vj, z));
+            SPRS_TRY(P.apply(vj, z));
             SPRS_TRY(this->spmv(z, w, 0, nullptr, nullptr, nullptr, nullptr));
             for (int i = 0; i <= j; ++i) SPRS_TRY(this->cdot(basis(i), w, &h[i]));
             for (int i = 0; i <= j; ++i) SPRS_TRY(axpy(sneg(h[i]), basis(i), w));
@@ -419,7 +420,7 @@ int Gmres<T>::run_literal_ilu(const sprs_ilu0 *P, const T *rhs, T *x, size_t max
         gm_backsub<T>(k, R.data(), g.data(), y.data());
         SPRS_TRY(dzero(c, u, n));
         for (int i = 0; i < k; ++i) SPRS_TRY(axpy(y[i], basis(i), u));
-        SPRS_TRY(ilu0_apply<T>(P, 0, u, u));
+        SPRS_TRY(P.apply(u, u));
         SPRS_TRY(axpy(sone<T>(), u, x));
         gabs = sabs(g[k]);
         if (gabs <= tol2) { *its_out = its; *res_out = gabs / rhs_norm; return SPRS_OK; }
@@ -428,9 +429,9 @@ int Gmres<T>::run_literal_ilu(const sprs_ilu0 *P, const T *rhs, T *x, size_t max
 }
 
 template <class T>
-int Gmres<T>::solve_dev_ilu(const sprs_ilu0 *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
+int Gmres<T>::solve_dev_applied(const AppliedPrec<T> &P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
                             size_t *its_out, Real<T> *res_out) {
-    return KrylovBase<T>::solve_ilu(*this, P, rhs, rhs_len, x, x_len, max_iter, tol, its_out, res_out);
+    return KrylovBase<T>::solve_applied(*this, P, rhs, rhs_len, x, x_len, max_iter, tol, its_out, res_out);
 }
 
 template class Gmres<double>;

@@ -267,7 +267,7 @@ struct GmXUpdate {
     __device__ __forceinline__ void epilogue() const {}
 };
 
-// ---- GmUForm / GmXAdd (ILU(0) only): GmXUpdate in two halves around the triangular solves u = P u (ilu0.hip), both keyed on the
+// ---- GmUForm / GmXAdd (applied preconditioners only: ILU(0), AMG): GmXUpdate in two halves around u = P u, both keyed on the
 // cycle GmStep recorded.  GmUForm: u = sum_{i < k} v_i y_i (from zero, i ascending).  GmXAdd: x += u*1.
 template <class T>
 struct GmUForm {

@@ -397,6 +397,16 @@ template int ilu0_apply<cplx>(const sprs_ilu0 *, int, const cplx *, cplx *);
 template int ilu0_apply<float>(const sprs_ilu0 *, int, const float *, float *);
 template int ilu0_apply<cplxf>(const sprs_ilu0 *, int, const cplxf *, cplxf *);
 
+template <class T>
+AppliedPrec<T> ilu0_prec(const sprs_ilu0 *P) {
+    return AppliedPrec<T>{P, [](const void *h, const sprs_csr *A, int dtype, size_t n) { return ilu0_check((const sprs_ilu0 *)h, A, dtype, n); },
+                          [](const void *h, const T *in, T *out) { return ilu0_apply<T>((const sprs_ilu0 *)h, 0, in, out); }};
+}
+template AppliedPrec<double> ilu0_prec<double>(const sprs_ilu0 *);
+template AppliedPrec<cplx> ilu0_prec<cplx>(const sprs_ilu0 *);
+template AppliedPrec<float> ilu0_prec<float>(const sprs_ilu0 *);
+template AppliedPrec<cplxf> ilu0_prec<cplxf>(const sprs_ilu0 *);
+
 }  // namespace sprs
 
 #define SPRS_G(...) try { __VA_ARGS__ } catch (...) { return SPRS_ERR_HIP; }

@@ -375,6 +375,26 @@ template <class T> int reduce_partials_host(sprs_ctx *c, const T *part, int P, T
 int ilu0_check(const sprs_ilu0 *P, const sprs_csr *A, int dtype, size_t n);
 template <class T> int ilu0_apply(const sprs_ilu0 *P, int which, const T *in, T *out);
 
+// ---- amg.hip
+// The same for an AMG handle: amg_check as ilu0_check, amg_apply: out = one V(1,1) cycle on in; in == out is allowed.
+int amg_check(const sprs_amg *P, const sprs_csr *A, int dtype, size_t n);
+template <class T> int amg_apply(const sprs_amg *P, const T *in, T *out);
+
+// ---- an applied preconditioner as CG and GMRES take it: a handle whose application is a chain of launches of its own
+// (ILU(0)'s triangular solves, AMG's cycle), asynchronous on the context's stream.  check: SPRS_INVALID_ARGUMENT for a null
+// handle, another scalar type or context, or a distributed A; SPRS_DIM_MISMATCH for another size.  apply: out = M in on device
+// vectors, in == out allowed.
+template <class T>
+struct AppliedPrec {
+    const void *h = nullptr;
+    int (*check_fn)(const void *h, const sprs_csr *A, int dtype, size_t n) = nullptr;
+    int (*apply_fn)(const void *h, const T *in, T *out) = nullptr;
+    int check(const sprs_csr *A, size_t n) const { return h && check_fn ? check_fn(h, A, dtype_of<T>::value, n) : SPRS_INVALID_ARGUMENT; }
+    int apply(const T *in, T *out) const { return apply_fn(h, in, out); }
+};
+template <class T> AppliedPrec<T> ilu0_prec(const sprs_ilu0 *P);   // the which = 0 solve
+template <class T> AppliedPrec<T> amg_prec(const sprs_amg *P);
+
 // ---- dist.hip
 // exchange the halo entries of the extended vector x (local part [0,n_local) already in place)
 template <class T> int halo_exchange(const sprs_csr *A, T *x_ext);

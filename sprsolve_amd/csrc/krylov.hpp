@@ -151,9 +151,9 @@ class KrylovBase {
     template <class S>
     static int solve(S &s, bool no_precond, const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter,
                      Real<T> tol, size_t *its_out, Real<T> *res_out);
-    // The same for an ILU(0) handle (ilu0.hip): S supplies run_ilu / run_literal_ilu.
+    // The same for an applied preconditioner (an ILU(0) or AMG handle's view, internal.hpp): S supplies run_applied / run_literal_applied.
     template <class S>
-    static int solve_ilu(S &s, const sprs_ilu0 *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
+    static int solve_applied(S &s, const AppliedPrec<T> &P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
                          size_t *its_out, Real<T> *res_out);
     // |rhs|; a zero right-hand side answers x = 0 (*zero = true: the solve is over, *res_out holds the norm)
     int zero_rhs(const T *rhs, T *x, Real<T> *rhs_norm, Real<T> *res_out, bool *zero);
@@ -219,8 +219,8 @@ class Cg : public KrylovBase<T> {
     void destroy() { state.destroy(); KrylovBase<T>::destroy(); }
     int solve_dev(const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
                   size_t *its_out, Real<T> *res_out);
-    // z = P r is the ILU(0) handle's two triangular solves
-    int solve_dev_ilu(const sprs_ilu0 *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
+    // z = P r is an applied preconditioner (ILU(0), AMG)
+    int solve_dev_applied(const AppliedPrec<T> &P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
                       size_t *its_out, Real<T> *res_out);
 
    private:
@@ -232,9 +232,9 @@ class Cg : public KrylovBase<T> {
     int run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
     template <class V>
     int run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
-    int start_ilu(const sprs_ilu0 *P, const T *rhs, T *x, Real<T> tol, Real<T> *rhs_norm, Real<T> *tol2, T *rho, bool *done, Real<T> *res_out);
-    int run_ilu(const sprs_ilu0 *P, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
-    int run_literal_ilu(const sprs_ilu0 *P, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
+    int start_applied(const AppliedPrec<T> &P, const T *rhs, T *x, Real<T> tol, Real<T> *rhs_norm, Real<T> *tol2, T *rho, bool *done, Real<T> *res_out);
+    int run_applied(const AppliedPrec<T> &P, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
+    int run_literal_applied(const AppliedPrec<T> &P, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
 };
 
 // Restarted GMRES for any non-singular A (recurrence: include/sprsolve_hip.h, sprs_gmres_*; kernels: gmres_fuse.hpp)
@@ -250,8 +250,8 @@ class Gmres : public KrylovBase<T> {
     void destroy();
     int solve_dev(const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
                   size_t *its_out, Real<T> *res_out);
-    // z = P v_j and u = P u are the ILU(0) handle's two triangular solves
-    int solve_dev_ilu(const sprs_ilu0 *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
+    // z = P v_j and u = P u are an applied preconditioner (ILU(0), AMG)
+    int solve_dev_applied(const AppliedPrec<T> &P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
                       size_t *its_out, Real<T> *res_out);
 
    private:
@@ -265,8 +265,8 @@ class Gmres : public KrylovBase<T> {
     int run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
     template <class V>
     int run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
-    int run_ilu(const sprs_ilu0 *P, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
-    int run_literal_ilu(const sprs_ilu0 *P, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
+    int run_applied(const AppliedPrec<T> &P, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
+    int run_literal_applied(const AppliedPrec<T> &P, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
 };
 
 // LSMR for min |rhs - A x|_2 (+ damping) on any A, rectangular included (recurrence: include/sprsolve_hip.h, sprs_lsmr_*; kernels:
@@ -416,16 +416,16 @@ int KrylovBase<T>::solve(S &s, bool no_precond, const sprs_diag *P, const T *rhs
 
 template <class T>
 template <class S>
-int KrylovBase<T>::solve_ilu(S &s, const sprs_ilu0 *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
+int KrylovBase<T>::solve_applied(S &s, const AppliedPrec<T> &P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
                              size_t *its_out, Real<T> *res_out) {
     size_t its_dummy; Real<T> res_dummy;
     if (!its_out) its_out = &its_dummy;
     if (!res_out) res_out = &res_dummy;
     if (rhs_len != s.n) return SPRS_INCOMPATIBLE_RHS_SIZE;
     if (x_len != s.n) return SPRS_INCOMPATIBLE_X_SIZE;
-    SPRS_TRY(ilu0_check(P, s.A, dtype_of<T>::value, s.n));
+    SPRS_TRY(P.check(s.A, s.n));
     SPRS_TRY(s.begin_solve());
-    const int st = s.mode == 1 ? s.run_literal_ilu(P, rhs, x, max_iter, tol, its_out, res_out) : s.run_ilu(P, rhs, x, max_iter, tol, its_out, res_out);
+    const int st = s.mode == 1 ? s.run_literal_applied(P, rhs, x, max_iter, tol, its_out, res_out) : s.run_applied(P, rhs, x, max_iter, tol, its_out, res_out);
     if (st >= SPRS_ERR_HIP) return st;
     SPRS_TRY(s.end_solve());
     return st;

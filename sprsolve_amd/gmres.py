@@ -1,6 +1,7 @@
 """Restarted GMRES for general (non-symmetric) operators (no reference analogue)."""
 from . import _lib
 from ._solver import _SolverBase
+from .amg import AMG
 from .ilu import ILU0
 
 
@@ -28,7 +29,9 @@ class GMRES(_SolverBase):
         return self._solve(None, rhs, x, max_iter, tol, False)
 
     def precond_solve(self, precond, rhs, x, max_iter, tol):
-        """Preconditioned from the right by a `DiagPrecond` (Jacobi) or an `ILU0`: the residual it reports is the true one's estimate."""
+        """Preconditioned from the right by a `DiagPrecond` (Jacobi), an `ILU0` or an `AMG`: the residual it reports is the true one's estimate."""
         if isinstance(precond, ILU0):
-            return self._solve_ilu(precond, rhs, x, max_iter, tol)
+            return self._solve_applied("ilu0", precond, rhs, x, max_iter, tol)
+        if isinstance(precond, AMG):
+            return self._solve_applied("amg", precond, rhs, x, max_iter, tol)
         return self._solve(precond, rhs, x, max_iter, tol, True)
