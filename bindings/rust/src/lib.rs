@@ -70,6 +70,7 @@ pub mod sys {
         pub fn sprs_csr_create_i64_z(ctx: *mut sprs_ctx, nrows: i64, ncols: i64, nnz: i64, row_ptr: *const i64,
             col_idx: *const i64, val: *const Complex64, storage_csc: c_int, out: *mut *mut sprs_csr) -> c_int;
         pub fn sprs_csr_destroy(a: *mut sprs_csr) -> c_int;
+        pub fn sprs_csr_matmul(a: *const sprs_csr, b: *const sprs_csr, out: *mut *mut sprs_csr, info: *mut i64) -> c_int;
         pub fn sprs_csr_stream_format(a: *const sprs_csr, n_offsets: *mut c_int, n_pairs: *mut c_int) -> c_int;
         pub fn sprs_csr_tile_plan(a: *const sprs_csr, n_tiles: *mut i64, n_tile_blocks: *mut i64, n_other_blocks: *mut i64) -> c_int;
         pub fn sprs_csr_chain_plan(a: *const sprs_csr, n_tiles: *mut i64, n_segments: *mut i64, n_chains: *mut i64, n_other_blocks: *mut i64) -> c_int;
@@ -462,6 +463,16 @@ impl<T: HipScalar> HipCsr<T> {
     }
     pub fn rows(&self) -> usize { self.size.0 }
     pub fn cols(&self) -> usize { self.size.1 }
+    /// C = self * other as an independent operator of shape (self.rows, other.cols), built on the device with the bits of the
+    /// serial row-by-row loop (csrc/spgemm.hip; the contract is stated at `sprs_csr_matmul` in the header).  `other`'s rows must
+    /// be strictly ascending.  The second value: rows taken by the short / table / dense kernel and the two path limits.
+    pub fn matmul(&self, other: &HipCsr<T>) -> Result<(HipCsr<T>, [i64; 5]), i32> {
+        let mut handle = ptr::null_mut();
+        let mut info = [0i64; 5];
+        let st = unsafe { sys::sprs_csr_matmul(self.handle, other.handle, &mut handle, info.as_mut_ptr()) };
+        if st != sys::SPRS_OK { return Err(st); }
+        Ok((HipCsr { ctx: self.ctx, handle, size: (self.size.0, other.size.1), _marker: PhantomData }, info))
+    }
     /// Which stream the SpMV reads: (0 plain CSR | 1 offset codes | 2 pair codes, distinct offsets, distinct pairs).
     /// Backend detail (csrc/spmv_dict.hip); y is bit-identical in all three.
     pub fn stream_format(&self) -> (i32, i32, i32) {

@@ -358,6 +358,33 @@ int sprs_csr_adjoint(const sprs_csr *A, int conjugate, sprs_csr **out);
  * val nnz entries of the handle's scalar type. */
 int sprs_csr_read(const sprs_csr *A, int32_t *row_ptr_host, int32_t *col_idx_host, void *val_host);
 
+/* ---------------------------------------------------------------- the product of two operators
+ * sprs_csr_matmul builds C = A B as an ordinary, independent handle of shape A.nrows x B.ncols: it owns its arrays, outlives A
+ * and B, and every sprs_mul_vec_* / sprs_mul_mat_* / solver entry point, sprs_csr_adjoint, sprs_csr_matmul itself and
+ * sprs_amg_create take it like any other handle.  The construction runs on the device only (csrc/spgemm.hip).
+ * The contract is the serial row-by-row loop, and the result has its bits in f64, c64, f32 and c32:
+ *   - row i of C comes from one accumulator per column, each starting at zero (+0);
+ *   - the stored entries a_ik of row i of A are walked in stored order, and for each the stored entries b_kj of row k of B in
+ *     stored order; each pair does acc_j = acc_j + a_ik * b_kj, two separately rounded operations (complex numbers by
+ *     components with the naive product formula).  No accumulator is initialised with its first product: 0 + (-0.0) is +0.0;
+ *   - the stored pattern is the structural one: an entry whose terms cancel to exactly zero stays stored;
+ *   - the columns of every row of C are strictly ascending;
+ *   - two calls on the same operands give the same bytes.
+ * Operands: single-GPU handles of one context and one scalar type (otherwise SPRS_INVALID_ARGUMENT, text in sprs_last_error);
+ * A.ncols != B.nrows: SPRS_DIM_MISMATCH.  The rows of A may be stored in any order and may hold duplicate columns (their
+ * contributions are folded in stored order).  The rows of B must be strictly ascending: checked on the device,
+ * SPRS_INVALID_ARGUMENT with the smallest offending row in the text.  A == B is allowed.  A product of more than 2^31 - 1
+ * stored entries: SPRS_INVALID_ARGUMENT.  Empty rows of A give empty rows of C, empty rows of B contribute nothing.
+ * Each row of A is dealt to one of three kernels by u_i = the sum of nnz(B row k) over its stored entries a_ik, an upper bound
+ * of its products: u_i <= 64 several rows per wavefront, small tables in LDS; u_i <= 1024 (2048 in f32) one workgroup per row
+ * and a hash table in LDS sized for twice that; larger rows one workgroup per row with a dense accumulator of B.ncols entries
+ * in device scratch.  At most 1024 such workgroups run, and no more than fit 256 MiB: the scratch of a call is bounded by
+ * max(256 MiB, B.ncols * (sizeof(scalar) + 4)) bytes whatever the matrices.  Further temporary device memory: 29 bytes per row
+ * of A + the result.
+ * info (may be NULL) receives 5 values: [0..2] the rows of A taken by the short / table / dense kernel, [3] the largest u_i of
+ * the short kernel, [4] the largest u_i of the table kernel for this scalar type. */
+int sprs_csr_matmul(const sprs_csr *A, const sprs_csr *B, sprs_csr **out, int64_t *info);
+
 /* ---------------------------------------------------------------- LSMR
  * Fong & Saunders' LSMR: x minimises |rhs - A x|_2, or with damp > 0 |[A; damp I] x - [rhs; 0]|_2, for A of ANY shape (m rows,
  * n columns; rank-deficient and inconsistent systems included; on an under-determined system started from x = 0 the minimum-norm

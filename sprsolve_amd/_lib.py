@@ -133,6 +133,7 @@ def _protos():
     P["sprs_axpy_cs"] = [_vp, _sz, C.c_float, _vp, _vp]
     P["sprs_csr_destroy"] = [_vp]
     P["sprs_csr_adjoint"] = [_vp, _int, _pp]
+    P["sprs_csr_matmul"] = [_vp, _vp, _pp, C.POINTER(_i64)]
     P["sprs_csr_read"] = [_vp, _vp, _vp, _vp]
     for k in ("bicgstab", "minres", "csminres", "cg", "gmres", "cgmany", "lsmr"):
         P["sprs_%s_destroy" % k] = [_vp]

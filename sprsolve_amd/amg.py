@@ -11,7 +11,7 @@ from .mat import MatVecMul
 
 class AMG(MatVecMul):
     """`AMG.new(A, theta=0.08, coarse_max=256, max_levels=16)`: a smoothed-aggregation hierarchy of a square single-GPU `HipCsr`,
-    built on the host at creation.  As a `MatVecMul` it applies one V(1,1) cycle with damped Jacobi (csrc/amg.hip);
+    built at creation (aggregation on the host, the sparse products on the device).  As a `MatVecMul` it applies one V(1,1) cycle with damped Jacobi (csrc/amg.hip);
     `CG.precond_solve` and `GMRES.precond_solve` take it in place of a `DiagPrecond`.  The handle owns its hierarchy: A may be
     closed afterwards."""
 

@@ -1,4 +1,5 @@
-// Smoothed-aggregation algebraic multigrid: the hierarchy (built on the host at creation, serial and deterministic) and the
+// Smoothed-aggregation algebraic multigrid: the hierarchy (built at creation: the aggregation and the prolongator formula on the
+// host, serial; the three sparse products of every level on the device, spgemm.hip, with the bits of the serial loop) and the
 // V(1,1) cycle that applies it as a preconditioner.  No reference analogue; the rules and the order of every sum are stated in
 // the header (sprs_amg_*) and restated by tests/_amg_ref.py.
 //
@@ -43,33 +44,6 @@ template <class T> inline Real<T> hmod(T a) {   // |a|: fabs, or sqrt(re re + im
 template <class T> inline bool bad_pivot(T u) {
     const Real<T> re = sre(u), im = sim(u);
     return !std::isfinite(re) || !std::isfinite(im) || (re == Real<T>(0) && im == Real<T>(0));
-}
-
-// C = A B row by row in Gustavson order: for a_ik with k ascending, for b_kj with j ascending, acc_j += a_ik b_kj (acc from zero);
-// the stored pattern is the structural one, columns sorted
-template <class T>
-bool spgemm(const HCsr<T> &A, const HCsr<T> &B, HCsr<T> &C) {
-    C.n = A.n; C.ncols = B.ncols;
-    C.ip.assign((size_t)A.n + 1, 0); C.ix.clear(); C.v.clear();
-    std::vector<T> acc((size_t)B.ncols, szero<T>());
-    std::vector<int32_t> mark((size_t)B.ncols, -1), cols;
-    for (int32_t i = 0; i < A.n; ++i) {
-        cols.clear();
-        for (int32_t p = A.ip[i]; p < A.ip[i + 1]; ++p) {
-            const int32_t k = A.ix[p];
-            const T a = A.v[p];
-            for (int32_t q = B.ip[k]; q < B.ip[k + 1]; ++q) {
-                const int32_t j = B.ix[q];
-                if (mark[j] != i) { mark[j] = i; acc[j] = szero<T>(); cols.push_back(j); }
-                acc[j] = sadd(acc[j], smul(a, B.v[q]));
-            }
-        }
-        std::sort(cols.begin(), cols.end());
-        if (C.ix.size() + cols.size() > (size_t)INT32_MAX) return false;
-        for (int32_t j : cols) { C.ix.push_back(j); C.v.push_back(acc[j]); }
-        C.ip[i + 1] = (int32_t)C.ix.size();
-    }
-    return true;
 }
 
 template <class T>
@@ -320,6 +294,54 @@ bool upload(U **dst, const U *src, size_t count, size_t pad = 2) {
     return count == 0 || hipMemcpy(*dst, src, sizeof(U) * count, hipMemcpyHostToDevice) == hipSuccess;
 }
 
+// A CSR matrix in HBM for the products of the set-up (spgemm.hip): owned, or borrowed from the caller's handle (level 0)
+template <class T>
+struct DCsr {
+    int32_t n = 0, ncols = 0;
+    int64_t nnz = 0;
+    int32_t *ip = nullptr, *ix = nullptr;
+    T *v = nullptr;
+    bool own = true;
+    DCsr() = default;
+    DCsr(const DCsr &) = delete;
+    DCsr &operator=(const DCsr &) = delete;
+    ~DCsr() { reset(); }
+    void reset() {
+        if (own) for (void *p : {(void *)ip, (void *)ix, (void *)v}) if (p) (void)hipFree(p);
+        ip = nullptr; ix = nullptr; v = nullptr; own = true;
+    }
+    void take(DCsr &o) {
+        reset();
+        n = o.n; ncols = o.ncols; nnz = o.nnz; ip = o.ip; ix = o.ix; v = o.v; own = o.own;
+        o.ip = nullptr; o.ix = nullptr; o.v = nullptr;
+    }
+};
+
+template <class T>
+bool to_device(const HCsr<T> &M, DCsr<T> &D) {
+    D.reset();
+    D.n = M.n; D.ncols = M.ncols; D.nnz = (int64_t)M.ix.size();
+    return upload(&D.ip, M.ip.data(), M.ip.size()) && upload(&D.ix, M.ix.data(), M.ix.size()) && upload(&D.v, M.v.data(), M.v.size());
+}
+
+template <class T>
+bool to_host(const DCsr<T> &D, HCsr<T> &M) {
+    M.n = D.n; M.ncols = D.ncols;
+    M.ip.resize((size_t)D.n + 1); M.ix.resize((size_t)D.nnz); M.v.resize((size_t)D.nnz);
+    if (hipMemcpy(M.ip.data(), D.ip, sizeof(int32_t) * M.ip.size(), hipMemcpyDeviceToHost) != hipSuccess) return false;
+    if (D.nnz == 0) return true;
+    return hipMemcpy(M.ix.data(), D.ix, sizeof(int32_t) * M.ix.size(), hipMemcpyDeviceToHost) == hipSuccess &&
+           hipMemcpy(M.v.data(), D.v, sizeof(T) * M.v.size(), hipMemcpyDeviceToHost) == hipSuccess;
+}
+
+// C = A B in Gustavson order on the device: the bits of the serial loop (the contract of sprs_csr_matmul)
+template <class T>
+int dev_product(sprs_ctx *c, const DCsr<T> &A, const DCsr<T> &B, DCsr<T> &C) {
+    C.reset();
+    C.n = A.n; C.ncols = B.ncols;
+    return spgemm_dev<T>(c, "sprs_amg", A.n, B.n, B.ncols, A.ip, A.ix, A.v, B.ip, B.ix, B.v, &C.ip, &C.ix, &C.v, &C.nnz, nullptr);
+}
+
 template <class T>
 bool build_sell(SellMat &M, const HCsr<T> &A) {
     M.n = A.n;
@@ -414,6 +436,9 @@ int amg_create(const sprs_csr *A, double theta_d, int64_t coarse_max, int64_t ma
             }
     // the hierarchy
     const R theta = (R)theta_d;
+    DCsr<T> dA;                                              // the level's operator in HBM: level 0 reads the handle's own arrays
+    dA.own = false; dA.n = dA.ncols = A0.n; dA.nnz = A->nnz;
+    dA.ip = A->row_ptr; dA.ix = A->col_idx; dA.v = (T *)A->val;
     while (true) {
         const int l = (int)H.size() - 1;
         HLevel<T> &Lh = H[l];
@@ -424,22 +449,27 @@ int amg_create(const sprs_csr *A, double theta_d, int64_t coarse_max, int64_t ma
         if (n <= coarse_max || l + 1 >= max_levels) break;
         const int32_t nc = aggregate(Lh.A, Lh.diag, (R)(theta * std::ldexp(R(1), -l)), Lh.agg);
         if (2 * (int64_t)nc > n) { Lh.agg.clear(); break; }    // the half-rows stop: this level is the coarsest
-        HCsr<T> Tm, AT, AP, Ac;
+        HCsr<T> Tm, AT, Ac;
         Tm.n = n; Tm.ncols = nc; Tm.ip.resize((size_t)n + 1); Tm.ix = Lh.agg; Tm.v.assign((size_t)n, sone<T>());
         for (int32_t i = 0; i <= n; ++i) Tm.ip[i] = i;
-        bool ok = spgemm(Lh.A, Tm, AT);
+        // the three products run on the device (spgemm.hip); A T and A_c come back for the host steps, A P never leaves HBM
+        DCsr<T> dT, dAT, dP, dR, dAP, dAc;
+        if (!to_device(Tm, dT)) return SPRS_ERR_HIP;
+        SPRS_TRY(dev_product(c, dA, dT, dAT));
+        if (!to_host(dAT, AT)) return SPRS_ERR_HIP;
+        dT.reset(); dAT.reset();
         Lh.P = AT;
-        for (int32_t i = 0; ok && i < n; ++i)                // p_ic = t_ic - (omega (A T)_ic) / d_i
+        for (int32_t i = 0; i < n; ++i)                      // p_ic = t_ic - (omega (A T)_ic) / d_i
             for (int32_t p = AT.ip[i]; p < AT.ip[i + 1]; ++p) {
                 const T t = AT.ix[p] == Lh.agg[i] ? sone<T>() : szero<T>();
                 Lh.P.v[p] = ssub(t, sdiv(smulr(AT.v[p], Lh.omega), Lh.diag[i]));
             }
         transpose_conj(Lh.P, Lh.R);
-        ok = ok && spgemm(Lh.A, Lh.P, AP) && spgemm(Lh.R, AP, Ac);
-        if (!ok) {
-            snprintf(c->err, sizeof(c->err), "sprs_amg: a coarse operator has more than 2^31 - 1 stored entries");
-            return SPRS_INVALID_ARGUMENT;
-        }
+        if (!to_device(Lh.P, dP) || !to_device(Lh.R, dR)) return SPRS_ERR_HIP;
+        SPRS_TRY(dev_product(c, dA, dP, dAP));
+        SPRS_TRY(dev_product(c, dR, dAP, dAc));
+        if (!to_host(dAc, Ac)) return SPRS_ERR_HIP;
+        dA.take(dAc);                                        // the next level's operator stays where it was formed
         H.emplace_back();
         H.back().A = std::move(Ac);
     }

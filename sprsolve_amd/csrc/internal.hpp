@@ -353,6 +353,30 @@ template <class T>
 int launch_spmm(const sprs_csr *A, const T *x, T *y, int ld, int k, int dot_mode, const T *u, T *part, const int *running);
 int spmm_grid(const sprs_csr *A);   // workgroups == partials per column of one launch
 
+// ---- transpose.hip / spgemm.hip / amg.hip
+struct DevBufs {     // the temporaries of one construction, released on every return path
+    std::vector<void *> p;
+    ~DevBufs() { for (void *q : p) if (q) (void)hipFree(q); }
+    template <class U> int alloc(sprs_ctx *c, U **out, size_t count) {
+        *out = nullptr;
+        SPRS_HIP_TRY(c, hipMalloc((void **)out, sizeof(U) * (count ? count : 1)));
+        p.push_back(*out);
+        return SPRS_OK;
+    }
+    void release(void *q) { for (auto &r : p) if (r == q) r = nullptr; }   // q now belongs to somebody else
+    void free(void *q) { for (auto &r : p) if (r == q) { (void)hipFree(q); r = nullptr; } }
+};
+
+// ---- spgemm.hip
+// C = A B on raw device CSR arrays (the contract of sprs_csr_matmul in the header; A is nrA x nrB, B is nrB x ncB): no handle is
+// created and no stream format planned.  On SPRS_OK *c_rp (nrA + 1), *c_ci and *c_v (*c_nnz entries; at least one is allocated)
+// are hipMalloc'd arrays that belong to the caller.  Checks on the device that A's columns lie in [0, nrB) and that B's rows are
+// strictly ascending in [0, ncB): SPRS_INVALID_ARGUMENT with a text that starts with `who`.  info: as sprs_csr_matmul, may be
+// null.  Blocking; the caller holds the context's lock and has set the device.
+template <class T>
+int spgemm_dev(sprs_ctx *c, const char *who, int64_t nrA, int64_t nrB, int64_t ncB, const int32_t *a_rp, const int32_t *a_ci, const T *a_v,
+               const int32_t *b_rp, const int32_t *b_ci, const T *b_v, int32_t **c_rp, int32_t **c_ci, T **c_v, int64_t *c_nnz, int64_t *info);
+
 // ---- blas1.hip  (all on ctx->stream, asynchronous)
 template <class T, class S> int launch_axpy(sprs_ctx *c, size_t n, S a, const T *x, T *y);
 template <class T> int launch_axpby(sprs_ctx *c, size_t n, T a, const T *x, T b, T *y);

@@ -51,19 +51,6 @@ __global__ __launch_bounds__(BLOCK) void adj_fill_kernel(int64_t nnz, int64_t nr
     }
 }
 
-struct DevBufs {     // the temporaries of one construction, released on every return path
-    std::vector<void *> p;
-    ~DevBufs() { for (void *q : p) if (q) (void)hipFree(q); }
-    template <class U> int alloc(sprs_ctx *c, U **out, size_t count) {
-        *out = nullptr;
-        SPRS_HIP_TRY(c, hipMalloc((void **)out, sizeof(U) * (count ? count : 1)));
-        p.push_back(*out);
-        return SPRS_OK;
-    }
-    void release(void *q) { for (auto &r : p) if (r == q) r = nullptr; }   // q now belongs to somebody else
-    void free(void *q) { for (auto &r : p) if (r == q) { (void)hipFree(q); r = nullptr; } }
-};
-
 template <class T, class CT>
 int adjoint_typed(const sprs_csr *A, int conj, int (*create_dev)(sprs_ctx *, int64_t, int64_t, int64_t, const int32_t *, const int32_t *, const CT *, int, sprs_csr **),
                   sprs_csr **out) {

@@ -90,6 +90,27 @@ class HipCsr(MatVecMul):
         check(_lib.lib().sprs_csr_adjoint(self.h, 1 if conjugate else 0, C.byref(h)), self.ctx.h)
         return HipCsr(h, self.ctx, self.dtype, (self.shape[1], self.shape[0]))     # owning, whatever view `self` is
 
+    def matmul(self, other, info=False):
+        """C = self @ other as an independent handle of shape (self.rows, other.cols), built on the device (csrc/spgemm.hip) with the
+        bits of the serial row-by-row loop: acc_j += a_ik * b_kj from +0 in the stored order of self's row, columns ascending, the
+        structural pattern kept.  `other`'s rows must be strictly ascending; both operands share dtype and context.
+        info=True: (C, [rows on the short, table and dense kernels, largest bound of the short kernel, of the table kernel])."""
+        if not isinstance(other, HipCsr):
+            raise TypeError("matmul takes a HipCsr right operand")
+        h = C.c_void_p()
+        inf = (C.c_int64 * 5)()
+        st = _lib.lib().sprs_csr_matmul(self.h, other.h, C.byref(h), inf)
+        if st == _lib.INVALID_ARGUMENT:
+            raise ValueError("sprsolve_hip: invalid argument: " + (_lib.lib().sprs_last_error(self.ctx.h) or b"").decode(errors="replace"))
+        check(st, self.ctx.h)
+        out = HipCsr(h, self.ctx, self.dtype, (self.shape[0], other.shape[1]))
+        return (out, [int(v) for v in inf]) if info else out
+
+    def __matmul__(self, other):
+        if not isinstance(other, HipCsr):
+            return NotImplemented
+        return self.matmul(other)
+
     def to_host(self):
         """(indptr, indices, data) of the handle's CSR arrays, copied from the device."""
         nnz = self.nnz()
