@@ -702,9 +702,35 @@ int sprs_dist_mul_vec_dev_c(const sprs_csr *A, sprs_c32 *x_ext_dev, sprs_c32 *y_
  * sprs_ilu0_read: the nnz factor values at A's CSR positions, l_ik below the diagonal, u_ij on and above it.
  * Solvers: a handle of another scalar type or context than the solver's A, a distributed A, or a NULL P is
  * SPRS_INVALID_ARGUMENT; another size is SPRS_DIM_MISMATCH.  z = P r, z = P v_j and u = P u of the recurrences are the
- * which = 0 solve; everything else (events, *its_out / *res_out, trace rows, both modes) is as stated for the solvers. */
+ * which = 0 solve; everything else (events, *its_out / *res_out, trace rows, both modes) is as stated for the solvers.
+ *
+ * Jacobi-sweep solves.  sprs_ilu0_create_sweeps(A, sweeps, ...) fixes a handle's mode at creation: sweeps = 0 is
+ * sprs_ilu0_create itself; sweeps < 0 or > SPRS_ILU0_MAX_SWEEPS is SPRS_INVALID_ARGUMENT; every other creation error is as
+ * above.  The factors are those of sprs_ilu0_create (sprs_ilu0_read returns the same values).  With sweeps = k >= 1 the three
+ * solves are replaced by k Jacobi sweeps from zero on each triangular system (a triangular matrix is its diagonal plus a
+ * nilpotent part, so the sweeps converge for every factor).  The same scalar operations as above; every sigma is folded from
+ * +0 over the row's stored entries in ascending column order, sigma = sigma + a_ij*x_j:
+ *     lower (which = 1):  y(1) = in;  y(m+1)_i = in_i - sigma_i, sigma_i over l_ij, j < i, reading y(m);  out = y(k)
+ *     upper (which = 2):  z(1)_i = in_i / u_ii;  z(m+1)_i = (in_i - sigma_i) / u_ii, sigma_i over u_ij, j > i, reading z(m);
+ *                         out = z(k)
+ *     application (which = 0):  the upper sweeps on the output of the lower sweeps.
+ * Every sweep reads only the previous sweep's vector (the handle owns the vectors the sweeps alternate between; never in
+ * place), so the result does not depend on the launch geometry and is the same bytes on every call.  The fold is the exact
+ * solve's own expression, so a row of level l holds its final bits from sweep l + 1 on: with k >= lower_levels (upper_levels)
+ * the sweeps return the exact solve bit for bit.  For Hermitian positive-definite A the k-sweep application is Hermitian
+ * positive definite up to rounding, so CG may take it.
+ * A sweep is one launch over the whole factor, one lane per row, the factors kept in natural row order in 64-row slices,
+ * slice-column-major (no level-major copy is kept).  Lower sweep 1 is no pass; upper sweep 1 of an application is stored by
+ * the last lower launch.  Launches: which = 1: k - 1 (k = 1: one device copy, nothing when in == out; k = 2 with in == out:
+ * one device copy more); which = 2: k; which = 0: 2k - 2, one for k = 1.  sprs_ilu0_levels reports the level counts of the
+ * pattern as for an exact handle and k - 1 / k as the two launch counts.  in == out is allowed for every `which`; `in` is
+ * never written unless it is `out`.  sprs_ilu0_sweeps: k, 0 for an exact handle, -1 for NULL.  Everything that takes a
+ * sprs_ilu0 (the solves, sprs_ilu0_cg_*, sprs_ilu0_gmres_*) takes either kind. */
+#define SPRS_ILU0_MAX_SWEEPS 4096
 typedef struct sprs_ilu0 sprs_ilu0;
 int sprs_ilu0_create(const sprs_csr *A, sprs_ilu0 **out, int64_t *row_out);   /* row_out may be NULL */
+int sprs_ilu0_create_sweeps(const sprs_csr *A, int sweeps, sprs_ilu0 **out, int64_t *row_out);   /* row_out may be NULL */
+int sprs_ilu0_sweeps(const sprs_ilu0 *P);
 int sprs_ilu0_destroy(sprs_ilu0 *P);           /* NULL is a no-op */
 int sprs_ilu0_levels(const sprs_ilu0 *P, int64_t *lower_levels, int64_t *upper_levels, int64_t *lower_launches, int64_t *upper_launches);   /* any pointer may be NULL */
 int sprs_ilu0_read(const sprs_ilu0 *P, void *val_host);

@@ -161,6 +161,8 @@ def _protos():
     P["sprs_csr_chain_plan"] = [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]
     P["sprs_csr_spmv_route"] = [_vp, _int, _int, C.POINTER(_int), C.POINTER(_int), C.POINTER(_int), C.POINTER(_i64), C.POINTER(_int), C.POINTER(_int)]
     P["sprs_ilu0_create"] = [_vp, _pp, C.POINTER(_i64)]
+    P["sprs_ilu0_create_sweeps"] = [_vp, _int, _pp, C.POINTER(_i64)]
+    P["sprs_ilu0_sweeps"] = [_vp]
     P["sprs_ilu0_destroy"] = [_vp]
     P["sprs_ilu0_levels"] = [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]
     P["sprs_ilu0_read"] = [_vp, _vp]

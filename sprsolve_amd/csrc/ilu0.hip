@@ -18,6 +18,13 @@
 //    another workgroup: stream order between launches is the only inter-workgroup synchronisation.
 // The factorisation runs on the same plan over a copy of A's values in CSR order (one lane per row, the row-k match by a
 // two-pointer merge); the level-major copies are laid out from its result.
+//
+// A handle created with sweeps = k >= 1 (sprs_ilu0_create_sweeps) factorises in the same way and then replaces both exact
+// solves by k Jacobi sweeps from the header's statement: one launch per sweep over the whole factor, whatever the level count.
+// Such a handle keeps its factors in NATURAL row order and no level-major copy: lane t of slice s owns row 64 s + t, the
+// storage is slice-column-major as above, so a slice is full whatever the levels look like and neighbouring lanes gather
+// neighbouring x.  A sweep reads the previous sweep's vector and writes another one (never in place), so its result does not
+// depend on the launch geometry; the handle owns the three vectors the sweeps alternate between.
 #include <algorithm>
 
 #include "device.hpp"
@@ -117,6 +124,50 @@ __global__ __launch_bounds__(BLOCK) void tri_batch_kernel(TriDev<T> F, int l0, i
     }
 }
 
+// ---- Jacobi sweeps on a factor in natural row order (row = 64 * slice + lane; IluTri::prow and ::lvl_slice stay empty)
+template <class T>
+struct SweepDev {
+    const int32_t *plen;                 // n rounded up to whole slices: entries of the row
+    const int64_t *sbase;
+    const int32_t *col;
+    const T *val, *piv;                  // piv: u_ii per row (upper factor only)
+};
+
+// One sweep, one wavefront per slice: next_i = rhs_i - sigma_i(prev) for the lower factor, the same divided by u_ii for the
+// upper one; tri_row's walk and fold.  `prev` is never `next`; `rhs` may be `next` (a lane reads rhs of its own row only).
+// FUSE (the last lower sweep of an application): the lane also stores the upper solve's first sweep, z1_i = next_i / u_ii.
+template <class T, bool UPPER, bool FUSE>
+__global__ __launch_bounds__(BLOCK) void sweep_kernel(SweepDev<T> F, int n, const T *rhs, const T *prev, T *next, const T *upiv, T *z1) {
+    const int s = (int)blockIdx.x * NWAVE + (int)(threadIdx.x >> 6), t = threadIdx.x & (WAVE - 1);
+    const int row = s * ILU_SLICE + t;
+    if (row >= n) return;
+    const int len = F.plen[row];
+    const int64_t b = F.sbase[s] + t;
+    T sigma = szero<T>();
+    int e = 0;
+    for (; e + 4 <= len; e += 4) {                                   // four gathers in flight, folded in order
+        int c[4]; T v[4], x[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { c[u] = F.col[b + (int64_t)(e + u) * ILU_SLICE]; v[u] = F.val[b + (int64_t)(e + u) * ILU_SLICE]; }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) x[u] = prev[c[u]];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) sigma = sadd(sigma, smul(v[u], x[u]));
+    }
+    for (; e < len; ++e) sigma = sadd(sigma, smul(F.val[b + (int64_t)e * ILU_SLICE], prev[F.col[b + (int64_t)e * ILU_SLICE]]));
+    T d = ssub(rhs[row], sigma);
+    if (UPPER) d = sdiv(d, F.piv[row]);
+    next[row] = d;
+    if (FUSE) z1[row] = sdiv(d, upiv[row]);
+}
+
+// the upper solve's first sweep on its own: out_i = in_i / u_ii (in may be out)
+template <class T>
+__global__ __launch_bounds__(BLOCK) void sweep_first_upper_kernel(int n, const T *in, const T *__restrict__ piv, T *out) {
+    const int row = (int)blockIdx.x * BLOCK + (int)threadIdx.x;
+    if (row < n) out[row] = sdiv(in[row], piv[row]);
+}
+
 // ---- the factorisation, in place on `a` (CSR order): row i by one lane
 template <class T>
 __device__ __forceinline__ void ilu_row(int i, const int32_t *__restrict__ rp, const int32_t *__restrict__ ci,
@@ -176,6 +227,8 @@ struct sprs_ilu0 {
     void *fval = nullptr;                // device, nnz of T: the factors at A's CSR positions (sprs_ilu0_read)
     IluTri L, U;
     void *ybuf = nullptr;                // device, n of T: y = L^-1 in of a which = 0 solve
+    int sweeps = 0;                      // 0: exact level-scheduled solves; k >= 1: k Jacobi sweeps on natural-order factors
+    void *sbuf[2] = {nullptr, nullptr};  // device, n of T each: with ybuf the vectors the sweeps alternate between (sweeps > 0)
     void *in_tmp = nullptr, *out_tmp = nullptr;   // staging of the host entry points (lazily allocated)
 };
 
@@ -197,6 +250,53 @@ int tri_solve(sprs_ctx *c, const IluTri &F, const T *in, T *out) {
             const int s0 = F.h_lvl_slice[p.l0], s1 = F.h_lvl_slice[p.l1];
             hipLaunchKernelGGL((tri_level_kernel<T, UPPER>), dim3((s1 - s0 + NWAVE - 1) / NWAVE), dim3(BLOCK), 0, c->stream, D, s0, s1, in, out);
         }
+    }
+    SPRS_HIP_TRY(c, hipGetLastError());
+    return SPRS_OK;
+}
+
+// The k-sweep solves of the header on the stream: which = 1 costs k - 1 launches, which = 2 k, which = 0 2k - 2 (one for k = 1).
+// Every sweep writes a vector that no lane of the launch reads as `prev`; only the last one writes `out`.
+template <class T>
+int sweeps_apply(const sprs_ilu0 *P, int which, const T *in, T *out) {
+    sprs_ctx *c = P->ctx;
+    const int n = (int)P->n, k = P->sweeps;
+    if (!n) return SPRS_OK;
+    const SweepDev<T> L{P->L.plen, P->L.sbase, P->L.col, (const T *)P->L.val, nullptr};
+    const SweepDev<T> U{P->U.plen, P->U.sbase, P->U.col, (const T *)P->U.val, (const T *)P->U.piv};
+    T *const buf[3] = {(T *)P->ybuf, (T *)P->sbuf[0], (T *)P->sbuf[1]};
+    const dim3 grid((unsigned)((P->L.nslice + NWAVE - 1) / NWAVE)), egrid((unsigned)((n + BLOCK - 1) / BLOCK));
+    const T *rhs = in;                   // the upper sweeps' right-hand side: y(k) of an application, `in` of which = 2
+    T *spare = buf[0];                   // with buf[2] the two vectors the upper sweeps alternate between
+    if (which != 2) {
+        if (k == 1 && which == 1) {      // y(1) = in: no pass at all
+            if (in != out) SPRS_HIP_TRY(c, hipMemcpyAsync(out, in, sizeof(T) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+            return SPRS_OK;
+        }
+        const T *prev = in;              // y(1)
+        if (which == 1 && k == 2 && in == out) {   // the only sweep would read y(1) where it writes: read a copy
+            SPRS_HIP_TRY(c, hipMemcpyAsync(buf[2], in, sizeof(T) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+            prev = buf[2];
+        }
+        for (int m = 2; m <= k; ++m) {
+            T *next = (m == k && which == 1) ? out : buf[m & 1];
+            if (m == k && which == 0)
+                hipLaunchKernelGGL((sweep_kernel<T, false, true>), grid, dim3(BLOCK), 0, c->stream, L, n, in, prev, next, U.piv, buf[2]);
+            else
+                hipLaunchKernelGGL((sweep_kernel<T, false, false>), grid, dim3(BLOCK), 0, c->stream, L, n, in, prev, next, (const T *)nullptr, (T *)nullptr);
+            prev = next;
+        }
+        if (which == 1) { SPRS_HIP_TRY(c, hipGetLastError()); return SPRS_OK; }
+        rhs = prev;                      // y(k): `in` itself for k = 1, else buf[k & 1]
+        spare = buf[(k & 1) ^ 1];
+    }
+    if (k == 1 || which == 2)            // z(1) on its own; an application with k >= 2 has it in buf[2] from the fused launch
+        hipLaunchKernelGGL((sweep_first_upper_kernel<T>), egrid, dim3(BLOCK), 0, c->stream, n, rhs, U.piv, k == 1 ? out : buf[2]);
+    const T *prev = buf[2];
+    for (int m = 2; m <= k; ++m) {
+        T *next = m == k ? out : (prev == buf[2] ? spare : buf[2]);
+        hipLaunchKernelGGL((sweep_kernel<T, true, false>), grid, dim3(BLOCK), 0, c->stream, U, n, rhs, prev, next, (const T *)nullptr, (T *)nullptr);
+        prev = next;
     }
     SPRS_HIP_TRY(c, hipGetLastError());
     return SPRS_OK;
@@ -268,8 +368,63 @@ int build_tri(IluTri &F, const std::vector<int32_t> &lvl_ptr, const std::vector<
     return ok ? SPRS_OK : SPRS_ERR_HIP;
 }
 
+// Host side of the natural-order layout of one factor (a sweeps handle): row i is lane i % 64 of slice i / 64.  plen is padded
+// to whole slices with empty rows; piv (filled when dpos is given) with ones.
 template <class T>
-int ilu0_create(const sprs_csr *A, sprs_ilu0 **out, int64_t *row_out) {
+struct NaturalTri {
+    int32_t nslice = 0;
+    std::vector<int32_t> plen, col;
+    std::vector<int64_t> sbase;
+    std::vector<T> val, piv;
+};
+
+template <class T, class EB, class EE>
+NaturalTri<T> layout_natural(int64_t n, const std::vector<int32_t> &ci, const std::vector<T> &fv, EB eb, EE ee, const std::vector<int32_t> *dpos) {
+    NaturalTri<T> N;
+    N.nslice = (int32_t)((n + ILU_SLICE - 1) / ILU_SLICE);
+    const size_t np = (size_t)N.nslice * ILU_SLICE;
+    N.plen.assign(np, 0);
+    N.sbase.assign((size_t)N.nslice, 0);
+    N.piv.assign(dpos ? np : 0, sone<T>());
+    int64_t slots = 0;
+    for (int32_t s = 0; s < N.nslice; ++s) {
+        const int64_t r0 = (int64_t)s * ILU_SLICE, r1 = std::min<int64_t>(r0 + ILU_SLICE, n);
+        int32_t width = 0;
+        for (int64_t i = r0; i < r1; ++i) {
+            N.plen[(size_t)i] = ee((int32_t)i) - eb((int32_t)i);
+            if (dpos) N.piv[(size_t)i] = fv[(size_t)(*dpos)[(size_t)i]];
+            width = std::max(width, N.plen[(size_t)i]);
+        }
+        N.sbase[(size_t)s] = slots;
+        slots += (int64_t)width * ILU_SLICE;
+    }
+    N.col.assign((size_t)slots, 0);
+    N.val.assign((size_t)slots, szero<T>());
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t b = eb((int32_t)i);
+        const size_t d0 = (size_t)N.sbase[(size_t)(i / ILU_SLICE)] + (size_t)(i % ILU_SLICE);
+        for (int32_t e = 0; e < N.plen[(size_t)i]; ++e) {
+            N.col[d0 + (size_t)e * ILU_SLICE] = ci[(size_t)b + e]; N.val[d0 + (size_t)e * ILU_SLICE] = fv[(size_t)b + e];
+        }
+    }
+    return N;
+}
+
+template <class T, class EB, class EE>
+int build_tri_natural(IluTri &F, int32_t nlev, int64_t n, const std::vector<int32_t> &ci, const std::vector<T> &fv, EB eb, EE ee,
+                      const std::vector<int32_t> *dpos) {
+    const NaturalTri<T> N = layout_natural<T>(n, ci, fv, eb, ee, dpos);
+    F.nlev = nlev;                       // reported by sprs_ilu0_levels; the sweeps follow no level plan
+    F.nslice = N.nslice;
+    T *dval = nullptr, *dpiv = nullptr;
+    bool ok = upload(&F.plen, N.plen) && upload(&F.sbase, N.sbase) && upload(&F.col, N.col) && upload(&dval, N.val);
+    F.val = dval;
+    if (ok && dpos) { ok = upload(&dpiv, N.piv); F.piv = dpiv; }
+    return ok ? SPRS_OK : SPRS_ERR_HIP;
+}
+
+template <class T>
+int ilu0_create(const sprs_csr *A, int sweeps, sprs_ilu0 **out, int64_t *row_out) {
     sprs_ctx *c = A->ctx;
     CtxLock lock(c);
     const int64_t n = A->nrows, nnz = A->nnz;
@@ -309,7 +464,7 @@ int ilu0_create(const sprs_csr *A, sprs_ilu0 **out, int64_t *row_out) {
     group_by_level(ulevel, nulev, uptr, urows);
 
     auto *P = new sprs_ilu0();
-    P->ctx = c; P->dtype = A->dtype; P->n = n; P->nnz = nnz;
+    P->ctx = c; P->dtype = A->dtype; P->n = n; P->nnz = nnz; P->sweeps = sweeps;
     int32_t *d_dpos = nullptr, *d_rows = nullptr, *d_lptr = nullptr;
     int *d_bad = nullptr;
     auto fail = [&](int st) {
@@ -321,6 +476,7 @@ int ilu0_create(const sprs_csr *A, sprs_ilu0 **out, int64_t *row_out) {
     if (hipMalloc((void **)&a, sizeof(T) * ((size_t)nnz + 2)) != hipSuccess) return fail(SPRS_ERR_HIP);
     P->fval = a;
     if (hipMalloc(&P->ybuf, sizeof(T) * ((size_t)n + 2)) != hipSuccess) return fail(SPRS_ERR_HIP);
+    for (void *&b : P->sbuf) if (sweeps && hipMalloc(&b, sizeof(T) * ((size_t)n + 2)) != hipSuccess) return fail(SPRS_ERR_HIP);
     if (!upload(&d_dpos, dpos) || !upload(&d_rows, lrows) || !upload(&d_lptr, lptr) || hipMalloc((void **)&d_bad, sizeof(int)) != hipSuccess)
         return fail(SPRS_ERR_HIP);
     int bad = INT32_MAX;
@@ -344,10 +500,12 @@ int ilu0_create(const sprs_csr *A, sprs_ilu0 **out, int64_t *row_out) {
         return fail(SPRS_ERR_HIP);
     }
     if (bad != INT32_MAX) { if (row_out) *row_out = bad; return fail(SPRS_ZERO_DIAGONAL); }
-    // the level-major copies of both factors
-    int st = build_tri<T>(P->L, lptr, lrows, ci, fv, [&](int32_t i) { return rp[i]; }, [&](int32_t i) { return dpos[i]; }, nullptr);
+    // the level-major copies of both factors, or (a sweeps handle) the natural-order ones in their place
+    auto lb = [&](int32_t i) { return rp[i]; }; auto le = [&](int32_t i) { return dpos[i]; };
+    auto ub = [&](int32_t i) { return dpos[i] + 1; }; auto ue = [&](int32_t i) { return rp[i + 1]; };
+    int st = sweeps ? build_tri_natural<T>(P->L, nlev, n, ci, fv, lb, le, nullptr) : build_tri<T>(P->L, lptr, lrows, ci, fv, lb, le, nullptr);
     if (st == SPRS_OK)
-        st = build_tri<T>(P->U, uptr, urows, ci, fv, [&](int32_t i) { return dpos[i] + 1; }, [&](int32_t i) { return rp[i + 1]; }, &dpos);
+        st = sweeps ? build_tri_natural<T>(P->U, nulev, n, ci, fv, ub, ue, &dpos) : build_tri<T>(P->U, uptr, urows, ci, fv, ub, ue, &dpos);
     if (st != SPRS_OK) return fail(st);
     for (void *p : {(void *)d_dpos, (void *)d_rows, (void *)d_lptr, (void *)d_bad}) (void)hipFree(p);
     *out = P;
@@ -387,6 +545,7 @@ int ilu0_apply(const sprs_ilu0 *P, int which, const T *in, T *out) {
     sprs_ctx *c = P->ctx;
     CtxLock lock(c);   // ybuf is per-handle scratch
     SPRS_HIP_TRY(c, hipSetDevice(c->device));
+    if (P->sweeps) return sweeps_apply<T>(P, which, in, out);
     if (which == 1) return tri_solve<T, false>(c, P->L, in, out);
     if (which == 2) return tri_solve<T, true>(c, P->U, in, out);
     SPRS_TRY((tri_solve<T, false>(c, P->L, in, (T *)P->ybuf)));
@@ -413,7 +572,7 @@ template AppliedPrec<cplxf> ilu0_prec<cplxf>(const sprs_ilu0 *);
 
 extern "C" {
 
-int sprs_ilu0_create(const sprs_csr *A, sprs_ilu0 **out, int64_t *row_out) {
+int sprs_ilu0_create_sweeps(const sprs_csr *A, int sweeps, sprs_ilu0 **out, int64_t *row_out) {
     SPRS_G(
         if (!A || !out) return SPRS_INVALID_ARGUMENT;
         *out = nullptr;
@@ -422,21 +581,29 @@ int sprs_ilu0_create(const sprs_csr *A, sprs_ilu0 **out, int64_t *row_out) {
             snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_ilu0: distributed operators are not supported (single GPU only)");
             return SPRS_INVALID_ARGUMENT;
         }
+        if (sweeps < 0 || sweeps > SPRS_ILU0_MAX_SWEEPS) {
+            snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_ilu0: sweeps must be in 0 .. %d (0 = exact solves), got %d", SPRS_ILU0_MAX_SWEEPS, sweeps);
+            return SPRS_INVALID_ARGUMENT;
+        }
         if (A->nrows != A->ncols) return SPRS_NOT_SQUARE;
         switch (A->dtype) {
-            case DT_D: return ilu0_create<double>(A, out, row_out);
-            case DT_Z: return ilu0_create<cplx>(A, out, row_out);
-            case DT_S: return ilu0_create<float>(A, out, row_out);
-            case DT_C: return ilu0_create<cplxf>(A, out, row_out);
+            case DT_D: return ilu0_create<double>(A, sweeps, out, row_out);
+            case DT_Z: return ilu0_create<cplx>(A, sweeps, out, row_out);
+            case DT_S: return ilu0_create<float>(A, sweeps, out, row_out);
+            case DT_C: return ilu0_create<cplxf>(A, sweeps, out, row_out);
         }
         return SPRS_INVALID_ARGUMENT;)
 }
+
+int sprs_ilu0_create(const sprs_csr *A, sprs_ilu0 **out, int64_t *row_out) { return sprs_ilu0_create_sweeps(A, 0, out, row_out); }
+
+int sprs_ilu0_sweeps(const sprs_ilu0 *P) { return P ? P->sweeps : -1; }
 
 int sprs_ilu0_destroy(sprs_ilu0 *P) {
     if (!P) return SPRS_OK;
     if (P->ctx) { (void)hipSetDevice(P->ctx->device); (void)hipStreamSynchronize(P->ctx->stream); }
     P->L.release(); P->U.release();
-    for (void *p : {P->fval, P->ybuf, P->in_tmp, P->out_tmp}) if (p) (void)hipFree(p);
+    for (void *p : {P->fval, P->ybuf, P->sbuf[0], P->sbuf[1], P->in_tmp, P->out_tmp}) if (p) (void)hipFree(p);
     delete P;
     return SPRS_OK;
 }
@@ -445,8 +612,8 @@ int sprs_ilu0_levels(const sprs_ilu0 *P, int64_t *lower_levels, int64_t *upper_l
     if (!P) return SPRS_INVALID_ARGUMENT;
     if (lower_levels) *lower_levels = P->L.nlev;
     if (upper_levels) *upper_levels = P->U.nlev;
-    if (lower_launches) *lower_launches = (int64_t)P->L.plan.size();
-    if (upper_launches) *upper_launches = (int64_t)P->U.plan.size();
+    if (lower_launches) *lower_launches = P->sweeps ? P->sweeps - 1 : (int64_t)P->L.plan.size();
+    if (upper_launches) *upper_launches = P->sweeps ? P->sweeps : (int64_t)P->U.plan.size();
     return SPRS_OK;
 }
 

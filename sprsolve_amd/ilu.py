@@ -1,4 +1,5 @@
-"""ILU(0) preconditioner with level-scheduled triangular solves (no reference analogue; include/sprsolve_hip.h, sprs_ilu0_*)."""
+"""ILU(0) preconditioner with level-scheduled or Jacobi-sweep triangular solves (no reference analogue; include/sprsolve_hip.h,
+sprs_ilu0_*)."""
 import ctypes as C
 
 import numpy as np
@@ -12,18 +13,25 @@ from .mat import MatVecMul
 class ILU0(MatVecMul):
     """`ILU0.new(A)`: the incomplete LU factorisation of a square single-GPU `HipCsr` on A's own pattern.  As a `MatVecMul` it
     applies M^-1 = U^-1 L^-1 (two triangular solves, level by level: csrc/ilu0.hip); `CG.precond_solve` and
-    `GMRES.precond_solve` take it in place of a `DiagPrecond`.  The handle owns its factors: A may be closed afterwards."""
+    `GMRES.precond_solve` take it in place of a `DiagPrecond`.  The handle owns its factors: A may be closed afterwards.
+    `ILU0.new(A, sweeps=k)`, k >= 1: the same factors, each triangular solve replaced by k Jacobi sweeps from zero (the header's
+    statement): one fully parallel launch per sweep instead of one per dependency level, 2k - 2 launches per application.  With
+    k at least the level count the sweeps return the exact solves bit for bit; a handful is usually enough for a preconditioner."""
 
     def __init__(self, handle, ctx, dtype, n, nnz):
         self.h, self.ctx, self.dtype, self.n, self.nnz = handle, ctx, np.dtype(dtype), int(n), int(nnz)
         self.s = sfx(self.dtype)
 
     @classmethod
-    def new(cls, A):
-        """Raises IncompatibleMatrixFormat (not square), ValueError (distributed A, unsorted or duplicate columns) or
-        ZeorDiagonalElem(row): a missing diagonal entry, or a pivot that is exactly zero or not finite."""
+    def new(cls, A, sweeps=0):
+        """sweeps = 0: exact level-scheduled solves; 1 .. 4096: that many Jacobi sweeps per triangular solve.
+        Raises IncompatibleMatrixFormat (not square), ValueError (distributed A, unsorted or duplicate columns, a sweep count
+        outside 0 .. 4096) or ZeorDiagonalElem(row): a missing diagonal entry, or a pivot that is exactly zero or not finite."""
+        sweeps = int(sweeps)
+        if not 0 <= sweeps <= 4096:
+            raise ValueError("sprsolve_hip: invalid argument: sweeps must be in 0 .. 4096 (0 = exact solves), got %d" % sweeps)
         h = C.c_void_p(); row = C.c_int64(-1)
-        st = _lib.lib().sprs_ilu0_create(A.h, C.byref(h), C.byref(row))
+        st = _lib.lib().sprs_ilu0_create_sweeps(A.h, sweeps, C.byref(h), C.byref(row))
         if st == _lib.ZERO_DIAGONAL:
             raise ZeorDiagonalElem(row.value)
         if st == _lib.INVALID_ARGUMENT:
@@ -32,9 +40,14 @@ class ILU0(MatVecMul):
         return cls(h, A.ctx, A.dtype, A.rows(), A.nnz())
 
     @property
+    def sweeps(self):
+        """Jacobi sweeps per triangular solve; 0 for exact solves."""
+        return int(_lib.lib().sprs_ilu0_sweeps(self.h))
+
+    @property
     def levels(self):
         """dict(lower_levels, upper_levels, lower_launches, upper_launches): dependency levels of the two solves and the kernel
-        launches one application of each costs."""
+        launches one application of each costs (a sweeps handle: sweeps - 1 and sweeps)."""
         v = [C.c_int64() for _ in range(4)]
         check(_lib.lib().sprs_ilu0_levels(self.h, *[C.byref(x) for x in v]), self.ctx.h)
         return dict(zip(("lower_levels", "upper_levels", "lower_launches", "upper_launches"), (x.value for x in v)))
@@ -61,7 +74,7 @@ class ILU0(MatVecMul):
                                                       v_out.ctypes.data_as(C.c_void_p), v_out.size), self.ctx.h)
 
     def mul_vec(self, v_in, v_out):
-        """v_out = U^-1 (L^-1 v_in); host arrays or device vectors (v_in may be v_out)."""
+        """v_out = U^-1 (L^-1 v_in), exactly or by sweeps as the handle was created; host arrays or device vectors (v_in may be v_out)."""
         self._apply(0, v_in, v_out)
 
     def mul_vec_unchecked(self, v_in, v_out):
