@@ -63,9 +63,12 @@ class _SolverBase:
                     steps=st.value, timed_dot_other=do.value, timed_fused_k2=t2.value, timed_fused_k4=t4.value)
 
     # ---- the call itself
-    def _solve(self, precond, rhs, x, max_iter, tol, want_precond):
+    def _solve(self, precond, rhs, x, max_iter, tol, want_precond, prefix=None):
+        """prefix: None for a `DiagPrecond` (or no preconditioner); "ilu0" / "amg" for CG / GMRES with such a handle for the
+        preconditioner: the same call under the name sprs_<prefix>_<solver>_solve[_dev]_*."""
         L = _lib.lib()
         its = C.c_size_t(0); res = _lib.REAL[self.s](0.0)
+        name = self.NAME if prefix is None else "%s_%s" % (prefix, self.NAME)
         dev = is_device_array(rhs)
         if dev != is_device_array(x):
             raise TypeError("rhs and x must both be host arrays or both be device vectors")
@@ -76,7 +79,7 @@ class _SolverBase:
                 st = getattr(L, "sprs_csminres_solve_dev_" + self.s)(self.h, rp, rl, xp, xl, int(max_iter), float(tol),
                                                                   C.byref(its), C.byref(res))
             else:
-                st = getattr(L, "sprs_%s_solve_dev_%s" % (self.NAME, self.s))(
+                st = getattr(L, "sprs_%s_solve_dev_%s" % (name, self.s))(
                     self.h, precond.h if precond is not None else None, rp, rl, xp, xl, int(max_iter), float(tol),
                     C.byref(its), C.byref(res))
         else:
@@ -85,31 +88,11 @@ class _SolverBase:
                 raise TypeError("x must be a contiguous %s ndarray (it is updated in place)" % self.dtype)
             rp, xp = rhs_a.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p)
             if want_precond:
-                st = getattr(L, "sprs_%s_precond_solve_%s" % (self.NAME, self.s))(
+                st = getattr(L, "sprs_%s_%s_%s" % (name, "precond_solve" if prefix is None else "solve", self.s))(
                     self.h, precond.h, rp, rhs_a.size, xp, x.size, int(max_iter), float(tol), C.byref(its), C.byref(res))
             else:
                 st = getattr(L, "sprs_%s_solve_%s" % (self.NAME, self.s))(
                     self.h, rp, rhs_a.size, xp, x.size, int(max_iter), float(tol), C.byref(its), C.byref(res))
-        return solve_result(st, its.value, res.value, self.A.ctx.h)
-
-    def _solve_applied(self, prefix, P, rhs, x, max_iter, tol):
-        """CG / GMRES with an ILU0 (prefix "ilu0") or AMG ("amg") handle for the preconditioner (sprs_<prefix>_*_solve_*)."""
-        L = _lib.lib()
-        its = C.c_size_t(0); res = _lib.REAL[self.s](0.0)
-        dev = is_device_array(rhs)
-        if dev != is_device_array(x):
-            raise TypeError("rhs and x must both be host arrays or both be device vectors")
-        if dev:
-            pre_sync(rhs, x)
-            st = getattr(L, "sprs_%s_%s_solve_dev_%s" % (prefix, self.NAME, self.s))(
-                self.h, P.h, dev_ptr(rhs), dev_len(rhs), dev_ptr(x), dev_len(x), int(max_iter), float(tol), C.byref(its), C.byref(res))
-        else:
-            rhs_a = np.ascontiguousarray(rhs, dtype=self.dtype)
-            if not (isinstance(x, np.ndarray) and x.dtype == self.dtype and x.flags.c_contiguous):
-                raise TypeError("x must be a contiguous %s ndarray (it is updated in place)" % self.dtype)
-            st = getattr(L, "sprs_%s_%s_solve_%s" % (prefix, self.NAME, self.s))(
-                self.h, P.h, rhs_a.ctypes.data_as(C.c_void_p), rhs_a.size, x.ctypes.data_as(C.c_void_p), x.size, int(max_iter),
-                float(tol), C.byref(its), C.byref(res))
         return solve_result(st, its.value, res.value, self.A.ctx.h)
 
     def close(self):

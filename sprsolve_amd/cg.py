@@ -19,7 +19,7 @@ class CG(_SolverBase):
     def precond_solve(self, precond, rhs, x, max_iter, tol):
         """Preconditioned by a `DiagPrecond` (Jacobi), an `ILU0` or an `AMG`; InvalidPreconditioner where conj(r).M^-1 r is not positive."""
         if isinstance(precond, ILU0):
-            return self._solve_applied("ilu0", precond, rhs, x, max_iter, tol)
+            return self._solve(precond, rhs, x, max_iter, tol, True, prefix="ilu0")
         if isinstance(precond, AMG):
-            return self._solve_applied("amg", precond, rhs, x, max_iter, tol)
+            return self._solve(precond, rhs, x, max_iter, tol, True, prefix="amg")
         return self._solve(precond, rhs, x, max_iter, tol, True)

@@ -506,53 +506,30 @@ int solver_destroy(sprs_solver_handle *h) {
 }
 
 // One solve.  Host slices (host = true), and device vectors that are not 16-byte aligned, go through the solver's aligned
-// rhs_buf / x_buf; other device vectors are used in place.
-template <class T, class SolverT>
-int solve(SolverT *s, bool host, const sprs_diag *P, const T *rhs, size_t rl, T *x, size_t xl, size_t max_iter, Real<T> tol,
+// rhs_buf / x_buf; other device vectors are used in place.  P: what SolverT::solve_dev takes — a sprs_diag (or null), and for
+// CG and GMRES also an ILU(0) or AMG handle's AppliedPrec view (sprs_ilu0_cg_*, sprs_amg_gmres_*, ...).
+template <class T, class SolverT, class P>
+int solve(SolverT *s, bool host, const P &prec, const T *rhs, size_t rl, T *x, size_t xl, size_t max_iter, Real<T> tol,
           size_t *its, Real<T> *res) {
-    if (!s || !rhs || !x) return SPRS_INVALID_ARGUMENT;
-    // size checks first (bicg_stab.rs:44-53): nothing is copied on a mismatch
+    const Precond<T> M(prec);
+    if (!s || (M.is_applied && !M.applied.h) || !rhs || !x) return SPRS_INVALID_ARGUMENT;
+    // size checks first (bicg_stab.rs:44-53): nothing is copied on a mismatch, nor where an applied handle is refused
     if (rl != s->n) return SPRS_INCOMPATIBLE_RHS_SIZE;
     if (xl != s->n) return SPRS_INCOMPATIBLE_X_SIZE;
+    if (M.is_applied) SPRS_TRY(M.applied.check(s->A, s->n));
     sprs_ctx *c = s->ctx;
     CtxLock lock(c);   // one solve at a time per context (its stream, its scratch)
     if (!host && ((reinterpret_cast<uintptr_t>(rhs) | reinterpret_cast<uintptr_t>(x)) & 15) == 0)
-        return s->solve_dev(P, rhs, rl, x, xl, max_iter, tol, its, res);
+        return s->solve_dev(prec, rhs, rl, x, xl, max_iter, tol, its, res);
     const hipMemcpyKind in = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, out = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     SPRS_HIP_TRY(c, hipSetDevice(c->device));
     if (!s->rhs_buf) SPRS_HIP_TRY(c, hipMalloc((void **)&s->rhs_buf, sizeof(T) * s->stride));
     if (!s->x_buf) SPRS_HIP_TRY(c, hipMalloc((void **)&s->x_buf, sizeof(T) * s->stride));
     SPRS_HIP_TRY(c, hipMemcpyAsync(s->rhs_buf, rhs, sizeof(T) * rl, in, c->stream));
     SPRS_HIP_TRY(c, hipMemcpyAsync(s->x_buf, x, sizeof(T) * xl, in, c->stream));
-    int st = s->solve_dev(P, s->rhs_buf, rl, s->x_buf, xl, max_iter, tol, its, res);
+    int st = s->solve_dev(prec, s->rhs_buf, rl, s->x_buf, xl, max_iter, tol, its, res);
     if (st >= SPRS_ERR_HIP) return st;
     // x is in/out in the reference and is left modified on Err as well
-    SPRS_HIP_TRY(c, hipMemcpyAsync(x, s->x_buf, sizeof(T) * xl, out, c->stream));
-    SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return st;
-}
-
-// The same with an applied preconditioner for P (an ILU(0) or AMG handle's view: sprs_ilu0_cg_*, sprs_amg_gmres_*, ...):
-// SolverT::solve_dev_applied.
-template <class T, class SolverT>
-int solve_applied(SolverT *s, bool host, const AppliedPrec<T> &P, const T *rhs, size_t rl, T *x, size_t xl, size_t max_iter, Real<T> tol,
-              size_t *its, Real<T> *res) {
-    if (!s || !P.h || !rhs || !x) return SPRS_INVALID_ARGUMENT;
-    if (rl != s->n) return SPRS_INCOMPATIBLE_RHS_SIZE;
-    if (xl != s->n) return SPRS_INCOMPATIBLE_X_SIZE;
-    SPRS_TRY(P.check(s->A, s->n));       // nothing is copied on a mismatch
-    sprs_ctx *c = s->ctx;
-    CtxLock lock(c);
-    if (!host && ((reinterpret_cast<uintptr_t>(rhs) | reinterpret_cast<uintptr_t>(x)) & 15) == 0)
-        return s->solve_dev_applied(P, rhs, rl, x, xl, max_iter, tol, its, res);
-    const hipMemcpyKind in = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, out = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    SPRS_HIP_TRY(c, hipSetDevice(c->device));
-    if (!s->rhs_buf) SPRS_HIP_TRY(c, hipMalloc((void **)&s->rhs_buf, sizeof(T) * s->stride));
-    if (!s->x_buf) SPRS_HIP_TRY(c, hipMalloc((void **)&s->x_buf, sizeof(T) * s->stride));
-    SPRS_HIP_TRY(c, hipMemcpyAsync(s->rhs_buf, rhs, sizeof(T) * rl, in, c->stream));
-    SPRS_HIP_TRY(c, hipMemcpyAsync(s->x_buf, x, sizeof(T) * xl, in, c->stream));
-    int st = s->solve_dev_applied(P, s->rhs_buf, rl, s->x_buf, xl, max_iter, tol, its, res);
-    if (st >= SPRS_ERR_HIP) return st;
     SPRS_HIP_TRY(c, hipMemcpyAsync(x, s->x_buf, sizeof(T) * xl, out, c->stream));
     SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
     return st;
@@ -904,10 +881,10 @@ SPRS_API(c, cplxf, sprs_c32, float)
 // CG and GMRES preconditioned by an ILU(0) handle (ilu0.hip) or an AMG handle (amg.hip): one path, the handle's AppliedPrec view
 #define SPRS_APPLIED_SOLVES(X, T, CT, R, NAME, S, PFX)                                                                 \
     int sprs_##PFX##_##NAME##_solve_##X(sprs_##NAME *h, const sprs_##PFX *P, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
-        SPRS_G(return solve_applied<T>(impl_of<S, T>(h), true, PFX##_prec<T>(P), (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);)  \
+        SPRS_G(return solve<T>(impl_of<S, T>(h), true, PFX##_prec<T>(P), (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);)  \
     }                                                                                                                  \
     int sprs_##PFX##_##NAME##_solve_dev_##X(sprs_##NAME *h, const sprs_##PFX *P, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
-        SPRS_G(return solve_applied<T>(impl_of<S, T>(h), false, PFX##_prec<T>(P), (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);) \
+        SPRS_G(return solve<T>(impl_of<S, T>(h), false, PFX##_prec<T>(P), (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);) \
     }
 #define SPRS_APPLIED_API(X, T, CT, R)                                                                 \
     SPRS_APPLIED_SOLVES(X, T, CT, R, cg, Cg, ilu0) SPRS_APPLIED_SOLVES(X, T, CT, R, gmres, Gmres, ilu0) \

@@ -136,9 +136,9 @@ int CgMany<T>::solve_dev(const sprs_diag *P, const T *rhs, size_t rhs_len, T *x,
     if (k < 1 || k > (size_t)kmax) return SPRS_INVALID_ARGUMENT;
     if (rhs_len != n * k) return SPRS_INCOMPATIBLE_RHS_SIZE;
     if (x_len != n * k) return SPRS_INCOMPATIBLE_X_SIZE;
-    return with_dinv<T>(P, n, [&](const auto *d) -> int {
+    return with_prec<T>(P, *this, [&](const auto &M) -> int {
         SPRS_HIP_TRY(ctx, hipSetDevice(ctx->device));
-        return run(d, rhs, x, (int)k, max_iter, tol, its_out, res_out, status_out);
+        return run(M.dinv, rhs, x, (int)k, max_iter, tol, its_out, res_out, status_out);
     });
 }
 

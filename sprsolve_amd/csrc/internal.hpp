@@ -404,10 +404,9 @@ template <class T> int ilu0_apply(const sprs_ilu0 *P, int which, const T *in, T 
 int amg_check(const sprs_amg *P, const sprs_csr *A, int dtype, size_t n);
 template <class T> int amg_apply(const sprs_amg *P, const T *in, T *out);
 
-// ---- an applied preconditioner as CG and GMRES take it: a handle whose application is a chain of launches of its own
-// (ILU(0)'s triangular solves, AMG's cycle), asynchronous on the context's stream.  check: SPRS_INVALID_ARGUMENT for a null
-// handle, another scalar type or context, or a distributed A; SPRS_DIM_MISMATCH for another size.  apply: out = M in on device
-// vectors, in == out allowed.
+// ---- an applied preconditioner: a handle whose application is a chain of launches of its own (ILU(0)'s triangular solves,
+// AMG's cycle), asynchronous on the context's stream.  check: SPRS_INVALID_ARGUMENT for a null handle, another scalar type or
+// context, or a distributed A; SPRS_DIM_MISMATCH for another size.  apply: out = M in on device vectors, in == out allowed.
 template <class T>
 struct AppliedPrec {
     const void *h = nullptr;
@@ -418,6 +417,19 @@ struct AppliedPrec {
 };
 template <class T> AppliedPrec<T> ilu0_prec(const sprs_ilu0 *P);   // the which = 0 solve
 template <class T> AppliedPrec<T> amg_prec(const sprs_amg *P);
+
+// ---- what a solve is preconditioned with, from the C entry points down: nothing (a null sprs_diag), a diagonal (Jacobi) or
+// an applied handle (CG and GMRES only: no other solver's solve_dev takes this type).  with_prec() (krylov.hpp) checks it and
+// resolves it into the Prec<T, V> the runs receive.
+template <class T>
+struct Precond {
+    const sprs_diag *diag = nullptr;
+    AppliedPrec<T> applied;
+    bool is_applied = false;            // (an applied one whose handle is null is still one: it is refused, not ignored)
+    Precond(const sprs_diag *d = nullptr) : diag(d) {}
+    Precond(const AppliedPrec<T> &a) : applied(a), is_applied(true) {}
+    bool any() const { return diag || is_applied; }
+};
 
 // ---- dist.hip
 // exchange the halo entries of the extended vector x (local part [0,n_local) already in place)

@@ -18,8 +18,10 @@
 //
 // What the hosts share is written once: KrylovBase (below; krylov_base.hip) with solve(), handoff() (a producer's partials to
 // their consumer: single GPU / mailbox / all-reduce), zero_rhs(), poll_interval(), comm_timeout(); StateBlock (the device +
-// pinned-host pair of the scalar state); with_dinv() (the preconditioner's checks and element type).  The main loops stay
-// apart: BiCGStab's restart, MINRES's deferred M3, CG's accounting of idle launches and GMRES's cycles have nothing in common.
+// pinned-host pair of the scalar state); with_prec() (the preconditioner's checks, its element type and the Prec<T, V> a run
+// receives: none, Jacobi, or an applied ILU(0) / AMG handle).  The main loops stay apart: BiCGStab's restart, MINRES's deferred
+// M3, CG's accounting of idle launches and GMRES's cycles have nothing in common.  Each solver has ONE run and ONE run_literal,
+// whatever it is preconditioned with.
 #pragma once
 #include "internal.hpp"
 
@@ -91,6 +93,21 @@ struct StateBlock {
     }
 };
 
+// The preconditioner as a run receives it (with_prec() below has checked it).  dinv: M^-1's diagonal, of V = T (a complex
+// diagonal) or Real<T>; it is read inside the solvers' own fused kernels.  applied (applied.h != null): z = M r is a chain of
+// launches of the handle's own; V is Real<T> then.  Both null: no preconditioner.
+template <class T, class V>
+struct Prec {
+    sprs_ctx *ctx = nullptr;
+    size_t n = 0;
+    const V *dinv = nullptr;
+    AppliedPrec<T> applied;
+    bool any() const { return dinv || applied.h; }
+    // out = M in as launches of its own: CG's start, the literal modes, and every application of an applied one
+    int apply(const T *in, T *out) const { return applied.h ? applied.apply(in, out) : launch_diag_apply<T, V>(ctx, n, dinv, in, out); }
+    operator const V *() const { return dinv; }   // the solvers that take no applied one keep their `const V *dinv` runs
+};
+
 // The partials of one reduction as their consumer kernel finds them (KrylovBase::handoff).
 template <class U>
 struct Part { const U *p; int P; unsigned int tag = 0; };   // tag != 0: p = this rank's mailbox entries of the hand-off, P = world
@@ -147,14 +164,11 @@ class KrylovBase {
     int end_solve();
     void trace_row(double a0, double a1, T b, T c, T d);
     // What the solvers' solve_dev share: argument defaults, size checks, the preconditioner's checks and element type, the
-    // literal-or-fused choice.  S supplies run<V> / run_literal<V>; no_precond: S takes no preconditioner (CSMINRES).
+    // literal-or-fused choice.  S supplies run<V> / run_literal<V>, which receive a Prec<T, V>; no_precond: S takes no
+    // preconditioner (CSMINRES).
     template <class S>
-    static int solve(S &s, bool no_precond, const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter,
+    static int solve(S &s, bool no_precond, const Precond<T> &P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter,
                      Real<T> tol, size_t *its_out, Real<T> *res_out);
-    // The same for an applied preconditioner (an ILU(0) or AMG handle's view, internal.hpp): S supplies run_applied / run_literal_applied.
-    template <class S>
-    static int solve_applied(S &s, const AppliedPrec<T> &P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
-                         size_t *its_out, Real<T> *res_out);
     // |rhs|; a zero right-hand side answers x = 0 (*zero = true: the solve is over, *res_out holds the norm)
     int zero_rhs(const T *rhs, T *x, Real<T> *rhs_norm, Real<T> *res_out, bool *zero);
     size_t poll_interval() const { return trace ? 1 : sprs::poll_interval(ctx); }   // a trace reads the state every iteration
@@ -217,24 +231,18 @@ class Cg : public KrylovBase<T> {
     StateBlock<CgState<T>> state;
     int create(const sprs_csr *A, size_t size);
     void destroy() { state.destroy(); KrylovBase<T>::destroy(); }
-    int solve_dev(const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
+    int solve_dev(const Precond<T> &P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
                   size_t *its_out, Real<T> *res_out);
-    // z = P r is an applied preconditioner (ILU(0), AMG)
-    int solve_dev_applied(const AppliedPrec<T> &P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
-                      size_t *its_out, Real<T> *res_out);
 
    private:
     friend class KrylovBase<T>;
     // the part both modes share: zero rhs, initial residual, z = M^-1 r, p = z, rho = conj(r).z; done = 1: answered already
     template <class V>
-    int start(const V *dinv, const T *rhs, T *x, Real<T> tol, Real<T> *rhs_norm, Real<T> *tol2, T *rho, bool *done, Real<T> *res_out);
+    int start(const Prec<T, V> &M, const T *rhs, T *x, Real<T> tol, Real<T> *rhs_norm, Real<T> *tol2, T *rho, bool *done, Real<T> *res_out);
     template <class V>
-    int run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
+    int run(const Prec<T, V> &M, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
     template <class V>
-    int run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
-    int start_applied(const AppliedPrec<T> &P, const T *rhs, T *x, Real<T> tol, Real<T> *rhs_norm, Real<T> *tol2, T *rho, bool *done, Real<T> *res_out);
-    int run_applied(const AppliedPrec<T> &P, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
-    int run_literal_applied(const AppliedPrec<T> &P, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
+    int run_literal(const Prec<T, V> &M, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
 };
 
 // Restarted GMRES for any non-singular A (recurrence: include/sprsolve_hip.h, sprs_gmres_*; kernels: gmres_fuse.hpp)
@@ -248,11 +256,8 @@ class Gmres : public KrylovBase<T> {
     T *coefs = nullptr;          // distributed: the m reduced coefficients of a pass, all-reduced in place
     int create(const sprs_csr *A, size_t size, size_t restart);
     void destroy();
-    int solve_dev(const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
+    int solve_dev(const Precond<T> &P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
                   size_t *its_out, Real<T> *res_out);
-    // z = P v_j and u = P u are an applied preconditioner (ILU(0), AMG)
-    int solve_dev_applied(const AppliedPrec<T> &P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
-                      size_t *its_out, Real<T> *res_out);
 
    private:
     friend class KrylovBase<T>;
@@ -262,11 +267,9 @@ class Gmres : public KrylovBase<T> {
     T *uvec() { return this->vec(m + 3); }                   // literal mode's x update
     void trace_step(double its, double g, double hn, T r, double c, T s);
     template <class V>
-    int run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
+    int run(const Prec<T, V> &M, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
     template <class V>
-    int run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
-    int run_applied(const AppliedPrec<T> &P, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
-    int run_literal_applied(const AppliedPrec<T> &P, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
+    int run_literal(const Prec<T, V> &M, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
 };
 
 // LSMR for min |rhs - A x|_2 (+ damping) on any A, rectangular included (recurrence: include/sprsolve_hip.h, sprs_lsmr_*; kernels:
@@ -380,55 +383,45 @@ int KrylovBase<T>::profiled(F &&run, bool one_kernel) {
     return st;
 }
 
-// The preconditioner as a solve takes it: P's size and scalar type are checked, then run(dinv) is called with dinv typed
-// const T * (a complex M^-1: complex T only) or const Real<T> * (null: no preconditioner).
-template <class T, class F>
-int with_dinv(const sprs_diag *P, size_t n, F &&run) {
-    if (P && P->n != n) return SPRS_DIM_MISMATCH;
-    if (P && P->t_dtype != dtype_of<T>::value) return SPRS_INVALID_ARGUMENT;
-    if (P && P->v_complex) {
-        if constexpr (is_complex<T>::value) return run((const T *)P->dinv);
+// The preconditioner as a solve takes it.  An applied handle passes its own check; a diagonal's size and scalar type are
+// checked.  Then run(M) is called with M a Prec<T, V> (s: the solver, for its context, A and n): V = T for a complex M^-1
+// (complex T only), Real<T> otherwise — for an applied one and for none as well.
+template <class T, class S, class F>
+int with_prec(const Precond<T> &P, const S &s, F &&run) {
+    using R = Real<T>;
+    if (P.is_applied) {
+        SPRS_TRY(P.applied.check(s.A, s.n));
+        return run(Prec<T, R>{s.ctx, s.n, nullptr, P.applied});
+    }
+    const sprs_diag *D = P.diag;
+    if (D && D->n != s.n) return SPRS_DIM_MISMATCH;
+    if (D && D->t_dtype != dtype_of<T>::value) return SPRS_INVALID_ARGUMENT;
+    if (D && D->v_complex) {
+        if constexpr (is_complex<T>::value) return run(Prec<T, T>{s.ctx, s.n, (const T *)D->dinv, {}});
         else return SPRS_INVALID_ARGUMENT;
     }
-    return run(P ? (const Real<T> *)P->dinv : (const Real<T> *)nullptr);
+    return run(Prec<T, R>{s.ctx, s.n, D ? (const R *)D->dinv : nullptr, {}});
 }
 
 template <class T>
 template <class S>
-int KrylovBase<T>::solve(S &s, bool no_precond, const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter,
+int KrylovBase<T>::solve(S &s, bool no_precond, const Precond<T> &P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter,
                          Real<T> tol, size_t *its_out, Real<T> *res_out) {
     size_t its_dummy; Real<T> res_dummy;
     if (!its_out) its_out = &its_dummy;
     if (!res_out) res_out = &res_dummy;
     if (rhs_len != s.n) return SPRS_INCOMPATIBLE_RHS_SIZE;                  // bicg_stab.rs:44-48, minres.rs:40-44
     if (x_len != s.n) return SPRS_INCOMPATIBLE_X_SIZE;                      // bicg_stab.rs:49-53, minres.rs:45-49
-    if (no_precond && P) return SPRS_INVALID_ARGUMENT;                      // CSMinRes has no precond_solve
-    return with_dinv<T>(P, s.n, [&](const auto *d) -> int {
-        using V = std::remove_cv_t<std::remove_pointer_t<decltype(d)>>;
+    if (no_precond && P.any()) return SPRS_INVALID_ARGUMENT;                // CSMinRes has no precond_solve
+    return with_prec<T>(P, s, [&](const auto &M) -> int {
+        using V = std::remove_cv_t<std::remove_pointer_t<decltype(M.dinv)>>;
         SPRS_TRY(s.begin_solve());
-        const int st = s.mode == 1 ? s.template run_literal<V>(d, rhs, x, max_iter, tol, its_out, res_out)
-                                   : s.template run<V>(d, rhs, x, max_iter, tol, its_out, res_out);
+        const int st = s.mode == 1 ? s.template run_literal<V>(M, rhs, x, max_iter, tol, its_out, res_out)
+                                   : s.template run<V>(M, rhs, x, max_iter, tol, its_out, res_out);
         if (st >= SPRS_ERR_HIP) return st;
         SPRS_TRY(s.end_solve());
         return st;
     });
-}
-
-template <class T>
-template <class S>
-int KrylovBase<T>::solve_applied(S &s, const AppliedPrec<T> &P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
-                             size_t *its_out, Real<T> *res_out) {
-    size_t its_dummy; Real<T> res_dummy;
-    if (!its_out) its_out = &its_dummy;
-    if (!res_out) res_out = &res_dummy;
-    if (rhs_len != s.n) return SPRS_INCOMPATIBLE_RHS_SIZE;
-    if (x_len != s.n) return SPRS_INCOMPATIBLE_X_SIZE;
-    SPRS_TRY(P.check(s.A, s.n));
-    SPRS_TRY(s.begin_solve());
-    const int st = s.mode == 1 ? s.run_literal_applied(P, rhs, x, max_iter, tol, its_out, res_out) : s.run_applied(P, rhs, x, max_iter, tol, its_out, res_out);
-    if (st >= SPRS_ERR_HIP) return st;
-    SPRS_TRY(s.end_solve());
-    return st;
 }
 
 }  // namespace sprs

@@ -31,7 +31,7 @@ class GMRES(_SolverBase):
     def precond_solve(self, precond, rhs, x, max_iter, tol):
         """Preconditioned from the right by a `DiagPrecond` (Jacobi), an `ILU0` or an `AMG`: the residual it reports is the true one's estimate."""
         if isinstance(precond, ILU0):
-            return self._solve_applied("ilu0", precond, rhs, x, max_iter, tol)
+            return self._solve(precond, rhs, x, max_iter, tol, True, prefix="ilu0")
         if isinstance(precond, AMG):
-            return self._solve_applied("amg", precond, rhs, x, max_iter, tol)
+            return self._solve(precond, rhs, x, max_iter, tol, True, prefix="amg")
         return self._solve(precond, rhs, x, max_iter, tol, True)
