@@ -725,7 +725,7 @@ int sprs_dist_mul_vec_dev_c(const sprs_csr *A, sprs_c32 *x_ext_dev, sprs_c32 *y_
  * one device copy more); which = 2: k; which = 0: 2k - 2, one for k = 1.  sprs_ilu0_levels reports the level counts of the
  * pattern as for an exact handle and k - 1 / k as the two launch counts.  in == out is allowed for every `which`; `in` is
  * never written unless it is `out`.  sprs_ilu0_sweeps: k, 0 for an exact handle, -1 for NULL.  Everything that takes a
- * sprs_ilu0 (the solves, sprs_ilu0_cg_*, sprs_ilu0_gmres_*) takes either kind. */
+ * sprs_ilu0 (the solves, sprs_ilu0_cg_*, sprs_ilu0_gmres_*, sprs_ilu0_bicgstab_*, sprs_ilu0_minres_*) takes either kind. */
 #define SPRS_ILU0_MAX_SWEEPS 4096
 typedef struct sprs_ilu0 sprs_ilu0;
 int sprs_ilu0_create(const sprs_csr *A, sprs_ilu0 **out, int64_t *row_out);   /* row_out may be NULL */
@@ -759,6 +759,35 @@ int sprs_ilu0_gmres_solve_dev_d(sprs_gmres *S, const sprs_ilu0 *P, const double 
 int sprs_ilu0_gmres_solve_dev_z(sprs_gmres *S, const sprs_ilu0 *P, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
 int sprs_ilu0_gmres_solve_dev_s(sprs_gmres *S, const sprs_ilu0 *P, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
 int sprs_ilu0_gmres_solve_dev_c(sprs_gmres *S, const sprs_ilu0 *P, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+/* BiCGStab and MINRES preconditioned by ILU(0): the recurrences of sprs_bicgstab_precond_solve_* and
+ * sprs_minres_precond_solve_* with P = the which = 0 solve wherever those multiply by the diagonal; arguments and status codes
+ * as sprs_ilu0_cg_solve_*.
+ *   BiCGStab (right preconditioning):  y = P p before v = A y and z = P s before t = A z (s = r - alpha v);
+ *     x -= alpha y ; x -= w z ; r = s - w t.  P need not be symmetric.  A fused iteration is five launches of the solver's
+ *     plus two applications, without a host wait.
+ *   MINRES:  w_new = P v_new after v_new = A w - beta v_old - alpha v, then b2 = conj(v_new).w_new and beta_new = sqrt(re b2).
+ *     SPRS_INVALID_PRECOND (its_out = the iteration, res_out = re b2) when re(b2) < eps or im(b2) > eps re(b2) — the rule of
+ *     the diagonal solve, unchanged.  P must be Hermitian positive definite: ILU(0) of a Hermitian positive-definite M-matrix
+ *     is; with an applied P on complex data im(b2) is rounding noise and no longer an exact zero, so the rule can in principle
+ *     fire on a valid P if that noise grows past eps re(b2).  A fused iteration is four launches of the solver's plus one
+ *     application.
+ * CSMINRES takes no preconditioner; the batched CG takes a diagonal only. */
+int sprs_ilu0_bicgstab_solve_d(sprs_bicgstab *S, const sprs_ilu0 *P, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_ilu0_bicgstab_solve_z(sprs_bicgstab *S, const sprs_ilu0 *P, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_ilu0_bicgstab_solve_s(sprs_bicgstab *S, const sprs_ilu0 *P, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_ilu0_bicgstab_solve_c(sprs_bicgstab *S, const sprs_ilu0 *P, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_ilu0_bicgstab_solve_dev_d(sprs_bicgstab *S, const sprs_ilu0 *P, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_ilu0_bicgstab_solve_dev_z(sprs_bicgstab *S, const sprs_ilu0 *P, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_ilu0_bicgstab_solve_dev_s(sprs_bicgstab *S, const sprs_ilu0 *P, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_ilu0_bicgstab_solve_dev_c(sprs_bicgstab *S, const sprs_ilu0 *P, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_ilu0_minres_solve_d(sprs_minres *S, const sprs_ilu0 *P, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_ilu0_minres_solve_z(sprs_minres *S, const sprs_ilu0 *P, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_ilu0_minres_solve_s(sprs_minres *S, const sprs_ilu0 *P, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_ilu0_minres_solve_c(sprs_minres *S, const sprs_ilu0 *P, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_ilu0_minres_solve_dev_d(sprs_minres *S, const sprs_ilu0 *P, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_ilu0_minres_solve_dev_z(sprs_minres *S, const sprs_ilu0 *P, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_ilu0_minres_solve_dev_s(sprs_minres *S, const sprs_ilu0 *P, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_ilu0_minres_solve_dev_c(sprs_minres *S, const sprs_ilu0 *P, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
 
 /* ---------------------------------------------------------------- smoothed-aggregation AMG preconditioner
  * An algebraic multigrid hierarchy of a square, single-GPU CSR handle (any of the four scalar types, taken from A) and the
@@ -838,6 +867,24 @@ int sprs_amg_gmres_solve_dev_d(sprs_gmres *S, const sprs_amg *P, const double *r
 int sprs_amg_gmres_solve_dev_z(sprs_gmres *S, const sprs_amg *P, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
 int sprs_amg_gmres_solve_dev_s(sprs_gmres *S, const sprs_amg *P, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
 int sprs_amg_gmres_solve_dev_c(sprs_gmres *S, const sprs_amg *P, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+/* BiCGStab and MINRES preconditioned by AMG: as sprs_ilu0_bicgstab_* / sprs_ilu0_minres_* with P = one cycle (Hermitian
+ * positive definite when A is; on an indefinite A, MINRES ends in SPRS_INVALID_PRECOND) */
+int sprs_amg_bicgstab_solve_d(sprs_bicgstab *S, const sprs_amg *P, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_amg_bicgstab_solve_z(sprs_bicgstab *S, const sprs_amg *P, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_amg_bicgstab_solve_s(sprs_bicgstab *S, const sprs_amg *P, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_amg_bicgstab_solve_c(sprs_bicgstab *S, const sprs_amg *P, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_amg_bicgstab_solve_dev_d(sprs_bicgstab *S, const sprs_amg *P, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_amg_bicgstab_solve_dev_z(sprs_bicgstab *S, const sprs_amg *P, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_amg_bicgstab_solve_dev_s(sprs_bicgstab *S, const sprs_amg *P, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_amg_bicgstab_solve_dev_c(sprs_bicgstab *S, const sprs_amg *P, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_amg_minres_solve_d(sprs_minres *S, const sprs_amg *P, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_amg_minres_solve_z(sprs_minres *S, const sprs_amg *P, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_amg_minres_solve_s(sprs_minres *S, const sprs_amg *P, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_amg_minres_solve_c(sprs_minres *S, const sprs_amg *P, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_amg_minres_solve_dev_d(sprs_minres *S, const sprs_amg *P, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_amg_minres_solve_dev_z(sprs_minres *S, const sprs_amg *P, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_amg_minres_solve_dev_s(sprs_minres *S, const sprs_amg *P, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_amg_minres_solve_dev_c(sprs_minres *S, const sprs_amg *P, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
 
 /* ---------------------------------------------------------------- multi-GPU (one process per GPU)
  * No reference analogue: the reference is single-process (rayon).  The matrix is row-partitioned;

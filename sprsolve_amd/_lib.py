@@ -118,7 +118,7 @@ def _protos():
         P["sprs_ilu0_solve_" + s] = [_vp, _int, _vp, _sz, _vp, _sz]
         P["sprs_amg_mul_vec_dev_" + s] = [_vp, _vp, _vp]
         P["sprs_amg_mul_vec_" + s] = [_vp, _vp, _sz, _vp, _sz]
-        for k in ("cg", "gmres"):
+        for k in ("cg", "gmres", "bicgstab", "minres"):
             for pc in ("ilu0", "amg"):
                 P["sprs_%s_%s_solve_%s" % (pc, k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
                 P["sprs_%s_%s_solve_dev_%s" % (pc, k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]

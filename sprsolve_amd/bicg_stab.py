@@ -1,6 +1,8 @@
 """BiCGStab — mirror of the reference's src/bicg_stab.rs."""
 from . import _lib
 from ._solver import _SolverBase
+from .amg import AMG
+from .ilu import ILU0
 
 
 class BiCGStab(_SolverBase):
@@ -14,5 +16,9 @@ class BiCGStab(_SolverBase):
         return self._solve(None, rhs, x, max_iter, tol, False)
 
     def precond_solve(self, precond, rhs, x, max_iter, tol):
-        """bicg_stab.rs:204-366 (right-preconditioned)."""
+        """bicg_stab.rs:204-366 (right-preconditioned) by a `DiagPrecond` (Jacobi), an `ILU0` or an `AMG`."""
+        if isinstance(precond, ILU0):
+            return self._solve(precond, rhs, x, max_iter, tol, True, prefix="ilu0")
+        if isinstance(precond, AMG):
+            return self._solve(precond, rhs, x, max_iter, tol, True, prefix="amg")
         return self._solve(precond, rhs, x, max_iter, tol, True)

@@ -11,3 +11,7 @@ class CSMinRes(_SolverBase):
     def solve(self, rhs, x, max_iter, tol):
         """cs_minres.rs:29-158."""
         return self._solve(None, rhs, x, max_iter, tol, False)
+
+    def precond_solve(self, precond, rhs, x, max_iter, tol):
+        """CSMinRes has no precond_solve upstream (cs_minres.rs) and takes no preconditioner here."""
+        raise TypeError("CSMinRes takes no preconditioner")

@@ -15,10 +15,11 @@ int BicgStab<T>::create(const sprs_csr *A, size_t size) {
 
 template <class T>
 template <class V>
-int BicgStab<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out) {
+int BicgStab<T>::run(const Prec<T, V> &M, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out) {
     sprs_ctx *c = this->ctx;
     const size_t n = this->n;
-    const bool pc = dinv != nullptr;
+    const V *dinv = M.dinv;
+    const bool pc = M.any(), applied = M.applied.h != nullptr;   // the 7-vector layout serves a diagonal and an applied M alike
     *its_out = 0; *res_out = 0.0;
 
     Real<T> rhs_norm = 0.0;
@@ -96,11 +97,18 @@ int BicgStab<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T>
         SPRS_TRY(this->spmv(y, v, 1, r0, partB, nullptr, d_status, false, &f));
         return this->handoff(0, GS, partB, &qB);
     };
+    // An applied M (ILU(0), AMG; right preconditioning as with a diagonal): K1 and K3 run without a preconditioner — K1 writes p
+    // only, K3 turns r into s — and y = M p, z = M s are chains of launches of the handle's own (internal.hpp, AppliedPrec)
+    // after them: 5 launches + 2 applications per iteration, no host wait inside one.  Once the status word has left ST_RUNNING
+    // the handle's launches still run until the next poll: they read p / r and write only y, z and the handle's scratch, never
+    // x, r, p, v or the state.  A restart (below) re-enters with K1(mode 1), so p, then y, then z are all rewritten before K5
+    // reads them.
     auto K3 = [&](int check) -> int {
         if (fuse) { pend_k3 = check; return (int)SPRS_OK; }     // formed by the next K4
-        return dispatch_bool(pc, [&](auto pc_tag) {
+        SPRS_TRY(dispatch_bool(dinv != nullptr, [&](auto pc_tag) {
             return launch_fused<T>(c, n, G, cw, BicgK3<T, V, decltype(pc_tag)::value>{d_state, qB.p, qB.P, check, v, r, dinv, z, T(), qB.tag, this->mb_timeout()});
-        });
+        }));
+        return applied ? M.apply(r, z) : (int)SPRS_OK;                                       // :343
     };
     auto K4 = [&]() -> int {                                                                 // :104/:175 t = A s ; t.t, t.r
         const Fin f = this->fin_for(1, partTT, partTR, GS);
@@ -131,15 +139,16 @@ int BicgStab<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T>
     };
     auto K1 = [&](int mode) -> int {
         if (fuse) { pend_k1 = mode; return (int)SPRS_OK; }      // formed by the next K2
-        return dispatch_bool(pc, [&](auto pc_tag) {
+        SPRS_TRY(dispatch_bool(dinv != nullptr, [&](auto pc_tag) {
             return launch_fused<T>(c, n, G, cw, BicgK1<T, V, decltype(pc_tag)::value>{d_state, qN.p, qRho.p, qN.P, mode, v, r, p, dinv, y, T(), T(), qN.tag, this->mb_timeout()});
-        });
+        }));
+        return applied ? M.apply(p, y) : (int)SPRS_OK;                                       // :328
     };
 
     // ---- unrolled first iteration (:87-120 / :258-293)
     if (pc) {
         SPRS_TRY(dcopy(c, p, r, n));                                        // :261
-        SPRS_TRY((launch_diag_apply<T, V>(c, n, dinv, p, y)));              // :262
+        SPRS_TRY(M.apply(p, y));                                            // :262
     } else {
         SPRS_TRY(dcopy(c, y, r, n));                                        // :91
     }
@@ -205,11 +214,11 @@ int BicgStab<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T>
 // literal mode: the reference's op list, one kernel per op, host-consumed scalars
 template <class T>
 template <class V>
-int BicgStab<T>::run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out,
+int BicgStab<T>::run_literal(const Prec<T, V> &M, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out,
                              Real<T> *res_out) {
     sprs_ctx *c = this->ctx;
     const size_t n = this->n;
-    const bool pc = dinv != nullptr;
+    const bool pc = M.any();
     *its_out = 0; *res_out = 0.0;
     Real<T> rhs_norm = 0.0;
     bool zero;
@@ -235,14 +244,14 @@ int BicgStab<T>::run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter,
     Real<T> r0_norm_tol = r0_norm * seps<Real<T>>();
     r0_norm_tol = r0_norm_tol * r0_norm_tol;
     T rho = sfromr<T>(r0_norm * r0_norm);
-    if (pc) { SPRS_TRY(dcopy(c, p, r, n)); SPRS_TRY((launch_diag_apply<T, V>(c, n, dinv, p, y))); }
+    if (pc) { SPRS_TRY(dcopy(c, p, r, n)); SPRS_TRY(M.apply(p, y)); }
     else SPRS_TRY(dcopy(c, y, r, n));
     SPRS_TRY(mv(y, v));
     T tmp;
     SPRS_TRY(cdot(r0, v, &tmp));
     T alpha = sdiv(rho, tmp);
     SPRS_TRY(axpy(sneg(alpha), v, r));
-    if (pc) SPRS_TRY((launch_diag_apply<T, V>(c, n, dinv, r, z)));
+    if (pc) SPRS_TRY(M.apply(r, z));
     SPRS_TRY(mv(sz, t));
     SPRS_TRY(cdot(t, t, &tmp));
     T w = szero<T>();
@@ -269,13 +278,13 @@ int BicgStab<T>::run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter,
         const T beta = smul(sdiv(rho, rho_old), sdiv(alpha, w));
         SPRS_TRY(launch_axpby<T>(c, n, smul(sneg(beta), w), v, beta, p));
         SPRS_TRY(axpy(sone<T>(), r, p));
-        if (pc) SPRS_TRY((launch_diag_apply<T, V>(c, n, dinv, p, y)));
+        if (pc) SPRS_TRY(M.apply(p, y));
         SPRS_TRY(mv(y, v));
         SPRS_TRY(cdot(r0, v, &tmp));
         if (sabs(tmp) <= 0.0) { *its_out = its; return SPRS_BREAKDOWN; }
         alpha = sdiv(rho, tmp);
         SPRS_TRY(axpy(sneg(alpha), v, r));
-        if (pc) SPRS_TRY((launch_diag_apply<T, V>(c, n, dinv, r, z)));
+        if (pc) SPRS_TRY(M.apply(r, z));
         SPRS_TRY(mv(sz, t));
         SPRS_TRY(cdot(t, t, &tmp));
         if (sre(tmp) > 0.0) { T tr; SPRS_TRY(cdot(t, r, &tr)); w = sdiv(tr, tmp); }
@@ -290,7 +299,7 @@ int BicgStab<T>::run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter,
 }
 
 template <class T>
-int BicgStab<T>::solve_dev(const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter,
+int BicgStab<T>::solve_dev(const Precond<T> &P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter,
                            Real<T> tol, size_t *its_out, Real<T> *res_out) {
     return KrylovBase<T>::solve(*this, false, P, rhs, rhs_len, x, x_len, max_iter, tol, its_out, res_out);
 }

@@ -506,8 +506,8 @@ int solver_destroy(sprs_solver_handle *h) {
 }
 
 // One solve.  Host slices (host = true), and device vectors that are not 16-byte aligned, go through the solver's aligned
-// rhs_buf / x_buf; other device vectors are used in place.  P: what SolverT::solve_dev takes — a sprs_diag (or null), and for
-// CG and GMRES also an ILU(0) or AMG handle's AppliedPrec view (sprs_ilu0_cg_*, sprs_amg_gmres_*, ...).
+// rhs_buf / x_buf; other device vectors are used in place.  P: what SolverT::solve_dev takes — a sprs_diag (or null), or an
+// ILU(0) or AMG handle's AppliedPrec view (sprs_ilu0_cg_*, sprs_amg_bicgstab_*, ...).
 template <class T, class SolverT, class P>
 int solve(SolverT *s, bool host, const P &prec, const T *rhs, size_t rl, T *x, size_t xl, size_t max_iter, Real<T> tol,
           size_t *its, Real<T> *res) {
@@ -878,7 +878,7 @@ SPRS_API(z, cplx, sprs_c64, double)
 SPRS_API(s, float, float, float)
 SPRS_API(c, cplxf, sprs_c32, float)
 
-// CG and GMRES preconditioned by an ILU(0) handle (ilu0.hip) or an AMG handle (amg.hip): one path, the handle's AppliedPrec view
+// BiCGStab, MINRES, CG and GMRES preconditioned by an ILU(0) handle (ilu0.hip) or an AMG handle (amg.hip): one path, the handle's AppliedPrec view
 #define SPRS_APPLIED_SOLVES(X, T, CT, R, NAME, S, PFX)                                                                 \
     int sprs_##PFX##_##NAME##_solve_##X(sprs_##NAME *h, const sprs_##PFX *P, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
         SPRS_G(return solve<T>(impl_of<S, T>(h), true, PFX##_prec<T>(P), (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);)  \
@@ -888,7 +888,9 @@ SPRS_API(c, cplxf, sprs_c32, float)
     }
 #define SPRS_APPLIED_API(X, T, CT, R)                                                                 \
     SPRS_APPLIED_SOLVES(X, T, CT, R, cg, Cg, ilu0) SPRS_APPLIED_SOLVES(X, T, CT, R, gmres, Gmres, ilu0) \
-    SPRS_APPLIED_SOLVES(X, T, CT, R, cg, Cg, amg) SPRS_APPLIED_SOLVES(X, T, CT, R, gmres, Gmres, amg)
+    SPRS_APPLIED_SOLVES(X, T, CT, R, cg, Cg, amg) SPRS_APPLIED_SOLVES(X, T, CT, R, gmres, Gmres, amg) \
+    SPRS_APPLIED_SOLVES(X, T, CT, R, bicgstab, BicgStab, ilu0) SPRS_APPLIED_SOLVES(X, T, CT, R, minres, MinRes, ilu0) \
+    SPRS_APPLIED_SOLVES(X, T, CT, R, bicgstab, BicgStab, amg) SPRS_APPLIED_SOLVES(X, T, CT, R, minres, MinRes, amg)
 SPRS_APPLIED_API(d, double, double, double)
 SPRS_APPLIED_API(z, cplx, sprs_c64, double)
 SPRS_APPLIED_API(s, float, float, float)

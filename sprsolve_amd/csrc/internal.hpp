@@ -419,7 +419,8 @@ template <class T> AppliedPrec<T> ilu0_prec(const sprs_ilu0 *P);   // the which 
 template <class T> AppliedPrec<T> amg_prec(const sprs_amg *P);
 
 // ---- what a solve is preconditioned with, from the C entry points down: nothing (a null sprs_diag), a diagonal (Jacobi) or
-// an applied handle (CG and GMRES only: no other solver's solve_dev takes this type).  with_prec() (krylov.hpp) checks it and
+// an applied handle (BiCGStab, MINRES, CG and GMRES; CSMINRES refuses any preconditioner and the batched CG takes a sprs_diag
+// only).  with_prec() (krylov.hpp) checks it and
 // resolves it into the Prec<T, V> the runs receive.
 template <class T>
 struct Precond {

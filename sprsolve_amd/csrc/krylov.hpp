@@ -105,7 +105,7 @@ struct Prec {
     bool any() const { return dinv || applied.h; }
     // out = M in as launches of its own: CG's start, the literal modes, and every application of an applied one
     int apply(const T *in, T *out) const { return applied.h ? applied.apply(in, out) : launch_diag_apply<T, V>(ctx, n, dinv, in, out); }
-    operator const V *() const { return dinv; }   // the solvers that take no applied one keep their `const V *dinv` runs
+    operator const V *() const { return dinv; }   // the batched CG takes no applied one and keeps its `const V *dinv` run
 };
 
 // The partials of one reduction as their consumer kernel finds them (KrylovBase::handoff).
@@ -195,15 +195,16 @@ class BicgStab : public KrylovBase<T> {
     StateBlock<BicgState<T>> state;
     int create(const sprs_csr *A, size_t size);
     void destroy() { state.destroy(); KrylovBase<T>::destroy(); }
-    int solve_dev(const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
+    // P: nothing, a diagonal (a `const sprs_diag *` converts) or an applied ILU(0) / AMG handle
+    int solve_dev(const Precond<T> &P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
                   size_t *its_out, Real<T> *res_out);
 
    private:
     friend class KrylovBase<T>;
     template <class V>
-    int run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
+    int run(const Prec<T, V> &M, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
     template <class V>
-    int run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
+    int run_literal(const Prec<T, V> &M, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
 };
 
 template <class T>
@@ -213,15 +214,16 @@ class MinRes : public KrylovBase<T> {
     bool saunders = false;  // CSMINRES
     int create(const sprs_csr *A, size_t size, bool saunders_);
     void destroy() { state.destroy(); KrylovBase<T>::destroy(); }
-    int solve_dev(const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
+    // P: nothing, a diagonal (a `const sprs_diag *` converts) or an applied ILU(0) / AMG handle
+    int solve_dev(const Precond<T> &P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
                   size_t *its_out, Real<T> *res_out);
 
    private:
     friend class KrylovBase<T>;
     template <class V>
-    int run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
+    int run(const Prec<T, V> &M, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
     template <class V>
-    int run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
+    int run_literal(const Prec<T, V> &M, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
 };
 
 // Conjugate gradients for Hermitian positive-definite A (recurrence: include/sprsolve_hip.h, sprs_cg_*; kernels: cg_fuse.hpp)

@@ -17,10 +17,11 @@ int MinRes<T>::create(const sprs_csr *A, size_t size, bool saunders_) {
 
 template <class T>
 template <class V>
-int MinRes<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out) {
+int MinRes<T>::run(const Prec<T, V> &M, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out) {
     sprs_ctx *c = this->ctx;
     const size_t n = this->n;
-    const bool pc = dinv != nullptr;
+    const V *dinv = M.dinv;
+    const bool pc = M.any(), applied = M.applied.h != nullptr;
     const bool sau = saunders && is_complex<T>::value;   // conj() is the identity on real data
     *its_out = 0; *res_out = 0.0;
 
@@ -41,7 +42,7 @@ int MinRes<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> t
     SPRS_TRY(this->norm2(v_new, &res_norm));                        // :81
     Real<T> beta_new;
     if (pc) {
-        SPRS_TRY((launch_diag_apply<T, V>(c, n, dinv, v_new, w_new)));      // :233
+        SPRS_TRY(M.apply(v_new, w_new));                                    // :233
         T b2;
         SPRS_TRY(this->cdot(v_new, w_new, &b2));               // :235
         if (sre(b2) < seps<Real<T>>() || sim(b2) > seps<Real<T>>() * sre(b2)) {                     // :236-244
@@ -138,9 +139,19 @@ int MinRes<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> t
                 SPRS_TRY(this->handoff(0, GS, partAlpha, &qA));
                 // beta_new^2 comes from conj(v_new).w_new (partBeta2) with a preconditioner, else from |v_new|^2 (pbeta)
                 const Fin fB = this->fin_for(1, pc ? (const void *)partBeta2 : (const void *)pbeta[cur_pb], nullptr, G);
-                SPRS_TRY(dispatch_bool(pc, [&](auto pc_tag) {
+                // An applied M (ILU(0), AMG): M2 runs without a preconditioner and updates v_new only (its |v_new|^2 partials go to
+                // pbeta and are not consumed), w_new = M v_new is a chain of launches of the handle's own (internal.hpp,
+                // AppliedPrec), then MinresVW forms the partials of conj(v_new).w_new that M3 expects: 3 launches + 1 application
+                // + MinresVW per iteration, no host wait inside one.  Once the status word has left ST_RUNNING the handle's launches
+                // still run until the next poll: they read v_new and write only w_new and the handle's scratch, never x, p, v or
+                // the state.
+                SPRS_TRY(dispatch_bool(dinv != nullptr, [&](auto pc_tag) {
                     return launch_fused<T>(c, n, G, cw, MinresM2<T, V, decltype(pc_tag)::value>{d_state, par, qA.p, qA.P, v_old, v, v_new, dinv, w_new, pbeta[cur_pb], partBeta2, fB, T(), T(), 0.0, T(), qA.tag, this->mb_timeout()});
                 }));
+                if (applied) {
+                    SPRS_TRY(M.apply(v_new, w_new));                                                     // :276
+                    SPRS_TRY(launch_fused<T>(c, n, G, cw, MinresVW<T>{d_state, v_new, w_new, partBeta2, T()}));   // :278
+                }
                 SPRS_TRY(pc ? this->handoff(1, G, partBeta2, &qB2) : this->handoff(1, G, pbeta[cur_pb], &qBt));
             }
             { T *tp = p_oold; p_oold = p_old; p_old = p; p = tp; }           // :151-154
@@ -194,11 +205,11 @@ int MinRes<T>::run(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> t
 
 template <class T>
 template <class V>
-int MinRes<T>::run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out,
+int MinRes<T>::run_literal(const Prec<T, V> &M, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out,
                            Real<T> *res_out) {
     sprs_ctx *c = this->ctx;
     const size_t n = this->n;
-    const bool pc = dinv != nullptr;
+    const bool pc = M.any();
     const bool sau = saunders;
     *its_out = 0; *res_out = 0.0;
     Real<T> rhs_norm = 0.0;
@@ -220,7 +231,7 @@ int MinRes<T>::run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter, R
     SPRS_TRY(this->norm2(v_new, &res_norm));
     Real<T> beta_new, beta_one;
     if (pc) {
-        SPRS_TRY((launch_diag_apply<T, V>(c, n, dinv, v_new, w_new)));
+        SPRS_TRY(M.apply(v_new, w_new));
         T b2;
         SPRS_TRY(this->cdot(v_new, w_new, &b2));
         if (sre(b2) < seps<Real<T>>() || sim(b2) > seps<Real<T>>() * sre(b2)) { *res_out = sre(b2); return SPRS_INVALID_PRECOND; }
@@ -255,7 +266,7 @@ int MinRes<T>::run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter, R
         SPRS_TRY(axpy(sfromr<T>(-beta), v_old, v_new));
         SPRS_TRY(axpy(sneg(alpha), v, v_new));
         if (pc) {
-            SPRS_TRY((launch_diag_apply<T, V>(c, n, dinv, v_new, w_new)));
+            SPRS_TRY(M.apply(v_new, w_new));
             T b2;
             SPRS_TRY(this->cdot(v_new, w_new, &b2));
             if (sre(b2) < seps<Real<T>>() || sim(b2) > seps<Real<T>>() * sre(b2)) { *its_out = its; *res_out = sre(b2); return SPRS_INVALID_PRECOND; }
@@ -291,7 +302,7 @@ int MinRes<T>::run_literal(const V *dinv, const T *rhs, T *x, size_t max_iter, R
 }
 
 template <class T>
-int MinRes<T>::solve_dev(const sprs_diag *P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter,
+int MinRes<T>::solve_dev(const Precond<T> &P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter,
                          Real<T> tol, size_t *its_out, Real<T> *res_out) {
     return KrylovBase<T>::solve(*this, saunders, P, rhs, rhs_len, x, x_len, max_iter, tol, its_out, res_out);
 }

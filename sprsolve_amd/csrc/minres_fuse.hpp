@@ -75,6 +75,30 @@ struct MinresM2 {
     }
 };
 
+// VW (applied preconditioners only: ILU(0), AMG): w_new = M v_new is a chain of launches of its own between M2 and M3, so M2 runs
+//     without a preconditioner and this pass forms the partials of conj(v_new).w_new (:278) that M3 expects, with the per-thread
+//     accumulation and block reduction of MinresM2<.., true>.  Reads v_new and w_new; no flags, waits on nothing.
+template <class T>
+struct MinresVW {
+    const MinresDev<T> *D; const T *v_new; const T *w_new; T *partBeta2;
+    T accT;
+    __device__ __forceinline__ bool prologue() {
+        if (D->status != ST_RUNNING) return false;
+        accT = szero<T>();
+        return true;
+    }
+    template <int PK, bool NT> __device__ __forceinline__ void run(int64_t i) {
+        const auto nv = ldp<T, PK, NT>(v_new, i); const auto wv = ldp<T, PK, NT>(w_new, i);
+#pragma unroll
+        for (int e = 0; e < PK; ++e) accT = sadd(accT, smul(sconj(nv.v[e]), wv.v[e]));          // :278
+    }
+    __device__ __forceinline__ void epilogue() {
+        __shared__ T smT[NWAVE];
+        const T s = block_sum(accT, smT);
+        if (threadIdx.x == 0) partBeta2[blockIdx.x] = s;
+    }
+};
+
 // M3  minres.rs:120-168 (cs_minres.rs:106-154 with SAUNDERS):  beta_new, normalise v_new
 //     [and w_new], Givens rotation, p = q - r2*p_old - r3*p_oold, p *= 1/r1, x += c*eta*beta_1*p,
 //     res_norm *= |s| ; converged?  eta *= -s

@@ -1,6 +1,8 @@
 """MINRES — mirror of the reference's src/minres.rs."""
 from . import _lib
 from ._solver import _SolverBase
+from .amg import AMG
+from .ilu import ILU0
 
 
 class MinRes(_SolverBase):
@@ -13,5 +15,10 @@ class MinRes(_SolverBase):
         return self._solve(None, rhs, x, max_iter, tol, False)
 
     def precond_solve(self, precond, rhs, x, max_iter, tol):
-        """minres.rs:178-341."""
+        """minres.rs:178-341, by a `DiagPrecond` (Jacobi), an `ILU0` or an `AMG`; the preconditioner must be Hermitian positive
+        definite (InvalidPreconditioner by the reference's rule, minres.rs:279-287)."""
+        if isinstance(precond, ILU0):
+            return self._solve(precond, rhs, x, max_iter, tol, True, prefix="ilu0")
+        if isinstance(precond, AMG):
+            return self._solve(precond, rhs, x, max_iter, tol, True, prefix="amg")
         return self._solve(precond, rhs, x, max_iter, tol, True)
