@@ -4,8 +4,8 @@
 // the header (sprs_amg_*) and restated by tests/_amg_ref.py.
 //
 // ilu0.hip's two ideas carry the device side:
-//  * every operator of the hierarchy (A_l, P_l, R_l) is stored in slices of 64 rows, slice-column-major, row lengths kept per
-//    row and padded slots skipped; ONE LANE folds ONE ROW left to right, so an application has the bits of the serial loop;
+//  * every operator of the hierarchy (A_l, P_l, R_l) is stored in the sliced-row layout of sell.hpp (position = row) and ONE
+//    LANE folds ONE ROW left to right with its sell_fold, so an application has the bits of the serial loop;
 //  * everything small is batched: the levels of at most AMG_TAIL_ROWS rows run in ONE launch of ONE workgroup — down, the
 //    coarse solve and up — with __syncthreads() between the steps (the barrier orders one step's stores before the next step's
 //    loads: all wavefronts of a workgroup share one CU and its L1).  The larger levels take five launches each: the
@@ -16,11 +16,11 @@
 #include <memory>
 
 #include "device.hpp"
+#include "sell.hpp"
 
 using namespace sprs;
 
 namespace sprs {
-constexpr int AMG_SLICE = WAVE;
 constexpr int AMG_TAIL_ROWS = 1024;      // levels of at most this many rows run inside the tail kernel
 constexpr int AMG_COARSE_LIMIT = 1024;   // largest coarse_max: the dense LU is applied by the tail kernel (AMG_COARSE_LIMIT <= AMG_TAIL_ROWS)
 constexpr int AMG_COARSE_SWEEPS = 8;     // damped-Jacobi sweeps in place of the LU when the coarsest level has more than coarse_max rows
@@ -40,10 +40,6 @@ struct HCsr {
 template <class T> inline Real<T> hmod(T a) {   // |a|: fabs, or sqrt(re re + im im) (not hypot: every step is one IEEE operation)
     if constexpr (is_complex<T>::value) return std::sqrt(ssq(a));
     else return std::fabs(a);
-}
-template <class T> inline bool bad_pivot(T u) {
-    const Real<T> re = sre(u), im = sim(u);
-    return !std::isfinite(re) || !std::isfinite(im) || (re == Real<T>(0) && im == Real<T>(0));
 }
 
 template <class T>
@@ -117,10 +113,9 @@ template <class T>
 int64_t take_diag(const HCsr<T> &A, std::vector<T> &diag) {
     diag.assign((size_t)A.n, szero<T>());
     for (int32_t i = 0; i < A.n; ++i) {
-        const int32_t *b = A.ix.data() + A.ip[i], *e = A.ix.data() + A.ip[i + 1];
-        const int32_t *d = std::lower_bound(b, e, i);
-        if (d == e || *d != i) return i;
-        diag[i] = A.v[(size_t)(d - A.ix.data())];
+        const int64_t d = diag_pos(A.ip.data(), A.ix.data(), i);
+        if (d < 0) return i;
+        diag[i] = A.v[(size_t)d];
         if (bad_pivot(diag[i])) return i;
     }
     return -1;
@@ -143,51 +138,13 @@ Real<T> jacobi_omega(const HCsr<T> &A, const std::vector<T> &diag) {
 }
 
 // ------------------------------------------------------------------------------------------------ device side
-template <class T>
-struct SellDev {
-    const int32_t *len;          // per row (padded to whole slices): entries of the row
-    const int64_t *sbase;        // per slice: first slot
-    const int32_t *col;
-    const T *val;
-};
-
-struct SellMat {                 // type-erased owner of one operator's device arrays
-    int32_t n = 0;
-    int32_t *len = nullptr; int64_t *sbase = nullptr; int32_t *col = nullptr; void *val = nullptr;
-    void release() {
-        for (void *p : {(void *)len, (void *)sbase, (void *)col, val}) if (p) (void)hipFree(p);
-        len = nullptr; sbase = nullptr; col = nullptr; val = nullptr;
-    }
-    template <class T> SellDev<T> dev() const { return SellDev<T>{len, sbase, col, (const T *)val}; }
-};
-
 enum : int { OP_MUL = 0, OP_ACC = 1, OP_RESID = 2, OP_JACOBI = 3 };
 
-// sigma = sum_j m_ij x_j of row `row`, left to right from zero
-template <class T>
-__device__ __forceinline__ T sell_sigma(const SellDev<T> &M, int row, const T *x) {
-    const int len = M.len[row];
-    const int64_t b = M.sbase[row >> 6] + (row & (AMG_SLICE - 1));
-    T sigma = szero<T>();
-    int e = 0;
-    for (; e + 4 <= len; e += 4) {                           // four gathers in flight, folded in order
-        int c[4]; T v[4], xv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { c[u] = M.col[b + (int64_t)(e + u) * AMG_SLICE]; v[u] = M.val[b + (int64_t)(e + u) * AMG_SLICE]; }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) xv[u] = x[c[u]];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) sigma = sadd(sigma, smul(v[u], xv[u]));
-    }
-    for (; e < len; ++e) sigma = sadd(sigma, smul(M.val[b + (int64_t)e * AMG_SLICE], x[M.col[b + (int64_t)e * AMG_SLICE]]));
-    return sigma;
-}
-
 // One row of one step.  OP_MUL: out = M x.  OP_ACC: out = y + M x (y may be out).  OP_RESID: out = y - M x.
-// OP_JACOBI: out = x + (omega (y - M x)) / d (out is not x; y may be out).
+// OP_JACOBI: out = x + (omega (y - M x)) / d (out is not x; y may be out).  M x: sell_fold, left to right from zero.
 template <class T, int OP>
 __device__ __forceinline__ void amg_row(const SellDev<T> &M, int row, const T *x, const T *y, const T *d, Real<T> omega, T *out) {
-    const T sigma = sell_sigma<T>(M, row, x);
+    const T sigma = sell_fold<T>(M, row, x);
     if (OP == OP_MUL) out[row] = sigma;
     else if (OP == OP_ACC) out[row] = sadd(y[row], sigma);
     else if (OP == OP_RESID) out[row] = ssub(y[row], sigma);
@@ -288,12 +245,6 @@ __global__ __launch_bounds__(BLOCK) void amg_tail_kernel(const TailLevel<T> *lv,
     }
 }
 
-template <class U>
-bool upload(U **dst, const U *src, size_t count, size_t pad = 2) {
-    if (hipMalloc((void **)dst, sizeof(U) * (count + pad)) != hipSuccess) return false;
-    return count == 0 || hipMemcpy(*dst, src, sizeof(U) * count, hipMemcpyHostToDevice) == hipSuccess;
-}
-
 // A CSR matrix in HBM for the products of the set-up (spgemm.hip): owned, or borrowed from the caller's handle (level 0)
 template <class T>
 struct DCsr {
@@ -321,7 +272,7 @@ template <class T>
 bool to_device(const HCsr<T> &M, DCsr<T> &D) {
     D.reset();
     D.n = M.n; D.ncols = M.ncols; D.nnz = (int64_t)M.ix.size();
-    return upload(&D.ip, M.ip.data(), M.ip.size()) && upload(&D.ix, M.ix.data(), M.ix.size()) && upload(&D.v, M.v.data(), M.v.size());
+    return dev_upload(&D.ip, M.ip.data(), M.ip.size()) && dev_upload(&D.ix, M.ix.data(), M.ix.size()) && dev_upload(&D.v, M.v.data(), M.v.size());
 }
 
 template <class T>
@@ -343,32 +294,9 @@ int dev_product(sprs_ctx *c, const DCsr<T> &A, const DCsr<T> &B, DCsr<T> &C) {
 }
 
 template <class T>
-bool build_sell(SellMat &M, const HCsr<T> &A) {
-    M.n = A.n;
-    const size_t nslice = ((size_t)A.n + AMG_SLICE - 1) / AMG_SLICE;
-    std::vector<int32_t> len(nslice * AMG_SLICE, 0);
-    std::vector<int64_t> sbase(nslice, 0);
-    int64_t slots = 0;
-    for (size_t s = 0; s < nslice; ++s) {
-        int32_t width = 0;
-        for (size_t i = s * AMG_SLICE; i < std::min((s + 1) * AMG_SLICE, (size_t)A.n); ++i) {
-            len[i] = A.ip[i + 1] - A.ip[i];
-            width = std::max(width, len[i]);
-        }
-        sbase[s] = slots;
-        slots += (int64_t)width * AMG_SLICE;
-    }
-    std::vector<int32_t> col((size_t)slots, 0);
-    std::vector<T> val((size_t)slots, szero<T>());
-    for (int32_t i = 0; i < A.n; ++i) {
-        const size_t b = (size_t)sbase[(size_t)i / AMG_SLICE] + (size_t)i % AMG_SLICE;
-        for (int32_t e = 0; e < len[i]; ++e) { col[b + (size_t)e * AMG_SLICE] = A.ix[(size_t)A.ip[i] + e]; val[b + (size_t)e * AMG_SLICE] = A.v[(size_t)A.ip[i] + e]; }
-    }
-    T *dval = nullptr;
-    const bool ok = upload(&M.len, len.data(), len.size()) && upload(&M.sbase, sbase.data(), sbase.size()) &&
-                    upload(&M.col, col.data(), col.size()) && upload(&dval, val.data(), val.size());
-    M.val = dval;
-    return ok;
+bool build_sell(SellMat &M, const HCsr<T> &A) {   // position = row
+    return M.upload(A.n, sell_pack<T>(A.n, [](size_t p) { return (int32_t)p; }, [&](int32_t i) { return A.ip[i]; }, [&](int32_t i) { return A.ip[i + 1]; },
+                                      A.ix.data(), A.v.data()));
 }
 
 struct AmgLevel {
@@ -421,19 +349,8 @@ int amg_create(const sprs_csr *A, double theta_d, int64_t coarse_max, int64_t ma
     std::vector<HLevel<T>> H(1);
     HCsr<T> &A0 = H[0].A;
     A0.n = A0.ncols = (int32_t)A->nrows;
-    A0.ip.assign((size_t)A->nrows + 1, 0); A0.ix.resize((size_t)A->nnz); A0.v.resize((size_t)A->nnz);
-    SPRS_HIP_TRY(c, hipMemcpyAsync(A0.ip.data(), A->row_ptr, sizeof(int32_t) * A0.ip.size(), hipMemcpyDeviceToHost, c->stream));
-    if (A->nnz) {
-        SPRS_HIP_TRY(c, hipMemcpyAsync(A0.ix.data(), A->col_idx, sizeof(int32_t) * A0.ix.size(), hipMemcpyDeviceToHost, c->stream));
-        SPRS_HIP_TRY(c, hipMemcpyAsync(A0.v.data(), A->val, sizeof(T) * A0.v.size(), hipMemcpyDeviceToHost, c->stream));
-    }
-    SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (int32_t i = 0; i < A0.n; ++i)
-        for (int32_t k = A0.ip[i] + 1; k < A0.ip[i + 1]; ++k)
-            if (A0.ix[k] <= A0.ix[k - 1]) {
-                snprintf(c->err, sizeof(c->err), "sprs_amg: the column indices of row %d are not strictly ascending", (int)i);
-                return SPRS_INVALID_ARGUMENT;
-            }
+    A0.v.resize((size_t)A->nnz);
+    SPRS_TRY(host_pattern(A, "sprs_amg", A0.ip, A0.ix, A0.v.data()));
     // the hierarchy
     const R theta = (R)theta_d;
     DCsr<T> dA;                                              // the level's operator in HBM: level 0 reads the handle's own arrays
@@ -507,7 +424,7 @@ int amg_create(const sprs_csr *A, double theta_d, int64_t coarse_max, int64_t ma
         bool ok = build_sell<T>(D.A, Lh.A);
         if (ok && l + 1 < nlev) ok = build_sell<T>(D.P, Lh.P) && build_sell<T>(D.R, Lh.R);
         T *dd = nullptr;
-        ok = ok && upload(&dd, Lh.diag.data(), Lh.diag.size());
+        ok = ok && dev_upload(&dd, Lh.diag.data(), Lh.diag.size());
         D.diag = dd;
         for (void **v : {&D.b, &D.x, &D.x2, &D.r}) ok = ok && hipMalloc(v, sizeof(T) * ((size_t)D.n + 2)) == hipSuccess;
         if (!ok) return SPRS_ERR_HIP;
@@ -517,7 +434,7 @@ int amg_create(const sprs_csr *A, double theta_d, int64_t coarse_max, int64_t ma
     }
     if (lu_n) {
         T *dl = nullptr;
-        if (!upload(&dl, lu.data(), lu.size())) { P->lu = dl; return SPRS_ERR_HIP; }
+        if (!dev_upload(&dl, lu.data(), lu.size())) { P->lu = dl; return SPRS_ERR_HIP; }
         P->lu = dl;
     }
     // the tail: every level of at most AMG_TAIL_ROWS rows (levels only shrink)
@@ -529,7 +446,7 @@ int amg_create(const sprs_csr *A, double theta_d, int64_t coarse_max, int64_t ma
         td[l] = TailLevel<T>{D.A.dev<T>(), D.P.dev<T>(), D.R.dev<T>(), (const T *)D.diag, (R)D.omega, D.n, (T *)D.b, (T *)D.x, (T *)D.x2, (T *)D.r};
     }
     TailLevel<T> *dt = nullptr;
-    if (!upload(&dt, td.data(), td.size())) { P->tail_desc = dt; return SPRS_ERR_HIP; }
+    if (!dev_upload(&dt, td.data(), td.size())) { P->tail_desc = dt; return SPRS_ERR_HIP; }
     P->tail_desc = dt;
     // launches of one application: five per level above the tail (three down, two up), the tail's one, and where the
     // coarsest level is above the tail its Jacobi sweeps
@@ -586,17 +503,7 @@ template <class T>
 int amg_apply_host(const sprs_amg *Pc, const T *in, size_t in_len, T *out, size_t out_len) {
     if (!Pc || !in || !out || Pc->dtype != dtype_of<T>::value) return SPRS_INVALID_ARGUMENT;
     if (in_len != (size_t)Pc->n || out_len != (size_t)Pc->n) return SPRS_DIM_MISMATCH;
-    sprs_amg *P = const_cast<sprs_amg *>(Pc);
-    sprs_ctx *c = P->ctx;
-    CtxLock lock(c);   // in_tmp / out_tmp are per-handle staging
-    SPRS_HIP_TRY(c, hipSetDevice(c->device));
-    if (!P->in_tmp) SPRS_HIP_TRY(c, hipMalloc(&P->in_tmp, sizeof(T) * ((size_t)P->n + 2)));
-    if (!P->out_tmp) SPRS_HIP_TRY(c, hipMalloc(&P->out_tmp, sizeof(T) * ((size_t)P->n + 2)));
-    SPRS_HIP_TRY(c, hipMemcpyAsync(P->in_tmp, in, sizeof(T) * in_len, hipMemcpyHostToDevice, c->stream));
-    SPRS_TRY(amg_apply<T>(P, (const T *)P->in_tmp, (T *)P->out_tmp));
-    SPRS_HIP_TRY(c, hipMemcpyAsync(out, P->out_tmp, sizeof(T) * out_len, hipMemcpyDeviceToHost, c->stream));
-    SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return SPRS_OK;
+    return staged_apply<T>(Pc, in, out, [&](const T *din, T *dout) { return amg_apply<T>(Pc, din, dout); });
 }
 
 template <class T> int amg_view_check(const void *h, const sprs_csr *A, int dtype, size_t n) { return amg_check((const sprs_amg *)h, A, dtype, n); }
@@ -606,11 +513,7 @@ template <class T> int amg_view_apply(const void *h, const T *in, T *out) { retu
 
 namespace sprs {
 
-int amg_check(const sprs_amg *P, const sprs_csr *A, int dtype, size_t n) {
-    if (!P || !A || P->dtype != dtype || P->ctx != A->ctx || A->dist) return SPRS_INVALID_ARGUMENT;
-    if ((size_t)P->n != n) return SPRS_DIM_MISMATCH;
-    return SPRS_OK;
-}
+int amg_check(const sprs_amg *P, const sprs_csr *A, int dtype, size_t n) { return applied_check(P, A, dtype, n); }
 
 template <class T>
 int amg_apply(const sprs_amg *P, const T *in, T *out) {

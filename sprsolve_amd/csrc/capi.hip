@@ -453,17 +453,7 @@ template <class T>
 int diag_apply_host(const sprs_diag *Pc, const T *in, size_t in_len, T *out, size_t out_len) {
     if (!Pc || !in || !out) return SPRS_INVALID_ARGUMENT;
     if (Pc->n != in_len || Pc->n != out_len) return SPRS_DIM_MISMATCH;     // precond.rs:39-41
-    sprs_diag *P = const_cast<sprs_diag *>(Pc);
-    sprs_ctx *c = P->ctx;
-    CtxLock lock(c);   // in_tmp / out_tmp are per-handle staging
-    SPRS_HIP_TRY(c, hipSetDevice(c->device));
-    if (!P->in_tmp) SPRS_HIP_TRY(c, hipMalloc(&P->in_tmp, sizeof(T) * (P->n + 2)));
-    if (!P->out_tmp) SPRS_HIP_TRY(c, hipMalloc(&P->out_tmp, sizeof(T) * (P->n + 2)));
-    SPRS_HIP_TRY(c, hipMemcpyAsync(P->in_tmp, in, sizeof(T) * in_len, hipMemcpyHostToDevice, c->stream));
-    SPRS_TRY(diag_apply_dev<T>(P, (const T *)P->in_tmp, (T *)P->out_tmp));
-    SPRS_HIP_TRY(c, hipMemcpyAsync(out, P->out_tmp, sizeof(T) * out_len, hipMemcpyDeviceToHost, c->stream));
-    SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return SPRS_OK;
+    return staged_apply<T>(Pc, in, out, [&](const T *din, T *dout) { return diag_apply_dev<T>(Pc, din, dout); });
 }
 
 // ------------------------------------------------------------------------------ solver handles

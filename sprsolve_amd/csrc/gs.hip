@@ -90,11 +90,8 @@ int gs_create(const sprs_csr *A, sprs_gauss_seidel **out) {
     }
     auto *G = new sprs_gauss_seidel();
     G->A = A; G->ctx = c; G->dtype = A->dtype; G->n = n;
-    G->lvl_ptr.assign((size_t)nlev + 1, 0);
-    for (int64_t i = 0; i < n; ++i) G->lvl_ptr[(size_t)level[i] + 1]++;
-    for (int32_t l = 0; l < nlev; ++l) G->lvl_ptr[l + 1] += G->lvl_ptr[l];
-    std::vector<int32_t> rows((size_t)n), fill(G->lvl_ptr.begin(), G->lvl_ptr.end() - (nlev ? 1 : 0));
-    for (int64_t i = 0; i < n; ++i) rows[(size_t)fill[level[i]]++] = (int32_t)i;     // ascending rows inside a level
+    std::vector<int32_t> rows;
+    group_by_level(level, nlev, G->lvl_ptr, rows);
     const size_t np = (size_t)n + 32;
     bool ok = hipMalloc((void **)&G->lvl_rows, sizeof(int32_t) * np) == hipSuccess &&
               hipMalloc(&G->diag, sizeof(T) * np) == hipSuccess && hipMalloc(&G->resid, sizeof(T) * np) == hipSuccess &&

@@ -6,10 +6,10 @@
 // ROW left to right — so factors and solves are bit-identical to the serial loop for all four scalar types.  What gs.hip does
 // not have:
 //  * Level-major storage.  L's strictly-lower entries and U's strictly-upper entries (the pivots apart) are re-laid level by
-//    level at creation: the rows of a level in ascending order, in slices of 64 rows, each slice stored slice-column-major —
-//    lane t of a wavefront reads entry e of its row at base + e * 64 + t, so every value and column load is one coalesced
-//    wavefront load instead of a walk through 64 scattered CSR rows.  Row lengths are kept per row and the padded slots are
-//    SKIPPED, never multiplied by zero (0 * inf and -0.0 would change bits).  A slice never spans two levels.
+//    level at creation in the sliced-row layout of sell.hpp: the rows of a level in ascending order at consecutive positions,
+//    every level starting a new slice (a slice never spans two levels), so every value and column load is one coalesced
+//    wavefront load instead of a walk through 64 scattered CSR rows.  A row is folded by sell.hpp's sell_fold, which skips
+//    the padded slots.
 //  * Small levels are batched.  A maximal run of consecutive levels of at most BLOCK rows each (at most ILU_MAX_BATCH_LEVELS of
 //    them) is ONE launch of ONE workgroup that loops over the levels with __syncthreads() between them: the head and the tail
 //    of a 3-D wavefront, every level of a 2-D grid, a tridiagonal matrix.  The vector being solved for is read and written
@@ -21,18 +21,19 @@
 //
 // A handle created with sweeps = k >= 1 (sprs_ilu0_create_sweeps) factorises in the same way and then replaces both exact
 // solves by k Jacobi sweeps from the header's statement: one launch per sweep over the whole factor, whatever the level count.
-// Such a handle keeps its factors in NATURAL row order and no level-major copy: lane t of slice s owns row 64 s + t, the
-// storage is slice-column-major as above, so a slice is full whatever the levels look like and neighbouring lanes gather
-// neighbouring x.  A sweep reads the previous sweep's vector and writes another one (never in place), so its result does not
-// depend on the launch geometry; the handle owns the three vectors the sweeps alternate between.
+// Such a handle keeps its factors in NATURAL row order and no level-major copy: the same layout with position = row, so a
+// slice is full whatever the levels look like and neighbouring lanes gather neighbouring x.  A sweep reads the previous
+// sweep's vector and writes another one (never in place), so its result does not depend on the launch geometry; the handle
+// owns the three vectors the sweeps alternate between.
 #include <algorithm>
 
 #include "device.hpp"
+#include "sell.hpp"
 
 using namespace sprs;
 
 namespace sprs {
-constexpr int ILU_SLICE = WAVE;              // rows per slice = lanes of a wavefront
+constexpr int ILU_SLICE = SELL_SLICE;
 // Levels per batched launch: bounds the run time of one kernel on a chain-like matrix (a level costs the one workgroup a few
 // dependent memory round trips, some microseconds; 128 of them stay well below a millisecond).
 constexpr int ILU_MAX_BATCH_LEVELS = 128;
@@ -54,30 +55,27 @@ std::vector<IluLaunch> make_plan(const std::vector<int32_t> &lvl_ptr) {
     return plan;
 }
 
-// One triangular factor in level-major storage.
+// One triangular factor: level-major with its plan, or (a sweeps handle; lvl_slice, prow and the plan stay empty) in natural order.
 struct IluTri {
-    int32_t nlev = 0, nslice = 0;
+    int32_t nlev = 0;
     std::vector<int32_t> h_lvl_slice;    // host: level l owns slices [h_lvl_slice[l], h_lvl_slice[l + 1])
     std::vector<IluLaunch> plan;
+    SellMat M;                           // the strict triangle
     int32_t *lvl_slice = nullptr;        // device copy
-    int32_t *prow = nullptr;             // device, nslice * 64: the row of (slice, lane), -1 = no row
-    int32_t *plen = nullptr;             // device, nslice * 64: its number of entries
-    int64_t *sbase = nullptr;            // device, nslice: first slot of the slice in col / val
-    int32_t *col = nullptr;              // device, slots
-    void *val = nullptr;                 // device, slots of T
-    void *piv = nullptr;                 // device, nslice * 64 of T: u_ii (upper factor only)
+    int32_t *prow = nullptr;             // device, per position: its row, -1 = no row
+    void *piv = nullptr;                 // device, per position of T: u_ii (upper factor only)
     void release() {
-        for (void *p : {(void *)lvl_slice, (void *)prow, (void *)plen, (void *)sbase, (void *)col, val, piv}) if (p) (void)hipFree(p);
-        lvl_slice = prow = plen = col = nullptr; sbase = nullptr; val = piv = nullptr;
+        M.release();
+        for (void *p : {(void *)lvl_slice, (void *)prow, piv}) if (p) (void)hipFree(p);
+        lvl_slice = prow = nullptr; piv = nullptr;
     }
 };
 
 template <class T>
 struct TriDev {
-    const int32_t *lvl_slice, *prow, *plen;
-    const int64_t *sbase;
-    const int32_t *col;
-    const T *val, *piv;
+    const int32_t *lvl_slice, *prow;
+    SellDev<T> M;
+    const T *piv;
 };
 
 // One row by one lane: sigma over the row's entries in ascending column order, then the row's own element.  `in` and `out` may
@@ -87,21 +85,8 @@ __device__ __forceinline__ void tri_row(const TriDev<T> &F, int s, int t, const 
     const int p = s * ILU_SLICE + t;
     const int row = F.prow[p];
     if (row < 0) return;
-    const int len = F.plen[p];
-    const int64_t b = F.sbase[s] + t;
-    T sigma = szero<T>();
-    int e = 0;
-    for (; e + 4 <= len; e += 4) {                                   // four gathers in flight, folded in order
-        int c[4]; T v[4], x[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { c[u] = F.col[b + (int64_t)(e + u) * ILU_SLICE]; v[u] = F.val[b + (int64_t)(e + u) * ILU_SLICE]; }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) x[u] = out[c[u]];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) sigma = sadd(sigma, smul(v[u], x[u]));
-    }
-    for (; e < len; ++e) sigma = sadd(sigma, smul(F.val[b + (int64_t)e * ILU_SLICE], out[F.col[b + (int64_t)e * ILU_SLICE]]));
-    const T d = ssub(in[row], sigma);
+    const T sigma = sell_fold<T>(F.M, p, out);
+    const T d = ssub(in[row], sigma);                                // (in[row] is loaded after the fold, not held across it)
     if (UPPER) out[row] = sdiv(d, F.piv[p]);
     else out[row] = d;
 }
@@ -124,37 +109,22 @@ __global__ __launch_bounds__(BLOCK) void tri_batch_kernel(TriDev<T> F, int l0, i
     }
 }
 
-// ---- Jacobi sweeps on a factor in natural row order (row = 64 * slice + lane; IluTri::prow and ::lvl_slice stay empty)
+// ---- Jacobi sweeps on a factor in natural row order (position = row)
 template <class T>
 struct SweepDev {
-    const int32_t *plen;                 // n rounded up to whole slices: entries of the row
-    const int64_t *sbase;
-    const int32_t *col;
-    const T *val, *piv;                  // piv: u_ii per row (upper factor only)
+    SellDev<T> M;
+    const T *piv;                        // u_ii per row (upper factor only)
 };
 
 // One sweep, one wavefront per slice: next_i = rhs_i - sigma_i(prev) for the lower factor, the same divided by u_ii for the
-// upper one; tri_row's walk and fold.  `prev` is never `next`; `rhs` may be `next` (a lane reads rhs of its own row only).
+// upper one.  `prev` is never `next`; `rhs` may be `next` (a lane reads rhs of its own row only).
 // FUSE (the last lower sweep of an application): the lane also stores the upper solve's first sweep, z1_i = next_i / u_ii.
 template <class T, bool UPPER, bool FUSE>
 __global__ __launch_bounds__(BLOCK) void sweep_kernel(SweepDev<T> F, int n, const T *rhs, const T *prev, T *next, const T *upiv, T *z1) {
     const int s = (int)blockIdx.x * NWAVE + (int)(threadIdx.x >> 6), t = threadIdx.x & (WAVE - 1);
     const int row = s * ILU_SLICE + t;
     if (row >= n) return;
-    const int len = F.plen[row];
-    const int64_t b = F.sbase[s] + t;
-    T sigma = szero<T>();
-    int e = 0;
-    for (; e + 4 <= len; e += 4) {                                   // four gathers in flight, folded in order
-        int c[4]; T v[4], x[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { c[u] = F.col[b + (int64_t)(e + u) * ILU_SLICE]; v[u] = F.val[b + (int64_t)(e + u) * ILU_SLICE]; }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) x[u] = prev[c[u]];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) sigma = sadd(sigma, smul(v[u], x[u]));
-    }
-    for (; e < len; ++e) sigma = sadd(sigma, smul(F.val[b + (int64_t)e * ILU_SLICE], prev[F.col[b + (int64_t)e * ILU_SLICE]]));
+    const T sigma = sell_fold<T>(F.M, row, prev);
     T d = ssub(rhs[row], sigma);
     if (UPPER) d = sdiv(d, F.piv[row]);
     next[row] = d;
@@ -212,9 +182,7 @@ __global__ __launch_bounds__(BLOCK) void ilu_batch_kernel(const int32_t *__restr
 template <class T>
 __global__ __launch_bounds__(BLOCK) void ilu_pivot_check_kernel(int n, const int32_t *__restrict__ dpos, const T *__restrict__ a, int *__restrict__ bad) {
     for (int row = blockIdx.x * BLOCK + threadIdx.x; row < n; row += gridDim.x * BLOCK) {
-        const T u = a[dpos[row]];
-        const Real<T> re = sre(u), im = sim(u);
-        if (!isfinite(re) || !isfinite(im) || (re == Real<T>(0) && im == Real<T>(0))) atomicMin(bad, row);
+        if (bad_pivot(a[dpos[row]])) atomicMin(bad, row);
     }
 }
 
@@ -236,7 +204,7 @@ namespace {
 
 template <class T>
 TriDev<T> tri_dev(const IluTri &F) {
-    return TriDev<T>{F.lvl_slice, F.prow, F.plen, F.sbase, F.col, (const T *)F.val, (const T *)F.piv};
+    return TriDev<T>{F.lvl_slice, F.prow, F.M.dev<T>(), (const T *)F.piv};
 }
 
 // out = F^-1 in: the launches of the factor's plan, asynchronous on the context's stream
@@ -262,10 +230,9 @@ int sweeps_apply(const sprs_ilu0 *P, int which, const T *in, T *out) {
     sprs_ctx *c = P->ctx;
     const int n = (int)P->n, k = P->sweeps;
     if (!n) return SPRS_OK;
-    const SweepDev<T> L{P->L.plen, P->L.sbase, P->L.col, (const T *)P->L.val, nullptr};
-    const SweepDev<T> U{P->U.plen, P->U.sbase, P->U.col, (const T *)P->U.val, (const T *)P->U.piv};
+    const SweepDev<T> L{P->L.M.dev<T>(), nullptr}, U{P->U.M.dev<T>(), (const T *)P->U.piv};
     T *const buf[3] = {(T *)P->ybuf, (T *)P->sbuf[0], (T *)P->sbuf[1]};
-    const dim3 grid((unsigned)((P->L.nslice + NWAVE - 1) / NWAVE)), egrid((unsigned)((n + BLOCK - 1) / BLOCK));
+    const dim3 grid((unsigned)((P->L.M.nslice + NWAVE - 1) / NWAVE)), egrid((unsigned)((n + BLOCK - 1) / BLOCK));
     const T *rhs = in;                   // the upper sweeps' right-hand side: y(k) of an application, `in` of which = 2
     T *spare = buf[0];                   // with buf[2] the two vectors the upper sweeps alternate between
     if (which != 2) {
@@ -302,125 +269,47 @@ int sweeps_apply(const sprs_ilu0 *P, int which, const T *in, T *out) {
     return SPRS_OK;
 }
 
-template <class U>
-bool upload(U **dst, const std::vector<U> &src, size_t pad = 1) {
-    if (hipMalloc((void **)dst, sizeof(U) * (src.size() + pad)) != hipSuccess) return false;
-    return src.empty() || hipMemcpy(*dst, src.data(), sizeof(U) * src.size(), hipMemcpyHostToDevice) == hipSuccess;
+// Host side of one factor: its packed strict triangle and (the upper factor) u_ii per position, ones where no row is.
+template <class T>
+struct TriHost {
+    SellPacked<T> S;
+    std::vector<T> piv;
+};
+
+// The row of every position from row_of (-1: none), row i's entries the CSR positions [eb(i), ee(i)) of ci / fv (the factorised
+// values); dpos: the diagonal's positions (the upper factor), or null.  The pivots are gathered in the packer's own pass.
+template <class T, class ROW, class EB, class EE>
+TriHost<T> pack_tri(int64_t npos, ROW row_of, const std::vector<int32_t> &ci, const std::vector<T> &fv, EB eb, EE ee, const std::vector<int32_t> *dpos) {
+    TriHost<T> H;
+    if (!dpos) { H.S = sell_pack<T>(npos, row_of, eb, ee, ci.data(), fv.data()); return H; }
+    H.piv.assign((size_t)(npos + ILU_SLICE - 1) / ILU_SLICE * ILU_SLICE, sone<T>());
+    H.S = sell_pack<T>(npos, row_of, eb, ee, ci.data(), fv.data(), [&](size_t p, int32_t i) { H.piv[p] = fv[(size_t)(*dpos)[(size_t)i]]; });
+    return H;
 }
 
-// rows in level order (ascending inside a level) and the levels' extents
-void group_by_level(const std::vector<int32_t> &level, int32_t nlev, std::vector<int32_t> &lvl_ptr, std::vector<int32_t> &rows) {
-    const size_t n = level.size();
-    lvl_ptr.assign((size_t)nlev + 1, 0);
-    for (size_t i = 0; i < n; ++i) lvl_ptr[(size_t)level[i] + 1]++;
-    for (int32_t l = 0; l < nlev; ++l) lvl_ptr[l + 1] += lvl_ptr[l];
-    std::vector<int32_t> fill(lvl_ptr.begin(), lvl_ptr.end() - 1);
-    rows.resize(n);
-    for (size_t i = 0; i < n; ++i) rows[(size_t)fill[level[i]]++] = (int32_t)i;
+template <class T>
+int upload_tri(IluTri &F, int64_t npos, const TriHost<T> &H) {
+    T *dpiv = nullptr;
+    const bool ok = F.M.upload(npos, H.S) && (H.piv.empty() || dev_upload(&dpiv, H.piv.data(), H.piv.size()));
+    F.piv = dpiv;
+    return ok ? SPRS_OK : SPRS_ERR_HIP;
 }
 
-// Level-major layout of one factor.  Row i's entries are the CSR positions [eb(i), ee(i)); fv holds the factorised values.
+// Level-major layout of one factor: the rows of level l at the positions from slice h_lvl_slice[l] on, and the launch plan.
+// All host work first, then the uploads.
 template <class T, class EB, class EE>
 int build_tri(IluTri &F, const std::vector<int32_t> &lvl_ptr, const std::vector<int32_t> &rows, const std::vector<int32_t> &ci,
               const std::vector<T> &fv, EB eb, EE ee, const std::vector<int32_t> *dpos) {
     const int32_t nlev = (int32_t)lvl_ptr.size() - 1;
-    F.nlev = nlev;
     F.h_lvl_slice.assign((size_t)nlev + 1, 0);
     for (int32_t l = 0; l < nlev; ++l) F.h_lvl_slice[l + 1] = F.h_lvl_slice[l] + (lvl_ptr[l + 1] - lvl_ptr[l] + ILU_SLICE - 1) / ILU_SLICE;
-    F.nslice = F.h_lvl_slice[nlev];
     F.plan = make_plan(lvl_ptr);
-    const size_t np = (size_t)F.nslice * ILU_SLICE;
-    std::vector<int32_t> prow(np, -1), plen(np, 0);
-    std::vector<int64_t> sbase((size_t)F.nslice, 0);
-    std::vector<T> piv(dpos ? np : 0, sone<T>());
-    int64_t slots = 0;
+    std::vector<int32_t> prow((size_t)F.h_lvl_slice[nlev] * ILU_SLICE, -1);
     for (int32_t l = 0; l < nlev; ++l)
-        for (int32_t s = F.h_lvl_slice[l]; s < F.h_lvl_slice[l + 1]; ++s) {
-            const int32_t r0 = lvl_ptr[l] + (s - F.h_lvl_slice[l]) * ILU_SLICE, r1 = std::min(r0 + ILU_SLICE, lvl_ptr[l + 1]);
-            int32_t width = 0;
-            for (int32_t r = r0; r < r1; ++r) {
-                const int32_t i = rows[r], len = ee(i) - eb(i);
-                const size_t p = (size_t)s * ILU_SLICE + (size_t)(r - r0);
-                prow[p] = i; plen[p] = len;
-                if (dpos) piv[p] = fv[(size_t)(*dpos)[i]];
-                width = std::max(width, len);
-            }
-            sbase[s] = slots;
-            slots += (int64_t)width * ILU_SLICE;
-        }
-    std::vector<int32_t> col((size_t)slots, 0);
-    std::vector<T> val((size_t)slots, szero<T>());
-    for (int32_t s = 0; s < F.nslice; ++s)
-        for (int t = 0; t < ILU_SLICE; ++t) {
-            const size_t p = (size_t)s * ILU_SLICE + t;
-            if (prow[p] < 0) continue;
-            const int32_t b = eb(prow[p]);
-            for (int32_t e = 0; e < plen[p]; ++e) {
-                const size_t d = (size_t)sbase[s] + (size_t)e * ILU_SLICE + t;
-                col[d] = ci[(size_t)b + e]; val[d] = fv[(size_t)b + e];
-            }
-        }
-    T *dval = nullptr, *dpiv = nullptr;
-    bool ok = upload(&F.lvl_slice, F.h_lvl_slice) && upload(&F.prow, prow) && upload(&F.plen, plen) && upload(&F.sbase, sbase) &&
-              upload(&F.col, col) && upload(&dval, val);
-    F.val = dval;
-    if (ok && dpos) { ok = upload(&dpiv, piv); F.piv = dpiv; }
-    return ok ? SPRS_OK : SPRS_ERR_HIP;
-}
-
-// Host side of the natural-order layout of one factor (a sweeps handle): row i is lane i % 64 of slice i / 64.  plen is padded
-// to whole slices with empty rows; piv (filled when dpos is given) with ones.
-template <class T>
-struct NaturalTri {
-    int32_t nslice = 0;
-    std::vector<int32_t> plen, col;
-    std::vector<int64_t> sbase;
-    std::vector<T> val, piv;
-};
-
-template <class T, class EB, class EE>
-NaturalTri<T> layout_natural(int64_t n, const std::vector<int32_t> &ci, const std::vector<T> &fv, EB eb, EE ee, const std::vector<int32_t> *dpos) {
-    NaturalTri<T> N;
-    N.nslice = (int32_t)((n + ILU_SLICE - 1) / ILU_SLICE);
-    const size_t np = (size_t)N.nslice * ILU_SLICE;
-    N.plen.assign(np, 0);
-    N.sbase.assign((size_t)N.nslice, 0);
-    N.piv.assign(dpos ? np : 0, sone<T>());
-    int64_t slots = 0;
-    for (int32_t s = 0; s < N.nslice; ++s) {
-        const int64_t r0 = (int64_t)s * ILU_SLICE, r1 = std::min<int64_t>(r0 + ILU_SLICE, n);
-        int32_t width = 0;
-        for (int64_t i = r0; i < r1; ++i) {
-            N.plen[(size_t)i] = ee((int32_t)i) - eb((int32_t)i);
-            if (dpos) N.piv[(size_t)i] = fv[(size_t)(*dpos)[(size_t)i]];
-            width = std::max(width, N.plen[(size_t)i]);
-        }
-        N.sbase[(size_t)s] = slots;
-        slots += (int64_t)width * ILU_SLICE;
-    }
-    N.col.assign((size_t)slots, 0);
-    N.val.assign((size_t)slots, szero<T>());
-    for (int64_t i = 0; i < n; ++i) {
-        const int32_t b = eb((int32_t)i);
-        const size_t d0 = (size_t)N.sbase[(size_t)(i / ILU_SLICE)] + (size_t)(i % ILU_SLICE);
-        for (int32_t e = 0; e < N.plen[(size_t)i]; ++e) {
-            N.col[d0 + (size_t)e * ILU_SLICE] = ci[(size_t)b + e]; N.val[d0 + (size_t)e * ILU_SLICE] = fv[(size_t)b + e];
-        }
-    }
-    return N;
-}
-
-template <class T, class EB, class EE>
-int build_tri_natural(IluTri &F, int32_t nlev, int64_t n, const std::vector<int32_t> &ci, const std::vector<T> &fv, EB eb, EE ee,
-                      const std::vector<int32_t> *dpos) {
-    const NaturalTri<T> N = layout_natural<T>(n, ci, fv, eb, ee, dpos);
-    F.nlev = nlev;                       // reported by sprs_ilu0_levels; the sweeps follow no level plan
-    F.nslice = N.nslice;
-    T *dval = nullptr, *dpiv = nullptr;
-    bool ok = upload(&F.plen, N.plen) && upload(&F.sbase, N.sbase) && upload(&F.col, N.col) && upload(&dval, N.val);
-    F.val = dval;
-    if (ok && dpos) { ok = upload(&dpiv, N.piv); F.piv = dpiv; }
-    return ok ? SPRS_OK : SPRS_ERR_HIP;
+        std::copy(rows.begin() + lvl_ptr[l], rows.begin() + lvl_ptr[l + 1], prow.begin() + (size_t)F.h_lvl_slice[l] * ILU_SLICE);
+    const TriHost<T> H = pack_tri<T>((int64_t)prow.size(), [&](size_t p) { return prow[p]; }, ci, fv, eb, ee, dpos);
+    if (!dev_upload(&F.lvl_slice, F.h_lvl_slice.data(), F.h_lvl_slice.size()) || !dev_upload(&F.prow, prow.data(), prow.size())) return SPRS_ERR_HIP;
+    return upload_tri<T>(F, (int64_t)prow.size(), H);
 }
 
 template <class T>
@@ -430,22 +319,12 @@ int ilu0_create(const sprs_csr *A, int sweeps, sprs_ilu0 **out, int64_t *row_out
     const int64_t n = A->nrows, nnz = A->nnz;
     SPRS_HIP_TRY(c, hipSetDevice(c->device));
     // the pattern on the host: its checks, the diagonal positions and both level rules
-    std::vector<int32_t> rp((size_t)n + 1, 0), ci((size_t)nnz);
-    SPRS_HIP_TRY(c, hipMemcpyAsync(rp.data(), A->row_ptr, sizeof(int32_t) * rp.size(), hipMemcpyDeviceToHost, c->stream));
-    if (nnz) SPRS_HIP_TRY(c, hipMemcpyAsync(ci.data(), A->col_idx, sizeof(int32_t) * ci.size(), hipMemcpyDeviceToHost, c->stream));
-    SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (int64_t i = 0; i < n; ++i)
-        for (int32_t k = rp[i] + 1; k < rp[i + 1]; ++k)
-            if (ci[k] <= ci[k - 1]) {
-                snprintf(c->err, sizeof(c->err), "sprs_ilu0: the column indices of row %lld are not strictly ascending", (long long)i);
-                return SPRS_INVALID_ARGUMENT;
-            }
+    std::vector<int32_t> rp, ci;
+    SPRS_TRY(host_pattern(A, "sprs_ilu0", rp, ci));
     std::vector<int32_t> dpos((size_t)n, -1);
     for (int64_t i = 0; i < n; ++i) {
-        const int32_t *b = ci.data() + rp[i], *e = ci.data() + rp[i + 1];
-        const int32_t *d = std::lower_bound(b, e, (int32_t)i);
-        if (d == e || *d != (int32_t)i) { if (row_out) *row_out = i; return SPRS_ZERO_DIAGONAL; }
-        dpos[i] = (int32_t)(d - ci.data());
+        dpos[i] = (int32_t)diag_pos(rp.data(), ci.data(), i);
+        if (dpos[i] < 0) { if (row_out) *row_out = i; return SPRS_ZERO_DIAGONAL; }
     }
     std::vector<int32_t> level((size_t)n, 0), ulevel((size_t)n, 0);
     int32_t nlev = n ? 1 : 0, nulev = n ? 1 : 0;
@@ -477,8 +356,8 @@ int ilu0_create(const sprs_csr *A, int sweeps, sprs_ilu0 **out, int64_t *row_out
     P->fval = a;
     if (hipMalloc(&P->ybuf, sizeof(T) * ((size_t)n + 2)) != hipSuccess) return fail(SPRS_ERR_HIP);
     for (void *&b : P->sbuf) if (sweeps && hipMalloc(&b, sizeof(T) * ((size_t)n + 2)) != hipSuccess) return fail(SPRS_ERR_HIP);
-    if (!upload(&d_dpos, dpos) || !upload(&d_rows, lrows) || !upload(&d_lptr, lptr) || hipMalloc((void **)&d_bad, sizeof(int)) != hipSuccess)
-        return fail(SPRS_ERR_HIP);
+    if (!dev_upload(&d_dpos, dpos.data(), dpos.size()) || !dev_upload(&d_rows, lrows.data(), lrows.size()) ||
+        !dev_upload(&d_lptr, lptr.data(), lptr.size()) || hipMalloc((void **)&d_bad, sizeof(int)) != hipSuccess) return fail(SPRS_ERR_HIP);
     int bad = INT32_MAX;
     if ((nnz && hipMemcpyAsync(a, A->val, sizeof(T) * (size_t)nnz, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) ||
         hipMemcpyAsync(d_bad, &bad, sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess) return fail(SPRS_ERR_HIP);
@@ -500,12 +379,14 @@ int ilu0_create(const sprs_csr *A, int sweeps, sprs_ilu0 **out, int64_t *row_out
         return fail(SPRS_ERR_HIP);
     }
     if (bad != INT32_MAX) { if (row_out) *row_out = bad; return fail(SPRS_ZERO_DIAGONAL); }
-    // the level-major copies of both factors, or (a sweeps handle) the natural-order ones in their place
+    // the level-major copies of both factors, or (a sweeps handle) the natural-order ones in their place: position = row, and
+    // the level counts for sprs_ilu0_levels only
     auto lb = [&](int32_t i) { return rp[i]; }; auto le = [&](int32_t i) { return dpos[i]; };
     auto ub = [&](int32_t i) { return dpos[i] + 1; }; auto ue = [&](int32_t i) { return rp[i + 1]; };
-    int st = sweeps ? build_tri_natural<T>(P->L, nlev, n, ci, fv, lb, le, nullptr) : build_tri<T>(P->L, lptr, lrows, ci, fv, lb, le, nullptr);
-    if (st == SPRS_OK)
-        st = sweeps ? build_tri_natural<T>(P->U, nulev, n, ci, fv, ub, ue, &dpos) : build_tri<T>(P->U, uptr, urows, ci, fv, ub, ue, &dpos);
+    auto natural = [](size_t p) { return (int32_t)p; };
+    P->L.nlev = nlev; P->U.nlev = nulev;
+    int st = sweeps ? upload_tri<T>(P->L, n, pack_tri<T>(n, natural, ci, fv, lb, le, nullptr)) : build_tri<T>(P->L, lptr, lrows, ci, fv, lb, le, nullptr);
+    if (st == SPRS_OK) st = sweeps ? upload_tri<T>(P->U, n, pack_tri<T>(n, natural, ci, fv, ub, ue, &dpos)) : build_tri<T>(P->U, uptr, urows, ci, fv, ub, ue, &dpos);
     if (st != SPRS_OK) return fail(st);
     for (void *p : {(void *)d_dpos, (void *)d_rows, (void *)d_lptr, (void *)d_bad}) (void)hipFree(p);
     *out = P;
@@ -516,28 +397,14 @@ template <class T>
 int ilu0_solve_host(const sprs_ilu0 *Pc, int which, const T *in, size_t in_len, T *out, size_t out_len) {
     if (!Pc || !in || !out || Pc->dtype != dtype_of<T>::value || which < 0 || which > 2) return SPRS_INVALID_ARGUMENT;
     if (in_len != (size_t)Pc->n || out_len != (size_t)Pc->n) return SPRS_DIM_MISMATCH;
-    sprs_ilu0 *P = const_cast<sprs_ilu0 *>(Pc);
-    sprs_ctx *c = P->ctx;
-    CtxLock lock(c);   // in_tmp / out_tmp are per-handle staging
-    SPRS_HIP_TRY(c, hipSetDevice(c->device));
-    if (!P->in_tmp) SPRS_HIP_TRY(c, hipMalloc(&P->in_tmp, sizeof(T) * ((size_t)P->n + 2)));
-    if (!P->out_tmp) SPRS_HIP_TRY(c, hipMalloc(&P->out_tmp, sizeof(T) * ((size_t)P->n + 2)));
-    SPRS_HIP_TRY(c, hipMemcpyAsync(P->in_tmp, in, sizeof(T) * in_len, hipMemcpyHostToDevice, c->stream));
-    SPRS_TRY(ilu0_apply<T>(P, which, (const T *)P->in_tmp, (T *)P->out_tmp));
-    SPRS_HIP_TRY(c, hipMemcpyAsync(out, P->out_tmp, sizeof(T) * out_len, hipMemcpyDeviceToHost, c->stream));
-    SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return SPRS_OK;
+    return staged_apply<T>(Pc, in, out, [&](const T *din, T *dout) { return ilu0_apply<T>(Pc, which, din, dout); });
 }
 
 }  // namespace
 
 namespace sprs {
 
-int ilu0_check(const sprs_ilu0 *P, const sprs_csr *A, int dtype, size_t n) {
-    if (!P || !A || P->dtype != dtype || P->ctx != A->ctx || A->dist) return SPRS_INVALID_ARGUMENT;
-    if ((size_t)P->n != n) return SPRS_DIM_MISMATCH;
-    return SPRS_OK;
-}
+int ilu0_check(const sprs_ilu0 *P, const sprs_csr *A, int dtype, size_t n) { return applied_check(P, A, dtype, n); }
 
 template <class T>
 int ilu0_apply(const sprs_ilu0 *P, int which, const T *in, T *out) {

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -392,9 +394,85 @@ template <class T> int norm2_host(sprs_ctx *c, size_t n, const T *x, Real<T> *ou
 // reduce `P` partials of T (or of double when T_is_real_partials) with the library's fixed order; blocking
 template <class T> int reduce_partials_host(sprs_ctx *c, const T *part, int P, T *out, sprs_comm *comm = nullptr);
 
+// ---- what the set-ups and host entry points of the preconditioner handles share (capi.hip's sprs_diag, ilu0.hip, amg.hip, gs.hip)
+// hipMalloc'd copy of a host array (two elements more than it holds: an empty one still owns an allocation)
+template <class U>
+bool dev_upload(U **dst, const U *src, size_t count) {
+    if (hipMalloc((void **)dst, sizeof(U) * (count + 2)) != hipSuccess) return false;
+    return count == 0 || hipMemcpy(*dst, src, sizeof(U) * count, hipMemcpyHostToDevice) == hipSuccess;
+}
+
+// A's pattern (and, where val_host is given, its nnz values) on the host, with the check that every row's columns ascend
+// strictly: SPRS_INVALID_ARGUMENT and a text that starts with `who`.  The caller holds the context's lock and has set the device.
+inline int host_pattern(const sprs_csr *A, const char *who, std::vector<int32_t> &rp, std::vector<int32_t> &ci, void *val_host = nullptr) {
+    sprs_ctx *c = A->ctx;
+    rp.assign((size_t)A->nrows + 1, 0); ci.resize((size_t)A->nnz);
+    SPRS_HIP_TRY(c, hipMemcpyAsync(rp.data(), A->row_ptr, sizeof(int32_t) * rp.size(), hipMemcpyDeviceToHost, c->stream));
+    if (A->nnz) SPRS_HIP_TRY(c, hipMemcpyAsync(ci.data(), A->col_idx, sizeof(int32_t) * ci.size(), hipMemcpyDeviceToHost, c->stream));
+    if (A->nnz && val_host) SPRS_HIP_TRY(c, hipMemcpyAsync(val_host, A->val, dtype_size(A->dtype) * (size_t)A->nnz, hipMemcpyDeviceToHost, c->stream));
+    SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int64_t i = 0; i < A->nrows; ++i)
+        for (int32_t k = rp[i] + 1; k < rp[i + 1]; ++k)
+            if (ci[k] <= ci[k - 1]) {
+                snprintf(c->err, sizeof(c->err), "%s: the column indices of row %lld are not strictly ascending", who, (long long)i);
+                return SPRS_INVALID_ARGUMENT;
+            }
+    return SPRS_OK;
+}
+
+// position of the diagonal entry of row i in ci (columns strictly ascending), or -1
+inline int64_t diag_pos(const int32_t *rp, const int32_t *ci, int64_t i) {
+    const int32_t *b = ci + rp[i], *e = ci + rp[i + 1], *d = std::lower_bound(b, e, (int32_t)i);
+    return d != e && *d == (int32_t)i ? d - ci : -1;
+}
+
+// a pivot nobody may divide by: exactly zero, or not finite
+template <class T> SPRS_HD bool bad_pivot(T u) {
+    using std::isfinite;
+    const Real<T> re = sre(u), im = sim(u);
+    return !isfinite(re) || !isfinite(im) || (re == Real<T>(0) && im == Real<T>(0));
+}
+
+// rows in level order (ascending inside a level) and the levels' extents
+inline void group_by_level(const std::vector<int32_t> &level, int32_t nlev, std::vector<int32_t> &lvl_ptr, std::vector<int32_t> &rows) {
+    const size_t n = level.size();
+    lvl_ptr.assign((size_t)nlev + 1, 0);
+    for (size_t i = 0; i < n; ++i) lvl_ptr[(size_t)level[i] + 1]++;
+    for (int32_t l = 0; l < nlev; ++l) lvl_ptr[l + 1] += lvl_ptr[l];
+    std::vector<int32_t> fill(lvl_ptr.begin(), lvl_ptr.end() - 1);
+    rows.resize(n);
+    for (size_t i = 0; i < n; ++i) rows[(size_t)fill[level[i]]++] = (int32_t)i;
+}
+
+// The host entry point of a handle H with {ctx, n, in_tmp, out_tmp}: `in` to the handle's staging vector, apply(in_tmp, out_tmp) on
+// the stream, the result back to `out`; blocking.  The caller has checked its arguments (n elements each way).
+template <class T, class H, class F>
+int staged_apply(const H *Pc, const T *in, T *out, F &&apply) {
+    H *P = const_cast<H *>(Pc);
+    sprs_ctx *c = P->ctx;
+    const size_t n = (size_t)P->n;
+    CtxLock lock(c);   // in_tmp / out_tmp are per-handle staging
+    SPRS_HIP_TRY(c, hipSetDevice(c->device));
+    if (!P->in_tmp) SPRS_HIP_TRY(c, hipMalloc(&P->in_tmp, sizeof(T) * (n + 2)));
+    if (!P->out_tmp) SPRS_HIP_TRY(c, hipMalloc(&P->out_tmp, sizeof(T) * (n + 2)));
+    SPRS_HIP_TRY(c, hipMemcpyAsync(P->in_tmp, in, sizeof(T) * n, hipMemcpyHostToDevice, c->stream));
+    SPRS_TRY(apply((const T *)P->in_tmp, (T *)P->out_tmp));
+    SPRS_HIP_TRY(c, hipMemcpyAsync(out, P->out_tmp, sizeof(T) * n, hipMemcpyDeviceToHost, c->stream));
+    SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SPRS_OK;
+}
+
+// What the solvers ask of an applied handle H with {ctx, dtype, n} before they use it: SPRS_INVALID_ARGUMENT unless P has the scalar
+// type `dtype` and lives on A's context and A is on one GPU, SPRS_DIM_MISMATCH unless it has n rows.
+template <class H>
+int applied_check(const H *P, const sprs_csr *A, int dtype, size_t n) {
+    if (!P || !A || P->dtype != dtype || P->ctx != A->ctx || A->dist) return SPRS_INVALID_ARGUMENT;
+    if ((size_t)P->n != n) return SPRS_DIM_MISMATCH;
+    return SPRS_OK;
+}
+
 // ---- ilu0.hip
-// The solvers' view of an ILU(0) handle.  ilu0_check: SPRS_INVALID_ARGUMENT unless P has the scalar type `dtype` and lives on A's
-// context and A is on one GPU, SPRS_DIM_MISMATCH unless it has n rows.  ilu0_apply: out = U^-1 L^-1 in (which = 0), L^-1 in (1) or
+// The solvers' view of an ILU(0) handle.  ilu0_check: applied_check.  ilu0_apply: out = U^-1 L^-1 in (which = 0), L^-1 in (1) or
 // U^-1 in (2) on device vectors, asynchronous on the context's stream; in == out is allowed.
 int ilu0_check(const sprs_ilu0 *P, const sprs_csr *A, int dtype, size_t n);
 template <class T> int ilu0_apply(const sprs_ilu0 *P, int which, const T *in, T *out);

@@ -3,6 +3,7 @@ tests/_ilu_sweeps_ref.py: the three solves BIT FOR BIT (host arrays, device vect
 the library's own exact handle, and CG / GMRES preconditioned by k = 3 sweeps with the comparisons, tolerances and margins of
 tests/test_gpu_ilu.py.  The checker's counts (tests/test_ilu_sweeps_cpu.py) stand behind every max_iter: twice the count."""
 import ctypes as C
+import functools
 import os
 import sys
 
@@ -104,6 +105,68 @@ def test_larger_grid_128_workgroups(sa):
     out = np.zeros(n)
     P.mul_vec(rhs, out)
     assert np.array_equal(bits(out), bits(want))
+
+
+# ------------------------------------------------------------------------------------------------ 3b. padded slots are skipped
+PROBE_N = 130                                                # two full slices of 64 rows and two rows
+PROBE_SEED = 20
+
+
+@functools.lru_cache(maxsize=None)
+def padding_probe(dtname):
+    """A 130-row system whose rows have 0 .. 9 off-diagonal entries (so every slice is padded) under a dominant diagonal, columns
+    ascending, and column 0 stored by rows 0, 5 and 70 only; a vector that is finite except for inf in entry 0; and the
+    checkers' solves of it.  Rows take their columns from their own residue class modulo 5, so the inf reaches rows of the
+    class of 0, 5 and 70 alone and four rows in five stay finite whatever PROBE_SEED draws.  A padded slot (column 0, value
+    zero) that were multiplied would read entry 0 and turn such a row into NaN.
+    -> ip, ix, data, v, the checker's factors, {(sweeps, which): checker's result}"""
+    dt = np.dtype(dtname)
+    rng = np.random.default_rng(PROBE_SEED)
+    n = PROBE_N
+    rows = []
+    for i in range(n):
+        cand = [j for j in range(1, n) if j % 5 == i % 5 and j != i]
+        cols = set(rng.choice(cand, size=(i + i // 10) % 10, replace=False).tolist()) | {i}
+        if i in (5, 70):
+            cols.add(0)
+        rows.append(sorted(cols))
+    assert sorted({len(r) - 1 - (i in (5, 70)) for i, r in enumerate(rows)}) == list(range(10))
+    ip = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
+    ix = np.concatenate(rows).astype(np.int32)
+    assert [i for i in range(n) if 0 in rows[i]] == [0, 5, 70]
+    data = rng.uniform(-1, 1, ix.size) + (1j * rng.uniform(-1, 1, ix.size) if dt.kind == "c" else 0)
+    data[ix == np.repeat(np.arange(n), np.diff(ip))] = 16.0
+    data = data.astype(dt)
+    v = (rng.uniform(-1, 1, n) + (1j * rng.uniform(-1, 1, n) if dt.kind == "c" else 0)).astype(dt)
+    v[0] = np.inf
+    f = ref.ilu0(ip, ix, data)
+    assert f.status == ref.OK
+    with np.errstate(all="ignore"):
+        want = {(k, which): (Sweeps(ip, ix, f.val, k) if k else ref.Applier(ip, ix, f.val)).solve(which, v) for k in (0, 2) for which in (1, 2)}
+    return ip, ix, data, v, f.val, want
+
+
+@pytest.mark.parametrize("dt", [F64, C32], ids=_ids)
+def test_padded_slots_are_skipped_not_multiplied(sa, dt):
+    ip, ix, data, v, f, want = padding_probe(np.dtype(dt).name)
+    n = PROBE_N
+    A = sa.HipCsr.new((n, n), ip, ix, data)
+    for k in (0, 2):                                                              # the exact solves, then two sweeps
+        P = sa.ILU0.new(A, sweeps=k)
+        assert np.array_equal(bits(P.factors()), bits(f))
+        for which in (1, 2):
+            w = want[k, which]
+            finite = np.isfinite(w)
+            print("%s sweeps %d which %d: the checker leaves %d of %d entries finite" % (np.dtype(dt).name, k, which, finite.sum(), n))
+            assert 2 * finite.sum() >= n                                          # (else the comparison below would say little)
+            out = np.zeros(n, dt)
+            _applies(P)[which](v, out)                                            # host entry point
+            d_v = sa.DevVec.from_numpy(v)
+            _applies(P)[which](d_v, d_v)                                          # in place on the device: entry 0 of `out` is inf from the start
+            for got, how in ((out, "host"), (d_v.to_numpy(), "in place")):
+                assert np.array_equal(bits(got[finite]), bits(w[finite])), (k, which, how)
+                assert not np.any(np.isfinite(got[~finite])), (k, which, how)
+        P.close()
 
 
 # ------------------------------------------------------------------------------------------------ 4. CG + sweeps
