@@ -105,6 +105,13 @@ int sprs_version(void);
  *                   rotation, p, x, convergence test) is not launched — the next SpMV multiplies by the un-normalised vector
  *                   scaled in its gathers and the element-wise work rides with the next iteration's second kernel: two launches
  *                   instead of three, fewer vector passes, bit-identical
+ *   "bicg_k5"       BiCGStab where "spmv_fuse" applies: the last update of an iteration (x, r' = s - w t, |r'|^2, r0.r') walks the
+ *                   chains as the SpMV before it did, with s in its windows.  1 = that SpMV (t = A s) keeps its two dots and stores
+ *                   nothing, the update folds t again for its own rows (the same bits); 2 = t is stored and loaded as before, the update
+ *                   walks the chains all the same (the two agree bit for bit); 0 = the update is the vector kernel.  With 1 and 2 the
+ *                   update's two dots are grouped by the chain walk: scalars and x differ from 0's in summation order only.
+ *                   -1 automatic = 1 while "spmv_fuse" is automatic too, 0 once "spmv_fuse" has been set (1 there means the flow
+ *                   that is bit-identical to 0) (per solve)
  *   "p2p_allreduce" distributed solves: the scalar hand-offs go through peer-to-peer mailboxes (no stream operation) instead of
  *                   ncclAllReduce: -1 / 1 wherever the communicator has them (sprs_comm_p2p), 0 = RCCL
  *                   (communicator creation: 0 sets none up; per solve)
@@ -976,6 +983,9 @@ int sprs_solver_get_profile(const void *solver, int kind, double *spmv_ms_total,
  * update p = (v (-beta w) + p beta) + r inside, K4 with K3's r -= alpha v inside (bicg_stab.rs:155-156,172).  Zero for the other
  * solvers (CG among them) and wherever the five-launch iteration ran. */
 int sprs_solver_get_fused_launches(const void *solver, int kind, int64_t *k2_fused, int64_t *k4_fused);
+/* How many launches of the last solve were BiCGStab's last update walking the chains (ctx knob "bicg_k5" 1 or 2).  They are not SpMV
+ * launches: sprs_solver_get_profile neither times nor counts them.  Zero for the other solvers and with "bicg_k5" 0. */
+int sprs_solver_get_chain_k5_launches(const void *solver, int kind, int64_t *launches);
 
 #ifdef __cplusplus
 }

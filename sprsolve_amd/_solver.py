@@ -59,7 +59,9 @@ class _SolverBase:
         check(_lib.lib().sprs_solver_get_fused_launches(self.h, self.KIND, C.byref(k2), C.byref(k4)), self.A.ctx.h)
         st = C.c_int64(); do = C.c_int64(); t2 = C.c_int64(); t4 = C.c_int64()
         check(_lib.lib().sprs_solver_get_profile_counts(self.h, self.KIND, C.byref(st), C.byref(do), C.byref(t2), C.byref(t4)), self.A.ctx.h)
-        return dict(spmv_ms_total=ms.value, spmv_launches=n.value, solve_ms=tot.value, fused_k2=k2.value, fused_k4=k4.value,
+        k5 = C.c_int64()
+        check(_lib.lib().sprs_solver_get_chain_k5_launches(self.h, self.KIND, C.byref(k5)), self.A.ctx.h)
+        return dict(spmv_ms_total=ms.value, spmv_launches=n.value, solve_ms=tot.value, fused_k2=k2.value, fused_k4=k4.value, chain_k5=k5.value,
                     steps=st.value, timed_dot_other=do.value, timed_fused_k2=t2.value, timed_fused_k4=t4.value)
 
     # ---- the call itself

@@ -126,9 +126,10 @@ struct BicgK3 {
 
 // ---- spmv_chain.hip: the chain SpMV with the preceding vector update formed on the fly (f64, no preconditioner, single GPU)
 // K3 into K4 (bicg_stab.rs:163-178):  alpha from partB (pro's prologue) ; s = r + v * (-alpha), formed on the fly and — s_out ==
-//   nullptr — not stored (the pair2 walk of the blocks outside the chains honours a non-null s_out) ; t = A s ; partials of t.t and t.s
+//   nullptr — not stored (the pair2 walk of the blocks outside the chains honours a non-null s_out) ; t = A s ; partials of t.t and t.s.
+//   store_t = false: t is not stored either (the same launch with the y store compiled out: K5 on the chains folds t again)
 int launch_chain_k4f(const sprs_csr *A, const SpmvRoute &rt, const BicgK3<double, double, false> &pro, const double *r, const double *v, double *s_out,
-                     double *t, double *partTT, double *partTR, const int *status);
+                     double *t, double *partTT, double *partTR, const int *status, bool store_t = true);
 // K1 into K2 (bicg_stab.rs:123-163):  norm / convergence / restart / beta (pro's prologue) ; p' = (v * (-beta w) + p * beta) + r -> p_out ;
 //   v' = A p' -> v_out ; partials of r0.v'
 int launch_chain_k2f(const sprs_csr *A, const SpmvRoute &rt, const BicgK1<double, double, false> &pro, const double *v_old, const double *p, const double *r,
@@ -203,5 +204,10 @@ struct BicgK5 {
         if (fin.counter) finalize_last_block<Real<T>, T>(fin, true, smD, smT);
     }
 };
+
+// K5 on the chains (bicgstab.hip, knob "bicg_k5"; spmv_chain.hip UPD): pro's prologue and epilogue, s = pro.r + pro.sv (-alpha) staged in
+//   the windows, t = A s folded again for the workgroup's rows (recompute) or loaded from pro.t, x updated in place, r' = s - w t -> r_out
+//   (not pro.r: other workgroups still read its windows) ; one partial of |r'|^2 and of r0.r' per workgroup of the SpMV grid
+int launch_chain_k5(const sprs_csr *A, const SpmvRoute &rt, const BicgK5<double, false, true> &pro, double *r_out, bool recompute);
 
 }  // namespace sprs

@@ -47,6 +47,16 @@ int BicgStab<T>::run(const Prec<T, V> &M, const T *rhs, T *x, size_t max_iter, R
     if constexpr (std::is_same<T, double>::value && std::is_same<V, double>::value)
         fuse = !pc && c->spmv_fuse != 0 && route.kernel == SpmvKernel::Chain;
     T *palt = fuse ? this->vec(5) : nullptr;
+    // ---- K5 on the chains (knob "bicg_k5", only where the fused input runs): K5 walks the chains as K4 did, with s in its windows, so
+    // t = A s need not travel through memory: K4 keeps its two dots and stores nothing, K5 folds t again for its own rows — K4's bits
+    // (1) — or, to pin that flow bit for bit, loads the t that K4 stored (2).  Its two dots are grouped by the chain walk, one partial per
+    // workgroup of the SpMV grid, so the scalars differ from the vector kernel's K5 (0) in summation order.  r' cannot be written over r
+    // (other workgroups still read r's windows): r alternates with the last work vector, as p does with palt.
+    // Automatic (-1) selects it only while "spmv_fuse" is automatic too: a caller who sets spmv_fuse = 1 asks for the flow that is
+    // bit-identical to spmv_fuse = 0, and that is flavour 0.
+    const int k5_knob = c->bicg_k5 >= 0 ? c->bicg_k5 : (c->spmv_fuse < 0 ? BICG_K5_DEFAULT : 0);
+    const int k5_chain = fuse ? k5_knob : 0;
+    T *ralt = k5_chain ? this->vec(6) : nullptr;
     int pend_k1 = -1, pend_k3 = -1;          // fused: the mode / breakdown flag of the update that the next SpMV forms
     bool s_pending = false;                  // fused: K4 formed s without storing it (K5 forms it again)
 
@@ -116,7 +126,7 @@ int BicgStab<T>::run(const Prec<T, V> &M, const T *rhs, T *x, size_t max_iter, R
             if (fuse && pend_k3 >= 0) {
                 const BicgK3<double, double, false> k3{d_state, qB.p, qB.P, pend_k3, v, r, nullptr, nullptr, 0.0};
                 pend_k3 = -1;
-                SPRS_TRY(this->profiled([&]() -> int { return launch_chain_k4f(this->A, route, k3, r, v, nullptr, t, partTT, partTR, d_status); }, true));
+                SPRS_TRY(this->profiled([&]() -> int { return launch_chain_k4f(this->A, route, k3, r, v, nullptr, t, partTT, partTR, d_status, k5_chain != 1); }, true));
                 this->stats.fused_k4 += 1;
                 this->mark_step(4);
                 s_pending = true;            // s was formed on the fly and not stored: K5 forms it again from r and v
@@ -127,6 +137,16 @@ int BicgStab<T>::run(const Prec<T, V> &M, const T *rhs, T *x, size_t max_iter, R
         return this->handoff(1, GS, partTT, &qTT, partTR, &qTR);
     };
     auto K5 = [&]() -> int {
+        if constexpr (std::is_same<T, double>::value && std::is_same<V, double>::value) {
+            if (k5_chain && s_pending) {     // (not an SpMV launch for the profile: neither timed nor counted as one)
+                const BicgK5<double, false, true> k5{d_state, qTT.p, qTR.p, qTT.P, y, nullptr, t, r0, x, r, partN, partRho, Fin{}, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0, v};
+                SPRS_TRY(launch_chain_k5(this->A, route, k5, ralt, k5_chain == 1));
+                this->stats.chain_k5 += 1;
+                s_pending = false;
+                std::swap(r, ralt);          // r' lives in the other buffer
+                return this->handoff(3, GS, partN, &qN, partRho, &qRho);
+            }
+        }
         const Fin f = this->fin_for(3, partN, partRho, G);
         auto k5 = [&](auto pc_tag, auto sv_tag) {
             constexpr bool PC = decltype(pc_tag)::value, SV = decltype(sv_tag)::value;
@@ -189,6 +209,7 @@ int BicgStab<T>::run(const Prec<T, V> &M, const T *rhs, T *x, size_t max_iter, R
                     // ... but the host rotated the buffers once for each of them as it enqueued: an odd number of idle iterations
                     // leaves every pair of names exchanged against what the last EXECUTED launches wrote
                     std::swap(p, palt); y = p; std::swap(v, t);
+                    if (k5_chain) std::swap(r, ralt);
                 }
                 SPRS_TRY(this->spmv(x, r, 0, nullptr, nullptr, nullptr, nullptr));  // :134
                 SPRS_TRY((launch_axpy<T, T>(c, n, sneg(sone<T>()), rhs, r)));       // :137

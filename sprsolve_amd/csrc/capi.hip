@@ -116,6 +116,7 @@ int sprs_ctx_set(sprs_ctx *c, const char *key, int64_t value) {
     else if (k == "spmv_tile") c->spmv_tile = value < 0 ? -1 : (value ? 1 : 0);
     else if (k == "spmv_chain") c->spmv_chain = value < 0 ? -1 : (value ? 1 : 0);
     else if (k == "spmv_fuse") c->spmv_fuse = value < 0 ? -1 : (value ? 1 : 0);
+    else if (k == "bicg_k5") { if (value > 2) return SPRS_INVALID_ARGUMENT; c->bicg_k5 = value < 0 ? -1 : (int)value; }
     else if (k == "p2p_allreduce") c->p2p_allreduce = value < 0 ? -1 : (value ? 1 : 0);
     else if (k == "p2p_timeout_ms") c->p2p_timeout_ms = value < 1 ? 1 : value;
     else if (k == "ew_chunk") c->ew_chunk = value < 0 ? -1 : (value ? 1 : 0);
@@ -143,6 +144,7 @@ int64_t sprs_ctx_get(const sprs_ctx *c, const char *key) {
     if (k == "spmv_tile") return c->spmv_tile;
     if (k == "spmv_chain") return c->spmv_chain;
     if (k == "spmv_fuse") return c->spmv_fuse;
+    if (k == "bicg_k5") return c->bicg_k5;
     if (k == "p2p_allreduce") return c->p2p_allreduce;
     if (k == "p2p_timeout_ms") return c->p2p_timeout_ms;
     if (k == "ew_chunk") return c->ew_chunk;
@@ -937,6 +939,13 @@ int sprs_solver_get_fused_launches(const void *solver, int kind, int64_t *k2_fus
     return with_base(const_cast<void *>(solver), kind, [&](auto *b) {
         if (k2_fused) *k2_fused = b->stats.fused_k2;
         if (k4_fused) *k4_fused = b->stats.fused_k4;
+        return (int)SPRS_OK;
+    });
+}
+
+int sprs_solver_get_chain_k5_launches(const void *solver, int kind, int64_t *launches) {
+    return with_base(const_cast<void *>(solver), kind, [&](auto *b) {
+        if (launches) *launches = b->stats.chain_k5;
         return (int)SPRS_OK;
     });
 }

@@ -21,6 +21,7 @@ namespace sprs {
 constexpr int BLOCK = 256;     // threads per workgroup (4 wavefronts of 64)
 constexpr uint32_t UNI2 = 0x40000000u;  // 128-row block descriptors (spmv_dict.hip), rb bit 30: every row has the SAME code sequence
 constexpr uint32_t SEAM2 = 0x20000000u; // ... bit 29 (with UNI2, full 128-row blocks): all rows but one or two; rb's low bits then describe those (spmv_dict.hip)
+constexpr int BICG_K5_DEFAULT = 1;   // what knob "bicg_k5" = -1 selects (bicgstab.hip).  1: + 5.9-6.3 % iterations/s at cfg 5 against 0, same box (profiles/k5_chain.md)
 constexpr int MAX_GRID = 4096; // upper bound of the streaming-kernel grid (= max partials per reduction)
 
 // device-side status word of a running solve
@@ -82,6 +83,7 @@ struct sprs_ctx {
     int spmv_tile = -1;    // f64 compressed streams: LDS x-window tiles for the near columns of uniform stencil runs (spmv_tile_kernel, spmv_tile_off_kernel): -1 automatic = vectors of 44 MiB and more (tile_wanted), 1 = every matrix that has such runs, 0 = off.  Read at creation; 0 also at launch
     int spmv_chain = -1;   // f64 pair codes, 3-D stencils: plane-streaming chains (spmv_chain_kernel): -1 automatic = wherever the tile plan is wanted and the chains fill the chip, 1 = wherever chains exist, 0 = off.  Read at creation; 0 also at launch
     int spmv_fuse = -1;    // BiCGStab (f64, no preconditioner, one GPU) on a handle whose SpMV runs through chains: K3 formed inside K4 and K1 inside K2 (bicgstab.hip, "fused SpMV input"); 0 = off.  Read per solve
+    int bicg_k5 = -1;      // ... and there BiCGStab's last update K5 walks the chains too (bicgstab.hip, "K5 on the chains"): 1 = K4 stores no t, K5 folds it again; 2 = K4 stores t, K5 loads it (the same walk: pins 1 bit for bit); 0 = the vector kernel; -1 automatic (BICG_K5_DEFAULT while spmv_fuse is -1 too, else 0).  Read per solve
     int ew_chunk = -1;     // fused recurrence kernels walk one contiguous eighth of the vectors per XCD: -1 automatic (fused_chunked), 0 / 1
     int stream_nt = -1;    // fused recurrence kernels access their vectors with non-temporal loads / stores: -1 auto (by vector size), 0 / 1
     int spmv_uniform = -1; // ... and blocks whose rows all repeat one code sequence read neither codes nor row_ptr; read at creation

@@ -60,6 +60,7 @@ struct SolverStats {
     double spmv_ms = 0.0, solve_ms = 0.0;
     int64_t spmv_launches = 0;
     int64_t fused_k2 = 0, fused_k4 = 0;   // of those (enqueued, profiled or not): chain launches that formed their input on the fly (K1 into K2 / K3 into K4)
+    int64_t chain_k5 = 0;                 // BiCGStab: launches of K5 on the chains (knob "bicg_k5"; not SpMV launches: neither timed nor counted above)
     // among the TIMED launches (spmv_launches): how many read a dot operand that is not their input vector, how many were fused K2 / K4
     int64_t timed_dot_other = 0, timed_fused_k2 = 0, timed_fused_k4 = 0;
     int64_t steps = 0;                    // SpMV-class steps of the solve, timed or not

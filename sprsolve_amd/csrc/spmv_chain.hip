@@ -32,8 +32,15 @@ constexpr int CH_WL = CH_ROWS + 2 * CH_W;         // 3072 doubles per window, th
 // structure — its prologue (the scalars of the recurrence and its convergence / restart / breakdown decisions, taken identically by
 // every workgroup from the same partials) runs at the top of this launch, the update itself while a window is staged, with the
 // update's own rounding sequence; the updated vector is written for the launch's own rows to `own` and never read back.
+// YST = false (K4 of BiCGStab's flow "bicg_k5" 1): y is not stored — the launch is its two dots.
+// UPD (bicgstab.hip, knob "bicg_k5"): BiCGStab's K5 on the chains.  FUSE == 2 with `pro` = BicgK5: its prologue (status, alpha, w from K4's
+// partials), s staged in the windows as K4 staged it, and per row pair the update of spmv_dict_dev.hpp's bicg_k5_row with t = A s
+// either folded again here — the same fold over the same window contents: K4's bits — (UPD 1) or loaded from where K4 stored it (UPD 2,
+// which skips the fold); x (pro.x) is updated in place, r' goes to `own`, the two sums to pro.partN / pro.partRho, one partial per
+// workgroup, and BicgK5's epilogue writes the state.  x, p, r0 (and t) of a 128-row block are requested while the block before it is
+// folded.
 struct NoPro { __device__ __forceinline__ bool prologue() { return true; } };
-template <int FUSE, class PRO, int DOT, bool UX, int UL, bool TRI>
+template <int FUSE, class PRO, int DOT, bool UX, int UL, bool TRI, bool YST = true, int UPD = 0>
 __global__ __launch_bounds__(BLOCK) void spmv_chain_kernel(const int4 *__restrict__ tiles, const int2 *__restrict__ segs, const int32_t *__restrict__ xstart,
                                                            const BlkDesc *__restrict__ desc, const TilePat pat,
                                                            int n_left, const int32_t *__restrict__ left_order,
@@ -46,7 +53,9 @@ __global__ __launch_bounds__(BLOCK) void spmv_chain_kernel(const int4 *__restric
                                                            double *__restrict__ own) {
     using T = double;
     constexpr int NV = FUSE == 0 ? 1 : FUSE;            // input vectors
-    static_assert(FUSE == 0 || (FUSE == 2 && DOT == 2 && UX) || (FUSE == 3 && DOT == 1 && !UX), "fused flavours: K3 into K4, K1 into K2");
+    static_assert(FUSE == 0 || (FUSE == 2 && DOT == 2 && UX && UPD == 0) || (FUSE == 3 && DOT == 1 && !UX) ||
+                  (FUSE == 2 && DOT == 0 && !UX && !YST && UPD != 0), "fused flavours: K3 into K4, K1 into K2, K5 on the chains");
+    static_assert((YST || FUSE == 2) && (UPD == 0 || FUSE == 2), "only BiCGStab's K4 / K5 drop the y store");
     constexpr int W = CH_W, WL = CH_WL;
     constexpr int NW = WL / 2 / BLOCK;                  // 16-byte window pieces per lane (6)
     constexpr int NQ = CH_B / NWAVE;                    // 128-row blocks per wavefront and tile (4)
@@ -64,9 +73,11 @@ __global__ __launch_bounds__(BLOCK) void spmv_chain_kernel(const int4 *__restric
     __syncthreads();
     if (run_state != ST_RUNNING) { fin_idle(fin, DOT == 2); return; }
     [[maybe_unused]] T c0 = 0.0, c1 = 0.0;              // coefficients of the fused update
+    [[maybe_unused]] T nw = 0.0;                        // UPD: -w
     if constexpr (FUSE != 0) {
         if (!pro.prologue()) return;                    // converged / restart requested / breakdown: the same decision in every workgroup
         if constexpr (FUSE == 2) c0 = pro.na; else { c0 = pro.a; c1 = pro.beta; }
+        if constexpr (UPD != 0) nw = pro.nw;
     }
     T d0 = 0.0, d1 = 0.0;
 
@@ -76,8 +87,9 @@ __global__ __launch_bounds__(BLOCK) void spmv_chain_kernel(const int4 *__restric
     const int sstep = gridDim.x >> 3;
     const int send = xstart[xcd + 1];
     // PF windows are in flight while a tile is folded: the register sets R[0 .. PF).  Two for the plain kernel and K3-in-K4; K1-in-K2
-    // holds three vectors per window and keeps one (a second set would spill).
-    constexpr int PF = FUSE == 3 ? 1 : 2;
+    // holds three vectors per window and keeps one (a second set would spill); K5 keeps one too (a second fits, 239-247 VGPRs, and
+    // measures the same: profiles/k5_chain.md §5).
+    constexpr int PF = (FUSE == 3 || UPD != 0) ? 1 : 2;
     struct WinRegs { u4v a[NW]; u4v b[NV >= 2 ? NW : 1]; u4v c[NV == 3 ? NW : 1]; };
     WinRegs R0;
     [[maybe_unused]] WinRegs R1;
@@ -148,6 +160,19 @@ __global__ __launch_bounds__(BLOCK) void spmv_chain_kernel(const int4 *__restric
                     __builtin_memcpy(&uu[q], &w4, 16);
                 }
             }
+            // UPD: x, p, r0 (and the stored t) of the lane's two rows in block q
+            struct UpdRegs { u4v x, p, q, t; };
+            [[maybe_unused]] UpdRegs ur[2];
+            [[maybe_unused]] auto upd_load = [&](int q, UpdRegs &U) {
+                if constexpr (UPD != 0) {
+                    const int g = ts + ((q * NWAVE + wv) << 7) + 2 * lane;
+                    U.x = __builtin_nontemporal_load(reinterpret_cast<const u4v *>(pro.x + g));
+                    U.p = __builtin_nontemporal_load(reinterpret_cast<const u4v *>(pro.y + g));
+                    U.q = __builtin_nontemporal_load(reinterpret_cast<const u4v *>(pro.r0 + g));
+                    if constexpr (UPD == 2) U.t = __builtin_nontemporal_load(reinterpret_cast<const u4v *>(pro.t + g));
+                }
+            };
+            upd_load(0, ur[0]);
             // operands of block q + 1 are read before block q is folded (the seam branch keeps the compiler from doing it)
             T opl[UL], oph[UL], ux0 = 0.0, ux1 = 0.0;
             auto read_ops = [&](int q) {
@@ -182,9 +207,13 @@ __global__ __launch_bounds__(BLOCK) void spmv_chain_kernel(const int4 *__restric
                 for (int t = 0; t < UL; ++t) { pl[t] = opl[t]; ph[t] = oph[t]; }
                 const T u0 = (DOT != 0 && !UX) ? uu[q].lo : ux0, u1 = (DOT != 0 && !UX) ? uu[q].hi : ux1;
                 [[maybe_unused]] const D2 mine{ux0, ux1};              // FUSE: the formed vector at the lane's own two rows
-                if (q + 1 < NQ) read_ops(q + 1);
+                if (q + 1 < NQ) { read_ops(q + 1); upd_load(q + 1, ur[(q + 1) & 1]); }
                 T acc0 = 0.0, acc1 = 0.0;
-                if (!seam) {
+                if constexpr (UPD == 2) {               // t as K4 stored it
+                    D2 tt;
+                    __builtin_memcpy(&tt, &ur[q & 1].t, 16);
+                    acc0 = tt.lo; acc1 = tt.hi;
+                } else if (!seam) {
 #pragma unroll
                     for (int t = 0; t < UL; ++t) {
                         acc0 = acc0 + pl[t] * pat.val[t];
@@ -221,10 +250,23 @@ __global__ __launch_bounds__(BLOCK) void spmv_chain_kernel(const int4 *__restric
                         }
                     }
                 }
-                const D2 yy{acc0, acc1};
-                u4v qv;
-                __builtin_memcpy(&qv, &yy, 16);
-                __builtin_nontemporal_store(qv, reinterpret_cast<u4v *>(y + (ts + ((q * NWAVE + wv) << 7) + 2 * lane)));
+                if constexpr (YST) {
+                    const D2 yy{acc0, acc1};
+                    u4v qv;
+                    __builtin_memcpy(&qv, &yy, 16);
+                    __builtin_nontemporal_store(qv, reinterpret_cast<u4v *>(y + (ts + ((q * NWAVE + wv) << 7) + 2 * lane)));
+                }
+                if constexpr (UPD != 0) {
+                    D2 xx, pp, qq, rr;
+                    __builtin_memcpy(&xx, &ur[q & 1].x, 16); __builtin_memcpy(&pp, &ur[q & 1].p, 16); __builtin_memcpy(&qq, &ur[q & 1].q, 16);
+                    bicg_k5_row(xx.lo, pp.lo, mine.lo, acc0, qq.lo, c0, nw, rr.lo, d0, d1);
+                    bicg_k5_row(xx.hi, pp.hi, mine.hi, acc1, qq.hi, c0, nw, rr.hi, d0, d1);
+                    const int g = ts + ((q * NWAVE + wv) << 7) + 2 * lane;
+                    u4v xo, ro;
+                    __builtin_memcpy(&xo, &xx, 16); __builtin_memcpy(&ro, &rr, 16);
+                    __builtin_nontemporal_store(xo, reinterpret_cast<u4v *>(pro.x + g));
+                    __builtin_nontemporal_store(ro, reinterpret_cast<u4v *>(own + g));
+                }
                 if constexpr (FUSE == 3) {          // (K3 in K4 stores nothing: K5 forms s again, bicg_fuse.hpp BicgK5<SV>)
                     u4v ov;
                     __builtin_memcpy(&ov, &mine, 16);
@@ -249,6 +291,15 @@ __global__ __launch_bounds__(BLOCK) void spmv_chain_kernel(const int4 *__restric
         for (int i = lane; i < CW2; i += WAVE) s_c[wv][i] = 0;                 // (wavefront-private slices: no barrier)
         if constexpr (FUSE == 0)
             pair2_walk<DOT, true>(n_left, 0, desc, left_order, row_ptr, code, XPlain{reinterpret_cast<const char *>(x)}, y, u, nrows, ncols, s_pair, s_c, d0, d1);
+        else if constexpr (UPD != 0)
+            pair2_walk<0, true, XFused<2>, false, BicgUpd<UPD>>(n_left, 0, desc, left_order, row_ptr, code,
+                                                                XFused<2>{reinterpret_cast<const char *>(x), reinterpret_cast<const char *>(in1), nullptr, c0, c1},
+                                                                nullptr, nullptr, nrows, ncols, s_pair, s_c, d0, d1, nullptr,
+                                                                BicgUpd<UPD>{pro.x, pro.y, pro.r0, pro.t, own, c0, nw});
+        else if constexpr (!YST)
+            pair2_walk<DOT, true, XFused<NV>, false>(n_left, 0, desc, left_order, row_ptr, code,
+                                                     XFused<NV>{reinterpret_cast<const char *>(x), reinterpret_cast<const char *>(in1), reinterpret_cast<const char *>(in2), c0, c1},
+                                                     nullptr, UX ? nullptr : u, nrows, ncols, s_pair, s_c, d0, d1, own);
         else
             pair2_walk<DOT, true, XFused<NV>>(n_left, 0, desc, left_order, row_ptr, code,
                                               XFused<NV>{reinterpret_cast<const char *>(x), reinterpret_cast<const char *>(in1), reinterpret_cast<const char *>(in2), c0, c1},
@@ -263,6 +314,10 @@ __global__ __launch_bounds__(BLOCK) void spmv_chain_kernel(const int4 *__restric
         if (tid == 0) st_partial(fin, part1 + blockIdx.x, d1);
     }
     if (DOT >= 1 && fin.counter) finalize_last_block<T, T>(fin, DOT == 2, red, red);
+    if constexpr (UPD != 0) {
+        pro.accN = d0; pro.accR = d1;
+        pro.epilogue();
+    }
 }
 
 }  // namespace
@@ -298,7 +353,7 @@ int launch_chain_pair(const sprs_csr *A, const SpmvRoute &r, const double *x, do
 
 
 int launch_chain_k4f(const sprs_csr *A, const SpmvRoute &rt, const BicgK3<double, double, false> &pro, const double *r, const double *v, double *s_out,
-                     double *t, double *partTT, double *partTR, const int *status) {
+                     double *t, double *partTT, double *partTR, const int *status, bool store_t) {
     sprs_ctx *c = A->ctx;
     const sprs_dict *D = A->dict;
     const sprs_chain_plan &CP = *rt.chain;
@@ -308,13 +363,39 @@ int launch_chain_k4f(const sprs_csr *A, const SpmvRoute &rt, const BicgK3<double
     TilePat tp;
     for (int k = 0; k < 8; ++k) { tp.off[k] = CP.off[k]; tp.val[k] = CP.val[k]; }
     typedef BicgK3<double, double, false> K3;
-#define SPRS_C4F(U, TR)                                                                                                 \
-    if (CP.ul == U && (CP.tri != 0) == TR)                                                                              \
-        SPRS_LAUNCH_SPMV(c, (spmv_chain_kernel<2, K3, 2, true, U, TR>), g, reinterpret_cast<const int4 *>(CP.tiles), reinterpret_cast<const int2 *>(CP.segs), \
+#define SPRS_C4L(U, TR, YST)                                                                                            \
+        SPRS_LAUNCH_SPMV(c, (spmv_chain_kernel<2, K3, 2, true, U, TR, YST>), g, reinterpret_cast<const int4 *>(CP.tiles), reinterpret_cast<const int2 *>(CP.segs), \
                          CP.xstart, wd, tp, CP.n_left, CP.left, A->row_ptr, D->pair_code, D->pair_off, pvd, r, t, (const double *)nullptr, partTT, partTR, status, \
-                         (int)A->nrows, (int)A->ncols, Fin{}, pro, v, (const double *)nullptr, s_out);
+                         (int)A->nrows, (int)A->ncols, Fin{}, pro, v, (const double *)nullptr, s_out)
+#define SPRS_C4F(U, TR)                                                                                                 \
+    if (CP.ul == U && (CP.tri != 0) == TR) { if (store_t) SPRS_C4L(U, TR, true); else SPRS_C4L(U, TR, false); }
     SPRS_CHAIN_SHAPES(SPRS_C4F)
 #undef SPRS_C4F
+#undef SPRS_C4L
+    SPRS_HIP_TRY(c, hipGetLastError());
+    return SPRS_OK;
+}
+
+int launch_chain_k5(const sprs_csr *A, const SpmvRoute &rt, const BicgK5<double, false, true> &pro, double *r_out, bool recompute) {
+    sprs_ctx *c = A->ctx;
+    const sprs_dict *D = A->dict;
+    const sprs_chain_plan &CP = *rt.chain;
+    const int g = rt.grid;
+    const BlkDesc *wd = rt.desc;
+    const double *pvd = reinterpret_cast<const double *>(D->pair_val);
+    TilePat tp;
+    for (int k = 0; k < 8; ++k) { tp.off[k] = CP.off[k]; tp.val[k] = CP.val[k]; }
+    typedef BicgK5<double, false, true> K5;
+    const int *status = &pro.S->status;
+#define SPRS_C5L(U, TR, UPD)                                                                                            \
+        SPRS_LAUNCH_SPMV(c, (spmv_chain_kernel<2, K5, 0, false, U, TR, false, UPD>), g, reinterpret_cast<const int4 *>(CP.tiles), reinterpret_cast<const int2 *>(CP.segs), \
+                         CP.xstart, wd, tp, CP.n_left, CP.left, A->row_ptr, D->pair_code, D->pair_off, pvd, (const double *)pro.r, (double *)nullptr, (const double *)nullptr, \
+                         (double *)nullptr, (double *)nullptr, status, (int)A->nrows, (int)A->ncols, Fin{}, pro, pro.sv, (const double *)nullptr, r_out)
+#define SPRS_C5F(U, TR)                                                                                                 \
+    if (CP.ul == U && (CP.tri != 0) == TR) { if (recompute) SPRS_C5L(U, TR, 1); else SPRS_C5L(U, TR, 2); }
+    SPRS_CHAIN_SHAPES(SPRS_C5F)
+#undef SPRS_C5F
+#undef SPRS_C5L
     SPRS_HIP_TRY(c, hipGetLastError());
     return SPRS_OK;
 }

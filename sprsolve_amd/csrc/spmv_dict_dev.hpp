@@ -333,6 +333,28 @@ struct XFused {
     }
 };
 
+// BiCGStab's last update (K5, bicg_fuse.hpp BicgK5) carried by a walk over row pairs whose t = A s the walk has just folded
+// (bicgstab.hip, knob "bicg_k5"): MODE 1 takes t from the fold, MODE 2 loads it from `t` (what K4 stored); both run BicgK5::run's
+// arithmetic in its order for the lane's rows, write x in place and r' = s + t (-w) to `rout` (never over r: other workgroups
+// still read r's windows), and add the rows' terms of |r'|^2 and r0.r' to the lane's two running sums.  NoUpd: a plain SpMV.
+struct NoUpd { static constexpr int MODE = 0; };
+template <int M>
+struct BicgUpd {
+    static constexpr int MODE = M;
+    double *x; const double *p, *r0, *t; double *rout;
+    double na, nw;                 // -alpha, -w
+};
+// one row: x += p (-alpha) + s (-w) ; r' = s + t (-w) ; accN += r'^2 ; accR += r0 r'  (bicg_stab.rs:188-196)
+__device__ __forceinline__ void bicg_k5_row(double &x, double p, double s, double t, double q, double na, double nw, double &rr,
+                                            double &accN, double &accR) {
+    double xx = x + p * na;
+    xx = xx + s * nw;
+    x = xx;
+    rr = s + t * nw;
+    accN = accN + rr * rr;
+    accR = accR + q * rr;
+}
+
 // FULL uniform block of the two-rows-per-lane kernels (every lane has both rows — the interior of a stencil): no row
 // masks, and no clamp either: the second row's column r0 + 1 + off is valid, so the 16-byte load at r0 + off stays
 // inside x.  Offset and value of a slot are wave-uniform: made scalars, the gather is SGPR base + lane offset and the
@@ -440,6 +462,7 @@ struct Blk2Loads {
     int a, b;                // row_ptr[i0], row_ptr[i0 + 1], i0 = min(ra + 2 lane, rb - 1)
     double u0, u1;           // dot operands of the lane's two rows
     double o0, o1;           // XFused: the formed vector at the lane's two rows (stored by the walk)
+    D2 kx, kp, kq, kt;       // BicgUpd: x, p, r0 (and the stored t) at the lane's two rows
     u4v wc;                  // 16 code bytes
     int di;                  // ... and the b128 slot they go to
 };
@@ -452,14 +475,17 @@ struct Blk2Loads {
 // YNT: y is written with non-temporal stores (HBM-sized vectors: the result is not read again before it has been evicted)
 // XS: where x comes from (XPlain: memory; XFused: formed on the fly).  With XFused the walk also STORES the formed vector for the
 // rows it owns (`own`, unless null), and where `u` is null the dot operand is that vector (K4's t.s).
-template <int DOT, bool YNT, class XS = XPlain>
+// YST: y is stored (false: the launch wants the dots, or the update below, only).  UP: BicgUpd — the walk applies BiCGStab's last
+// update to the rows it owns and adds to d0 / d1 that update's two sums (DOT must be 0 then).
+template <int DOT, bool YNT, class XS = XPlain, bool YST = true, class UP = NoUpd>
 __device__ __forceinline__ void pair2_walk(int n_wide, int xcd_chunk, const BlkDesc *__restrict__ desc,
                                            const int32_t *__restrict__ order, const int32_t *__restrict__ row_ptr,
                                            const uint8_t *__restrict__ code, const XS xs,
                                            double *__restrict__ y, const double *__restrict__ u, int nrows, int ncols,
                                            const PairEnt<double> *s_pair, uint32_t (*s_c)[CW2], double &d0, double &d1,
-                                           double *__restrict__ own = nullptr) {
+                                           double *__restrict__ own = nullptr, const UP up = UP{}) {
     using T = double;
+    static_assert(UP::MODE == 0 || (XS::FUSED && DOT == 0 && !YST), "the update needs s from the walk and owns both running sums");
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint8_t *cb = reinterpret_cast<const uint8_t *>(s_c[wv]);
@@ -519,6 +545,16 @@ __device__ __forceinline__ void pair2_walk(int n_wide, int xcd_chunk, const BlkD
             L.o1 = oo.hi;
             if (DOT != 0 && u_is_x) { L.u0 = L.o0; L.u1 = L.o1; }
         }
+        if constexpr (UP::MODE != 0) {                                          // (a lane's only row at the matrix end: the pairs' second halves)
+            const int p0 = min(r0, nrows - 2);
+            const bool odd = r0 != p0;
+            auto pair_at = [&](const double *b) {
+                const D2 w = *reinterpret_cast<const D2 *>(reinterpret_cast<const char *>(b) + (uint32_t)p0 * 8u);
+                return D2{odd ? w.hi : w.lo, w.hi};
+            };
+            L.kx = pair_at(up.x); L.kp = pair_at(up.p); L.kq = pair_at(up.r0);
+            if constexpr (UP::MODE == 2) L.kt = pair_at(up.t);
+        }
         const int shift = L.pa & 3;
         const int nq = L.uni ? 1 : max((shift + L.nn + 15) >> 4, 1);            // 16-byte pieces covering the codes, <= 65 (uniform: the first row's only)
         L.di = min(lane, nq - 1);
@@ -532,10 +568,12 @@ __device__ __forceinline__ void pair2_walk(int n_wide, int xcd_chunk, const BlkD
     int c_seam1 = 0, c_seam2 = 0;
     T c_u0 = 0.0, c_u1 = 0.0;
     [[maybe_unused]] T c_o0 = 0.0, c_o1 = 0.0;
+    [[maybe_unused]] D2 c_kx{0.0, 0.0}, c_kp{0.0, 0.0}, c_kq{0.0, 0.0}, c_kt{0.0, 0.0};
     auto stage = [&](const Blk2Loads &L) {
         const int shift = L.pa & 3;
         c_uni = L.uni;
         if constexpr (XS::FUSED) { c_o0 = L.o0; c_o1 = L.o1; }
+        if constexpr (UP::MODE != 0) { c_kx = L.kx; c_kp = L.kp; c_kq = L.kq; if constexpr (UP::MODE == 2) c_kt = L.kt; }
         if (L.uni) {
             // every lane holds the same 16 bytes [pa - shift, pa - shift + 16): the pattern starts `shift` bytes in
             const uint64_t lo = (uint64_t)__builtin_amdgcn_readfirstlane(L.wc.x) | ((uint64_t)__builtin_amdgcn_readfirstlane(L.wc.y) << 32);
@@ -664,20 +702,33 @@ __device__ __forceinline__ void pair2_walk(int n_wide, int xcd_chunk, const BlkD
         }
         }
         if (r0 + 1 < c_rb) {
-            if constexpr (YNT) {
+            if constexpr (YST && YNT) {
                 const D2 yy{acc0, acc1};
                 u4v q;
                 __builtin_memcpy(&q, &yy, 16);
                 __builtin_nontemporal_store(q, reinterpret_cast<u4v *>(reinterpret_cast<char *>(y) + r8));
-            } else {
+            } else if constexpr (YST) {
                 *reinterpret_cast<D2 *>(reinterpret_cast<char *>(y) + r8) = D2{acc0, acc1};
             }
             if (DOT == 1) { d0 = d0 + c_u0 * acc0; d0 = d0 + c_u1 * acc1; }
             if (DOT == 2) { d0 = d0 + acc0 * acc0; d1 = d1 + acc0 * c_u0; d0 = d0 + acc1 * acc1; d1 = d1 + acc1 * c_u1; }
             if constexpr (XS::FUSED) { if (own != nullptr) *reinterpret_cast<D2 *>(reinterpret_cast<char *>(own) + r8) = D2{c_o0, c_o1}; }
+            if constexpr (UP::MODE != 0) {
+                D2 xx = c_kx, rr;
+                bicg_k5_row(xx.lo, c_kp.lo, c_o0, UP::MODE == 2 ? c_kt.lo : acc0, c_kq.lo, up.na, up.nw, rr.lo, d0, d1);
+                bicg_k5_row(xx.hi, c_kp.hi, c_o1, UP::MODE == 2 ? c_kt.hi : acc1, c_kq.hi, up.na, up.nw, rr.hi, d0, d1);
+                *reinterpret_cast<D2 *>(reinterpret_cast<char *>(up.x) + r8) = xx;
+                *reinterpret_cast<D2 *>(reinterpret_cast<char *>(up.rout) + r8) = rr;
+            }
         } else if (r0 < c_rb) {
             if constexpr (XS::FUSED) { if (own != nullptr) *reinterpret_cast<T *>(reinterpret_cast<char *>(own) + r8) = c_o0; }
-            *reinterpret_cast<T *>(reinterpret_cast<char *>(y) + r8) = acc0;
+            if constexpr (YST) *reinterpret_cast<T *>(reinterpret_cast<char *>(y) + r8) = acc0;
+            if constexpr (UP::MODE != 0) {
+                T xx = c_kx.lo, rr;
+                bicg_k5_row(xx, c_kp.lo, c_o0, UP::MODE == 2 ? c_kt.lo : acc0, c_kq.lo, up.na, up.nw, rr, d0, d1);
+                *reinterpret_cast<T *>(reinterpret_cast<char *>(up.x) + r8) = xx;
+                *reinterpret_cast<T *>(reinterpret_cast<char *>(up.rout) + r8) = rr;
+            }
             if (DOT == 1) d0 = d0 + c_u0 * acc0;
             if (DOT == 2) { d0 = d0 + acc0 * acc0; d1 = d1 + acc0 * c_u0; }
         }
