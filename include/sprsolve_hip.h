@@ -893,6 +893,90 @@ int sprs_amg_minres_solve_dev_z(sprs_minres *S, const sprs_amg *P, const sprs_c6
 int sprs_amg_minres_solve_dev_s(sprs_minres *S, const sprs_amg *P, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
 int sprs_amg_minres_solve_dev_c(sprs_minres *S, const sprs_amg *P, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
 
+/* ---------------------------------------------------------------- factorised sparse approximate inverse (FSAI) preconditioner
+ * M = G^H G, G sparse lower triangular on a pattern fixed up front, for a square single-GPU CSR handle of any of the four
+ * scalar types that is Hermitian positive definite.  The reference has no such preconditioner.  Applying M is two ordinary
+ * SpMVs, so there are no dependent launches and no levels; M is Hermitian positive definite by construction, so CG and MINRES
+ * never end in SPRS_INVALID_PRECOND with it.  The handle owns everything it derives and borrows nothing from A after creation.
+ * A is TAKEN as Hermitian: only stored entries a(r, c) with c <= r are ever read, and nothing checks the upper triangle.
+ * create(A, power):  SPRS_NOT_SQUARE;  SPRS_INVALID_ARGUMENT (text in sprs_last_error) for a distributed A, power other than
+ * 1 or 2, a row whose column indices are not strictly ascending, and a row of G above the cap (below).  *row_out is -1 unless
+ * stated.  Every scalar operation is in the handle's scalar type and rounded once, complex products are (ac - bd, ad + bc),
+ * sqrt and / are correctly rounded, nothing is fused.
+ * 1. Pattern.  P = pattern(A) for power 1; for power 2 the structural pattern of A A: row i is the union of the patterns of
+ *    the rows k of A over the stored columns k of row i (an entry that cancels to zero stays).  Row i of G has the columns
+ *    J_i = { j in P_i : j <= i }, ascending: j_0 < ... < j_{m-1}.  If i is not in J_i, or a(i, i) is not stored:
+ *    SPRS_ZERO_DIAGONAL with *row_out = the smallest such row.  Else if m > SPRS_FSAI_MAX_ROW: SPRS_INVALID_ARGUMENT, and
+ *    sprs_last_error names the smallest such row and its length; nothing is truncated.
+ * 2. The local matrix.  For q <= p: s_pq = a(j_p, j_q), read from row j_p of A, +0 where that entry is not stored; the
+ *    diagonal takes re(a(j_p, j_p)) only.
+ * 3. Cholesky S = C C^H, column q = 0 .. m - 1:
+ *        d = re(s_qq);  for k = 0 .. q - 1 ascending:  d = d - (re(c_qk)*re(c_qk) + im(c_qk)*im(c_qk))   [real: d - c_qk*c_qk]
+ *        d not finite or d <= 0:  A is not positive definite on this pattern: SPRS_INVALID_PRECOND, *row_out = the smallest
+ *        such row i (SPRS_ZERO_DIAGONAL wins where both occur);   c_qq = sqrt(d), real
+ *        for p > q:  t = s_pq;  for k = 0 .. q - 1 ascending:  t = t - c_pk*conj(c_qk);   c_pq = t / c_qq, component-wise
+ * 4. The row of G (the conjugate of C^-H e_last):
+ *        g_{m-1} = 1 / c_{m-1,m-1};  for p = m - 2 .. 0:  acc = +0;  for q = m - 1 down to p + 1:  acc = acc + c_qp*g_q
+ *        (no conjugate);  g_p = (-acc) / c_pp, component-wise;   G(i, j_p) = g_p.
+ *    Every element's updates come in a fixed order, so any loop nest and lane mapping gives the same bits.  diag(G A G^H) = 1
+ *    up to rounding; where J_i is the whole lower triangle, G^H G = A^-1.
+ * 5. Application.  out = GH (G in): two SpMVs on two ordinary handles, G (adopting the arrays built on the device) and
+ *    GH = sprs_csr_adjoint(G, 1), each with whatever stream format its creation found; the result has the bits of the
+ *    SpMV's row fold on every route.  The handle owns the intermediate vector, so calls on one context serialise; the _dev
+ *    form is asynchronous on the context's stream; in == out is allowed.  Host slices of the wrong length: SPRS_DIM_MISMATCH.
+ * Steps 2 to 4 run on the device in one pass over the rows, binned by length (csrc/fsai.hip).
+ * sprs_fsai_info: rows, nnz(G), the longest row of G and the power; any pointer may be NULL.  sprs_fsai_factor: a BORROWED
+ * handle, which = 0: G, 1: GH (another value is SPRS_INVALID_ARGUMENT); it lives as long as P and is not destroyed by the
+ * caller; sprs_csr_read, sprs_csr_stream_format and sprs_mul_vec_* take it like any handle.
+ * Solvers: as for ILU(0) (same errors); z = P r, z = P v_j and u = P u of the recurrences are one application. */
+#define SPRS_FSAI_MAX_ROW 64
+typedef struct sprs_fsai sprs_fsai;
+int sprs_fsai_create(const sprs_csr *A, int power, sprs_fsai **out, int64_t *row_out);   /* row_out may be NULL */
+int sprs_fsai_destroy(sprs_fsai *P);           /* NULL is a no-op */
+int sprs_fsai_info(const sprs_fsai *P, int64_t *n, int64_t *nnz_g, int64_t *max_row, int64_t *power);
+int sprs_fsai_factor(const sprs_fsai *P, int which, const sprs_csr **out);
+int sprs_fsai_mul_vec_dev_d(const sprs_fsai *P, const double *in_dev, double *out_dev);
+int sprs_fsai_mul_vec_dev_z(const sprs_fsai *P, const sprs_c64 *in_dev, sprs_c64 *out_dev);
+int sprs_fsai_mul_vec_dev_s(const sprs_fsai *P, const float *in_dev, float *out_dev);
+int sprs_fsai_mul_vec_dev_c(const sprs_fsai *P, const sprs_c32 *in_dev, sprs_c32 *out_dev);
+int sprs_fsai_mul_vec_d(const sprs_fsai *P, const double *in_host, size_t in_len, double *out_host, size_t out_len);
+int sprs_fsai_mul_vec_z(const sprs_fsai *P, const sprs_c64 *in_host, size_t in_len, sprs_c64 *out_host, size_t out_len);
+int sprs_fsai_mul_vec_s(const sprs_fsai *P, const float *in_host, size_t in_len, float *out_host, size_t out_len);
+int sprs_fsai_mul_vec_c(const sprs_fsai *P, const sprs_c32 *in_host, size_t in_len, sprs_c32 *out_host, size_t out_len);
+/* CG, GMRES, BiCGStab and MINRES preconditioned by FSAI: as sprs_ilu0_*_solve_* with P = one application */
+int sprs_fsai_cg_solve_d(sprs_cg *S, const sprs_fsai *P, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_fsai_cg_solve_z(sprs_cg *S, const sprs_fsai *P, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_fsai_cg_solve_s(sprs_cg *S, const sprs_fsai *P, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_fsai_cg_solve_c(sprs_cg *S, const sprs_fsai *P, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_fsai_cg_solve_dev_d(sprs_cg *S, const sprs_fsai *P, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_fsai_cg_solve_dev_z(sprs_cg *S, const sprs_fsai *P, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_fsai_cg_solve_dev_s(sprs_cg *S, const sprs_fsai *P, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_fsai_cg_solve_dev_c(sprs_cg *S, const sprs_fsai *P, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_fsai_gmres_solve_d(sprs_gmres *S, const sprs_fsai *P, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_fsai_gmres_solve_z(sprs_gmres *S, const sprs_fsai *P, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_fsai_gmres_solve_s(sprs_gmres *S, const sprs_fsai *P, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_fsai_gmres_solve_c(sprs_gmres *S, const sprs_fsai *P, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_fsai_gmres_solve_dev_d(sprs_gmres *S, const sprs_fsai *P, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_fsai_gmres_solve_dev_z(sprs_gmres *S, const sprs_fsai *P, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_fsai_gmres_solve_dev_s(sprs_gmres *S, const sprs_fsai *P, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_fsai_gmres_solve_dev_c(sprs_gmres *S, const sprs_fsai *P, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_fsai_bicgstab_solve_d(sprs_bicgstab *S, const sprs_fsai *P, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_fsai_bicgstab_solve_z(sprs_bicgstab *S, const sprs_fsai *P, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_fsai_bicgstab_solve_s(sprs_bicgstab *S, const sprs_fsai *P, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_fsai_bicgstab_solve_c(sprs_bicgstab *S, const sprs_fsai *P, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_fsai_bicgstab_solve_dev_d(sprs_bicgstab *S, const sprs_fsai *P, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_fsai_bicgstab_solve_dev_z(sprs_bicgstab *S, const sprs_fsai *P, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_fsai_bicgstab_solve_dev_s(sprs_bicgstab *S, const sprs_fsai *P, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_fsai_bicgstab_solve_dev_c(sprs_bicgstab *S, const sprs_fsai *P, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_fsai_minres_solve_d(sprs_minres *S, const sprs_fsai *P, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_fsai_minres_solve_z(sprs_minres *S, const sprs_fsai *P, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_fsai_minres_solve_s(sprs_minres *S, const sprs_fsai *P, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_fsai_minres_solve_c(sprs_minres *S, const sprs_fsai *P, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_fsai_minres_solve_dev_d(sprs_minres *S, const sprs_fsai *P, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_fsai_minres_solve_dev_z(sprs_minres *S, const sprs_fsai *P, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_fsai_minres_solve_dev_s(sprs_minres *S, const sprs_fsai *P, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_fsai_minres_solve_dev_c(sprs_minres *S, const sprs_fsai *P, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+
 /* ---------------------------------------------------------------- multi-GPU (one process per GPU)
  * No reference analogue: the reference is single-process (rayon).  The matrix is row-partitioned;
  * rank r owns rows [r0, r1) and the matching slices of every vector.  A distributed operator is the

@@ -13,6 +13,7 @@ from .cg_many import CGMany  # noqa: F401
 from .cs_minres import CSMinRes  # noqa: F401
 from .gauss_seidel import GaussSeidel  # noqa: F401
 from .gmres import GMRES  # noqa: F401
+from .fsai import FSAI  # noqa: F401
 from .ilu import ILU0  # noqa: F401
 from .lsmr import LSMR  # noqa: F401
 from .device import Context, DevVec, default_ctx  # noqa: F401

@@ -118,8 +118,10 @@ def _protos():
         P["sprs_ilu0_solve_" + s] = [_vp, _int, _vp, _sz, _vp, _sz]
         P["sprs_amg_mul_vec_dev_" + s] = [_vp, _vp, _vp]
         P["sprs_amg_mul_vec_" + s] = [_vp, _vp, _sz, _vp, _sz]
+        P["sprs_fsai_mul_vec_dev_" + s] = [_vp, _vp, _vp]
+        P["sprs_fsai_mul_vec_" + s] = [_vp, _vp, _sz, _vp, _sz]
         for k in ("cg", "gmres", "bicgstab", "minres"):
-            for pc in ("ilu0", "amg"):
+            for pc in ("ilu0", "amg", "fsai"):
                 P["sprs_%s_%s_solve_%s" % (pc, k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
                 P["sprs_%s_%s_solve_dev_%s" % (pc, k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
     for s in ("d", "z"):          # mixed-precision refinement: H = f64 / c64 over L = f32 / c32; every real scalar is a double
@@ -171,6 +173,10 @@ def _protos():
     P["sprs_amg_info"] = [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]
     P["sprs_amg_level_info"] = [_vp, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), _pd]
     P["sprs_amg_level_read"] = [_vp, _i64, _int, _vp, _vp, _vp, _vp]
+    P["sprs_fsai_create"] = [_vp, _int, _pp, C.POINTER(_i64)]
+    P["sprs_fsai_destroy"] = [_vp]
+    P["sprs_fsai_info"] = [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]
+    P["sprs_fsai_factor"] = [_vp, _int, _pp]
     P["sprs_gauss_seidel_create"] = [_vp, _pp]
     P["sprs_gauss_seidel_destroy"] = [_vp]
     for s in ("d", "s"):

@@ -66,7 +66,7 @@ class _SolverBase:
 
     # ---- the call itself
     def _solve(self, precond, rhs, x, max_iter, tol, want_precond, prefix=None):
-        """prefix: None for a `DiagPrecond` (or no preconditioner); "ilu0" / "amg" for BiCGStab / MINRES / CG / GMRES with such a handle for the
+        """prefix: None for a `DiagPrecond` (or no preconditioner); "ilu0" / "amg" / "fsai" for BiCGStab / MINRES / CG / GMRES with such a handle for the
         preconditioner: the same call under the name sprs_<prefix>_<solver>_solve[_dev]_*."""
         L = _lib.lib()
         its = C.c_size_t(0); res = _lib.REAL[self.s](0.0)

@@ -2,6 +2,7 @@
 from . import _lib
 from ._solver import _SolverBase
 from .amg import AMG
+from .fsai import FSAI
 from .ilu import ILU0
 
 
@@ -16,9 +17,11 @@ class BiCGStab(_SolverBase):
         return self._solve(None, rhs, x, max_iter, tol, False)
 
     def precond_solve(self, precond, rhs, x, max_iter, tol):
-        """bicg_stab.rs:204-366 (right-preconditioned) by a `DiagPrecond` (Jacobi), an `ILU0` or an `AMG`."""
+        """bicg_stab.rs:204-366 (right-preconditioned) by a `DiagPrecond` (Jacobi), an `ILU0`, an `AMG` or an `FSAI`."""
         if isinstance(precond, ILU0):
             return self._solve(precond, rhs, x, max_iter, tol, True, prefix="ilu0")
         if isinstance(precond, AMG):
             return self._solve(precond, rhs, x, max_iter, tol, True, prefix="amg")
+        if isinstance(precond, FSAI):
+            return self._solve(precond, rhs, x, max_iter, tol, True, prefix="fsai")
         return self._solve(precond, rhs, x, max_iter, tol, True)

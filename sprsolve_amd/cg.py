@@ -2,6 +2,7 @@
 from . import _lib
 from ._solver import _SolverBase
 from .amg import AMG
+from .fsai import FSAI
 from .ilu import ILU0
 
 
@@ -17,9 +18,11 @@ class CG(_SolverBase):
         return self._solve(None, rhs, x, max_iter, tol, False)
 
     def precond_solve(self, precond, rhs, x, max_iter, tol):
-        """Preconditioned by a `DiagPrecond` (Jacobi), an `ILU0` or an `AMG`; InvalidPreconditioner where conj(r).M^-1 r is not positive."""
+        """Preconditioned by a `DiagPrecond` (Jacobi), an `ILU0`, an `AMG` or an `FSAI`; InvalidPreconditioner where conj(r).M^-1 r is not positive."""
         if isinstance(precond, ILU0):
             return self._solve(precond, rhs, x, max_iter, tol, True, prefix="ilu0")
         if isinstance(precond, AMG):
             return self._solve(precond, rhs, x, max_iter, tol, True, prefix="amg")
+        if isinstance(precond, FSAI):
+            return self._solve(precond, rhs, x, max_iter, tol, True, prefix="fsai")
         return self._solve(precond, rhs, x, max_iter, tol, True)

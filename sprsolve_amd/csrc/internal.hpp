@@ -484,8 +484,13 @@ template <class T> int ilu0_apply(const sprs_ilu0 *P, int which, const T *in, T 
 int amg_check(const sprs_amg *P, const sprs_csr *A, int dtype, size_t n);
 template <class T> int amg_apply(const sprs_amg *P, const T *in, T *out);
 
+// ---- fsai.hip
+// The same for an FSAI handle: fsai_check as ilu0_check, fsai_apply: out = G^H (G in), two launch_spmv calls; in == out is allowed.
+int fsai_check(const sprs_fsai *P, const sprs_csr *A, int dtype, size_t n);
+template <class T> int fsai_apply(const sprs_fsai *P, const T *in, T *out);
+
 // ---- an applied preconditioner: a handle whose application is a chain of launches of its own (ILU(0)'s triangular solves,
-// AMG's cycle), asynchronous on the context's stream.  check: SPRS_INVALID_ARGUMENT for a null handle, another scalar type or
+// AMG's cycle, FSAI's two SpMVs), asynchronous on the context's stream.  check: SPRS_INVALID_ARGUMENT for a null handle, another scalar type or
 // context, or a distributed A; SPRS_DIM_MISMATCH for another size.  apply: out = M in on device vectors, in == out allowed.
 template <class T>
 struct AppliedPrec {
@@ -497,6 +502,7 @@ struct AppliedPrec {
 };
 template <class T> AppliedPrec<T> ilu0_prec(const sprs_ilu0 *P);   // the which = 0 solve
 template <class T> AppliedPrec<T> amg_prec(const sprs_amg *P);
+template <class T> AppliedPrec<T> fsai_prec(const sprs_fsai *P);
 
 // ---- what a solve is preconditioned with, from the C entry points down: nothing (a null sprs_diag), a diagonal (Jacobi) or
 // an applied handle (BiCGStab, MINRES, CG and GMRES; CSMINRES refuses any preconditioner and the batched CG takes a sprs_diag

@@ -2,6 +2,7 @@
 from . import _lib
 from ._solver import _SolverBase
 from .amg import AMG
+from .fsai import FSAI
 from .ilu import ILU0
 
 
@@ -29,9 +30,11 @@ class GMRES(_SolverBase):
         return self._solve(None, rhs, x, max_iter, tol, False)
 
     def precond_solve(self, precond, rhs, x, max_iter, tol):
-        """Preconditioned from the right by a `DiagPrecond` (Jacobi), an `ILU0` or an `AMG`: the residual it reports is the true one's estimate."""
+        """Preconditioned from the right by a `DiagPrecond` (Jacobi), an `ILU0`, an `AMG` or an `FSAI`: the residual it reports is the true one's estimate."""
         if isinstance(precond, ILU0):
             return self._solve(precond, rhs, x, max_iter, tol, True, prefix="ilu0")
         if isinstance(precond, AMG):
             return self._solve(precond, rhs, x, max_iter, tol, True, prefix="amg")
+        if isinstance(precond, FSAI):
+            return self._solve(precond, rhs, x, max_iter, tol, True, prefix="fsai")
         return self._solve(precond, rhs, x, max_iter, tol, True)

@@ -2,6 +2,7 @@
 from . import _lib
 from ._solver import _SolverBase
 from .amg import AMG
+from .fsai import FSAI
 from .ilu import ILU0
 
 
@@ -15,10 +16,12 @@ class MinRes(_SolverBase):
         return self._solve(None, rhs, x, max_iter, tol, False)
 
     def precond_solve(self, precond, rhs, x, max_iter, tol):
-        """minres.rs:178-341, by a `DiagPrecond` (Jacobi), an `ILU0` or an `AMG`; the preconditioner must be Hermitian positive
+        """minres.rs:178-341, by a `DiagPrecond` (Jacobi), an `ILU0`, an `AMG` or an `FSAI`; the preconditioner must be Hermitian positive
         definite (InvalidPreconditioner by the reference's rule, minres.rs:279-287)."""
         if isinstance(precond, ILU0):
             return self._solve(precond, rhs, x, max_iter, tol, True, prefix="ilu0")
         if isinstance(precond, AMG):
             return self._solve(precond, rhs, x, max_iter, tol, True, prefix="amg")
+        if isinstance(precond, FSAI):
+            return self._solve(precond, rhs, x, max_iter, tol, True, prefix="fsai")
         return self._solve(precond, rhs, x, max_iter, tol, True)
