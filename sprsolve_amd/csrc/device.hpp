@@ -143,6 +143,21 @@ __device__ __forceinline__ void finalize_last_block(const Fin &fin, bool two, TA
     if (threadIdx.x == 0) __hip_atomic_store(fin.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
 }
 
+// The tail of every SpMV kernel (DOT as in launch_spmv; d0 / d1: the thread's running sums): one partial per workgroup and dot,
+// then the finalize where the launch asks for one.  Called by all threads of every workgroup that did not leave idle.
+template <int DOT, class T>
+__device__ __forceinline__ void spmv_dot_epilogue(T d0, T d1, T *red, T *part0, T *part1, const Fin &fin) {
+    if (DOT >= 1) {
+        d0 = block_sum(d0, red);
+        if (threadIdx.x == 0) st_partial(fin, part0 + blockIdx.x, d0);
+    }
+    if (DOT == 2) {
+        d1 = block_sum(d1, red);
+        if (threadIdx.x == 0) st_partial(fin, part1 + blockIdx.x, d1);
+    }
+    if (DOT >= 1 && fin.counter) finalize_last_block<T, T>(fin, DOT == 2, red, red);
+}
+
 // ---- peer-to-peer hand-off (struct P2pBox, internal.hpp): posted by finalize_last_block, summed by the consumers' prologues
 // One 16-byte cell per reduced value (a real scalar: the value and a zero pad; a complex one: re, im — the layout of `red`).
 template <class TV> __device__ __forceinline__ void to_cell(TV v, unsigned int *w) {          // 4 words

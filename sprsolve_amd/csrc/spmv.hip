@@ -411,15 +411,7 @@ __global__ __launch_bounds__(BLOCK) void spmv_kernel(int n_rowblk, int xcd_chunk
         }
     }
     if (run_state != ST_RUNNING) { fin_idle(fin, DOT == 2); return; }           // a wavefront that had no row block comes straight here
-    if (DOT >= 1) {
-        d0 = block_sum(d0, red);
-        if (tid == 0) st_partial(fin, part0 + blockIdx.x, d0);
-    }
-    if (DOT == 2) {
-        d1 = block_sum(d1, red);
-        if (tid == 0) st_partial(fin, part1 + blockIdx.x, d1);
-    }
-    if (DOT >= 1 && fin.counter) finalize_last_block<T, T>(fin, DOT == 2, red, red);
+    spmv_dot_epilogue<DOT>(d0, d1, red, part0, part1, fin);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -535,15 +527,7 @@ __global__ __launch_bounds__(BLOCK) void spmv_wide_kernel(int n_rowblk, int xcd_
         }
     }
     if (run_state != ST_RUNNING) { fin_idle(fin, DOT == 2); return; }
-    if (DOT >= 1) {
-        d0 = block_sum(d0, red);
-        if (tid == 0) st_partial(fin, part0 + blockIdx.x, d0);
-    }
-    if (DOT == 2) {
-        d1 = block_sum(d1, red);
-        if (tid == 0) st_partial(fin, part1 + blockIdx.x, d1);
-    }
-    if (DOT >= 1 && fin.counter) finalize_last_block<T, T>(fin, DOT == 2, red, red);
+    spmv_dot_epilogue<DOT>(d0, d1, red, part0, part1, fin);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -9,9 +9,9 @@
 // windows.  No far load exists; every element of x crosses the vector L1 (T + 2W) / T = 1.5 times instead of 3.25, independent of
 // what survives in an L2; the loads of the window after next fly over the fold of the current tile.  A tile = CH_B consecutive
 // FULL uniform 128-row blocks (plain or seam, mark_uniform_kernel) of the matrix's most frequent pattern, which must be
-// far, near.., far with offsets -Pf .. +Pf, Pf even (build_chain_plan, spmv_dict.hip).  The fold per row is full_uniform_block's /
-// spmv_tile_kernel's — the same products in the same left-to-right order, seam rows under scalar tests — with every operand
-// taken from LDS: y bit-identical.  The 128-row blocks outside the chains (boundary planes, the blocks around boundary lines,
+// far, near.., far with offsets -Pf .. +Pf, Pf even (build_chain_plan, spmv_dict.hip).  The fold per row is pair_fold
+// (spmv_dict_dev.hpp), which spmv_tile_kernel calls too — the per-block kernel's products in the same left-to-right order, seam
+// rows under scalar tests — with every operand taken from LDS: y bit-identical.  The 128-row blocks outside the chains (boundary planes, the blocks around boundary lines,
 // remainders of runs) are walked by the same launch afterwards (pair2_walk), so a launch writes all of y and one dot partial per
 // workgroup.
 #include "spmv_dict_dev.hpp"
@@ -201,7 +201,6 @@ __global__ __launch_bounds__(BLOCK) void spmv_chain_kernel(const int4 *__restric
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
                 const uint32_t rbq = (uint32_t)__builtin_amdgcn_readfirstlane((int)rbc[q]);
-                const bool seam = (rbq & SEAM2) != 0;
                 T pl[UL], ph[UL];
 #pragma unroll
                 for (int t = 0; t < UL; ++t) { pl[t] = opl[t]; ph[t] = oph[t]; }
@@ -213,49 +212,10 @@ __global__ __launch_bounds__(BLOCK) void spmv_chain_kernel(const int4 *__restric
                     D2 tt;
                     __builtin_memcpy(&tt, &ur[q & 1].t, 16);
                     acc0 = tt.lo; acc1 = tt.hi;
-                } else if (!seam) {
-#pragma unroll
-                    for (int t = 0; t < UL; ++t) {
-                        acc0 = acc0 + pl[t] * pat.val[t];
-                        acc1 = acc1 + ph[t] * pat.val[t];
-                    }
                 } else {
-                    // (spmv_tile_kernel's seam fold) local rows k and k + 1 fold only the slots of their masks, with their own
-                    // value where they carry one
-                    const int seam1 = __builtin_amdgcn_readfirstlane(nnc[q]) >> 16, seam2 = (int)(rbq & 0x3ffffffu);
-                    const int kk = seam1 & 127, maskA = (seam1 >> 7) & 255, maskB = seam2 & 255;
-                    const bool a0 = 2 * lane == kk, a1 = 2 * lane + 1 == kk, b0s = 2 * lane == kk + 1, b1s = 2 * lane + 1 == kk + 1;
-                    if ((seam2 & 0x3000000) == 0) {
-#pragma unroll
-                        for (int t = 0; t < UL; ++t) {
-                            const bool am = ((maskA >> t) & 1) == 0, bm = ((maskB >> t) & 1) == 0;       // scalar
-                            const T n0 = acc0 + pl[t] * pat.val[t], n1 = acc1 + ph[t] * pat.val[t];
-                            if (!am && !bm) { acc0 = n0; acc1 = n1; }
-                            else {
-                                acc0 = ((am && a0) || (bm && b0s)) ? acc0 : n0;
-                                acc1 = ((am && a1) || (bm && b1s)) ? acc1 : n1;
-                            }
-                        }
-                    } else {
-                        const T valA = s_pair[(seam2 >> 8) & 255].val, valB = s_pair[(seam2 >> 16) & 255].val;
-                        const bool ovA = ((seam2 >> 24) & 1) != 0, ovB = ((seam2 >> 25) & 1) != 0;
-                        const int pm0 = a0 ? maskA : (b0s ? maskB : 255), pm1 = a1 ? maskA : (b1s ? maskB : 255);
-                        const bool o0 = (a0 && ovA) || (b0s && ovB), o1 = (a1 && ovA) || (b1s && ovB);
-                        const T v0 = a0 ? valA : valB, v1 = a1 ? valA : valB;
-#pragma unroll
-                        for (int t = 0; t < UL; ++t) {
-                            const T n0 = acc0 + pl[t] * (o0 ? v0 : pat.val[t]), n1 = acc1 + ph[t] * (o1 ? v1 : pat.val[t]);
-                            acc0 = ((pm0 >> t) & 1) ? n0 : acc0;
-                            acc1 = ((pm1 >> t) & 1) ? n1 : acc1;
-                        }
-                    }
+                    pair_fold<UL>(pl, ph, pat.val, rbq, nnc[q], s_pair, lane, acc0, acc1);
                 }
-                if constexpr (YST) {
-                    const D2 yy{acc0, acc1};
-                    u4v qv;
-                    __builtin_memcpy(&qv, &yy, 16);
-                    __builtin_nontemporal_store(qv, reinterpret_cast<u4v *>(y + (ts + ((q * NWAVE + wv) << 7) + 2 * lane)));
-                }
+                row_pair_out<DOT, YST>(y + (ts + ((q * NWAVE + wv) << 7) + 2 * lane), acc0, acc1, u0, u1, d0, d1);
                 if constexpr (UPD != 0) {
                     D2 xx, pp, qq, rr;
                     __builtin_memcpy(&xx, &ur[q & 1].x, 16); __builtin_memcpy(&pp, &ur[q & 1].p, 16); __builtin_memcpy(&qq, &ur[q & 1].q, 16);
@@ -272,8 +232,6 @@ __global__ __launch_bounds__(BLOCK) void spmv_chain_kernel(const int4 *__restric
                     __builtin_memcpy(&ov, &mine, 16);
                     __builtin_nontemporal_store(ov, reinterpret_cast<u4v *>(own + (ts + ((q * NWAVE + wv) << 7) + 2 * lane)));
                 }
-                if (DOT == 1) { d0 = d0 + u0 * acc0; d0 = d0 + u1 * acc1; }
-                if (DOT == 2) { d0 = d0 + acc0 * acc0; d1 = d1 + acc0 * u0; d0 = d0 + acc1 * acc1; d1 = d1 + acc1 * u1; }
             }
             __syncthreads();                            // the previous window's slot is free for the window after next
             ts_prev = ts;
@@ -305,15 +263,7 @@ __global__ __launch_bounds__(BLOCK) void spmv_chain_kernel(const int4 *__restric
                                               XFused<NV>{reinterpret_cast<const char *>(x), reinterpret_cast<const char *>(in1), reinterpret_cast<const char *>(in2), c0, c1},
                                               y, UX ? nullptr : u, nrows, ncols, s_pair, s_c, d0, d1, own);
     }
-    if (DOT >= 1) {
-        d0 = block_sum(d0, red);
-        if (tid == 0) st_partial(fin, part0 + blockIdx.x, d0);
-    }
-    if (DOT == 2) {
-        d1 = block_sum(d1, red);
-        if (tid == 0) st_partial(fin, part1 + blockIdx.x, d1);
-    }
-    if (DOT >= 1 && fin.counter) finalize_last_block<T, T>(fin, DOT == 2, red, red);
+    spmv_dot_epilogue<DOT>(d0, d1, red, part0, part1, fin);
     if constexpr (UPD != 0) {
         pro.accN = d0; pro.accR = d1;
         pro.epilogue();
@@ -324,102 +274,63 @@ __global__ __launch_bounds__(BLOCK) void spmv_chain_kernel(const int4 *__restric
 
 int chain_rows() { return CH_ROWS; }
 
-int launch_chain_pair(const sprs_csr *A, const SpmvRoute &r, const double *x, double *y, int dot_mode, const double *u,
-                      double *part0, double *part1, const int *status, const Fin &fin) {
+// One launch of the chain kernel: the plan's and the pair stream's arguments, which every flavour takes alike, then the flavour's.
+// kern(integral_constant UL, bool_constant TRI): the flavour's kernel for the plan's shape.
+template <class Kern, class PRO>
+int launch_chain(const sprs_csr *A, const SpmvRoute &rt, Kern kern, const double *x, double *y, const double *u, double *part0, double *part1,
+                 const int *status, const Fin &fin, const PRO &pro, const double *in1, const double *in2, double *own) {
     sprs_ctx *c = A->ctx;
     const sprs_dict *D = A->dict;
-    const sprs_chain_plan &CP = *r.chain;
-    const int g = r.grid;
-    const BlkDesc *wd = r.desc;
-    const double *pvd = reinterpret_cast<const double *>(D->pair_val);
-    TilePat tp;
-    for (int t = 0; t < 8; ++t) { tp.off[t] = CP.off[t]; tp.val[t] = CP.val[t]; }
-    const bool ux = dot_mode != 0 && u == x;
-#define SPRS_CSPMV(DM, UXV, U, TR) SPRS_LAUNCH_SPMV(c, (spmv_chain_kernel<0, NoPro, DM, UXV, U, TR>), g, reinterpret_cast<const int4 *>(CP.tiles), reinterpret_cast<const int2 *>(CP.segs), \
-                                                    CP.xstart, wd, tp, CP.n_left, CP.left, A->row_ptr, D->pair_code, D->pair_off, pvd, x, y, u, part0, part1, status,   \
-                                                    (int)A->nrows, (int)A->ncols, fin, NoPro{}, nullptr, nullptr, nullptr)
-#define SPRS_CSHAPE(U, TR)                                                                                           \
-    if (CP.ul == U && (CP.tri != 0) == TR) {                                                                         \
-        if (dot_mode == 0) SPRS_CSPMV(0, false, U, TR);                                                              \
-        else if (dot_mode == 1) { if (ux) SPRS_CSPMV(1, true, U, TR); else SPRS_CSPMV(1, false, U, TR); }            \
-        else if (ux) SPRS_CSPMV(2, true, U, TR); else SPRS_CSPMV(2, false, U, TR);                                   \
-    }
+    const sprs_chain_plan &CP = *rt.chain;
+    const TilePat tp = tile_pat(CP);
+#define SPRS_CSHAPE(U, TR)                                                                                                                 \
+    if (CP.ul == U && (CP.tri != 0) == TR)                                                                                                 \
+        SPRS_LAUNCH_SPMV(c, kern(std::integral_constant<int, U>{}, std::bool_constant<TR>{}), rt.grid, reinterpret_cast<const int4 *>(CP.tiles), \
+                         reinterpret_cast<const int2 *>(CP.segs), CP.xstart, rt.desc, tp, CP.n_left, CP.left, A->row_ptr, D->pair_code, D->pair_off, \
+                         reinterpret_cast<const double *>(D->pair_val), x, y, u, part0, part1, status, (int)A->nrows, (int)A->ncols, fin, pro, in1, in2, own);
     SPRS_CHAIN_SHAPES(SPRS_CSHAPE)
 #undef SPRS_CSHAPE
-#undef SPRS_CSPMV
     SPRS_HIP_TRY(c, hipGetLastError());
     return SPRS_OK;
 }
 
+int launch_chain_pair(const sprs_csr *A, const SpmvRoute &r, const double *x, double *y, int dot_mode, const double *u,
+                      double *part0, double *part1, const int *status, const Fin &fin) {
+    int rc = SPRS_OK;
+    // UX: the dot operand is the input vector; without a dot, one kernel
+    with_dot(dot_mode, u == x, [&](auto dm, auto ux) {
+        constexpr int DM = decltype(dm)::value;
+        constexpr bool UXV = DM != 0 && decltype(ux)::value;
+        rc = launch_chain(A, r, [](auto ul, auto tri) { return &spmv_chain_kernel<0, NoPro, DM, UXV, decltype(ul)::value, decltype(tri)::value>; },
+                          x, y, u, part0, part1, status, fin, NoPro{}, nullptr, nullptr, nullptr);
+    });
+    return rc;
+}
 
 int launch_chain_k4f(const sprs_csr *A, const SpmvRoute &rt, const BicgK3<double, double, false> &pro, const double *r, const double *v, double *s_out,
                      double *t, double *partTT, double *partTR, const int *status, bool store_t) {
-    sprs_ctx *c = A->ctx;
-    const sprs_dict *D = A->dict;
-    const sprs_chain_plan &CP = *rt.chain;
-    const int g = rt.grid;
-    const BlkDesc *wd = rt.desc;
-    const double *pvd = reinterpret_cast<const double *>(D->pair_val);
-    TilePat tp;
-    for (int k = 0; k < 8; ++k) { tp.off[k] = CP.off[k]; tp.val[k] = CP.val[k]; }
     typedef BicgK3<double, double, false> K3;
-#define SPRS_C4L(U, TR, YST)                                                                                            \
-        SPRS_LAUNCH_SPMV(c, (spmv_chain_kernel<2, K3, 2, true, U, TR, YST>), g, reinterpret_cast<const int4 *>(CP.tiles), reinterpret_cast<const int2 *>(CP.segs), \
-                         CP.xstart, wd, tp, CP.n_left, CP.left, A->row_ptr, D->pair_code, D->pair_off, pvd, r, t, (const double *)nullptr, partTT, partTR, status, \
-                         (int)A->nrows, (int)A->ncols, Fin{}, pro, v, (const double *)nullptr, s_out)
-#define SPRS_C4F(U, TR)                                                                                                 \
-    if (CP.ul == U && (CP.tri != 0) == TR) { if (store_t) SPRS_C4L(U, TR, true); else SPRS_C4L(U, TR, false); }
-    SPRS_CHAIN_SHAPES(SPRS_C4F)
-#undef SPRS_C4F
-#undef SPRS_C4L
-    SPRS_HIP_TRY(c, hipGetLastError());
-    return SPRS_OK;
+    auto go = [&](auto yst) {
+        return launch_chain(A, rt, [](auto ul, auto tri) { return &spmv_chain_kernel<2, K3, 2, true, decltype(ul)::value, decltype(tri)::value, decltype(yst)::value>; },
+                            r, t, nullptr, partTT, partTR, status, Fin{}, pro, v, nullptr, s_out);
+    };
+    return store_t ? go(std::true_type{}) : go(std::false_type{});
 }
 
 int launch_chain_k5(const sprs_csr *A, const SpmvRoute &rt, const BicgK5<double, false, true> &pro, double *r_out, bool recompute) {
-    sprs_ctx *c = A->ctx;
-    const sprs_dict *D = A->dict;
-    const sprs_chain_plan &CP = *rt.chain;
-    const int g = rt.grid;
-    const BlkDesc *wd = rt.desc;
-    const double *pvd = reinterpret_cast<const double *>(D->pair_val);
-    TilePat tp;
-    for (int k = 0; k < 8; ++k) { tp.off[k] = CP.off[k]; tp.val[k] = CP.val[k]; }
     typedef BicgK5<double, false, true> K5;
-    const int *status = &pro.S->status;
-#define SPRS_C5L(U, TR, UPD)                                                                                            \
-        SPRS_LAUNCH_SPMV(c, (spmv_chain_kernel<2, K5, 0, false, U, TR, false, UPD>), g, reinterpret_cast<const int4 *>(CP.tiles), reinterpret_cast<const int2 *>(CP.segs), \
-                         CP.xstart, wd, tp, CP.n_left, CP.left, A->row_ptr, D->pair_code, D->pair_off, pvd, (const double *)pro.r, (double *)nullptr, (const double *)nullptr, \
-                         (double *)nullptr, (double *)nullptr, status, (int)A->nrows, (int)A->ncols, Fin{}, pro, pro.sv, (const double *)nullptr, r_out)
-#define SPRS_C5F(U, TR)                                                                                                 \
-    if (CP.ul == U && (CP.tri != 0) == TR) { if (recompute) SPRS_C5L(U, TR, 1); else SPRS_C5L(U, TR, 2); }
-    SPRS_CHAIN_SHAPES(SPRS_C5F)
-#undef SPRS_C5F
-#undef SPRS_C5L
-    SPRS_HIP_TRY(c, hipGetLastError());
-    return SPRS_OK;
+    auto go = [&](auto upd) {
+        return launch_chain(A, rt, [](auto ul, auto tri) { return &spmv_chain_kernel<2, K5, 0, false, decltype(ul)::value, decltype(tri)::value, false, decltype(upd)::value>; },
+                            pro.r, nullptr, nullptr, nullptr, nullptr, &pro.S->status, Fin{}, pro, pro.sv, nullptr, r_out);
+    };
+    return recompute ? go(std::integral_constant<int, 1>{}) : go(std::integral_constant<int, 2>{});
 }
 
 int launch_chain_k2f(const sprs_csr *A, const SpmvRoute &rt, const BicgK1<double, double, false> &pro, const double *v_old, const double *p, const double *r,
                      double *p_out, double *v_out, const double *r0, double *partB, const int *status) {
-    sprs_ctx *c = A->ctx;
-    const sprs_dict *D = A->dict;
-    const sprs_chain_plan &CP = *rt.chain;
-    const int g = rt.grid;
-    const BlkDesc *wd = rt.desc;
-    const double *pvd = reinterpret_cast<const double *>(D->pair_val);
-    TilePat tp;
-    for (int k = 0; k < 8; ++k) { tp.off[k] = CP.off[k]; tp.val[k] = CP.val[k]; }
     typedef BicgK1<double, double, false> K1;
-#define SPRS_C2F(U, TR)                                                                                                 \
-    if (CP.ul == U && (CP.tri != 0) == TR)                                                                              \
-        SPRS_LAUNCH_SPMV(c, (spmv_chain_kernel<3, K1, 1, false, U, TR>), g, reinterpret_cast<const int4 *>(CP.tiles), reinterpret_cast<const int2 *>(CP.segs), \
-                         CP.xstart, wd, tp, CP.n_left, CP.left, A->row_ptr, D->pair_code, D->pair_off, pvd, v_old, v_out, r0, partB, (double *)nullptr, status, \
-                         (int)A->nrows, (int)A->ncols, Fin{}, pro, p, r, p_out);
-    SPRS_CHAIN_SHAPES(SPRS_C2F)
-#undef SPRS_C2F
-    SPRS_HIP_TRY(c, hipGetLastError());
-    return SPRS_OK;
+    return launch_chain(A, rt, [](auto ul, auto tri) { return &spmv_chain_kernel<3, K1, 1, false, decltype(ul)::value, decltype(tri)::value>; },
+                        v_old, v_out, r0, partB, nullptr, status, Fin{}, pro, p, r, p_out);
 }
 
 }  // namespace sprs

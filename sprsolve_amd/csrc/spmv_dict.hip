@@ -393,15 +393,7 @@ __global__ __launch_bounds__(BLOCK) void spmv_dict_kernel(int n_rowblk, int xcd_
     T d0 = szero<T>(), d1 = szero<T>();
     dict_walk<T, DOT, CONJX, PAIR, WV>(n_rowblk, xcd_chunk, desc, order, row_ptr, code, val, x, y, u, tail2, g2_last, s_pair, s_off8, s_c,
                                        &s_v[0][0], PAIR ? 0 : CAP + 16, d0, d1, rowval);
-    if (DOT >= 1) {
-        d0 = block_sum(d0, red);
-        if (tid == 0) st_partial(fin, part0 + blockIdx.x, d0);
-    }
-    if (DOT == 2) {
-        d1 = block_sum(d1, red);
-        if (tid == 0) st_partial(fin, part1 + blockIdx.x, d1);
-    }
-    if (DOT >= 1 && fin.counter) finalize_last_block<T, T>(fin, DOT == 2, red, red);
+    spmv_dot_epilogue<DOT>(d0, d1, red, part0, part1, fin);
 }
 
 // M1 of MINRES' iteration k + 1 on the UN-NORMALISED v_new of iteration k (minres_fuse.hpp; minres.hip "M3 deferred"): the launch runs
@@ -578,15 +570,7 @@ __global__ __launch_bounds__(BLOCK) void spmv_pair2_kernel(int n_wide, int xcd_c
 
     T d0 = 0.0, d1 = 0.0;
     pair2_walk<DOT, YNT>(n_wide, xcd_chunk, desc, order, row_ptr, code, XPlain{reinterpret_cast<const char *>(x)}, y, u, nrows, ncols, s_pair, s_c, d0, d1);
-    if (DOT >= 1) {
-        d0 = block_sum(d0, red);
-        if (tid == 0) st_partial(fin, part0 + blockIdx.x, d0);
-    }
-    if (DOT == 2) {
-        d1 = block_sum(d1, red);
-        if (tid == 0) st_partial(fin, part1 + blockIdx.x, d1);
-    }
-    if (DOT >= 1 && fin.counter) finalize_last_block<T, T>(fin, DOT == 2, red, red);
+    spmv_dot_epilogue<DOT>(d0, d1, red, part0, part1, fin);
 }
 
 // one thread per candidate tile (blocks [t TILE_B, (t + 1) TILE_B)): its pattern (up to 8 codes, low byte first) and

@@ -1,6 +1,7 @@
 // Device-side building blocks of the compressed-stream SpMV kernels, shared by their translation units: spmv_dict.hip (creation,
-// the per-block kernels, the launch dispatcher), spmv_tile.hip (LDS x-window tiles of the f64 pair-code stream) and
-// spmv_tile_off.hip (the same for the f64 offset-code stream).  Split out of spmv_dict.hip in round 4 so that the three
+// the per-block kernels, the launch dispatcher), spmv_tile.hip (LDS x-window tiles of the f64 pair-code stream),
+// spmv_tile_off.hip (the same for the f64 offset-code stream) and spmv_chain.hip (plane-streaming chains).  The row-pair fold of
+// the pair-code stream (pair_fold) and the steps the window kernels share are defined here, once.  Split out of spmv_dict.hip in round 4 so that the three
 // compile in parallel (profiles/r04_tuning.md "build cost"); the code is unchanged.
 #pragma once
 #include "device.hpp"
@@ -378,6 +379,72 @@ __device__ __forceinline__ double wave_shift_down(double next_for_last_lane, dou
     const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)(o >> 32), (int)(uint32_t)(q >> 32), 0x130, 0xf, 0xf, false);
     return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
 }
+// ---- The row-pair fold of the pair-code stream over a FULL uniform 128-row block, written once: lane l folds row 2l from pl[]
+// into acc0 and row 2l + 1 from ph[] into acc1, slot by slot from the left, with the pattern's values val[] (wave-uniform).
+// A SEAM block (mark_uniform_kernel) is uniform but for its local rows k and k + 1, which lack some slots or carry a value of
+// their own (a row with a value of its own has exactly one slot).  Its two words: seam1 (the descriptor's nn >> 16) = k | maskA << 7,
+// seam2 (rb's low 26 bits) = maskB | codeA << 8 | codeB << 16 | ownA << 24 | ownB << 25 — the slots rows k / k + 1 have (0xff: all of
+// them), the pair codes of their own values and whether they carry one.  A skipped slot leaves the sum as it is: every row is
+// the left fold over the slots it has, whichever branch folds it.
+// The general seam fold: per lane and row the mask of its slots and, where the row has a value of its own, that value.
+// UL == 0: run-time length `ulen` (full_uniform_block's generic flavour), else UL slots.
+template <int UL>
+__device__ __forceinline__ void seam_fold_masked(const double *pl, const double *ph, const double *val, int ulen, int seam1, int seam2,
+                                                 const PairEnt<double> *s_pair, int lane, double &acc0, double &acc1) {
+    using T = double;
+    const int k = seam1 & 127, maskA = (seam1 >> 7) & 255, maskB = seam2 & 255;
+    const T valA = s_pair[(seam2 >> 8) & 255].val, valB = s_pair[(seam2 >> 16) & 255].val;
+    const bool ovA = ((seam2 >> 24) & 1) != 0, ovB = ((seam2 >> 25) & 1) != 0;
+    const bool a0 = 2 * lane == k, a1 = 2 * lane + 1 == k, b0 = 2 * lane == k + 1, b1 = 2 * lane + 1 == k + 1;
+    const int pm0 = a0 ? maskA : (b0 ? maskB : 255), pm1 = a1 ? maskA : (b1 ? maskB : 255);
+    const bool o0 = (a0 && ovA) || (b0 && ovB), o1 = (a1 && ovA) || (b1 && ovB);
+    const T v0 = a0 ? valA : valB, v1 = a1 ? valA : valB;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        if (UL == 0 ? t >= ulen : t >= UL) break;
+        const T n0 = acc0 + pl[t] * (o0 ? v0 : val[t]), n1 = acc1 + ph[t] * (o1 ? v1 : val[t]);
+        acc0 = ((pm0 >> t) & 1) ? n0 : acc0;
+        acc1 = ((pm1 >> t) & 1) ? n1 : acc1;
+    }
+}
+// The fold of the window kernels (spmv_tile_kernel, spmv_chain_kernel): plain blocks, and seam blocks in two branches.  No row
+// with a value of its own (a stencil's line seam): a slot BOTH rows have is a plain step for the whole wavefront (scalar tests),
+// otherwise the lanes of row k or k + 1 alone keep their sum — a line seam costs two masked steps, not UL.  Else the general fold.
+// rb, nn: the block's descriptor words as loaded (wave-uniform).  Two things in the shape below are measured, not taste
+// (profiles/window_fold_refactor.md): the seam words are taken out of rb / nn INSIDE the seam branch (decoded in front of the
+// call, the chain kernel's scalar tests compile to other branches and its launch is 2 % slower), and the lane predicates
+// stand in front of both seam branches, where the general fold's own copies of them fold into these.
+template <int UL>
+__device__ __forceinline__ void pair_fold(const double *pl, const double *ph, const double *val, uint32_t rb, int nn,
+                                          const PairEnt<double> *s_pair, int lane, double &acc0, double &acc1) {
+    using T = double;
+    if ((rb & SEAM2) == 0) {
+#pragma unroll
+        for (int t = 0; t < UL; ++t) {
+            acc0 = acc0 + pl[t] * val[t];
+            acc1 = acc1 + ph[t] * val[t];
+        }
+    } else {
+        const int seam1 = __builtin_amdgcn_readfirstlane(nn) >> 16, seam2 = (int)(rb & 0x3ffffffu);
+        const int k = seam1 & 127, maskA = (seam1 >> 7) & 255, maskB = seam2 & 255;
+        const bool a0 = 2 * lane == k, a1 = 2 * lane + 1 == k, b0 = 2 * lane == k + 1, b1 = 2 * lane + 1 == k + 1;
+        if ((seam2 & 0x3000000) == 0) {
+#pragma unroll
+            for (int t = 0; t < UL; ++t) {
+                const bool am = ((maskA >> t) & 1) == 0, bm = ((maskB >> t) & 1) == 0;       // scalar
+                const T n0 = acc0 + pl[t] * val[t], n1 = acc1 + ph[t] * val[t];
+                if (!am && !bm) { acc0 = n0; acc1 = n1; }
+                else {
+                    acc0 = ((am && a0) || (bm && b0)) ? acc0 : n0;
+                    acc1 = ((am && a1) || (bm && b1)) ? acc1 : n1;
+                }
+            }
+        } else {
+            seam_fold_masked<UL>(pl, ph, val, UL, seam1, seam2, s_pair, lane, acc0, acc1);
+        }
+    }
+}
+
 template <int UL, int SC, class XS, class AfterLoads>
 __device__ __forceinline__ void full_uniform_block(const PairEnt<double> *s_pair, uint64_t pat, int ulen, bool seam, int seam1, int seam2, const XS &xs,
                                                    uint32_t r8, uint32_t ra8, int lane, AfterLoads &&after_loads,
@@ -424,22 +491,7 @@ __device__ __forceinline__ void full_uniform_block(const PairEnt<double> *s_pair
             acc1 = acc1 + ph[t] * av[t];
         }
     } else {
-        // seam block: local rows k and k + 1 fold only the slots of their masks, with their own value where they carry one
-        // (a row with a value of its own has exactly one slot)
-        const int k = seam1 & 127, maskA = (seam1 >> 7) & 255, maskB = seam2 & 255;
-        const T valA = s_pair[(seam2 >> 8) & 255].val, valB = s_pair[(seam2 >> 16) & 255].val;
-        const bool ovA = ((seam2 >> 24) & 1) != 0, ovB = ((seam2 >> 25) & 1) != 0;
-        const bool a0 = 2 * lane == k, a1 = 2 * lane + 1 == k, b0 = 2 * lane == k + 1, b1 = 2 * lane + 1 == k + 1;
-        const int pm0 = a0 ? maskA : (b0 ? maskB : 255), pm1 = a1 ? maskA : (b1 ? maskB : 255);
-        const bool o0 = (a0 && ovA) || (b0 && ovB), o1 = (a1 && ovA) || (b1 && ovB);
-        const T v0 = a0 ? valA : valB, v1 = a1 ? valA : valB;
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            if (UL == 0 ? t >= ulen : t >= UL) break;
-            const T n0 = acc0 + pl[t] * (o0 ? v0 : av[t]), n1 = acc1 + ph[t] * (o1 ? v1 : av[t]);
-            acc0 = ((pm0 >> t) & 1) ? n0 : acc0;
-            acc1 = ((pm1 >> t) & 1) ? n1 : acc1;
-        }
+        seam_fold_masked<UL>(pl, ph, av, ulen, seam1, seam2, s_pair, lane, acc0, acc1);
     }
 }
 template <class XS, class AfterLoads>
@@ -747,13 +799,106 @@ __device__ __forceinline__ void pair2_walk(int n_wide, int xcd_chunk, const BlkD
 // (the +-plane neighbours) one by one.  So: a tile = TILE_B consecutive FULL uniform 128-row blocks (plain or seam,
 // mark_uniform_kernel) that share one pattern whose slots are, in row order, FL far slots, UL - FL - FH near slots, FH
 // far slots (sorted columns give exactly that).  The workgroup stages the window in LDS with 16-byte loads, issues the far
-// pair loads of all its rows, and every lane folds its two rows' slots left to right — the same products in the same order
-// as full_uniform_block, x taken from LDS for the near slots: y bit-identical.  Tiles are dealt to the XCDs by their
+// pair loads of all its rows, and every lane folds its two rows' slots left to right (pair_fold above) — the same products in
+// the same order as full_uniform_block, x taken from LDS for the near slots: y bit-identical.  Tiles are dealt to the XCDs by their
 // phase within the far period (tile_plan below) so that a far window was some tile's near window on the same L2.  The
 // 128-row blocks outside the tiles (boundary planes, the tiles a boundary line cuts, the matrix ends) are walked by the
 // same launch afterwards (pair2_walk), so the launch writes all of y and one partial per workgroup.
 constexpr int TILE_ROWS = 4096, TILE_W = 512, TILE_W_WIDE = 1536, TILE_B = TILE_ROWS / (2 * WAVE);
 struct TilePat { int32_t off[8]; double val[8]; };
+// the pattern of a tile or chain plan as a kernel argument (the offset-code stream's plan has no values: zeros)
+template <class Plan>
+inline TilePat tile_pat(const Plan &p) {
+    TilePat tp;
+    for (int t = 0; t < 8; ++t) { tp.off[t] = p.off[t]; tp.val[t] = p.val[t]; }
+    return tp;
+}
+
+// ---- The steps spmv_tile_kernel (spmv_tile.hip) and spmv_tile_off_kernel (spmv_tile_off.hip) share.  The kernels keep their own
+// LDS layout, value path and the ORDER in which they issue these steps (measured, see there).
+// A workgroup's walk over its XCD's section of the tile list.  Entries: {first 128-row block, first row}; `ent` is the tile the
+// loop is at, requested a tile ahead (`ent1`: the one after it).
+struct TileCursor { int s, sstep, send; int2 ent, ent1; };
+__device__ __forceinline__ TileCursor tile_cursor(const int2 *tile_list, const int32_t *xstart) {
+    const int xcd = blockIdx.x & 7;
+    TileCursor c;
+    c.sstep = gridDim.x >> 3;
+    c.send = xstart[xcd + 1];
+    c.s = xstart[xcd] + (blockIdx.x >> 3);
+    c.ent = c.s < c.send ? tile_list[c.s] : int2{0, 0};
+    c.ent1 = c.s + c.sstep < c.send ? tile_list[c.s + c.sstep] : int2{0, 0};
+    return c;
+}
+// this tile's first row; `ent` moves on to the next tile (whose words the kernel loads before its barrier) and the entry after
+// that is requested
+__device__ __forceinline__ int tile_cursor_take(TileCursor &c, const int2 *tile_list) {
+    const int ts = __builtin_amdgcn_readfirstlane(c.ent.y);
+    c.ent = c.ent1;
+    if (c.s + 2 * c.sstep < c.send) c.ent1 = tile_list[c.s + 2 * c.sstep];
+    return ts;
+}
+// the seam words of the wavefront's NQ blocks of the tile whose first block is b0 (wave-uniform: scalar loads), read a tile ahead
+template <int NQ>
+__device__ __forceinline__ void tile_seam_words(const BlkDesc *desc, int b0, int wv, uint32_t (&rbw)[NQ], int (&nnw)[NQ]) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) { const BlkDesc d = desc[b0 + q * NWAVE + wv]; rbw[q] = (uint32_t)d.rb; nnw[q] = d.nn; }
+}
+// the window [wbase, wbase + 2 NW BLOCK): 16-byte loads, and its staging once every wavefront has read the previous tile's
+template <int NW>
+__device__ __forceinline__ void window_load(const double *wbase, int tid, u4v (&wreg)[NW]) {
+#pragma unroll
+    for (int i = 0; i < NW; ++i) wreg[i] = *reinterpret_cast<const u4v *>(wbase + 2 * (tid + i * BLOCK));
+}
+template <int NW>
+__device__ __forceinline__ void window_stage(double *win, int tid, const u4v (&wreg)[NW]) {
+    __syncthreads();                                                            // the previous tile's window has been read
+#pragma unroll
+    for (int i = 0; i < NW; ++i) *reinterpret_cast<u4v *>(&win[2 * (tid + i * BLOCK)]) = wreg[i];
+    __syncthreads();
+}
+// the far pairs of the lane's rows g, g + 1 (the pattern's FL leading and FH trailing slots) and, unless the dot operand is
+// x itself, the rows' dot operands (read once: non-temporal)
+template <int DOT, bool UX, int UL, int FL, int FH>
+__device__ __forceinline__ void tile_far_loads(const double *x, const double *u, const TilePat &pat, int g, D2 *far, D2 &uu) {
+    const double *xr = x + g;
+#pragma unroll
+    for (int k = 0; k < FL; ++k) far[k] = *reinterpret_cast<const D2 *>(xr + pat.off[k]);
+#pragma unroll
+    for (int k = 0; k < FH; ++k) far[FL + k] = *reinterpret_cast<const D2 *>(xr + pat.off[UL - FH + k]);
+    if (DOT != 0 && !UX) {
+        const u4v w4 = __builtin_nontemporal_load(reinterpret_cast<const u4v *>(u + g));
+        __builtin_memcpy(&uu, &w4, 16);
+    }
+}
+// the near slots (offsets noff[0 .. NN)) of the rows at window index li, li + 1
+template <int NN>
+__device__ __forceinline__ void tile_read_near(const double *win, int li, const int32_t *noff, double (&npl)[NN], double (&nph)[NN]) {
+#pragma unroll
+    for (int t = 0; t < NN; ++t) { npl[t] = win[li + noff[t]]; nph[t] = win[li + noff[t] + 1]; }
+}
+// the row pair's UL slots in pattern order: far, near.., far
+template <int UL, int FL, int FH>
+__device__ __forceinline__ void tile_slots(const D2 *far, const double *npl, const double *nph, double (&pl)[UL], double (&ph)[UL]) {
+#pragma unroll
+    for (int t = 0; t < UL; ++t) {
+        if (t < FL) { pl[t] = far[t].lo; ph[t] = far[t].hi; }
+        else if (t >= UL - FH) { pl[t] = far[t - (UL - FH) + FL].lo; ph[t] = far[t - (UL - FH) + FL].hi; }
+        else { pl[t] = npl[t - FL]; ph[t] = nph[t - FL]; }
+    }
+}
+// What the window kernels (the chains too) do with a folded row pair: the 16-byte non-temporal store of y[g], y[g + 1] = yp[0], yp[1]
+// (YST) and the rows' terms of the launch's dots (DOT as in launch_spmv; u0, u1: the rows' dot operands)
+template <int DOT, bool YST = true>
+__device__ __forceinline__ void row_pair_out(double *yp, double acc0, double acc1, double u0, double u1, double &d0, double &d1) {
+    if constexpr (YST) {
+        const D2 yy{acc0, acc1};
+        u4v qv;
+        __builtin_memcpy(&qv, &yy, 16);
+        __builtin_nontemporal_store(qv, reinterpret_cast<u4v *>(yp));
+    }
+    if (DOT == 1) { d0 = d0 + u0 * acc0; d0 = d0 + u1 * acc1; }
+    if (DOT == 2) { d0 = d0 + acc0 * acc0; d1 = d1 + acc0 * u0; d0 = d0 + acc1 * acc1; d1 = d1 + acc1 * u1; }
+}
 
 // (UL, FL, FH) shapes spmv_tile_kernel is built for: 7-point 3-D, 5-point 2-D with a far or a near line band, 3-point 1-D, and
 // bands with two far diagonals

@@ -1,4 +1,4 @@
-// LDS x-window tiles of the f64 OFFSET-CODE stream (a value per entry; design notes in spmv_dict_dev.hpp, profiles/r03_tuning.md §9).
+// LDS x-window tiles of the f64 OFFSET-CODE stream (a value per entry; design notes and the tile steps shared with spmv_tile.hip in spmv_dict_dev.hpp, profiles/r03_tuning.md §9).
 #include "spmv_dict_dev.hpp"
 
 namespace sprs {
@@ -46,49 +46,29 @@ __global__ __launch_bounds__(BLOCK) void spmv_tile_off_kernel(const int2 *__rest
     if (run_state != ST_RUNNING) { fin_idle(fin, DOT == 2); return; }
     T d0 = 0.0, d1 = 0.0;
 
-    const int xcd = blockIdx.x & 7;
-    const int sstep = gridDim.x >> 3;
-    const int send = xstart[xcd + 1];
-    int s = xstart[xcd] + (blockIdx.x >> 3);
-    // tile entries {first 128-row block, first row} and per block its seam words and its first entry: scalar loads a tile ahead
-    int2 ent = s < send ? tile_list[s] : int2{0, 0};
-    int2 ent1 = s + sstep < send ? tile_list[s + sstep] : int2{0, 0};
+    TileCursor cur = tile_cursor(tile_list, xstart);
+    // per block its seam words and its first entry: scalar loads a tile ahead
     uint32_t rbw[NQ]; int nnw[NQ], vbw[NQ];
     auto load_words = [&](int b0, int ts) {
+        tile_seam_words(desc, b0, wv, rbw, nnw);
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const BlkDesc d = desc[b0 + q * NWAVE + wv];
-            rbw[q] = (uint32_t)d.rb; nnw[q] = d.nn; vbw[q] = row_ptr[ts + ((q * NWAVE + wv) << 7)];
-        }
+        for (int q = 0; q < NQ; ++q) vbw[q] = row_ptr[ts + ((q * NWAVE + wv) << 7)];
     };
-    load_words(__builtin_amdgcn_readfirstlane(ent.x), __builtin_amdgcn_readfirstlane(ent.y));
+    load_words(__builtin_amdgcn_readfirstlane(cur.ent.x), __builtin_amdgcn_readfirstlane(cur.ent.y));
     T *vs = vsl[wv];
-    for (; s < send; s += sstep) {
-        const int ts = __builtin_amdgcn_readfirstlane(ent.y);
-        ent = ent1;
-        if (s + 2 * sstep < send) ent1 = tile_list[s + 2 * sstep];
+    for (; cur.s < cur.send; cur.s += cur.sstep) {
+        const int ts = tile_cursor_take(cur, tile_list);
         uint32_t rbc[NQ]; int nnc[NQ], vbc[NQ];
 #pragma unroll
         for (int q = 0; q < NQ; ++q) { rbc[q] = rbw[q]; nnc[q] = nnw[q]; vbc[q] = __builtin_amdgcn_readfirstlane(vbw[q]); }
-        // ---- loads: the window, the far pairs (and dot operands) of the lane's NQ row pairs, the first block's values
+        // ---- loads: the window, the far pairs (and dot operands) of the lane's NQ row pairs, the first block's values, then the
+        // next tile's words
         u4v wreg[NW];
-        const T *wbase = x + (ts - W);
-#pragma unroll
-        for (int i = 0; i < NW; ++i) wreg[i] = *reinterpret_cast<const u4v *>(wbase + 2 * (tid + i * BLOCK));
+        window_load(x + (ts - W), tid, wreg);
         D2 far[NQ][FL + FH > 0 ? FL + FH : 1];
         D2 uu[NQ];
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const T *xr = x + (ts + ((q * NWAVE + wv) << 7) + 2 * lane);
-#pragma unroll
-            for (int k = 0; k < FL; ++k) far[q][k] = *reinterpret_cast<const D2 *>(xr + pat.off[k]);
-#pragma unroll
-            for (int k = 0; k < FH; ++k) far[q][FL + k] = *reinterpret_cast<const D2 *>(xr + pat.off[UL - FH + k]);
-            if (DOT != 0 && !UX) {
-                const u4v w4 = __builtin_nontemporal_load(reinterpret_cast<const u4v *>(u + (ts + ((q * NWAVE + wv) << 7) + 2 * lane)));
-                __builtin_memcpy(&uu[q], &w4, 16);
-            }
-        }
+        for (int q = 0; q < NQ; ++q) tile_far_loads<DOT, UX, UL, FL, FH>(x, u, pat, ts + ((q * NWAVE + wv) << 7) + 2 * lane, far[q], uu[q]);
         u4v vreg[NV];
         auto load_vals = [&](int vb) {                  // chunks [vb >> 1, (vb >> 1) + VROW / 2]: the block's values from its 16-byte boundary
             const u4v *v2 = reinterpret_cast<const u4v *>(val) + (vb >> 1);
@@ -96,18 +76,10 @@ __global__ __launch_bounds__(BLOCK) void spmv_tile_off_kernel(const int2 *__rest
             for (int i = 0; i < NV; ++i) vreg[i] = __builtin_nontemporal_load(v2 + min(lane + i * WAVE, VROW / 2));      // read once: 720 -> 674 us (profiles/r03_tuning.md §9)
         };
         load_vals(vbc[0]);
-        if (s + sstep < send) load_words(__builtin_amdgcn_readfirstlane(ent.x), __builtin_amdgcn_readfirstlane(ent.y));
-        __syncthreads();                                                        // the previous tile's window has been read
-#pragma unroll
-        for (int i = 0; i < NW; ++i) *reinterpret_cast<u4v *>(&win[2 * (tid + i * BLOCK)]) = wreg[i];
-        __syncthreads();
-        T npl[NN], nph[NN];
-        auto read_near = [&](int q) {
-            const int li = W + ((q * NWAVE + wv) << 7) + 2 * lane;
-#pragma unroll
-            for (int t = 0; t < NN; ++t) { npl[t] = win[li + pat.off[FL + t]]; nph[t] = win[li + pat.off[FL + t] + 1]; }
-        };
-        read_near(0);
+        if (cur.s + cur.sstep < cur.send) load_words(__builtin_amdgcn_readfirstlane(cur.ent.x), __builtin_amdgcn_readfirstlane(cur.ent.y));
+        window_stage(win, tid, wreg);
+        T npl[NN], nph[NN];                             // the near reads of block q + 1 go out before block q is folded (spmv_tile_kernel)
+        tile_read_near(win, W + (wv << 7) + 2 * lane, pat.off + FL, npl, nph);
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
             // this block's values: registers -> the wavefront's slice (stream order), then the next block's loads go out
@@ -120,15 +92,10 @@ __global__ __launch_bounds__(BLOCK) void spmv_tile_off_kernel(const int2 *__rest
             const int shift = vbc[q] & 1;
             const int li = W + ((q * NWAVE + wv) << 7) + 2 * lane;              // window index of x[r0]
             T pl[UL], ph[UL];
-#pragma unroll
-            for (int t = 0; t < UL; ++t) {
-                if (t < FL) { pl[t] = far[q][t].lo; ph[t] = far[q][t].hi; }
-                else if (t >= UL - FH) { pl[t] = far[q][t - (UL - FH) + FL].lo; ph[t] = far[q][t - (UL - FH) + FL].hi; }
-                else { pl[t] = npl[t - FL]; ph[t] = nph[t - FL]; }
-            }
+            tile_slots<UL, FL, FH>(far[q], npl, nph, pl, ph);
             T ux0 = 0.0, ux1 = 0.0;
             if (DOT != 0 && UX) { ux0 = win[li]; ux1 = win[li + 1]; }
-            if (q + 1 < NQ) read_near(q + 1);
+            if (q + 1 < NQ) tile_read_near(win, W + (((q + 1) * NWAVE + wv) << 7) + 2 * lane, pat.off + FL, npl, nph);
             T acc0 = 0.0, acc1 = 0.0;
             if (!seam) {
                 const T *v0 = vs + shift + 2 * lane * UL;
@@ -155,15 +122,8 @@ __global__ __launch_bounds__(BLOCK) void spmv_tile_off_kernel(const int2 *__rest
                     acc1 = h1 ? n1 : acc1; p1 += h1 ? 1 : 0;
                 }
             }
-            const D2 yy{acc0, acc1};
-            u4v qv;
-            __builtin_memcpy(&qv, &yy, 16);
-            __builtin_nontemporal_store(qv, reinterpret_cast<u4v *>(y + (ts + ((q * NWAVE + wv) << 7) + 2 * lane)));
-            if (DOT == 1) { d0 = d0 + (UX ? ux0 : uu[q].lo) * acc0; d0 = d0 + (UX ? ux1 : uu[q].hi) * acc1; }
-            if (DOT == 2) {
-                const T u0 = UX ? ux0 : uu[q].lo, u1 = UX ? ux1 : uu[q].hi;
-                d0 = d0 + acc0 * acc0; d1 = d1 + acc0 * u0; d0 = d0 + acc1 * acc1; d1 = d1 + acc1 * u1;
-            }
+            row_pair_out<DOT>(y + (ts + ((q * NWAVE + wv) << 7) + 2 * lane), acc0, acc1, (DOT != 0 && !UX) ? uu[q].lo : ux0,
+                              (DOT != 0 && !UX) ? uu[q].hi : ux1, d0, d1);
             wave_lds_fence();                                                   // the slice is free for the next block's values
         }
     }
@@ -172,15 +132,7 @@ __global__ __launch_bounds__(BLOCK) void spmv_tile_off_kernel(const int2 *__rest
         dict_walk<T, DOT, false, false, true>(n_left, 0, desc64, left_order, row_ptr, code, val, x, y, u, tail2, g2_last,
                                              (const PairEnt<T> *)nullptr, s_off8, s_c, &vsl[0][0], VS, d0, d1);
     }
-    if (DOT >= 1) {
-        d0 = block_sum(d0, red);
-        if (tid == 0) st_partial(fin, part0 + blockIdx.x, d0);
-    }
-    if (DOT == 2) {
-        d1 = block_sum(d1, red);
-        if (tid == 0) st_partial(fin, part1 + blockIdx.x, d1);
-    }
-    if (DOT >= 1 && fin.counter) finalize_last_block<T, T>(fin, DOT == 2, red, red);
+    spmv_dot_epilogue<DOT>(d0, d1, red, part0, part1, fin);
 }
 
 }  // namespace
@@ -190,26 +142,23 @@ int launch_tile_off(const sprs_csr *A, const SpmvRoute &r, const double *x, doub
     sprs_ctx *c = A->ctx;
     const sprs_dict *D = A->dict;
     const sprs_tile_plan &TP = *r.tile;
-    const int g = r.grid;
     const BlkDesc *desc64 = r.desc;       // the 64-row blocks outside the tiles
     int g2_last;
     const V2d *tail2 = dict_tail2(A, g2_last);
-    TilePat tp;
-    for (int t = 0; t < 8; ++t) { tp.off[t] = TP.off[t]; tp.val[t] = 0.0; }
-    const bool ux = dot_mode != 0 && u == x;      // the dot operand is the input vector (mul_vec_dot, MINRES' v.Av, K4 without a preconditioner)
+    const TilePat tp = tile_pat(TP);
     const BlkDesc *owd = reinterpret_cast<const BlkDesc *>(D->owide_desc);
     const double *v = reinterpret_cast<const double *>(A->val);
-#define SPRS_TOSPMV(DM, UXV, U, L, H) SPRS_LAUNCH_SPMV(c, (spmv_tile_off_kernel<DM, UXV, U, L, H>), g, reinterpret_cast<const int2 *>(TP.list), TP.xstart, owd, tp, \
-                                                       TP.n_left, TP.left, desc64, A->row_ptr, D->idx_code, D->off_tab, v, x, y, u, part0, part1, status, fin, tail2, g2_last)
-#define SPRS_TOSHAPE(U, L, H)                                                                                        \
-    if (TP.ul == U && TP.fl == L && TP.fh == H) {                                                                    \
-        if (dot_mode == 0) SPRS_TOSPMV(0, false, U, L, H);                                                           \
-        else if (dot_mode == 1) { if (ux) SPRS_TOSPMV(1, true, U, L, H); else SPRS_TOSPMV(1, false, U, L, H); }      \
-        else if (ux) SPRS_TOSPMV(2, true, U, L, H); else SPRS_TOSPMV(2, false, U, L, H);                             \
-    }
-    SPRS_TILE_SHAPES(SPRS_TOSHAPE)
+    // UX: the dot operand is the input vector (mul_vec_dot, MINRES' v.Av, K4 without a preconditioner); without a dot, one kernel
+    with_dot(dot_mode, u == x, [&](auto dm, auto ux) {
+        constexpr int DM = decltype(dm)::value;
+        constexpr bool UXV = DM != 0 && decltype(ux)::value;
+#define SPRS_TOSHAPE(U, L, H)                                                                                                             \
+    if (TP.ul == U && TP.fl == L && TP.fh == H)                                                                                           \
+        SPRS_LAUNCH_SPMV(c, (spmv_tile_off_kernel<DM, UXV, U, L, H>), r.grid, reinterpret_cast<const int2 *>(TP.list), TP.xstart, owd, tp, \
+                         TP.n_left, TP.left, desc64, A->row_ptr, D->idx_code, D->off_tab, v, x, y, u, part0, part1, status, fin, tail2, g2_last);
+        SPRS_TILE_SHAPES(SPRS_TOSHAPE)
 #undef SPRS_TOSHAPE
-#undef SPRS_TOSPMV
+    });
     SPRS_HIP_TRY(c, hipGetLastError());
     return SPRS_OK;
 }
