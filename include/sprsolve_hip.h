@@ -1038,6 +1038,78 @@ int sprs_dist_csr_create_allgather_dev_c(sprs_comm *comm, int64_t n_local, int64
 int sprs_dist_mul_vec_dev_d(const sprs_csr *A, double *x_ext_dev, double *y_local_dev);
 int sprs_dist_mul_vec_dev_z(const sprs_csr *A, sprs_c64 *x_ext_dev, sprs_c64 *y_local_dev);
 
+/* ---------------------------------------------------------------- thick-restart Lanczos eigensolver
+ * The k algebraically largest or smallest eigenpairs of a square A that is assumed Hermitian (as with CG, that is not checked):
+ * thick-restart Lanczos (Wu & Simon; equal to Hermitian Krylov-Schur) with full reorthogonalisation by classical Gram-Schmidt
+ * applied twice.  The reference has no such solver.  Single GPU: a distributed A is refused with SPRS_INVALID_ARGUMENT (text in
+ * sprs_last_error).  The handle owns ncv + 2 vectors: v_0 .. v_m (m = ncv) and w.
+ * Vectors and the CGS2 coefficients h_i, c_i are of type T.  T_ij, theta_i, S, beta, res_i, anorm, scale are double for all four
+ * scalar types: the projected matrix is real symmetric for complex A too (its diagonal holds Re(conj_dot(v_j, A v_j)), its
+ * sub-diagonal norms, and after a restart Ritz values and real multiples of a real eigenvector matrix).  beta is the square root,
+ * taken in T::Real, of a sum of squares formed in T::Real.  conj_dot(a, b) = sum conj(a_i) b_i.
+ *     beta0 = norm2(v0);  NaN or 0: SPRS_BREAKDOWN (*matvecs_out = 0, *restarts_out = 0).  v_0 = v0 * (1 / beta0)
+ *     T = 0, j0 = 0, anorm = 0, scale = 0
+ *     cycle c = 1, 2, ...:
+ *         for j = j0 .. m - 1:
+ *             w = A v_j
+ *             pass 1:  h_i = conj_dot(v_i, w) for i = 0 .. j, all on the same w;  then for i = 0 .. j in order: w += v_i*(-h_i)
+ *             pass 2:  c_i = conj_dot(v_i, w) for i = 0 .. j, all on the same w;  then for i = 0 .. j in order: w += v_i*(-c_i);
+ *                      h_i = h_i + c_i
+ *             T_jj = Re(h_j);  beta = norm2(w);  NaN: SPRS_BREAKDOWN
+ *             scale = max(scale, |T_jj|)
+ *             if beta <= 64 eps(T::Real) scale: an invariant subspace, m_eff = j + 1, leave the loop (v_{j+1} is not formed)
+ *             scale = max(scale, beta);  if j + 1 < m: T_{j+1,j} = T_{j,j+1} = beta;   v_{j+1} = w * (1 / beta)   (also at j = m - 1)
+ *         (m_eff = m where the loop ran out)
+ *         (theta, S) = the eigendecomposition of T[:m_eff, :m_eff] (below), theta descending (SPRS_EIGSH_LARGEST) or ascending
+ *                      (SPRS_EIGSH_SMALLEST), ties by index, the columns of S with it
+ *         res_i = beta |S[m_eff - 1, i]|;  anorm = max(anorm, max |theta_i|);  nconv = the number of LEADING i < k with
+ *                      res_i <= tol anorm
+ *         invariant subspace:  m_eff >= k: SPRS_OK with nconv = k;  else SPRS_BREAKDOWN
+ *         nconv == k:          SPRS_OK
+ *         c == max_restarts:   SPRS_INSUFFICIENT_ITER (the outputs are the current leading k pairs, nconv as counted)
+ *         restart:  p = min(k + max(k, 4), m - 2);  V[:, :p] = V[:, :m] S[:, :p];  v_p = v_m;
+ *                   T = diag(theta_0 .. theta_{p-1}),  T_{p,i} = T_{i,p} = beta S[m - 1, i] (i < p);  j0 = p
+ *     outputs:  vals_i = theta_i and res_i (absolute) for i < k, rounded to T::Real;  X = V[:, :m_eff] S[:, :k] as k contiguous
+ *               vectors of n (vecs may be NULL);  nconv;  restarts = c;  matvecs = the products A v that ran
+ * Only T's diagonal, sub-diagonal and the restart's arrow row are kept from a step; the other CGS2 coefficients serve the
+ * reorthogonalisation alone.  The coefficients of V S are S rounded once to T::Real, and every output element is summed over
+ * i ascending from zero, one real-by-T product and one sum per term, each rounded once.  Eigenvector phases are whatever falls
+ * out.  On SPRS_BREAKDOWN vals / res hold the last Ritz values computed (zeros where there were none) and vecs is not written.
+ * The eigendecomposition: cyclic Jacobi on T with S = I.  m_eff is rounded up to an even M (an odd m_eff carries one idle
+ * index).  A sweep is M - 1 rounds; round r rotates the M / 2 disjoint pairs (M - 1, r) and ((r + i) mod (M - 1),
+ * (r - i) mod (M - 1)), i = 1 .. M / 2 - 1, each ordered p < q, all from the same T:  T_pq == 0: nothing;  else
+ * tau = (T_qq - T_pp) / (2 T_pq), t = sign(tau) / (|tau| + sqrt(1 + tau^2)) (sign(0) = 1), c = 1 / sqrt(1 + t^2), s = t c;
+ * columns: x_p' = c x_p - s x_q, x_q' = s x_p + c x_q on T and S, then the same on T's rows, then T_pq = T_qp = 0 exactly.
+ * Before every sweep off(T)^2 = the sum of the squared off-diagonal entries is compared with eps^2 |T|_F^2 (|T|_F of the
+ * input): at or below it the diagonal holds theta; after 30 sweeps above it the solve ends in SPRS_BREAKDOWN, never a silent
+ * result.
+ * create:  ncv = 0 means min(32, n);  SPRS_INVALID_ARGUMENT unless 3 <= ncv <= min(SPRS_EIGSH_MAX_NCV, n);  SPRS_NOT_SQUARE;
+ *          SPRS_DIM_MISMATCH for size != rows.
+ * solve:   SPRS_INVALID_ARGUMENT unless 1 <= k <= ncv - 2, which is one of the two and max_restarts >= 1;
+ *          SPRS_INCOMPATIBLE_RHS_SIZE for v0_len != n;  SPRS_INCOMPATIBLE_X_SIZE for a non-null vecs with vecs_len != k n.
+ *          vals_out and res_out hold k entries; the three counters may be NULL.
+ * Not provided for this solver: a literal mode, the trace, the profile hooks and a sprs_solver_* kind.
+ * Limits: a single start vector finds one copy of a multiple eigenvalue; convergence is governed by the relative gap, so the
+ * smallest modes of a large Laplacian take thousands of products; a start vector inside an invariant subspace yields that
+ * subspace's extreme pairs, not A's. */
+typedef struct sprs_eigsh sprs_eigsh;
+#define SPRS_EIGSH_MAX_NCV 64
+enum { SPRS_EIGSH_LARGEST = 0, SPRS_EIGSH_SMALLEST = 1 };
+int sprs_eigsh_destroy(sprs_eigsh *S);         /* NULL is a no-op */
+int sprs_eigsh_create_d(const sprs_csr *A, size_t size, size_t ncv, sprs_eigsh **out);
+int sprs_eigsh_create_z(const sprs_csr *A, size_t size, size_t ncv, sprs_eigsh **out);
+int sprs_eigsh_create_s(const sprs_csr *A, size_t size, size_t ncv, sprs_eigsh **out);
+int sprs_eigsh_create_c(const sprs_csr *A, size_t size, size_t ncv, sprs_eigsh **out);
+int sprs_eigsh_solve_d(sprs_eigsh *S, size_t k, int which, const double *v0, size_t v0_len, size_t max_restarts, double tol, double *vals_out, double *vecs_out_or_null, size_t vecs_len, double *res_out, size_t *nconv_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_eigsh_solve_z(sprs_eigsh *S, size_t k, int which, const sprs_c64 *v0, size_t v0_len, size_t max_restarts, double tol, double *vals_out, sprs_c64 *vecs_out_or_null, size_t vecs_len, double *res_out, size_t *nconv_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_eigsh_solve_s(sprs_eigsh *S, size_t k, int which, const float *v0, size_t v0_len, size_t max_restarts, float tol, float *vals_out, float *vecs_out_or_null, size_t vecs_len, float *res_out, size_t *nconv_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_eigsh_solve_c(sprs_eigsh *S, size_t k, int which, const sprs_c32 *v0, size_t v0_len, size_t max_restarts, float tol, float *vals_out, sprs_c32 *vecs_out_or_null, size_t vecs_len, float *res_out, size_t *nconv_out, size_t *restarts_out, size_t *matvecs_out);
+/* the same with v0 and vecs on the device (any alignment); vals, res and the counters stay on the host */
+int sprs_eigsh_solve_dev_d(sprs_eigsh *S, size_t k, int which, const double *v0_dev, size_t v0_len, size_t max_restarts, double tol, double *vals_out, double *vecs_dev_or_null, size_t vecs_len, double *res_out, size_t *nconv_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_eigsh_solve_dev_z(sprs_eigsh *S, size_t k, int which, const sprs_c64 *v0_dev, size_t v0_len, size_t max_restarts, double tol, double *vals_out, sprs_c64 *vecs_dev_or_null, size_t vecs_len, double *res_out, size_t *nconv_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_eigsh_solve_dev_s(sprs_eigsh *S, size_t k, int which, const float *v0_dev, size_t v0_len, size_t max_restarts, float tol, float *vals_out, float *vecs_dev_or_null, size_t vecs_len, float *res_out, size_t *nconv_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_eigsh_solve_dev_c(sprs_eigsh *S, size_t k, int which, const sprs_c32 *v0_dev, size_t v0_len, size_t max_restarts, float tol, float *vals_out, sprs_c32 *vecs_dev_or_null, size_t vecs_len, float *res_out, size_t *nconv_out, size_t *restarts_out, size_t *matvecs_out);
+
 /* ---------------------------------------------------------------- solver options / instrumentation
  * `solver` is a handle of any of the solver types below, `kind` says which. */
 enum { SPRS_SOLVER_BICGSTAB = 1, SPRS_SOLVER_MINRES = 2, SPRS_SOLVER_CSMINRES = 3, SPRS_SOLVER_CG = 4, SPRS_SOLVER_GMRES = 5, SPRS_SOLVER_LSMR = 6 };

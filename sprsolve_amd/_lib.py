@@ -18,6 +18,8 @@ ERR_HIP, ERR_RCCL, ERR_NO_DEVICE = 100, 101, 102
 SOLVER_BICGSTAB, SOLVER_MINRES, SOLVER_CSMINRES, SOLVER_CG, SOLVER_GMRES, SOLVER_LSMR = 1, 2, 3, 4, 5, 6
 GMRES_MAX_RESTART = 64
 INNER_CG, INNER_GMRES = 0, 1
+EIGSH_MAX_NCV = 64
+EIGSH_LARGEST, EIGSH_SMALLEST = 0, 1
 
 
 class c64(C.Structure):
@@ -95,6 +97,9 @@ def _protos():
         P["sprs_lsmr_create_" + s] = [_vp, _vp, _pp]
         for k in ("solve", "solve_dev"):
             P["sprs_lsmr_%s_%s" % (k, s)] = [_vp, _vp, _sz, _vp, _sz, re_, _sz, re_, _psz, pre, pre]
+        P["sprs_eigsh_create_" + s] = [_vp, _sz, _sz, _pp]
+        for k in ("solve", "solve_dev"):
+            P["sprs_eigsh_%s_%s" % (k, s)] = [_vp, _sz, _int, _vp, _sz, _sz, re_, pre, _vp, _sz, pre, _psz, _psz, _psz]
         P["sprs_dot_" + s] = [_vp, _sz, _vp, _vp, _vp]
         P["sprs_conj_dot_" + s] = [_vp, _sz, _vp, _vp, _vp]
         P["sprs_norm2_" + s] = [_vp, _sz, _vp, pre]
@@ -137,7 +142,7 @@ def _protos():
     P["sprs_csr_adjoint"] = [_vp, _int, _pp]
     P["sprs_csr_matmul"] = [_vp, _vp, _pp, C.POINTER(_i64)]
     P["sprs_csr_read"] = [_vp, _vp, _vp, _vp]
-    for k in ("bicgstab", "minres", "csminres", "cg", "gmres", "cgmany", "lsmr"):
+    for k in ("bicgstab", "minres", "csminres", "cg", "gmres", "cgmany", "lsmr", "eigsh"):
         P["sprs_%s_destroy" % k] = [_vp]
     for s in ("d", "zd", "z", "s", "cs", "c"):
         P["sprs_diag_precond_create_" + s] = [_vp, _sz, _vp, _pp]

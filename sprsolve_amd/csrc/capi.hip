@@ -600,6 +600,50 @@ int lsmr_solve(Lsmr<T> *s, bool host, const T *rhs, size_t rl, T *x, size_t xl, 
     return st;
 }
 
+// Eigsh<T> behind a sprs_eigsh: a square single-GPU A, ncv = 0 means min(32, n)
+template <class T>
+int eigsh_create(const sprs_csr *A, size_t size, size_t ncv, sprs_eigsh **out) {
+    if (!A || !out) return SPRS_INVALID_ARGUMENT;
+    *out = nullptr;
+    if (A->dtype != dtype_of<T>::value) return SPRS_INVALID_ARGUMENT;
+    if (A->dist) {
+        snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_eigsh: distributed operators are not supported (single GPU only)");
+        return SPRS_INVALID_ARGUMENT;
+    }
+    if (A->nrows != A->ncols) return SPRS_NOT_SQUARE;
+    if ((int64_t)size != A->nrows) return SPRS_DIM_MISMATCH;
+    if (ncv == 0) ncv = std::min<size_t>(32, size);
+    if (ncv < 3 || ncv > std::min<size_t>(SPRS_EIGSH_MAX_NCV, size)) {
+        snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_eigsh: ncv = %zu is outside 3 .. min(%d, n = %zu)", ncv, SPRS_EIGSH_MAX_NCV, size);
+        return SPRS_INVALID_ARGUMENT;
+    }
+    CtxLock lock(A->ctx);
+    sprs_eigsh *h = new sprs_eigsh();
+    h->dtype = dtype_of<T>::value;
+    auto *s = new Eigsh<T>();
+    h->impl = s;
+    const int st = s->create(A, size, ncv);
+    if (st != SPRS_OK) { s->destroy(); delete s; delete h; return st; }
+    *out = h;
+    return SPRS_OK;
+}
+
+// One eigensolve.  v0 is copied into the basis and the vectors are written by the rotation kernel (device) or copied out of
+// the basis (host), so no alignment is asked of either.
+template <class T>
+int eigsh_solve(Eigsh<T> *s, bool host, size_t k, int which, const T *v0, size_t v0_len, size_t max_restarts, Real<T> tol, Real<T> *vals,
+                T *vecs, size_t vecs_len, Real<T> *res, size_t *nconv, size_t *restarts, size_t *matvecs) {
+    if (!s || !v0 || !vals || !res) return SPRS_INVALID_ARGUMENT;
+    if (k < 1 || k + 2 > (size_t)s->m || (which != SPRS_EIGSH_LARGEST && which != SPRS_EIGSH_SMALLEST) || max_restarts < 1)
+        return SPRS_INVALID_ARGUMENT;
+    if (v0_len != s->n) return SPRS_INCOMPATIBLE_RHS_SIZE;
+    if (vecs && vecs_len != k * s->n) return SPRS_INCOMPATIBLE_X_SIZE;
+    size_t dummy[3];
+    CtxLock lock(s->ctx);
+    return s->solve(k, which, v0, host, max_restarts, tol, vals, vecs, host, res, nconv ? nconv : dummy, restarts ? restarts : dummy + 1,
+                    matvecs ? matvecs : dummy + 2);
+}
+
 // the S<T> behind a handle, or null where the handle holds another scalar type
 template <template <class> class S, class T>
 S<T> *impl_of(sprs_solver_handle *h) { return (h && h->dtype == dtype_of<T>::value) ? (S<T> *)h->impl : nullptr; }
@@ -758,6 +802,7 @@ int sprs_cg_destroy(sprs_cg *S) { return solver_destroy<Cg>(S); }
 int sprs_gmres_destroy(sprs_gmres *S) { return solver_destroy<Gmres>(S); }
 int sprs_cgmany_destroy(sprs_cg_many *S) { return solver_destroy<CgMany>(S); }
 int sprs_lsmr_destroy(sprs_lsmr *S) { return solver_destroy<Lsmr>(S); }
+int sprs_eigsh_destroy(sprs_eigsh *S) { return solver_destroy<Eigsh>(S); }
 
 // ---- a solver's entry points per scalar type.  NAME = the handle is sprs_NAME, S = its class, CREATE = the arguments of S<T>::create
 #define SPRS_SOLVER_SOLVES(X, T, CT, R, NAME, S)                                                                       \
@@ -829,6 +874,16 @@ int sprs_lsmr_destroy(sprs_lsmr *S) { return solver_destroy<Lsmr>(S); }
     }                                                                                                                  \
     int sprs_lsmr_solve_dev_##X(sprs_lsmr *h, const CT *rhs, size_t rl, CT *x, size_t xl, R damp, size_t mi, R tol, size_t *its, R *res, R *ares) { \
         SPRS_G(return lsmr_solve<T>(impl_of<Lsmr, T>(h), false, (const T *)rhs, rl, (T *)x, xl, damp, mi, tol, its, res, ares);) \
+    }                                                                                                                  \
+    /* thick-restart Lanczos: ncv = the basis size (0 = min(32, n)) */                                                 \
+    int sprs_eigsh_create_##X(const sprs_csr *A, size_t n, size_t ncv, sprs_eigsh **out) { SPRS_G(return eigsh_create<T>(A, n, ncv, out);) } \
+    int sprs_eigsh_solve_##X(sprs_eigsh *h, size_t k, int which, const CT *v0, size_t vl, size_t mr, R tol, R *vals, CT *vecs, size_t xl, \
+                             R *res, size_t *nconv, size_t *restarts, size_t *matvecs) {                               \
+        SPRS_G(return eigsh_solve<T>(impl_of<Eigsh, T>(h), true, k, which, (const T *)v0, vl, mr, tol, vals, (T *)vecs, xl, res, nconv, restarts, matvecs);) \
+    }                                                                                                                  \
+    int sprs_eigsh_solve_dev_##X(sprs_eigsh *h, size_t k, int which, const CT *v0, size_t vl, size_t mr, R tol, R *vals, CT *vecs, size_t xl, \
+                                 R *res, size_t *nconv, size_t *restarts, size_t *matvecs) {                           \
+        SPRS_G(return eigsh_solve<T>(impl_of<Eigsh, T>(h), false, k, which, (const T *)v0, vl, mr, tol, vals, (T *)vecs, xl, res, nconv, restarts, matvecs);) \
     }                                                                                                                  \
     int sprs_dot_##X(sprs_ctx *c, size_t n, const CT *x, const CT *y, CT *o) { SPRS_CHK(c && o); return dot_host<T>(c, n, (const T *)x, (const T *)y, false, (T *)o); } \
     int sprs_conj_dot_##X(sprs_ctx *c, size_t n, const CT *x, const CT *y, CT *o) { SPRS_CHK(c && o); return dot_host<T>(c, n, (const T *)x, (const T *)y, true, (T *)o); } \

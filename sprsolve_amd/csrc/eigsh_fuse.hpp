@@ -1,0 +1,310 @@
+// Thick-restart Lanczos (sprs_eigsh_*): the kernels that are its own (the solver itself: Eigsh<T> in eigsh.hip).  No reference
+// analogue — the recurrence is the one stated in the header.  One Lanczos step j of a cycle:
+//   SpMV      w = A v_j                                                   (KrylovBase::spmv, any route, no fused dot)
+//   GmDots / GmUpdate / GmDots / GmUpdate<SECOND>                         (gmres_fuse.hpp, on LzState: CGS2 against v_0 .. v_j,
+//                                                                          w - sum v_i c_i into the slot of v_{j+1}, partials of its norm)
+//   LzStep    (one workgroup) T_jj, beta, the invariant-subspace threshold, T_{j+1,j}, the count of products ; sets `skip`
+//   GmScale   v_{j+1} *= 1 / beta
+// per cycle LzRitz (one workgroup: the eigenpairs of T by cyclic Jacobi in LDS, their order, res, anorm, nconv, the events, the
+// coefficient block S rounded to T::Real, the restarted T) and, where the host restarts, LzRotate (V[:, :p] <- V[:, :m] S[:, :p]
+// in place) ; per solve LzNrm + LzStart + GmScale before the first cycle and LzRotate once more for the eigenvectors.
+// The conventions are gmres_fuse.hpp's: partials re-reduced in the same order by every consumer, `status` ends the solve and
+// `skip` the rest of a cycle's blind launches, the host reads nothing but the head of the state (once a cycle).
+#pragma once
+#include "gmres_fuse.hpp"
+
+namespace sprs {
+
+constexpr int LZ_MAXM = SPRS_EIGSH_MAX_NCV;
+static_assert(LZ_MAXM <= GM_MAXM, "GmUpdate stages one coefficient per basis vector in an array of GM_MAXM");
+constexpr int LZ_LD = LZ_MAXM + 1;          // LzRitz's row stride in LDS (odd: a column walk meets every bank once)
+constexpr int LZ_MAX_SWEEPS = 30;
+
+// What the host reads (once a cycle) ...
+template <class T>
+struct LzHead {
+    int status, skip;
+    int nconv, m_eff;           // m_eff: rows of the projected problem (m, or j + 1 of the step that met an invariant subspace)
+    int invariant;
+    int k, which;               // set by the host per solve
+    long long matvecs, cycle;   // SpMVs that ran ; the cycle of the last step that ran (0: none)
+    Real<T> scale;              // 1 / beta0 or 1 / beta for GmScale
+    double beta, anorm, tscale, tol;
+};
+// ... what it reads besides when the solve is over (theta, res: everything before h) and the rest of the device-resident state.
+// T is real symmetric whatever the scalar type, and is kept in double.
+template <class T>
+struct LzState {
+    LzHead<T> hd;
+    double theta[LZ_MAXM], res[LZ_MAXM];     // the Ritz values in the order of `which` and their residual estimates
+    T h[LZ_MAXM];                            // GmUpdate's running column of CGS2 coefficients
+    double Tm[LZ_MAXM * LZ_MAXM];            // row-major, leading dimension LZ_MAXM
+    Real<T> coef[LZ_MAXM * LZ_MAXM];         // coef[i * LZ_MAXM + c] = S[i, c] rounded once to T::Real, columns in the order of `which`
+};
+
+// ---- LzNrm: partials of |v|^2 (the start vector, already in the slot of v_0)
+template <class T>
+struct LzNrm {
+    const T *v; Real<T> *partN;
+    Real<T> accN;
+    __device__ __forceinline__ bool prologue() { accN = 0.0; return true; }
+    template <int PK, bool NT> __device__ __forceinline__ void run(int64_t i) {
+        const auto xv = ldp<T, PK, NT>(v, i);
+#pragma unroll
+        for (int e = 0; e < PK; ++e) accN = accN + ssq(xv.v[e]);
+    }
+    __device__ __forceinline__ void epilogue() {
+        __shared__ Real<T> smD[NWAVE];
+        const Real<T> sN = block_sum(accN, smD);
+        if (threadIdx.x == 0) partN[blockIdx.x] = sN;
+    }
+};
+
+// LzStart: beta0 = |v0| from LzNrm's partials ; NaN or 0: breakdown ; scale = 1 / beta0 and the first cycle may run
+template <class T>
+__global__ __launch_bounds__(BLOCK) void lz_start_kernel(LzState<T> *S, const Real<T> *partN, int P) {
+    __shared__ Real<T> smD[NWAVE];
+    LzHead<T> &H = S->hd;
+    const Real<T> sN = reduce_partials(partN, P, smD);
+    if (threadIdx.x != 0) return;
+    const Real<T> beta0 = ssqrt(sN);
+    if (!(beta0 > Real<T>(0))) { H.skip = 1; H.status = ST_BREAKDOWN; return; }
+    H.scale = Real<T>(1) / beta0;
+    H.skip = 0;
+}
+
+// LzStep: step j of cycle `cycle`.  beta from GmUpdate<SECOND>'s partials, T_jj = Re(h_j), the threshold, the sub-diagonal.
+template <class T>
+__global__ __launch_bounds__(BLOCK) void lz_step_kernel(LzState<T> *S, const Real<T> *partN, int P, int j, int m, long long cycle) {
+    __shared__ Real<T> smD[NWAVE];
+    LzHead<T> &H = S->hd;
+    const int skip = H.skip;
+    const Real<T> sN = reduce_partials(partN, P, smD);
+    if (skip != 0 || threadIdx.x != 0) return;
+    const double beta = (double)ssqrt(sN), tjj = (double)sre(S->h[j]);
+    H.matvecs += 1; H.cycle = cycle;
+    if (!(beta >= 0.0)) { H.skip = 1; H.status = ST_BREAKDOWN; return; }
+    S->Tm[j * LZ_MAXM + j] = tjj;
+    double sc = fmax(H.tscale, fabs(tjj));
+    H.beta = beta;
+    if (beta <= 64.0 * (double)seps<Real<T>>() * sc) {      // an invariant subspace: v_{j+1} is not formed
+        H.tscale = sc; H.m_eff = j + 1; H.invariant = 1; H.skip = 1;
+        return;
+    }
+    sc = fmax(sc, beta);
+    H.tscale = sc;
+    if (j + 1 < m) { S->Tm[(j + 1) * LZ_MAXM + j] = beta; S->Tm[j * LZ_MAXM + j + 1] = beta; }
+    else H.m_eff = m;
+    H.scale = Real<T>(1) / ssqrt(sN);
+}
+
+// Round r of the round-robin pairing of M (even) indices: pair 0 is (M - 1, r), pair i is ((r + i) mod (M - 1),
+// (r - i) mod (M - 1)) — M / 2 disjoint pairs a round, every pair once in M - 1 rounds.  Returned with p < q.
+__device__ __forceinline__ void lz_pair(int i, int r, int M, int &p, int &q) {
+    int a, b;
+    if (i == 0) { a = M - 1; b = r; }
+    else { a = (r + i) % (M - 1); b = (r - i + (M - 1)) % (M - 1); }
+    p = a < b ? a : b; q = a < b ? b : a;
+}
+
+// LzRitz: (theta, S) of T[:m_eff, :m_eff] by cyclic Jacobi (round-robin order, the rotated entry set to exactly zero; stop at
+// off(T) <= eps |T|_F, LZ_MAX_SWEEPS sweeps at most, the cap being a breakdown), theta sorted for `which`, res, anorm, nconv,
+// the events, the coefficient block, the restarted T (p kept pairs + the arrow row).  Every element of T and S is updated by one
+// thread per phase and every sum has a fixed order: the result does not depend on timing.
+template <class T>
+__global__ __launch_bounds__(BLOCK) void lz_ritz_kernel(LzState<T> *S, int m, int p) {
+    __shared__ double sA[LZ_MAXM * LZ_LD], sV[LZ_MAXM * LZ_LD];
+    __shared__ double sc[LZ_MAXM / 2], ss[LZ_MAXM / 2], sth[LZ_MAXM], smD[NWAVE];
+    __shared__ int sperm[LZ_MAXM];
+    LzHead<T> &H = S->hd;
+    if (H.status != ST_RUNNING) return;
+    const int tid = threadIdx.x, me = H.m_eff, M = (me + 1) & ~1;
+    const int k = H.k, which = H.which, invariant = H.invariant;
+    const double beta = H.beta;
+    double fro = 0.0;
+    for (int e = tid; e < M * M; e += BLOCK) {
+        const int r = e / M, c = e % M;
+        const double a = (r < me && c < me) ? S->Tm[r * LZ_MAXM + c] : 0.0;     // (an odd m_eff: one idle index)
+        sA[r * LZ_LD + c] = a; sV[r * LZ_LD + c] = r == c ? 1.0 : 0.0;
+        fro += a * a;
+    }
+    const double fro2 = block_sum(fro, smD), eps = seps<double>();
+    int sweeps = 0;
+    bool conv = false;
+    for (;;) {
+        double off = 0.0;
+        for (int e = tid; e < M * M; e += BLOCK) {
+            const int r = e / M, c = e % M;
+            const double a = sA[r * LZ_LD + c];
+            if (r != c) off += a * a;
+        }
+        const double off2 = block_sum(off, smD);
+        if (off2 <= eps * eps * fro2) { conv = true; break; }
+        if (sweeps == LZ_MAX_SWEEPS) break;
+        for (int r = 0; r < M - 1; ++r) {
+            if (tid < M / 2) {
+                int pp, qq;
+                lz_pair(tid, r, M, pp, qq);
+                const double apq = sA[pp * LZ_LD + qq];
+                double c = 1.0, s = 0.0;
+                if (apq != 0.0) {
+                    const double tau = (sA[qq * LZ_LD + qq] - sA[pp * LZ_LD + pp]) / (2.0 * apq);
+                    const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
+                    c = 1.0 / sqrt(1.0 + t * t); s = t * c;
+                }
+                sc[tid] = c; ss[tid] = s;
+            }
+            __syncthreads();
+            for (int e = tid; e < M * (M / 2); e += BLOCK) {       // T <- T J, S <- S J
+                const int i = e / M, row = e % M;
+                int pp, qq;
+                lz_pair(i, r, M, pp, qq);
+                const double c = sc[i], s = ss[i];
+                const double ap = sA[row * LZ_LD + pp], aq = sA[row * LZ_LD + qq];
+                sA[row * LZ_LD + pp] = c * ap - s * aq; sA[row * LZ_LD + qq] = s * ap + c * aq;
+                const double vp = sV[row * LZ_LD + pp], vq = sV[row * LZ_LD + qq];
+                sV[row * LZ_LD + pp] = c * vp - s * vq; sV[row * LZ_LD + qq] = s * vp + c * vq;
+            }
+            __syncthreads();
+            for (int e = tid; e < M * (M / 2); e += BLOCK) {       // T <- J^T T
+                const int i = e / M, col = e % M;
+                int pp, qq;
+                lz_pair(i, r, M, pp, qq);
+                const double c = sc[i], s = ss[i];
+                const double ap = sA[pp * LZ_LD + col], aq = sA[qq * LZ_LD + col];
+                sA[pp * LZ_LD + col] = c * ap - s * aq; sA[qq * LZ_LD + col] = s * ap + c * aq;
+            }
+            __syncthreads();
+            if (tid < M / 2) {
+                int pp, qq;
+                lz_pair(tid, r, M, pp, qq);
+                sA[pp * LZ_LD + qq] = 0.0; sA[qq * LZ_LD + pp] = 0.0;
+            }
+            __syncthreads();
+        }
+        ++sweeps;
+    }
+    if (!conv) {
+        if (tid == 0) { H.skip = 1; H.status = ST_BREAKDOWN; }
+        return;
+    }
+    // the order of `which`: rank by value, ties by index
+    if (tid < me) {
+        const double ti = sA[tid * LZ_LD + tid];
+        int rank = 0;
+        for (int j = 0; j < me; ++j) {
+            const double tj = sA[j * LZ_LD + j];
+            const bool first = which == SPRS_EIGSH_LARGEST ? tj > ti : tj < ti;
+            rank += (first || (tj == ti && j < tid)) ? 1 : 0;
+        }
+        sperm[rank] = tid;
+    }
+    __syncthreads();
+    if (tid < me) {
+        const int i = sperm[tid];
+        const double th = sA[i * LZ_LD + i], rs = beta * fabs(sV[(me - 1) * LZ_LD + i]);
+        sth[tid] = th;
+        S->theta[tid] = th; S->res[tid] = rs;
+    }
+    __syncthreads();
+    for (int e = tid; e < me * me; e += BLOCK) {
+        const int i = e / me, c = e % me;
+        S->coef[i * LZ_MAXM + c] = (Real<T>)sV[i * LZ_LD + sperm[c]];
+    }
+    if (!invariant) {
+        // T <- diag(theta_0 .. theta_{p-1}), T_{p,i} = T_{i,p} = beta S[m-1, i] (i < p), zero elsewhere
+        for (int e = tid; e < me * me; e += BLOCK) {
+            const int r = e / me, c = e % me;
+            double v = 0.0;
+            if (r == c && r < p) v = sth[r];
+            else if (r == p && c < p) v = beta * sV[(me - 1) * LZ_LD + sperm[c]];
+            else if (c == p && r < p) v = beta * sV[(me - 1) * LZ_LD + sperm[r]];
+            S->Tm[r * LZ_MAXM + c] = v;
+        }
+    }
+    if (tid == 0) {
+        double an = H.anorm;
+        for (int i = 0; i < me; ++i) an = fmax(an, fabs(sth[i]));
+        int nc = 0;
+        const int kk = k < me ? k : me;
+        while (nc < kk && beta * fabs(sV[(me - 1) * LZ_LD + sperm[nc]]) <= H.tol * an) ++nc;
+        H.anorm = an;
+        if (invariant) {
+            if (me >= k) { H.nconv = k; H.status = ST_CONVERGED; }
+            else { H.nconv = nc; H.skip = 1; H.status = ST_BREAKDOWN; }
+        } else {
+            H.nconv = nc;
+            if (nc == k) { H.skip = 1; H.status = ST_CONVERGED; }
+        }
+    }
+}
+
+// ---- LzRotate: out[:, c] = sum_{i < me} V[:, i] coef[i, c] for c < q, from zero, i ascending; out may be V itself.
+// A workgroup stages the me x q coefficient block in LDS once, then takes tiles of 64 packs (16 bytes each: 64 rows of c64, 128
+// of f64 / c32, 256 of f32): it stages the tile of all me basis vectors in LDS (me KiB; coalesced 16-byte loads, non-temporal
+// where NT, all of a thread's loads in flight together) and only then, behind a barrier, forms and stores the q outputs — the
+// tile's rows are read by this workgroup alone, so no row of V is written before it has been read.  Lane l of every wavefront
+// owns pack l of the tile; wavefront w forms columns CB w .. CB w + CB - 1, CB (w + 4) .. : CB accumulator packs on one LDS
+// read of the tile, the coefficients read wave-uniformly (one broadcast LDS read per CB columns).  CB = 2 for q <= 8 (all four
+// wavefronts have columns), 4 beyond.
+template <class T, bool NT, int CB>
+__global__ __launch_bounds__(BLOCK) void lz_rotate_kernel(const Real<T> *__restrict__ cf, const T *V, int64_t vstride, int64_t n, int me, int q,
+                                                          T *out, int64_t ostride, int packed_out) {
+    constexpr int PK = pack_width<T>::value, R = WAVE * PK;
+    extern __shared__ __align__(16) unsigned char lz_tile_raw[];
+    Pack<T, PK> *tile = reinterpret_cast<Pack<T, PK> *>(lz_tile_raw);                           // [me][WAVE] packs
+    Real<T> *cfs = reinterpret_cast<Real<T> *>(lz_tile_raw + (size_t)me * WAVE * 16);           // [me][qp], columns q .. qp - 1 zero
+    const int qp = (q + CB - 1) / CB * CB;
+    for (int e = threadIdx.x; e < me * qp; e += BLOCK) {
+        const int i = e / qp, c = e % qp;
+        cfs[e] = c < q ? cf[i * LZ_MAXM + c] : Real<T>(0);
+    }
+    const int lane = threadIdx.x & (WAVE - 1), wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t ntile = (n + R - 1) / R;
+    for (int64_t t = blockIdx.x; t < ntile; t += gridDim.x) {
+        const int64_t pack0 = t * WAVE;
+#pragma unroll 8
+        for (int id = threadIdx.x; id < me * WAVE; id += BLOCK) {
+            const int i = id >> 6, l = id & (WAVE - 1);
+            Pack<T, PK> v;
+#pragma unroll
+            for (int e = 0; e < PK; ++e) v.v[e] = szero<T>();
+            if ((pack0 + l) * PK < n) v = ldp<T, PK, NT>(V + (int64_t)i * vstride, pack0 + l);    // (the basis is padded to whole packs)
+            tile[id] = v;
+        }
+        __syncthreads();
+        const int64_t row = (pack0 + lane) * PK;
+        for (int c0 = wv * CB; c0 < q; c0 += NWAVE * CB) {
+            Pack<T, PK> acc[CB];
+#pragma unroll
+            for (int b = 0; b < CB; ++b)
+#pragma unroll
+                for (int e = 0; e < PK; ++e) acc[b].v[e] = szero<T>();
+#pragma unroll 4
+            for (int i = 0; i < me; ++i) {
+                const Pack<T, PK> v = tile[i * WAVE + lane];
+                const Real<T> *s = cfs + i * qp + c0;
+#pragma unroll
+                for (int b = 0; b < CB; ++b) {
+                    const Real<T> sb = s[b];
+#pragma unroll
+                    for (int e = 0; e < PK; ++e) acc[b].v[e] = sadd(acc[b].v[e], smulr(v.v[e], sb));
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < CB; ++b) {
+                if (c0 + b >= q) break;
+                T *o = out + (int64_t)(c0 + b) * ostride;
+                if (packed_out && row + PK <= n) stp<T, PK, NT>(o, pack0 + lane, acc[b]);
+                else {
+#pragma unroll
+                    for (int e = 0; e < PK; ++e)
+                        if (row + e < n) o[row + e] = acc[b].v[e];
+                }
+            }
+        }
+        __syncthreads();     // the tile is overwritten by the next one
+    }
+}
+
+}  // namespace sprs

@@ -67,9 +67,10 @@ __device__ __forceinline__ void reduce_coefs(const T *__restrict__ part, int64_t
 }
 
 // ---- GmDots: partials of conj(v_{i0 + b}).w for b < nb <= B, one pass over w and the nb basis vectors
-template <class T, int B>
+// (H: the head that carries `skip` — GMRES's, or the Lanczos eigensolver's LzHead of eigsh_fuse.hpp)
+template <class T, int B, class H = GmresHead<T>>
 struct GmDots {
-    const GmresHead<T> *S; const T *V; int64_t vstride; int i0, nb; const T *w; T *part; int pstride;
+    const H *S; const T *V; int64_t vstride; int i0, nb; const T *w; T *part; int pstride;
     T acc[B];
     __device__ __forceinline__ bool prologue() {
         if (S->skip != 0) return false;
@@ -104,9 +105,10 @@ struct GmDots {
 
 // ---- GmUpdate: the j + 1 coefficients from their partials, then out = w - sum v_i coef_i in one pass.
 // SECOND: pass 2 — h_i += c_i in the state, out is the slot of v_{j+1}, partials of |out|^2 for GmStep.
-template <class T, bool SECOND>
+// (St: the state that carries hd.skip and the column h — GMRES's, or LzState of eigsh_fuse.hpp)
+template <class T, bool SECOND, class St = GmresState<T>>
 struct GmUpdate {
-    GmresState<T> *S; const T *part; int64_t pstride; int P; int j;
+    St *S; const T *part; int64_t pstride; int P; int j;
     const T *V; int64_t vstride; const T *w; T *out; Real<T> *partN; Fin fin;
     T *cf; Real<T> accN;
     __device__ __forceinline__ bool prologue() {
@@ -185,9 +187,9 @@ struct GmResid {
 };
 
 // ---- GmScale: v *= scale (1 / beta, 1 / hn: recorded by GmStart / GmStep, launches of their own)
-template <class T>
+template <class T, class H = GmresHead<T>>
 struct GmScale {
-    const GmresHead<T> *S; T *v;
+    const H *S; T *v;
     Real<T> a;
     __device__ __forceinline__ bool prologue() {
         const int skip = S->skip;

@@ -1,8 +1,9 @@
 // Krylov recurrences (host side, C++) over device-resident vectors and scalars: the solver objects behind sprs_bicgstab,
-// sprs_minres / sprs_csminres, sprs_cg, sprs_gmres, sprs_cg_many and sprs_lsmr.  One translation unit per solver (bicgstab.hip, minres.hip,
-// cg.hip, gmres.hip, cg_many.hip, lsmr.hip), each with its recurrence comment; its kernels are the functors of its *_fuse.hpp, all run by
+// sprs_minres / sprs_csminres, sprs_cg, sprs_gmres, sprs_cg_many, sprs_lsmr and sprs_eigsh.  One translation unit per solver (bicgstab.hip,
+// minres.hip, cg.hip, gmres.hip, cg_many.hip, lsmr.hip, eigsh.hip), each with its recurrence comment; its kernels are the functors of its *_fuse.hpp, all run by
 // fused_kernel (fused_launch.hpp).  BiCGStab and MINRES / CSMINRES follow the reference (src/bicg_stab.rs, src/minres.rs,
-// src/cs_minres.rs); CG, GMRES, the batched CG and LSMR have no reference analogue: include/sprsolve_hip.h states their recurrences.
+// src/cs_minres.rs); CG, GMRES, the batched CG, LSMR and the Lanczos eigensolver have no reference analogue: include/sprsolve_hip.h
+// states their recurrences.
 //
 // Two execution modes per solver (sprs_solver_set_mode; the batched CG is fused only):
 //  * fused (default): the full-vector passes of an iteration are regrouped into a few kernels (BiCGStab 13 passes -> 5 kernels,
@@ -275,6 +276,30 @@ class Gmres : public KrylovBase<T> {
     int run_literal(const Prec<T, V> &M, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
 };
 
+// Thick-restart Lanczos for the extreme eigenpairs of a Hermitian A (recurrence: include/sprsolve_hip.h, sprs_eigsh_*; kernels:
+// eigsh_fuse.hpp and GMRES's multi-vector Gram-Schmidt).  Single GPU, one mode; of KrylovBase it uses the work vectors, the
+// partial slots and spmv() — no literal mode, trace or profile.
+template <class T> struct LzState;      // eigsh_fuse.hpp
+template <class T>
+class Eigsh : public KrylovBase<T> {
+   public:
+    StateBlock<LzState<T>> state;        // the host pushes its head and reads the head once a cycle
+    int m = 32;                          // ncv: the basis size
+    T *dots = nullptr;                   // [m][dots_grid] partials of the multi-dots
+    int dots_grid = 0;
+    int create(const sprs_csr *A, size_t size, size_t ncv);
+    void destroy();
+    // v0: n entries (host where v0_host); vecs: k contiguous vectors of n entries or null (host where vecs_host: the basis is
+    // rotated in place and copied out; device: LzRotate writes them, any alignment); vals / res / the counters: host
+    int solve(size_t k, int which, const T *v0, bool v0_host, size_t max_restarts, Real<T> tol, Real<T> *vals_out, T *vecs, bool vecs_host,
+              Real<T> *res_out, size_t *nconv_out, size_t *restarts_out, size_t *matvecs_out);
+
+   private:
+    T *basis(int i) { return this->vec(i); }                 // v_0 .. v_m
+    T *wvec() { return this->vec(m + 1); }
+    int rotate(int me, int q, T *out, int64_t ostride);      // out[:, :q] = V[:, :me] S[:, :q]
+};
+
 // LSMR for min |rhs - A x|_2 (+ damping) on any A, rectangular included (recurrence: include/sprsolve_hip.h, sprs_lsmr_*; kernels:
 // lsmr_fuse.hpp).  Two operators and two vector lengths: KrylovBase carries A, the m = rows side (u, w) and everything that
 // is not tied to a length (context, poll, trace, profile, partial slots); the n = cols side (v, w', h, hbar) is held here.
@@ -441,3 +466,4 @@ struct sprs_cg : sprs_solver_handle {};
 struct sprs_gmres : sprs_solver_handle {};
 struct sprs_cg_many : sprs_solver_handle {};
 struct sprs_lsmr : sprs_solver_handle {};
+struct sprs_eigsh : sprs_solver_handle {};
