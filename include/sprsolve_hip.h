@@ -1110,6 +1110,91 @@ int sprs_eigsh_solve_dev_z(sprs_eigsh *S, size_t k, int which, const sprs_c64 *v
 int sprs_eigsh_solve_dev_s(sprs_eigsh *S, size_t k, int which, const float *v0_dev, size_t v0_len, size_t max_restarts, float tol, float *vals_out, float *vecs_dev_or_null, size_t vecs_len, float *res_out, size_t *nconv_out, size_t *restarts_out, size_t *matvecs_out);
 int sprs_eigsh_solve_dev_c(sprs_eigsh *S, size_t k, int which, const sprs_c32 *v0_dev, size_t v0_len, size_t max_restarts, float tol, float *vals_out, sprs_c32 *vecs_dev_or_null, size_t vecs_len, float *res_out, size_t *nconv_out, size_t *restarts_out, size_t *matvecs_out);
 
+/* ---------------------------------------------------------------- preconditioned block eigensolver (LOBPCG)
+ * The k algebraically smallest or largest eigenpairs of a square A that is assumed Hermitian (not checked), by locally optimal
+ * block preconditioned conjugate gradients (Knyazev) on a block of b vectors, 1 <= b <= SPRS_LOBPCG_MAX_BLOCK and 6 b <= n, with
+ * a Rayleigh-Ritz step on [X, P, W] per iteration.  The preconditioner M (Hermitian positive definite, about A^-1 for the
+ * smallest pairs) is nothing, a sprs_diag, or an ILU(0), AMG or FSAI handle.  The reference has no such solver.  Single GPU: a
+ * distributed A is refused with SPRS_INVALID_ARGUMENT (text in sprs_last_error).  The handle owns 6 b contiguous vectors:
+ * X, P, W, AX, AP, AW.  A solve wants the first k <= b pairs in the order of `which` (SPRS_EIGSH_LARGEST / _SMALLEST); the other
+ * b - k columns are guard vectors.
+ * Vectors, the Gram sums and the coefficients C are of type T; G, K, L, K^, Z, theta, s, res, anorm are double (complex double
+ * for complex T) for all four scalar types.  conj_dot(a, b) = sum conj(a_i) b_i.
+ *   start:  X = X0 (b vectors);  AX_c = A X_c;  one Rayleigh-Ritz step (below) on S = [X], AS = [AX], m = b:
+ *           X = S C, AX = AS C, theta = its b Ritz values;  P = AP = 0
+ *   iteration it = 1, 2, ...:
+ *     1. r_c = AX_c - theta_c X_c for c < b, theta_c rounded once to T::Real;  res_c = norm2(r_c), the square root taken in
+ *        T::Real of a sum of squares formed in T::Real;  a NaN: SPRS_BREAKDOWN
+ *     2. nconv = the number of LEADING c < k with res_c <= tol anorm, anorm = the largest |Ritz value| of any projected problem
+ *        so far (all of a problem's Ritz values, not only the first b).  nconv == k: SPRS_OK with iters = it - 1.
+ *        it > max_iter: SPRS_INSUFFICIENT_ITER with iters = max_iter (the outputs are the current leading k pairs)
+ *     3. W_c = M r_c (W_c = r_c without a preconditioner; a diagonal M inside the residual kernel, an applied one in place)
+ *     4. AW_c = A W_c
+ *     5. Rayleigh-Ritz on S = [X, P, W], AS = [AX, AP, AW], m = 3 b;  at it = 1: S = [X, W], m = 2 b
+ *        (1) G = S^H S, K = S^H AS from their upper triangles (G_ij = conj_dot(S_i, S_j), K_ij = conj_dot(S_i, AS_j), i <= j,
+ *            summed in T), the lower triangles their conjugates, the diagonals real
+ *        (2) s_i = G_ii^(-1/2);  G^ = diag(s) G diag(s).  A G_ii that is not a positive finite number: failure
+ *        (3) Cholesky G^ = L L^H, column by column.  Failure when a pivot G^_jj - sum_q |L_jq|^2 (= L_jj^2) is not greater than
+ *            64 m eps(T::Real)
+ *        (4) failure with P in the basis: steps (2) - (8) once more on the [X, W] sub-blocks of G and K (m = 2 b), the P rows
+ *            of C zero, restarts += 1.  Failure without P: SPRS_BREAKDOWN
+ *        (5) K^ = L^-1 diag(s) K diag(s) L^-H, taken Hermitian from its upper triangle with a real diagonal
+ *        (6) K^ = Z Theta Z^H by cyclic Jacobi: the order and stopping rule of sprs_eigsh_* (round-robin pairs on m rounded up
+ *            to even, off^2 <= eps^2 |K^|_F^2 before every sweep, 30 sweeps, then SPRS_BREAKDOWN).  With u = K^_pq / |K^_pq|,
+ *            tau = (K^_qq - K^_pp) / (2 |K^_pq|), t, c, s as there and sc = s u:  columns x_p' = c x_p - conj(sc) x_q,
+ *            x_q' = sc x_p + c x_q on K^ and Z;  rows row_p' = c row_p - sc row_q, row_q' = conj(sc) row_p + c row_q on K^;
+ *            then K^_pq = K^_qp = 0 and Im K^_pp = Im K^_qq = 0 exactly
+ *        (7) Theta ascending (SMALLEST) or descending (LARGEST), ties by index, the columns of Z with it
+ *        (8) C = diag(s) L^-H Z;  anorm = max(anorm, max_i |Theta_i|)
+ *     6. C_X = the first b columns of C, C_P = C_X with its X rows zero, both rounded once to T:
+ *        X = S C_X, P = S C_P, AX = AS C_X, AP = AS C_P (every element summed over the rows of C ascending from zero, one product
+ *        and one sum per term, each rounded once);  theta = the first b entries of Theta
+ * A NaN anywhere ends the solve with SPRS_BREAKDOWN, and so does a zero column of X0 (G_ii = 0 at the start) or a start block of
+ * deficient rank (the Cholesky rule).  matvecs = b (iters + 1) on SPRS_OK and SPRS_INSUFFICIENT_ITER.
+ * outputs:  vals_i = theta_i and res_i (absolute) for i < k, rounded to T::Real;  X_0 .. X_{k-1} as k contiguous vectors of n
+ *           (vecs may be NULL);  nconv, iters, restarts (the [X, W] fallbacks), matvecs.  On SPRS_BREAKDOWN vecs is not written.
+ * create:   block = 0 means min(8, n / 6);  SPRS_INVALID_ARGUMENT (text in sprs_last_error) for block > 8, 6 block > n, a
+ *           distributed A or another scalar type;  SPRS_NOT_SQUARE;  SPRS_DIM_MISMATCH for size != rows.
+ * solve:    SPRS_INVALID_ARGUMENT unless 1 <= k <= block, which is one of the two and max_iter >= 1;  X0 NULL selects the default
+ *           block (column c: U[-1, 1) from the library's splitmix64 streams 100 + 2 c, the imaginary parts 101 + 2 c), else
+ *           SPRS_INCOMPATIBLE_RHS_SIZE for x0_len != block n;  SPRS_INCOMPATIBLE_X_SIZE for a non-null vecs with
+ *           vecs_len != k n.  vals_out and res_out hold k entries; the four counters may be NULL.  A sprs_diag of another size:
+ *           SPRS_DIM_MISMATCH, of another scalar type: SPRS_INVALID_ARGUMENT.
+ * Not provided for this solver: a literal mode, the trace, the profile hooks and a sprs_solver_* kind.
+ * Limits: there is no soft locking, converged columns stay in the iteration; with k = block (no guard vectors) convergence can
+ * take ten times the iterations, so choose block > k; the block is at most 8 wide; the host does not wait inside an
+ * iteration, so up to `poll` iterations' launches run as no-ops after the event. */
+typedef struct sprs_lobpcg sprs_lobpcg;
+#define SPRS_LOBPCG_MAX_BLOCK 8
+int sprs_lobpcg_destroy(sprs_lobpcg *S);       /* NULL is a no-op */
+int sprs_lobpcg_create_d(const sprs_csr *A, size_t size, size_t block, sprs_lobpcg **out);
+int sprs_lobpcg_create_z(const sprs_csr *A, size_t size, size_t block, sprs_lobpcg **out);
+int sprs_lobpcg_create_s(const sprs_csr *A, size_t size, size_t block, sprs_lobpcg **out);
+int sprs_lobpcg_create_c(const sprs_csr *A, size_t size, size_t block, sprs_lobpcg **out);
+int sprs_lobpcg_solve_d(sprs_lobpcg *S, const sprs_diag *P_or_null, size_t k, int which, const double *X0_or_null, size_t x0_len, size_t max_iter, double tol, double *vals_out, double *vecs_out_or_null, size_t vecs_len, double *res_out, size_t *nconv_out, size_t *iters_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_lobpcg_solve_z(sprs_lobpcg *S, const sprs_diag *P_or_null, size_t k, int which, const sprs_c64 *X0_or_null, size_t x0_len, size_t max_iter, double tol, double *vals_out, sprs_c64 *vecs_out_or_null, size_t vecs_len, double *res_out, size_t *nconv_out, size_t *iters_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_lobpcg_solve_s(sprs_lobpcg *S, const sprs_diag *P_or_null, size_t k, int which, const float *X0_or_null, size_t x0_len, size_t max_iter, float tol, float *vals_out, float *vecs_out_or_null, size_t vecs_len, float *res_out, size_t *nconv_out, size_t *iters_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_lobpcg_solve_c(sprs_lobpcg *S, const sprs_diag *P_or_null, size_t k, int which, const sprs_c32 *X0_or_null, size_t x0_len, size_t max_iter, float tol, float *vals_out, sprs_c32 *vecs_out_or_null, size_t vecs_len, float *res_out, size_t *nconv_out, size_t *iters_out, size_t *restarts_out, size_t *matvecs_out);
+/* the same with X0 and vecs on the device (any alignment); vals, res and the counters stay on the host */
+int sprs_lobpcg_solve_dev_d(sprs_lobpcg *S, const sprs_diag *P_or_null, size_t k, int which, const double *X0_dev_or_null, size_t x0_len, size_t max_iter, double tol, double *vals_out, double *vecs_dev_or_null, size_t vecs_len, double *res_out, size_t *nconv_out, size_t *iters_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_lobpcg_solve_dev_z(sprs_lobpcg *S, const sprs_diag *P_or_null, size_t k, int which, const sprs_c64 *X0_dev_or_null, size_t x0_len, size_t max_iter, double tol, double *vals_out, sprs_c64 *vecs_dev_or_null, size_t vecs_len, double *res_out, size_t *nconv_out, size_t *iters_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_lobpcg_solve_dev_s(sprs_lobpcg *S, const sprs_diag *P_or_null, size_t k, int which, const float *X0_dev_or_null, size_t x0_len, size_t max_iter, float tol, float *vals_out, float *vecs_dev_or_null, size_t vecs_len, float *res_out, size_t *nconv_out, size_t *iters_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_lobpcg_solve_dev_c(sprs_lobpcg *S, const sprs_diag *P_or_null, size_t k, int which, const sprs_c32 *X0_dev_or_null, size_t x0_len, size_t max_iter, float tol, float *vals_out, sprs_c32 *vecs_dev_or_null, size_t vecs_len, float *res_out, size_t *nconv_out, size_t *iters_out, size_t *restarts_out, size_t *matvecs_out);
+/* ... preconditioned by an ILU(0), AMG or FSAI handle, checked as the Krylov solvers check it: SPRS_INVALID_ARGUMENT for a null handle,
+ * another scalar type or context, SPRS_DIM_MISMATCH for another size */
+int sprs_ilu0_lobpcg_solve_dev_d(sprs_lobpcg *S, const sprs_ilu0 *P, size_t k, int which, const double *X0_dev_or_null, size_t x0_len, size_t max_iter, double tol, double *vals_out, double *vecs_dev_or_null, size_t vecs_len, double *res_out, size_t *nconv_out, size_t *iters_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_ilu0_lobpcg_solve_dev_z(sprs_lobpcg *S, const sprs_ilu0 *P, size_t k, int which, const sprs_c64 *X0_dev_or_null, size_t x0_len, size_t max_iter, double tol, double *vals_out, sprs_c64 *vecs_dev_or_null, size_t vecs_len, double *res_out, size_t *nconv_out, size_t *iters_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_ilu0_lobpcg_solve_dev_s(sprs_lobpcg *S, const sprs_ilu0 *P, size_t k, int which, const float *X0_dev_or_null, size_t x0_len, size_t max_iter, float tol, float *vals_out, float *vecs_dev_or_null, size_t vecs_len, float *res_out, size_t *nconv_out, size_t *iters_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_ilu0_lobpcg_solve_dev_c(sprs_lobpcg *S, const sprs_ilu0 *P, size_t k, int which, const sprs_c32 *X0_dev_or_null, size_t x0_len, size_t max_iter, float tol, float *vals_out, sprs_c32 *vecs_dev_or_null, size_t vecs_len, float *res_out, size_t *nconv_out, size_t *iters_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_amg_lobpcg_solve_dev_d(sprs_lobpcg *S, const sprs_amg *P, size_t k, int which, const double *X0_dev_or_null, size_t x0_len, size_t max_iter, double tol, double *vals_out, double *vecs_dev_or_null, size_t vecs_len, double *res_out, size_t *nconv_out, size_t *iters_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_amg_lobpcg_solve_dev_z(sprs_lobpcg *S, const sprs_amg *P, size_t k, int which, const sprs_c64 *X0_dev_or_null, size_t x0_len, size_t max_iter, double tol, double *vals_out, sprs_c64 *vecs_dev_or_null, size_t vecs_len, double *res_out, size_t *nconv_out, size_t *iters_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_amg_lobpcg_solve_dev_s(sprs_lobpcg *S, const sprs_amg *P, size_t k, int which, const float *X0_dev_or_null, size_t x0_len, size_t max_iter, float tol, float *vals_out, float *vecs_dev_or_null, size_t vecs_len, float *res_out, size_t *nconv_out, size_t *iters_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_amg_lobpcg_solve_dev_c(sprs_lobpcg *S, const sprs_amg *P, size_t k, int which, const sprs_c32 *X0_dev_or_null, size_t x0_len, size_t max_iter, float tol, float *vals_out, sprs_c32 *vecs_dev_or_null, size_t vecs_len, float *res_out, size_t *nconv_out, size_t *iters_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_fsai_lobpcg_solve_dev_d(sprs_lobpcg *S, const sprs_fsai *P, size_t k, int which, const double *X0_dev_or_null, size_t x0_len, size_t max_iter, double tol, double *vals_out, double *vecs_dev_or_null, size_t vecs_len, double *res_out, size_t *nconv_out, size_t *iters_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_fsai_lobpcg_solve_dev_z(sprs_lobpcg *S, const sprs_fsai *P, size_t k, int which, const sprs_c64 *X0_dev_or_null, size_t x0_len, size_t max_iter, double tol, double *vals_out, sprs_c64 *vecs_dev_or_null, size_t vecs_len, double *res_out, size_t *nconv_out, size_t *iters_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_fsai_lobpcg_solve_dev_s(sprs_lobpcg *S, const sprs_fsai *P, size_t k, int which, const float *X0_dev_or_null, size_t x0_len, size_t max_iter, float tol, float *vals_out, float *vecs_dev_or_null, size_t vecs_len, float *res_out, size_t *nconv_out, size_t *iters_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_fsai_lobpcg_solve_dev_c(sprs_lobpcg *S, const sprs_fsai *P, size_t k, int which, const sprs_c32 *X0_dev_or_null, size_t x0_len, size_t max_iter, float tol, float *vals_out, sprs_c32 *vecs_dev_or_null, size_t vecs_len, float *res_out, size_t *nconv_out, size_t *iters_out, size_t *restarts_out, size_t *matvecs_out);
+
 /* ---------------------------------------------------------------- solver options / instrumentation
  * `solver` is a handle of any of the solver types below, `kind` says which. */
 enum { SPRS_SOLVER_BICGSTAB = 1, SPRS_SOLVER_MINRES = 2, SPRS_SOLVER_CSMINRES = 3, SPRS_SOLVER_CG = 4, SPRS_SOLVER_GMRES = 5, SPRS_SOLVER_LSMR = 6 };

@@ -16,6 +16,7 @@ from .gauss_seidel import GaussSeidel  # noqa: F401
 from .gmres import GMRES  # noqa: F401
 from .fsai import FSAI  # noqa: F401
 from .ilu import ILU0  # noqa: F401
+from .lobpcg import Lobpcg  # noqa: F401
 from .lsmr import LSMR  # noqa: F401
 from .device import Context, DevVec, default_ctx  # noqa: F401
 from .mat import HipCsr, MatVecMul  # noqa: F401

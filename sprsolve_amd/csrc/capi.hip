@@ -644,6 +644,76 @@ int eigsh_solve(Eigsh<T> *s, bool host, size_t k, int which, const T *v0, size_t
                     matvecs ? matvecs : dummy + 2);
 }
 
+// Lobpcg<T> behind a sprs_lobpcg: a square single-GPU A, block = 0 means min(8, n / 6)
+template <class T>
+int lobpcg_create(const sprs_csr *A, size_t size, size_t block, sprs_lobpcg **out) {
+    if (!A || !out) return SPRS_INVALID_ARGUMENT;
+    *out = nullptr;
+    if (A->dtype != dtype_of<T>::value) {
+        snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_lobpcg: the operator holds another scalar type");
+        return SPRS_INVALID_ARGUMENT;
+    }
+    if (A->dist) {
+        snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_lobpcg: distributed operators are not supported (single GPU only)");
+        return SPRS_INVALID_ARGUMENT;
+    }
+    if (A->nrows != A->ncols) return SPRS_NOT_SQUARE;
+    if ((int64_t)size != A->nrows) return SPRS_DIM_MISMATCH;
+    if (block == 0) block = std::min<size_t>(SPRS_LOBPCG_MAX_BLOCK, size / 6);
+    if (block < 1 || block > SPRS_LOBPCG_MAX_BLOCK || 6 * block > size) {
+        snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_lobpcg: block = %zu is outside 1 .. min(%d, n / 6 = %zu)", block, SPRS_LOBPCG_MAX_BLOCK, size / 6);
+        return SPRS_INVALID_ARGUMENT;
+    }
+    CtxLock lock(A->ctx);
+    sprs_lobpcg *h = new sprs_lobpcg();
+    h->dtype = dtype_of<T>::value;
+    auto *s = new Lobpcg<T>();
+    h->impl = s;
+    const int st = s->create(A, size, block);
+    if (st != SPRS_OK) { s->destroy(); delete s; delete h; return st; }
+    *out = h;
+    return SPRS_OK;
+}
+
+// The default start block: column c holds U[-1, 1) doubles from the top 53 bits of counter-based splitmix64, seed "PRSOLVE",
+// stream 100 + 2 c (the imaginary parts: stream 101 + 2 c), rounded to T — sprsolve_amd.gen.uniform's values.
+inline double lobpcg_uniform(uint64_t stream, uint64_t i) {
+    uint64_t z = 0x5052534F4C5645ull + stream * 0xD1B54A32D192ED03ull + (i + 1) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z = z ^ (z >> 31);
+    return -1.0 + 2.0 * ((double)(z >> 11) * (1.0 / 9007199254740992.0));
+}
+template <class T>
+void lobpcg_default_x0(size_t n, int b, std::vector<T> &X0) {
+    X0.resize(n * (size_t)b);
+    for (int c = 0; c < b; ++c)
+        for (size_t i = 0; i < n; ++i) {
+            T v = sfromr<T>((Real<T>)lobpcg_uniform(100 + 2 * (uint64_t)c, i));
+            if constexpr (is_complex<T>::value) v.im = (Real<T>)lobpcg_uniform(101 + 2 * (uint64_t)c, i);
+            X0[(size_t)c * n + i] = v;
+        }
+}
+
+// One LOBPCG solve.  X0 is copied into the work block and the vectors are written by the rotation kernel (device) or copied out
+// of the work block (host), so no alignment is asked of either.  prec: a sprs_diag (or null) or an applied handle's view.
+template <class T, class P>
+int lobpcg_solve(Lobpcg<T> *s, bool host, const P &prec, size_t k, int which, const T *X0, size_t x0_len, size_t max_iter, Real<T> tol,
+                 Real<T> *vals, T *vecs, size_t vecs_len, Real<T> *res, size_t *nconv, size_t *iters, size_t *restarts, size_t *matvecs) {
+    const Precond<T> M(prec);
+    if (!s || (M.is_applied && !M.applied.h) || !vals || !res) return SPRS_INVALID_ARGUMENT;
+    if (k < 1 || k > (size_t)s->b || (which != SPRS_EIGSH_LARGEST && which != SPRS_EIGSH_SMALLEST) || max_iter < 1) return SPRS_INVALID_ARGUMENT;
+    if (X0 && x0_len != (size_t)s->b * s->n) return SPRS_INCOMPATIBLE_RHS_SIZE;
+    if (vecs && vecs_len != k * s->n) return SPRS_INCOMPATIBLE_X_SIZE;
+    size_t dummy[4];
+    std::vector<T> def;
+    bool x0_host = host;
+    if (!X0) { lobpcg_default_x0<T>(s->n, s->b, def); X0 = def.data(); x0_host = true; }
+    CtxLock lock(s->ctx);
+    return s->solve_dev(M, k, which, X0, x0_host, max_iter, tol, vals, vecs, host, res, nconv ? nconv : dummy, iters ? iters : dummy + 1,
+                        restarts ? restarts : dummy + 2, matvecs ? matvecs : dummy + 3);
+}
+
 // the S<T> behind a handle, or null where the handle holds another scalar type
 template <template <class> class S, class T>
 S<T> *impl_of(sprs_solver_handle *h) { return (h && h->dtype == dtype_of<T>::value) ? (S<T> *)h->impl : nullptr; }
@@ -803,6 +873,7 @@ int sprs_gmres_destroy(sprs_gmres *S) { return solver_destroy<Gmres>(S); }
 int sprs_cgmany_destroy(sprs_cg_many *S) { return solver_destroy<CgMany>(S); }
 int sprs_lsmr_destroy(sprs_lsmr *S) { return solver_destroy<Lsmr>(S); }
 int sprs_eigsh_destroy(sprs_eigsh *S) { return solver_destroy<Eigsh>(S); }
+int sprs_lobpcg_destroy(sprs_lobpcg *S) { return solver_destroy<Lobpcg>(S); }
 
 // ---- a solver's entry points per scalar type.  NAME = the handle is sprs_NAME, S = its class, CREATE = the arguments of S<T>::create
 #define SPRS_SOLVER_SOLVES(X, T, CT, R, NAME, S)                                                                       \
@@ -885,6 +956,16 @@ int sprs_eigsh_destroy(sprs_eigsh *S) { return solver_destroy<Eigsh>(S); }
                                  R *res, size_t *nconv, size_t *restarts, size_t *matvecs) {                           \
         SPRS_G(return eigsh_solve<T>(impl_of<Eigsh, T>(h), false, k, which, (const T *)v0, vl, mr, tol, vals, (T *)vecs, xl, res, nconv, restarts, matvecs);) \
     }                                                                                                                  \
+    /* LOBPCG: block = the block size (0 = min(8, n / 6)) */                                                           \
+    int sprs_lobpcg_create_##X(const sprs_csr *A, size_t n, size_t block, sprs_lobpcg **out) { SPRS_G(return lobpcg_create<T>(A, n, block, out);) } \
+    int sprs_lobpcg_solve_##X(sprs_lobpcg *h, const sprs_diag *P, size_t k, int which, const CT *x0, size_t x0l, size_t mi, R tol, R *vals, CT *vecs, \
+                              size_t xl, R *res, size_t *nconv, size_t *iters, size_t *restarts, size_t *matvecs) {    \
+        SPRS_G(return lobpcg_solve<T>(impl_of<Lobpcg, T>(h), true, P, k, which, (const T *)x0, x0l, mi, tol, vals, (T *)vecs, xl, res, nconv, iters, restarts, matvecs);) \
+    }                                                                                                                  \
+    int sprs_lobpcg_solve_dev_##X(sprs_lobpcg *h, const sprs_diag *P, size_t k, int which, const CT *x0, size_t x0l, size_t mi, R tol, R *vals, CT *vecs, \
+                                  size_t xl, R *res, size_t *nconv, size_t *iters, size_t *restarts, size_t *matvecs) { \
+        SPRS_G(return lobpcg_solve<T>(impl_of<Lobpcg, T>(h), false, P, k, which, (const T *)x0, x0l, mi, tol, vals, (T *)vecs, xl, res, nconv, iters, restarts, matvecs);) \
+    }                                                                                                                  \
     int sprs_dot_##X(sprs_ctx *c, size_t n, const CT *x, const CT *y, CT *o) { SPRS_CHK(c && o); return dot_host<T>(c, n, (const T *)x, (const T *)y, false, (T *)o); } \
     int sprs_conj_dot_##X(sprs_ctx *c, size_t n, const CT *x, const CT *y, CT *o) { SPRS_CHK(c && o); return dot_host<T>(c, n, (const T *)x, (const T *)y, true, (T *)o); } \
     int sprs_norm2_##X(sprs_ctx *c, size_t n, const CT *x, R *o) { SPRS_CHK(c && o); return norm2_host<T>(c, n, (const T *)x, o); } \
@@ -933,13 +1014,20 @@ SPRS_API(c, cplxf, sprs_c32, float)
     int sprs_##PFX##_##NAME##_solve_dev_##X(sprs_##NAME *h, const sprs_##PFX *P, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
         SPRS_G(return solve<T>(impl_of<S, T>(h), false, PFX##_prec<T>(P), (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);) \
     }
+// LOBPCG preconditioned by such a handle: the device entry only
+#define SPRS_APPLIED_LOBPCG(X, T, CT, R, PFX)                                                                          \
+    int sprs_##PFX##_lobpcg_solve_dev_##X(sprs_lobpcg *h, const sprs_##PFX *P, size_t k, int which, const CT *x0, size_t x0l, size_t mi, R tol, R *vals, \
+                                          CT *vecs, size_t xl, R *res, size_t *nconv, size_t *iters, size_t *restarts, size_t *matvecs) { \
+        SPRS_G(return lobpcg_solve<T>(impl_of<Lobpcg, T>(h), false, PFX##_prec<T>(P), k, which, (const T *)x0, x0l, mi, tol, vals, (T *)vecs, xl, res, nconv, iters, restarts, matvecs);) \
+    }
 #define SPRS_APPLIED_API(X, T, CT, R)                                                                 \
     SPRS_APPLIED_SOLVES(X, T, CT, R, cg, Cg, ilu0) SPRS_APPLIED_SOLVES(X, T, CT, R, gmres, Gmres, ilu0) \
     SPRS_APPLIED_SOLVES(X, T, CT, R, cg, Cg, amg) SPRS_APPLIED_SOLVES(X, T, CT, R, gmres, Gmres, amg) \
     SPRS_APPLIED_SOLVES(X, T, CT, R, bicgstab, BicgStab, ilu0) SPRS_APPLIED_SOLVES(X, T, CT, R, minres, MinRes, ilu0) \
     SPRS_APPLIED_SOLVES(X, T, CT, R, bicgstab, BicgStab, amg) SPRS_APPLIED_SOLVES(X, T, CT, R, minres, MinRes, amg) \
     SPRS_APPLIED_SOLVES(X, T, CT, R, cg, Cg, fsai) SPRS_APPLIED_SOLVES(X, T, CT, R, gmres, Gmres, fsai) \
-    SPRS_APPLIED_SOLVES(X, T, CT, R, bicgstab, BicgStab, fsai) SPRS_APPLIED_SOLVES(X, T, CT, R, minres, MinRes, fsai)
+    SPRS_APPLIED_SOLVES(X, T, CT, R, bicgstab, BicgStab, fsai) SPRS_APPLIED_SOLVES(X, T, CT, R, minres, MinRes, fsai) \
+    SPRS_APPLIED_LOBPCG(X, T, CT, R, ilu0) SPRS_APPLIED_LOBPCG(X, T, CT, R, amg) SPRS_APPLIED_LOBPCG(X, T, CT, R, fsai)
 SPRS_APPLIED_API(d, double, double, double)
 SPRS_APPLIED_API(z, cplx, sprs_c64, double)
 SPRS_APPLIED_API(s, float, float, float)

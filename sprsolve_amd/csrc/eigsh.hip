@@ -30,31 +30,10 @@ void Eigsh<T>::destroy() {
     KrylovBase<T>::destroy();
 }
 
-// out[:, c] = sum_i V[:, i] S[i, c], c < q, i < me: one LzRotate launch; LDS a workgroup: me KiB of tile + the coefficient block
+// out[:, c] = sum_i V[:, i] S[i, c], c < q, i < me: one LzRotate launch
 template <class T>
 int Eigsh<T>::rotate(int me, int q, T *out, int64_t ostride) {
-    sprs_ctx *c = this->ctx;
-    constexpr int PK = pack_width<T>::value;
-    const int64_t n = (int64_t)this->n, ntile = (n + WAVE * PK - 1) / (WAVE * PK);
-    const int cb = q <= 8 ? 2 : 4, qp = (q + cb - 1) / cb * cb;
-    const size_t lds = (size_t)me * WAVE * 16 + (size_t)me * qp * sizeof(Real<T>);
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, ((size_t)160 << 10) / lds));    // workgroups a CU's 160 KiB of LDS holds
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ntile, (int64_t)c->num_cu * per_cu));
-    const int packed = (aligned16(out) && (ostride * (int64_t)sizeof(T)) % 16 == 0) ? 1 : 0;
-    const Real<T> *cf = state.dev->coef;
-    const bool nt = stream_loads_nt(c, this->n * sizeof(T));
-    hipError_t attr = hipSuccess;
-    auto launch = [&](auto kernel) {
-        // more dynamic LDS than the default 64 KiB limit of a launch (ncv near 64): raise the kernel's limit first
-        if (lds > ((size_t)64 << 10)) attr = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
-        if (attr != hipSuccess) return;
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), lds, c->stream, cf, (const T *)basis(0), (int64_t)this->stride, n, me, q, out, ostride, packed);
-    };
-    if (cb == 2) { if (nt) launch(lz_rotate_kernel<T, true, 2>); else launch(lz_rotate_kernel<T, false, 2>); }
-    else { if (nt) launch(lz_rotate_kernel<T, true, 4>); else launch(lz_rotate_kernel<T, false, 4>); }
-    SPRS_HIP_TRY(c, attr);
-    SPRS_HIP_TRY(c, hipGetLastError());
-    return SPRS_OK;
+    return launch_lz_rotate<T, Real<T>>(this->ctx, (const Real<T> *)state.dev->coef, (const T *)basis(0), (int64_t)this->stride, (int64_t)this->n, me, q, out, ostride);
 }
 
 template <class T>

@@ -11,6 +11,8 @@
 // The conventions are gmres_fuse.hpp's: partials re-reduced in the same order by every consumer, `status` ends the solve and
 // `skip` the rest of a cycle's blind launches, the host reads nothing but the head of the state (once a cycle).
 #pragma once
+#include <algorithm>
+
 #include "gmres_fuse.hpp"
 
 namespace sprs {
@@ -247,17 +249,23 @@ __global__ __launch_bounds__(BLOCK) void lz_ritz_kernel(LzState<T> *S, int m, in
 // owns pack l of the tile; wavefront w forms columns CB w .. CB w + CB - 1, CB (w + 4) .. : CB accumulator packs on one LDS
 // read of the tile, the coefficients read wave-uniformly (one broadcast LDS read per CB columns).  CB = 2 for q <= 8 (all four
 // wavefronts have columns), 4 beyond.
-template <class T, bool NT, int CB>
-__global__ __launch_bounds__(BLOCK) void lz_rotate_kernel(const Real<T> *__restrict__ cf, const T *V, int64_t vstride, int64_t n, int me, int q,
-                                                          T *out, int64_t ostride, int packed_out) {
+// CF: the coefficients' type, T::Real (Lanczos: S is real for complex A too) or T (LOBPCG, lobpcg_fuse.hpp).  Guard: nothing, or
+// one `const int *` to a status word — a launch enqueued blind returns at once unless it reads ST_RUNNING.
+template <class T, bool NT, int CB, class CF = Real<T>, class... Guard>
+__global__ __launch_bounds__(BLOCK) void lz_rotate_kernel(const CF *__restrict__ cf, const T *V, int64_t vstride, int64_t n, int me, int q,
+                                                          T *out, int64_t ostride, int packed_out, Guard... guard) {
     constexpr int PK = pack_width<T>::value, R = WAVE * PK;
+    if constexpr (sizeof...(Guard) != 0) {
+        const int *const g[] = {guard...};
+        if (*g[0] != ST_RUNNING) return;
+    }
     extern __shared__ __align__(16) unsigned char lz_tile_raw[];
     Pack<T, PK> *tile = reinterpret_cast<Pack<T, PK> *>(lz_tile_raw);                           // [me][WAVE] packs
-    Real<T> *cfs = reinterpret_cast<Real<T> *>(lz_tile_raw + (size_t)me * WAVE * 16);           // [me][qp], columns q .. qp - 1 zero
+    CF *cfs = reinterpret_cast<CF *>(lz_tile_raw + (size_t)me * WAVE * 16);                     // [me][qp], columns q .. qp - 1 zero
     const int qp = (q + CB - 1) / CB * CB;
     for (int e = threadIdx.x; e < me * qp; e += BLOCK) {
         const int i = e / qp, c = e % qp;
-        cfs[e] = c < q ? cf[i * LZ_MAXM + c] : Real<T>(0);
+        cfs[e] = c < q ? cf[i * LZ_MAXM + c] : CF{};
     }
     const int lane = threadIdx.x & (WAVE - 1), wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t ntile = (n + R - 1) / R;
@@ -283,12 +291,12 @@ __global__ __launch_bounds__(BLOCK) void lz_rotate_kernel(const Real<T> *__restr
 #pragma unroll 4
             for (int i = 0; i < me; ++i) {
                 const Pack<T, PK> v = tile[i * WAVE + lane];
-                const Real<T> *s = cfs + i * qp + c0;
+                const CF *s = cfs + i * qp + c0;
 #pragma unroll
                 for (int b = 0; b < CB; ++b) {
-                    const Real<T> sb = s[b];
+                    const CF sb = s[b];
 #pragma unroll
-                    for (int e = 0; e < PK; ++e) acc[b].v[e] = sadd(acc[b].v[e], smulr(v.v[e], sb));
+                    for (int e = 0; e < PK; ++e) acc[b].v[e] = sadd(acc[b].v[e], smulv(v.v[e], sb));
                 }
             }
 #pragma unroll
@@ -305,6 +313,32 @@ __global__ __launch_bounds__(BLOCK) void lz_rotate_kernel(const Real<T> *__restr
         }
         __syncthreads();     // the tile is overwritten by the next one
     }
+}
+
+// One LzRotate launch on the context's stream: out[:, c] = sum_{i < me} V[:, i] cf[i * LZ_MAXM + c], c < q.  LDS a workgroup: me KiB
+// of tile + the coefficient block.
+template <class T, class CF, class... Guard>
+static int launch_lz_rotate(sprs_ctx *c, const CF *cf, const T *V, int64_t vstride, int64_t n, int me, int q, T *out, int64_t ostride, Guard... guard) {
+    constexpr int PK = pack_width<T>::value;
+    const int64_t ntile = (n + WAVE * PK - 1) / (WAVE * PK);
+    const int cb = q <= 8 ? 2 : 4, qp = (q + cb - 1) / cb * cb;
+    const size_t lds = (size_t)me * WAVE * 16 + (size_t)me * qp * sizeof(CF);
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, ((size_t)160 << 10) / lds));    // workgroups a CU's 160 KiB of LDS holds
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ntile, (int64_t)c->num_cu * per_cu));
+    const int packed = (aligned16(out) && (ostride * (int64_t)sizeof(T)) % 16 == 0) ? 1 : 0;
+    const bool nt = stream_loads_nt(c, (size_t)n * sizeof(T));
+    hipError_t attr = hipSuccess;
+    auto launch = [&](auto kernel) {
+        // more dynamic LDS than the default 64 KiB limit of a launch (ncv near 64): raise the kernel's limit first
+        if (lds > ((size_t)64 << 10)) attr = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
+        if (attr != hipSuccess) return;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), lds, c->stream, cf, V, vstride, n, me, q, out, ostride, packed, guard...);
+    };
+    if (cb == 2) { if (nt) launch(lz_rotate_kernel<T, true, 2, CF, Guard...>); else launch(lz_rotate_kernel<T, false, 2, CF, Guard...>); }
+    else { if (nt) launch(lz_rotate_kernel<T, true, 4, CF, Guard...>); else launch(lz_rotate_kernel<T, false, 4, CF, Guard...>); }
+    SPRS_HIP_TRY(c, attr);
+    SPRS_HIP_TRY(c, hipGetLastError());
+    return SPRS_OK;
 }
 
 }  // namespace sprs

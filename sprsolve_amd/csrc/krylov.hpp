@@ -1,6 +1,6 @@
 // Krylov recurrences (host side, C++) over device-resident vectors and scalars: the solver objects behind sprs_bicgstab,
-// sprs_minres / sprs_csminres, sprs_cg, sprs_gmres, sprs_cg_many, sprs_lsmr and sprs_eigsh.  One translation unit per solver (bicgstab.hip,
-// minres.hip, cg.hip, gmres.hip, cg_many.hip, lsmr.hip, eigsh.hip), each with its recurrence comment; its kernels are the functors of its *_fuse.hpp, all run by
+// sprs_minres / sprs_csminres, sprs_cg, sprs_gmres, sprs_cg_many, sprs_lsmr, sprs_eigsh and sprs_lobpcg.  One translation unit per solver (bicgstab.hip,
+// minres.hip, cg.hip, gmres.hip, cg_many.hip, lsmr.hip, eigsh.hip, lobpcg.hip), each with its recurrence comment; its kernels are the functors of its *_fuse.hpp, all run by
 // fused_kernel (fused_launch.hpp).  BiCGStab and MINRES / CSMINRES follow the reference (src/bicg_stab.rs, src/minres.rs,
 // src/cs_minres.rs); CG, GMRES, the batched CG, LSMR and the Lanczos eigensolver have no reference analogue: include/sprsolve_hip.h
 // states their recurrences.
@@ -300,6 +300,32 @@ class Eigsh : public KrylovBase<T> {
     int rotate(int me, int q, T *out, int64_t ostride);      // out[:, :q] = V[:, :me] S[:, :q]
 };
 
+// LOBPCG for the extreme eigenpairs of a Hermitian A, with any of the preconditioners (recurrence: include/sprsolve_hip.h,
+// sprs_lobpcg_*; kernels: lobpcg_fuse.hpp and the Lanczos rotation).  Single GPU, one mode; of KrylovBase it uses the work vectors
+// and spmv() — no literal mode, trace or profile.
+template <class T> struct LobState;     // lobpcg_fuse.hpp
+template <class T>
+class Lobpcg : public KrylovBase<T> {
+   public:
+    StateBlock<LobState<T>> state;       // the host pushes it per solve and reads its head once per `poll` iterations
+    int b = 0;                           // the block size: work holds X, P, W, AX, AP, AW, b contiguous vectors each
+    T *gpart = nullptr;                  // [walker][G's upper triangle, K's upper triangle] partials of LobGram
+    Real<T> *rpart = nullptr;            // [column][MAX_GRID] partials of the residual norms
+    void *gsum = nullptr;                // G's and K's upper triangles summed in double (complex double for complex T)
+    int create(const sprs_csr *A, size_t size, size_t block);
+    void destroy();
+    // X0: b contiguous vectors of n entries (host where x0_host); vecs: k contiguous vectors of n entries or null (host where
+    // vecs_host; device: the rotation kernel writes them, any alignment); vals / res / the counters: host
+    int solve_dev(const Precond<T> &P, size_t k, int which, const T *X0, bool x0_host, size_t max_iter, Real<T> tol, Real<T> *vals_out, T *vecs,
+                  bool vecs_host, Real<T> *res_out, size_t *nconv_out, size_t *iters_out, size_t *restarts_out, size_t *matvecs_out);
+
+   private:
+    int gram(int layout, int m);
+    template <class V>
+    int run(const Prec<T, V> &M, size_t k, int which, const T *X0, bool x0_host, size_t max_iter, Real<T> tol, Real<T> *vals_out, T *vecs,
+            bool vecs_host, Real<T> *res_out, size_t *nconv_out, size_t *iters_out, size_t *restarts_out, size_t *matvecs_out);
+};
+
 // LSMR for min |rhs - A x|_2 (+ damping) on any A, rectangular included (recurrence: include/sprsolve_hip.h, sprs_lsmr_*; kernels:
 // lsmr_fuse.hpp).  Two operators and two vector lengths: KrylovBase carries A, the m = rows side (u, w) and everything that
 // is not tied to a length (context, poll, trace, profile, partial slots); the n = cols side (v, w', h, hbar) is held here.
@@ -467,3 +493,4 @@ struct sprs_gmres : sprs_solver_handle {};
 struct sprs_cg_many : sprs_solver_handle {};
 struct sprs_lsmr : sprs_solver_handle {};
 struct sprs_eigsh : sprs_solver_handle {};
+struct sprs_lobpcg : sprs_solver_handle {};
