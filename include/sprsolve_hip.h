@@ -1195,6 +1195,94 @@ int sprs_fsai_lobpcg_solve_dev_z(sprs_lobpcg *S, const sprs_fsai *P, size_t k, i
 int sprs_fsai_lobpcg_solve_dev_s(sprs_lobpcg *S, const sprs_fsai *P, size_t k, int which, const float *X0_dev_or_null, size_t x0_len, size_t max_iter, float tol, float *vals_out, float *vecs_dev_or_null, size_t vecs_len, float *res_out, size_t *nconv_out, size_t *iters_out, size_t *restarts_out, size_t *matvecs_out);
 int sprs_fsai_lobpcg_solve_dev_c(sprs_lobpcg *S, const sprs_fsai *P, size_t k, int which, const sprs_c32 *X0_dev_or_null, size_t x0_len, size_t max_iter, float tol, float *vals_out, sprs_c32 *vecs_dev_or_null, size_t vecs_len, float *res_out, size_t *nconv_out, size_t *iters_out, size_t *restarts_out, size_t *matvecs_out);
 
+/* ---------------------------------------------------------------- truncated SVD (thick-restart Lanczos bidiagonalisation)
+ * The k largest or smallest singular triplets A v_i = sigma_i u_i, A^H u_i = sigma_i v_i (nothing conjugated) of an r x c matrix A
+ * of any shape: Golub-Kahan-Lanczos bidiagonalisation with a thick restart on plain Ritz vectors and full reorthogonalisation
+ * of both bases by classical Gram-Schmidt applied twice.  The reference has no such solver.  Single GPU: a distributed A is
+ * refused with SPRS_INVALID_ARGUMENT (text in sprs_last_error).  The handle borrows a handle of A^H (sprs_csr_adjoint with
+ * conjugate = 1) or builds and owns one.
+ * Op = A and OpH = A^H where r >= c; otherwise Op = A^H and OpH = A, and U and V change places on output.  So Op is M x N with
+ * M >= N, and the start vector v0 lives in the small space: N = min(r, c) entries (a start vector in the large space would carry
+ * a null-space component into B).  The handle owns 2 l + 3 vectors, l = ncv: p_0 .. p_l and w' of N entries, q_0 .. q_{l-1} and
+ * w of M entries.
+ * Vectors and the CGS2 coefficients are of type T.  B (l x l, upper triangular), sigma_i, X, Y, alpha, beta, res_i, anorm, scale
+ * are double for all four scalar types: the projected matrix is real for complex A too (its diagonal and super-diagonal hold
+ * norms, and after a restart singular values and real multiples of a real singular-vector matrix).  alpha and beta are square
+ * roots, taken in T::Real, of sums of squares formed in T::Real.  conj_dot(a, b) = sum conj(a_i) b_i.
+ *     beta0 = norm2(v0);  NaN or 0: SPRS_BREAKDOWN (*matvecs_out = 0, *restarts_out = 0).  p_0 = v0 * (1 / beta0)
+ *     B = 0, j0 = 0, anorm = 0, scale = 0
+ *     cycle c = 1, 2, ...:
+ *         for j = j0 .. l - 1:
+ *             w = Op p_j
+ *             j > 0:   pass 1:  h_i = conj_dot(q_i, w) for i = 0 .. j - 1, all on the same w;  then for i in order: w += q_i*(-h_i)
+ *                      pass 2:  the same once more on the updated w
+ *             alpha = norm2(w);  NaN: SPRS_BREAKDOWN;  alpha <= 64 eps(T::Real) scale: Op is numerically rank-deficient along the
+ *                      basis, SPRS_BREAKDOWN (a limit, not worked round)
+ *             B_jj = alpha;  scale = max(scale, alpha);  q_j = w * (1 / alpha)
+ *             w' = OpH q_j
+ *             pass 1, pass 2:  the same against p_0 .. p_j
+ *             beta = norm2(w');  NaN: SPRS_BREAKDOWN
+ *             if beta <= 64 eps(T::Real) scale: an invariant subspace, m_eff = j + 1, beta = 0 (the residuals are zero), leave
+ *                      the loop (p_{j+1} is not formed)
+ *             scale = max(scale, beta);  if j + 1 < l: B_{j,j+1} = beta;   p_{j+1} = w' * (1 / beta)   (also at j = l - 1)
+ *         (m_eff = l where the loop ran out)
+ *         B[:m_eff, :m_eff] = X Sigma Y^T (below), sigma descending (SPRS_SVDS_LARGEST) or ascending (SPRS_SVDS_SMALLEST), ties
+ *                      by index, the columns of X and Y with it
+ *         res_i = beta |X[m_eff - 1, i]|;  anorm = max(anorm, max sigma_i);  nconv = the number of LEADING i < k with
+ *                      res_i <= tol anorm
+ *         invariant subspace:  m_eff >= k: SPRS_OK with nconv = k;  else SPRS_BREAKDOWN
+ *         nconv == k:          SPRS_OK
+ *         c == max_restarts:   SPRS_INSUFFICIENT_ITER (the outputs are the current leading k triplets, nconv as counted)
+ *         restart:  p = min(k + max(k, 4), l - 2);  P[:, :p] = P[:, :l] Y[:, :p];  Q[:, :p] = Q[:, :l] X[:, :p];  p_p = p_l;
+ *                   B = diag(sigma_0 .. sigma_{p-1}) with the spike column B_{i,p} = beta X[l - 1, i] (i < p), zero elsewhere;
+ *                   j0 = p  (the next step's first Gram-Schmidt, against q_0 .. q_{p-1}, removes the spike by itself)
+ *     outputs:  vals_i = sigma_i and res_i (absolute) for i < k, rounded to T::Real;  V = P[:, :m_eff] Y[:, :k] and
+ *               U = Q[:, :m_eff] X[:, :k] (the other way round where Op = A^H) as k contiguous vectors of c and of r entries (both
+ *               pointers or neither);  nconv;  restarts = c;  matvecs = the products with either operator that ran: without an
+ *               invariant subspace 2 l + 2 (l - p)(restarts - 1)
+ * Only alpha and beta are kept from a step; the other entries of B are known from its structure and the CGS2 coefficients serve
+ * the reorthogonalisation alone.  The coefficients of P Y and Q X are Y and X rounded once to T::Real, and every output element
+ * is summed over i ascending from zero, one real-by-T product and one sum per term, each rounded once.  Phases and signs of the
+ * singular vectors are whatever falls out.  On SPRS_BREAKDOWN vals / res hold the last values computed (zeros where there were
+ * none) and the vectors are not written.
+ * The projected SVD: one-sided (Hestenes) Jacobi on the columns of G = B with Y = I, in double; the Gram matrix B^T B is never
+ * formed, so sigma and X keep relative accuracy for the small singular values.  m_eff is rounded up to an even M (an odd m_eff
+ * carries one zero column, which never rotates).  A sweep is M - 1 rounds; round r takes the M / 2 disjoint pairs (M - 1, r) and
+ * ((r + i) mod (M - 1), (r - i) mod (M - 1)), i = 1 .. M / 2 - 1, each ordered p < q, all from the same G:
+ * a = |g_p|^2, b = |g_q|^2, c = g_p.g_q;  |c| <= eps sqrt(a b): nothing;  else zeta = (b - a) / (2 c),
+ * t = sign(zeta) / (|zeta| + sqrt(1 + zeta^2)) (sign(0) = 1), cs = 1 / sqrt(1 + t^2), sn = cs t;
+ * g_p' = cs g_p - sn g_q, g_q' = sn g_p + cs g_q, and the same on Y.  A sweep without a rotation ends the iteration; 30 sweeps
+ * with one end the solve in SPRS_BREAKDOWN, never a silent result.  Then sigma_i = |g_i| (zero or NaN: SPRS_BREAKDOWN) and
+ * x_i = g_i / sigma_i.
+ * create:  ncv = 0 means min(32, min(r, c));  SPRS_INVALID_ARGUMENT (text in sprs_last_error) unless
+ *          3 <= ncv <= min(SPRS_SVDS_MAX_NCV, min(r, c)), for a distributed A and for an AH of another shape, scalar type or context.
+ * solve:   SPRS_INVALID_ARGUMENT unless 1 <= k <= ncv - 2, which is one of the two, max_restarts >= 1 and u_out, v_out are both
+ *          given or both NULL;  SPRS_INCOMPATIBLE_RHS_SIZE for v0_len != min(r, c);  SPRS_INCOMPATIBLE_X_SIZE for u_len != k r or
+ *          v_len != k c where the vectors are given.  vals_out and res_out hold k entries; the three counters may be NULL.
+ *          SPRS_INSUFFICIENT_ITER fills everything, SPRS_BREAKDOWN everything but the vectors.
+ * Not provided for this solver: a literal mode, the trace, the profile hooks, a sprs_solver_* kind and a Rust binding.
+ * Limits: plain Ritz extraction at a restart (no harmonic or refined vectors), so the smallest triplets of an ill-conditioned A
+ * converge slowly or not at all within max_restarts; both bases are fully reorthogonalised; a single start vector finds one copy
+ * of a multiple singular value; a numerically rank-deficient operator ends in SPRS_BREAKDOWN; the projected SVD runs in one
+ * workgroup. */
+typedef struct sprs_svds sprs_svds;
+#define SPRS_SVDS_MAX_NCV 64
+enum { SPRS_SVDS_LARGEST = 0, SPRS_SVDS_SMALLEST = 1 };
+int sprs_svds_destroy(sprs_svds *S);           /* NULL is a no-op */
+int sprs_svds_create_d(const sprs_csr *A, const sprs_csr *AH_or_null, size_t ncv, sprs_svds **out);
+int sprs_svds_create_z(const sprs_csr *A, const sprs_csr *AH_or_null, size_t ncv, sprs_svds **out);
+int sprs_svds_create_s(const sprs_csr *A, const sprs_csr *AH_or_null, size_t ncv, sprs_svds **out);
+int sprs_svds_create_c(const sprs_csr *A, const sprs_csr *AH_or_null, size_t ncv, sprs_svds **out);
+int sprs_svds_solve_d(sprs_svds *S, size_t k, int which, const double *v0, size_t v0_len, size_t max_restarts, double tol, double *vals_out, double *u_out_or_null, size_t u_len, double *v_out_or_null, size_t v_len, double *res_out, size_t *nconv_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_svds_solve_z(sprs_svds *S, size_t k, int which, const sprs_c64 *v0, size_t v0_len, size_t max_restarts, double tol, double *vals_out, sprs_c64 *u_out_or_null, size_t u_len, sprs_c64 *v_out_or_null, size_t v_len, double *res_out, size_t *nconv_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_svds_solve_s(sprs_svds *S, size_t k, int which, const float *v0, size_t v0_len, size_t max_restarts, float tol, float *vals_out, float *u_out_or_null, size_t u_len, float *v_out_or_null, size_t v_len, float *res_out, size_t *nconv_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_svds_solve_c(sprs_svds *S, size_t k, int which, const sprs_c32 *v0, size_t v0_len, size_t max_restarts, float tol, float *vals_out, sprs_c32 *u_out_or_null, size_t u_len, sprs_c32 *v_out_or_null, size_t v_len, float *res_out, size_t *nconv_out, size_t *restarts_out, size_t *matvecs_out);
+/* the same with v0, u and v on the device (any alignment); vals, res and the counters stay on the host */
+int sprs_svds_solve_dev_d(sprs_svds *S, size_t k, int which, const double *v0_dev, size_t v0_len, size_t max_restarts, double tol, double *vals_out, double *u_dev_or_null, size_t u_len, double *v_dev_or_null, size_t v_len, double *res_out, size_t *nconv_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_svds_solve_dev_z(sprs_svds *S, size_t k, int which, const sprs_c64 *v0_dev, size_t v0_len, size_t max_restarts, double tol, double *vals_out, sprs_c64 *u_dev_or_null, size_t u_len, sprs_c64 *v_dev_or_null, size_t v_len, double *res_out, size_t *nconv_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_svds_solve_dev_s(sprs_svds *S, size_t k, int which, const float *v0_dev, size_t v0_len, size_t max_restarts, float tol, float *vals_out, float *u_dev_or_null, size_t u_len, float *v_dev_or_null, size_t v_len, float *res_out, size_t *nconv_out, size_t *restarts_out, size_t *matvecs_out);
+int sprs_svds_solve_dev_c(sprs_svds *S, size_t k, int which, const sprs_c32 *v0_dev, size_t v0_len, size_t max_restarts, float tol, float *vals_out, sprs_c32 *u_dev_or_null, size_t u_len, sprs_c32 *v_dev_or_null, size_t v_len, float *res_out, size_t *nconv_out, size_t *restarts_out, size_t *matvecs_out);
+
 /* ---------------------------------------------------------------- solver options / instrumentation
  * `solver` is a handle of any of the solver types below, `kind` says which. */
 enum { SPRS_SOLVER_BICGSTAB = 1, SPRS_SOLVER_MINRES = 2, SPRS_SOLVER_CSMINRES = 3, SPRS_SOLVER_CG = 4, SPRS_SOLVER_GMRES = 5, SPRS_SOLVER_LSMR = 6 };

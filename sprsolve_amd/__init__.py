@@ -23,5 +23,6 @@ from .mat import HipCsr, MatVecMul  # noqa: F401
 from .minres import MinRes  # noqa: F401
 from .precond import DiagPrecond  # noqa: F401
 from .refine import Refine  # noqa: F401
+from .svds import Svds  # noqa: F401
 
 __version__ = "0.1.0"

@@ -644,6 +644,53 @@ int eigsh_solve(Eigsh<T> *s, bool host, size_t k, int which, const T *v0, size_t
                     matvecs ? matvecs : dummy + 2);
 }
 
+// Svds<T> behind a sprs_svds: a single-GPU A of any shape, its adjoint handle borrowed (checked here) or built by the solver,
+// ncv = 0 means min(32, min(rows, cols))
+template <class T>
+int svds_create(const sprs_csr *A, const sprs_csr *AH, size_t ncv, sprs_svds **out) {
+    if (!A || !out) return SPRS_INVALID_ARGUMENT;
+    *out = nullptr;
+    auto refuse = [&](const char *why) {
+        snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_svds: %s", why);
+        return SPRS_INVALID_ARGUMENT;
+    };
+    if (A->dtype != dtype_of<T>::value) return refuse("the operator holds another scalar type");
+    if (A->dist || (AH && AH->dist)) return refuse("distributed operators are not supported (single GPU only)");
+    if (AH && (AH->dtype != A->dtype || AH->ctx != A->ctx)) return refuse("the adjoint handle holds another scalar type or context");
+    if (AH && (AH->nrows != A->ncols || AH->ncols != A->nrows)) return refuse("the adjoint handle is not cols x rows");
+    const size_t small = (size_t)std::min(A->nrows, A->ncols);
+    if (ncv == 0) ncv = std::min<size_t>(32, small);
+    if (ncv < 3 || ncv > std::min<size_t>(SPRS_SVDS_MAX_NCV, small)) {
+        snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_svds: ncv = %zu is outside 3 .. min(%d, min(rows, cols) = %zu)", ncv, SPRS_SVDS_MAX_NCV, small);
+        return SPRS_INVALID_ARGUMENT;
+    }
+    CtxLock lock(A->ctx);
+    sprs_svds *h = new sprs_svds();
+    h->dtype = dtype_of<T>::value;
+    auto *s = new Svds<T>();
+    h->impl = s;
+    const int st = s->create(A, AH, ncv);
+    if (st != SPRS_OK) { s->destroy(); delete s; delete h; return st; }
+    *out = h;
+    return SPRS_OK;
+}
+
+// One truncated SVD.  v0 is copied into the basis and the vectors are written by the rotation kernel (device) or copied out of
+// the bases (host), so no alignment is asked of either.
+template <class T>
+int svds_solve(Svds<T> *s, bool host, size_t k, int which, const T *v0, size_t v0_len, size_t max_restarts, Real<T> tol, Real<T> *vals, T *u,
+               size_t u_len, T *v, size_t v_len, Real<T> *res, size_t *nconv, size_t *restarts, size_t *matvecs) {
+    if (!s || !v0 || !vals || !res || (u == nullptr) != (v == nullptr)) return SPRS_INVALID_ARGUMENT;
+    if (k < 1 || k + 2 > (size_t)s->m || (which != SPRS_SVDS_LARGEST && which != SPRS_SVDS_SMALLEST) || max_restarts < 1)
+        return SPRS_INVALID_ARGUMENT;
+    if (v0_len != s->lenN) return SPRS_INCOMPATIBLE_RHS_SIZE;
+    if (u && (u_len != k * s->rows || v_len != k * s->cols)) return SPRS_INCOMPATIBLE_X_SIZE;
+    size_t dummy[3];
+    CtxLock lock(s->ctx);
+    return s->solve(k, which, v0, host, max_restarts, tol, vals, u, v, res, nconv ? nconv : dummy, restarts ? restarts : dummy + 1,
+                    matvecs ? matvecs : dummy + 2);
+}
+
 // Lobpcg<T> behind a sprs_lobpcg: a square single-GPU A, block = 0 means min(8, n / 6)
 template <class T>
 int lobpcg_create(const sprs_csr *A, size_t size, size_t block, sprs_lobpcg **out) {
@@ -874,6 +921,7 @@ int sprs_cgmany_destroy(sprs_cg_many *S) { return solver_destroy<CgMany>(S); }
 int sprs_lsmr_destroy(sprs_lsmr *S) { return solver_destroy<Lsmr>(S); }
 int sprs_eigsh_destroy(sprs_eigsh *S) { return solver_destroy<Eigsh>(S); }
 int sprs_lobpcg_destroy(sprs_lobpcg *S) { return solver_destroy<Lobpcg>(S); }
+int sprs_svds_destroy(sprs_svds *S) { return solver_destroy<Svds>(S); }
 
 // ---- a solver's entry points per scalar type.  NAME = the handle is sprs_NAME, S = its class, CREATE = the arguments of S<T>::create
 #define SPRS_SOLVER_SOLVES(X, T, CT, R, NAME, S)                                                                       \
@@ -955,6 +1003,16 @@ int sprs_lobpcg_destroy(sprs_lobpcg *S) { return solver_destroy<Lobpcg>(S); }
     int sprs_eigsh_solve_dev_##X(sprs_eigsh *h, size_t k, int which, const CT *v0, size_t vl, size_t mr, R tol, R *vals, CT *vecs, size_t xl, \
                                  R *res, size_t *nconv, size_t *restarts, size_t *matvecs) {                           \
         SPRS_G(return eigsh_solve<T>(impl_of<Eigsh, T>(h), false, k, which, (const T *)v0, vl, mr, tol, vals, (T *)vecs, xl, res, nconv, restarts, matvecs);) \
+    }                                                                                                                  \
+    /* truncated SVD: A of any shape and its adjoint handle (NULL: built and owned), ncv = the basis size (0 = min(32, min(rows, cols))) */ \
+    int sprs_svds_create_##X(const sprs_csr *A, const sprs_csr *AH, size_t ncv, sprs_svds **out) { SPRS_G(return svds_create<T>(A, AH, ncv, out);) } \
+    int sprs_svds_solve_##X(sprs_svds *h, size_t k, int which, const CT *v0, size_t vl, size_t mr, R tol, R *vals, CT *u, size_t ul, CT *v, size_t vvl, \
+                            R *res, size_t *nconv, size_t *restarts, size_t *matvecs) {                                \
+        SPRS_G(return svds_solve<T>(impl_of<Svds, T>(h), true, k, which, (const T *)v0, vl, mr, tol, vals, (T *)u, ul, (T *)v, vvl, res, nconv, restarts, matvecs);) \
+    }                                                                                                                  \
+    int sprs_svds_solve_dev_##X(sprs_svds *h, size_t k, int which, const CT *v0, size_t vl, size_t mr, R tol, R *vals, CT *u, size_t ul, CT *v, size_t vvl, \
+                                R *res, size_t *nconv, size_t *restarts, size_t *matvecs) {                            \
+        SPRS_G(return svds_solve<T>(impl_of<Svds, T>(h), false, k, which, (const T *)v0, vl, mr, tol, vals, (T *)u, ul, (T *)v, vvl, res, nconv, restarts, matvecs);) \
     }                                                                                                                  \
     /* LOBPCG: block = the block size (0 = min(8, n / 6)) */                                                           \
     int sprs_lobpcg_create_##X(const sprs_csr *A, size_t n, size_t block, sprs_lobpcg **out) { SPRS_G(return lobpcg_create<T>(A, n, block, out);) } \

@@ -1,8 +1,8 @@
 // Krylov recurrences (host side, C++) over device-resident vectors and scalars: the solver objects behind sprs_bicgstab,
-// sprs_minres / sprs_csminres, sprs_cg, sprs_gmres, sprs_cg_many, sprs_lsmr, sprs_eigsh and sprs_lobpcg.  One translation unit per solver (bicgstab.hip,
-// minres.hip, cg.hip, gmres.hip, cg_many.hip, lsmr.hip, eigsh.hip, lobpcg.hip), each with its recurrence comment; its kernels are the functors of its *_fuse.hpp, all run by
+// sprs_minres / sprs_csminres, sprs_cg, sprs_gmres, sprs_cg_many, sprs_lsmr, sprs_eigsh, sprs_lobpcg and sprs_svds.  One translation unit per solver (bicgstab.hip,
+// minres.hip, cg.hip, gmres.hip, cg_many.hip, lsmr.hip, eigsh.hip, lobpcg.hip, svds.hip), each with its recurrence comment; its kernels are the functors of its *_fuse.hpp, all run by
 // fused_kernel (fused_launch.hpp).  BiCGStab and MINRES / CSMINRES follow the reference (src/bicg_stab.rs, src/minres.rs,
-// src/cs_minres.rs); CG, GMRES, the batched CG, LSMR and the Lanczos eigensolver have no reference analogue: include/sprsolve_hip.h
+// src/cs_minres.rs); CG, GMRES, the batched CG, LSMR, the two eigensolvers and the truncated SVD have no reference analogue: include/sprsolve_hip.h
 // states their recurrences.
 //
 // Two execution modes per solver (sprs_solver_set_mode; the batched CG is fused only):
@@ -353,6 +353,39 @@ class Lsmr : public KrylovBase<T> {
     int run_literal(const T *rhs, T *x, R damp, size_t max_iter, R tol, size_t *its_out, R *res_out, R *ares_out);
 };
 
+// Thick-restart Lanczos bidiagonalisation for the extreme singular triplets of any A, rectangular included (recurrence:
+// include/sprsolve_hip.h, sprs_svds_*; kernels: svds_fuse.hpp, GMRES's multi-vector Gram-Schmidt and the Lanczos rotation).  Two
+// operators and two vector lengths, as LSMR: Op = A and OpH = A^H where rows >= cols, else the other way round, so that Op is
+// M x N with M >= N.  KrylovBase carries the M side (q_0 .. q_{l-1}, w) and the partial slots; the N side (p_0 .. p_l, w') is
+// held here.  Single GPU, one mode — no literal mode, trace or profile.
+template <class T> struct SvState;      // svds_fuse.hpp
+template <class T>
+class Svds : public KrylovBase<T> {
+   public:
+    using R = Real<T>;
+    StateBlock<SvState<T>> state;        // the host pushes its head and reads the head once a cycle
+    const sprs_csr *AH = nullptr;        // the adjoint handle: the caller's, or built here (own_AH)
+    sprs_csr *own_AH = nullptr;
+    const sprs_csr *Op = nullptr, *OpH = nullptr;
+    bool swapped = false;                // Op = A^H: U and V change places on output
+    int m = 32;                          // ncv: the basis size l
+    size_t rows = 0, cols = 0, lenM = 0, lenN = 0, stride_n = 0;
+    T *work_n = nullptr;                 // (m + 2) * stride_n
+    T *dots = nullptr;                   // [m][dots_grid] partials of the multi-dots, dots_grid = the larger side's grid
+    int dots_grid = 0;
+    int create(const sprs_csr *A, const sprs_csr *AH_or_null, size_t ncv);
+    void destroy();
+    // v0: min(rows, cols) entries (host where host); u / v: k contiguous vectors of rows / cols entries, both or neither (host:
+    // the bases are rotated in place and copied out; device: LzRotate writes them, any alignment); vals / res / the counters: host
+    int solve(size_t k, int which, const T *v0, bool host, size_t max_restarts, R tol, R *vals_out, T *u, T *v, R *res_out, size_t *nconv_out,
+              size_t *restarts_out, size_t *matvecs_out);
+
+   private:
+    T *pvec(int i) { return work_n + (size_t)i * stride_n; }     // p_0 .. p_m, then w'
+    T *qvec(int i) { return this->vec(i); }                      // q_0 .. q_{m-1}, then w
+    int grid_of(size_t len) const;
+};
+
 // Conjugate gradients on a block of up to kmax <= 8 right-hand sides at once (cg_many.hip; kernels: spmm.hip, cg_many_fuse.hpp).
 // Every column runs Cg<T>'s recurrence on its own scalars and stops on its own events.  Single GPU, fused mode only.
 template <class T> struct CgManyState;   // cg_many_fuse.hpp
@@ -494,3 +527,4 @@ struct sprs_cg_many : sprs_solver_handle {};
 struct sprs_lsmr : sprs_solver_handle {};
 struct sprs_eigsh : sprs_solver_handle {};
 struct sprs_lobpcg : sprs_solver_handle {};
+struct sprs_svds : sprs_solver_handle {};
