@@ -1283,6 +1283,83 @@ int sprs_svds_solve_dev_z(sprs_svds *S, size_t k, int which, const sprs_c64 *v0_
 int sprs_svds_solve_dev_s(sprs_svds *S, size_t k, int which, const float *v0_dev, size_t v0_len, size_t max_restarts, float tol, float *vals_out, float *u_dev_or_null, size_t u_len, float *v_dev_or_null, size_t v_len, float *res_out, size_t *nconv_out, size_t *restarts_out, size_t *matvecs_out);
 int sprs_svds_solve_dev_c(sprs_svds *S, size_t k, int which, const sprs_c32 *v0_dev, size_t v0_len, size_t max_restarts, float tol, float *vals_out, sprs_c32 *u_dev_or_null, size_t u_len, sprs_c32 *v_dev_or_null, size_t v_len, float *res_out, size_t *nconv_out, size_t *restarts_out, size_t *matvecs_out);
 
+/* ---------------------------------------------------------------- matrix exponential propagator
+ * w = exp(tA) v for a square A of any kind (non-symmetric, complex) and a finite real t of T::Real, negative or zero included:
+ * Arnoldi projection on a Krylov space of m = ncv vectors with the error-controlled sub-stepping of Expokit's expv (Sidje, ACM
+ * TOMS 24, 1998), full orthogonalisation by classical Gram-Schmidt applied twice.  The reference has no such operation.  Single
+ * GPU: a distributed A is refused with SPRS_INVALID_ARGUMENT (text in sprs_last_error).  The handle owns ncv + 3 vectors:
+ * v_0 .. v_m, p and one that stages the result.
+ * Vectors and the CGS2 coefficients h_i, c_i are of type T.  The projected matrix H, F, every tau, the error estimates and beta
+ * as used in the control are double for real T and complex double / double for complex T (the rule of sprs_eigsh_*).  beta, hn
+ * and avnorm are square roots, taken in T::Real, of sums of squares formed in T::Real.  conj_dot(a, b) = sum conj(a_i) b_i.
+ *     tol == 0 means sqrt(eps(T::Real));  sgn = sign(t), t_out = |t|, t_now = 0, w = v, tau = tau0 (0: not set yet)
+ *     gamma = 0.9, delta = 1.2, at most 10 attempts per sub-step
+ *     t_out == 0:  w = v bit for bit, SPRS_OK, all counters 0
+ *     sub-step s = 1, 2, ...:
+ *         beta = norm2(w);  NaN: SPRS_BREAKDOWN;  0: w = 0, SPRS_OK
+ *         hump = max(hump, beta);  v_0 = w * (1 / beta);  H = 0 ((m+2) x (m+2));  scale = 0
+ *         for j = 0 .. m - 1:
+ *             p = A v_j
+ *             pass 1:  h_i = conj_dot(v_i, p) for i = 0 .. j, all on the same p;  then for i = 0 .. j in order: p += v_i*(-h_i)
+ *             pass 2:  c_i = conj_dot(v_i, p) for i = 0 .. j, all on the same p;  then for i = 0 .. j in order: p += v_i*(-c_i);
+ *                      h_i = h_i + c_i                                     (exactly the passes of sprs_eigsh_*)
+ *             H[i, j] = h_i for i <= j;  hn = norm2(p);  NaN: SPRS_BREAKDOWN;  scale = max(scale, max_i |h_i|)
+ *             if hn <= 64 eps(T::Real) scale: a happy breakdown, m_eff = j + 1, leave the loop (v_{j+1} is not formed)
+ *             scale = max(scale, hn);  H[j+1, j] = hn;  v_{j+1} = p * (1 / hn)          (also at j = m - 1)
+ *         rem = t_out - t_now
+ *         happy:  tau_s = rem;  F = smallexp(sgn tau_s H[:m_eff, :m_eff]);  c_i = beta F[i, 0] for i < m_eff;  err = 0
+ *         else:   avnorm = norm2(A v_m)  (one more product, counted);  H[m+1, m] = 1
+ *                 tau not set:  anorm = the largest row sum of |H[:m+1, :m]|;  fact = ((m+1)/e)^(m+1) sqrt(2 pi (m+1));
+ *                               tau = round2((1/anorm) ((fact tol) / (4 beta anorm))^(1/m))
+ *                 tau_s = tau if tau < rem, else rem
+ *                 attempt a = 1, 2, ...:
+ *                     F = smallexp(sgn tau_s H)   (all m + 2 rows);  e1 = beta |F[m, 0]|;  e2 = beta |F[m+1, 0]| avnorm
+ *                     e1 > 10 e2: err = e2, xm = 1/m;   else e1 > e2: err = e1 e2 / (e1 - e2), xm = 1/m;   else err = e1, xm = 1/(m-1)
+ *                     a NaN err: SPRS_BREAKDOWN;  err <= delta tau_s tol: accept, leave the loop
+ *                     a == 10 (the tenth rejection of this sub-step): SPRS_BREAKDOWN
+ *                     tau_s = round2(gamma tau_s (tau_s tol / err)^xm);  not finite or not > 0: SPRS_BREAKDOWN;  rejects += 1
+ *                 c_i = beta F[i, 0] for i <= m;   tau = round2(gamma tau_s (tau_s tol / max(err, DBL_MIN))^xm)
+ *         w = sum_i v_i c_i   (c rounded once to T, from zero, i ascending, one product and one sum per term, each rounded once)
+ *         t_now = t_out where tau_s == rem, else t_now + tau_s;  err_sum += err;  steps += 1
+ *         t_now >= t_out: SPRS_OK;   steps == max_steps: SPRS_INSUFFICIENT_ITER  (w is the state at t_done = sgn t_now)
+ *     outputs:  w;  err = err_sum, hump and t_done rounded to T::Real;  steps;  rejects;  matvecs = the products A v that ran
+ * round2(x) rounds a finite x > 0 to two significant decimal digits as Expokit does, and returns anything else as it is:
+ * y = x, u = 0;  while y >= 100: y = y / 10, u += 1;  while y < 10: y = y * 10, u -= 1  (330 steps each at the most);
+ * r = floor(y + 0.55);  then r = r * 10, u times, or r = r / 10, -u times.
+ * smallexp(X) for an M x M matrix X, M <= m + 2, is its exponential by Taylor scaling and squaring:  nrm = the largest column sum
+ * of |X|, not finite: SPRS_BREAKDOWN;  s = the least integer >= 0 with nrm 2^-s <= 1/2, s > 64: SPRS_BREAKDOWN;  Y = X 2^-s
+ * (exact);  E = I, then for q = 18, 17, .., 1: E = I + (Y E) / q;  then s times E = E E.  Every entry of a product is summed over
+ * the inner index ascending from zero, one product and one sum per term, by one thread, without atomics: the result does not
+ * depend on timing.  |z| of a complex entry is hypot(re, im).
+ * Where this departs from Expokit: anorm comes from the first projected matrix, not from the caller; Taylor scaling and squaring
+ * of degree 18 stands in for the Pade approximant (three small matrices and no linear solve: it fits one workgroup's local
+ * memory); t_now is set to t_out by the sub-step that takes all that remains, so that a rounding of t_now + tau_s cannot ask
+ * for one more; a step size that is no longer a positive finite number ends the solve.  As in Expokit beta and the estimates
+ * are absolute: the sum of the accepted estimates is at most delta |t| tol.
+ * create:  ncv = 0 means min(30, n);  SPRS_INVALID_ARGUMENT unless 3 <= ncv <= min(SPRS_EXPM_MAX_NCV, n);  SPRS_NOT_SQUARE;
+ *          SPRS_DIM_MISMATCH for size != rows.
+ * apply:   SPRS_INVALID_ARGUMENT unless t, tol >= 0 and tau0 >= 0 are finite and max_steps >= 1;  SPRS_INCOMPATIBLE_RHS_SIZE for
+ *          v_len != n;  SPRS_INCOMPATIBLE_X_SIZE for w_len != n.  w may be v.  The six outputs may be NULL.  On SPRS_BREAKDOWN w is
+ *          not written.
+ * Not provided: phi-functions, several output times in one call, a Lanczos shortcut for Hermitian A, a literal mode, the trace,
+ * the profile hooks and a sprs_solver_* kind. */
+typedef struct sprs_expm sprs_expm;
+#define SPRS_EXPM_MAX_NCV 48
+int sprs_expm_destroy(sprs_expm *S);           /* NULL is a no-op */
+int sprs_expm_create_d(const sprs_csr *A, size_t size, size_t ncv, sprs_expm **out);
+int sprs_expm_create_z(const sprs_csr *A, size_t size, size_t ncv, sprs_expm **out);
+int sprs_expm_create_s(const sprs_csr *A, size_t size, size_t ncv, sprs_expm **out);
+int sprs_expm_create_c(const sprs_csr *A, size_t size, size_t ncv, sprs_expm **out);
+int sprs_expm_apply_d(sprs_expm *S, double t, const double *v, size_t v_len, double tol, size_t max_steps, double tau0, double *w, size_t w_len, double *err_out, double *hump_out, double *t_done_out, size_t *steps_out, size_t *rejects_out, size_t *matvecs_out);
+int sprs_expm_apply_z(sprs_expm *S, double t, const sprs_c64 *v, size_t v_len, double tol, size_t max_steps, double tau0, sprs_c64 *w, size_t w_len, double *err_out, double *hump_out, double *t_done_out, size_t *steps_out, size_t *rejects_out, size_t *matvecs_out);
+int sprs_expm_apply_s(sprs_expm *S, float t, const float *v, size_t v_len, float tol, size_t max_steps, float tau0, float *w, size_t w_len, float *err_out, float *hump_out, float *t_done_out, size_t *steps_out, size_t *rejects_out, size_t *matvecs_out);
+int sprs_expm_apply_c(sprs_expm *S, float t, const sprs_c32 *v, size_t v_len, float tol, size_t max_steps, float tau0, sprs_c32 *w, size_t w_len, float *err_out, float *hump_out, float *t_done_out, size_t *steps_out, size_t *rejects_out, size_t *matvecs_out);
+/* the same with v and w on the device (any alignment); the six outputs stay on the host */
+int sprs_expm_apply_dev_d(sprs_expm *S, double t, const double *v_dev, size_t v_len, double tol, size_t max_steps, double tau0, double *w_dev, size_t w_len, double *err_out, double *hump_out, double *t_done_out, size_t *steps_out, size_t *rejects_out, size_t *matvecs_out);
+int sprs_expm_apply_dev_z(sprs_expm *S, double t, const sprs_c64 *v_dev, size_t v_len, double tol, size_t max_steps, double tau0, sprs_c64 *w_dev, size_t w_len, double *err_out, double *hump_out, double *t_done_out, size_t *steps_out, size_t *rejects_out, size_t *matvecs_out);
+int sprs_expm_apply_dev_s(sprs_expm *S, float t, const float *v_dev, size_t v_len, float tol, size_t max_steps, float tau0, float *w_dev, size_t w_len, float *err_out, float *hump_out, float *t_done_out, size_t *steps_out, size_t *rejects_out, size_t *matvecs_out);
+int sprs_expm_apply_dev_c(sprs_expm *S, float t, const sprs_c32 *v_dev, size_t v_len, float tol, size_t max_steps, float tau0, sprs_c32 *w_dev, size_t w_len, float *err_out, float *hump_out, float *t_done_out, size_t *steps_out, size_t *rejects_out, size_t *matvecs_out);
+
 /* ---------------------------------------------------------------- solver options / instrumentation
  * `solver` is a handle of any of the solver types below, `kind` says which. */
 enum { SPRS_SOLVER_BICGSTAB = 1, SPRS_SOLVER_MINRES = 2, SPRS_SOLVER_CSMINRES = 3, SPRS_SOLVER_CG = 4, SPRS_SOLVER_GMRES = 5, SPRS_SOLVER_LSMR = 6 };

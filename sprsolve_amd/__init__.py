@@ -12,6 +12,7 @@ from .cg import CG  # noqa: F401
 from .cg_many import CGMany  # noqa: F401
 from .cs_minres import CSMinRes  # noqa: F401
 from .eigsh import Eigsh  # noqa: F401
+from .expm import Expm, expm_multiply  # noqa: F401
 from .gauss_seidel import GaussSeidel  # noqa: F401
 from .gmres import GMRES  # noqa: F401
 from .fsai import FSAI  # noqa: F401

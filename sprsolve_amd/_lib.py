@@ -23,6 +23,7 @@ EIGSH_LARGEST, EIGSH_SMALLEST = 0, 1
 LOBPCG_MAX_BLOCK = 8
 SVDS_MAX_NCV = 64
 SVDS_LARGEST, SVDS_SMALLEST = 0, 1
+EXPM_MAX_NCV = 48
 
 
 class c64(C.Structure):
@@ -109,6 +110,9 @@ def _protos():
         P["sprs_svds_create_" + s] = [_vp, _vp, _sz, _pp]
         for k in ("solve", "solve_dev"):
             P["sprs_svds_%s_%s" % (k, s)] = [_vp, _sz, _int, _vp, _sz, _sz, re_, pre, _vp, _sz, _vp, _sz, pre, _psz, _psz, _psz]
+        P["sprs_expm_create_" + s] = [_vp, _sz, _sz, _pp]
+        for k in ("apply", "apply_dev"):
+            P["sprs_expm_%s_%s" % (k, s)] = [_vp, re_, _vp, _sz, re_, _sz, re_, _vp, _sz, pre, pre, pre, _psz, _psz, _psz]
         P["sprs_dot_" + s] = [_vp, _sz, _vp, _vp, _vp]
         P["sprs_conj_dot_" + s] = [_vp, _sz, _vp, _vp, _vp]
         P["sprs_norm2_" + s] = [_vp, _sz, _vp, pre]
@@ -151,7 +155,7 @@ def _protos():
     P["sprs_csr_adjoint"] = [_vp, _int, _pp]
     P["sprs_csr_matmul"] = [_vp, _vp, _pp, C.POINTER(_i64)]
     P["sprs_csr_read"] = [_vp, _vp, _vp, _vp]
-    for k in ("bicgstab", "minres", "csminres", "cg", "gmres", "cgmany", "lsmr", "eigsh", "lobpcg", "svds"):
+    for k in ("bicgstab", "minres", "csminres", "cg", "gmres", "cgmany", "lsmr", "eigsh", "lobpcg", "svds", "expm"):
         P["sprs_%s_destroy" % k] = [_vp]
     for s in ("d", "zd", "z", "s", "cs", "c"):
         P["sprs_diag_precond_create_" + s] = [_vp, _sz, _vp, _pp]

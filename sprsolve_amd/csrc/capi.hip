@@ -644,6 +644,51 @@ int eigsh_solve(Eigsh<T> *s, bool host, size_t k, int which, const T *v0, size_t
                     matvecs ? matvecs : dummy + 2);
 }
 
+// Expm<T> behind a sprs_expm: a square single-GPU A, ncv = 0 means min(30, n)
+template <class T>
+int expm_create(const sprs_csr *A, size_t size, size_t ncv, sprs_expm **out) {
+    if (!A || !out) return SPRS_INVALID_ARGUMENT;
+    *out = nullptr;
+    if (A->dtype != dtype_of<T>::value) return SPRS_INVALID_ARGUMENT;
+    if (A->dist) {
+        snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_expm: distributed operators are not supported (single GPU only)");
+        return SPRS_INVALID_ARGUMENT;
+    }
+    if (A->nrows != A->ncols) return SPRS_NOT_SQUARE;
+    if ((int64_t)size != A->nrows) return SPRS_DIM_MISMATCH;
+    if (ncv == 0) ncv = std::min<size_t>(30, size);
+    if (ncv < 3 || ncv > std::min<size_t>(SPRS_EXPM_MAX_NCV, size)) {
+        snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_expm: ncv = %zu is outside 3 .. min(%d, n = %zu)", ncv, SPRS_EXPM_MAX_NCV, size);
+        return SPRS_INVALID_ARGUMENT;
+    }
+    CtxLock lock(A->ctx);
+    sprs_expm *h = new sprs_expm();
+    h->dtype = dtype_of<T>::value;
+    auto *s = new Expm<T>();
+    h->impl = s;
+    const int st = s->create(A, size, ncv);
+    if (st != SPRS_OK) { s->destroy(); delete s; delete h; return st; }
+    *out = h;
+    return SPRS_OK;
+}
+
+// One propagation.  v is copied into the basis and w is written by the combination kernel (an aligned device w) or copied out of
+// the staging vector, so no alignment is asked of either and w may be v.
+template <class T>
+int expm_apply(Expm<T> *s, bool host, Real<T> t, const T *v, size_t v_len, Real<T> tol, size_t max_steps, Real<T> tau0, T *w, size_t w_len,
+               Real<T> *err, Real<T> *hump, Real<T> *t_done, size_t *steps, size_t *rejects, size_t *matvecs) {
+    if (!s || !v || !w) return SPRS_INVALID_ARGUMENT;
+    if (!std::isfinite(t) || !(tol >= Real<T>(0)) || !std::isfinite(tol) || !(tau0 >= Real<T>(0)) || !std::isfinite(tau0) || max_steps < 1)
+        return SPRS_INVALID_ARGUMENT;
+    if (v_len != s->n) return SPRS_INCOMPATIBLE_RHS_SIZE;
+    if (w_len != s->n) return SPRS_INCOMPATIBLE_X_SIZE;
+    size_t dummy[3];
+    Real<T> rdummy[3];
+    CtxLock lock(s->ctx);
+    return s->apply(t, v, host, tol, max_steps, tau0, w, err ? err : rdummy, hump ? hump : rdummy + 1, t_done ? t_done : rdummy + 2,
+                    steps ? steps : dummy, rejects ? rejects : dummy + 1, matvecs ? matvecs : dummy + 2);
+}
+
 // Svds<T> behind a sprs_svds: a single-GPU A of any shape, its adjoint handle borrowed (checked here) or built by the solver,
 // ncv = 0 means min(32, min(rows, cols))
 template <class T>
@@ -922,6 +967,7 @@ int sprs_lsmr_destroy(sprs_lsmr *S) { return solver_destroy<Lsmr>(S); }
 int sprs_eigsh_destroy(sprs_eigsh *S) { return solver_destroy<Eigsh>(S); }
 int sprs_lobpcg_destroy(sprs_lobpcg *S) { return solver_destroy<Lobpcg>(S); }
 int sprs_svds_destroy(sprs_svds *S) { return solver_destroy<Svds>(S); }
+int sprs_expm_destroy(sprs_expm *S) { return solver_destroy<Expm>(S); }
 
 // ---- a solver's entry points per scalar type.  NAME = the handle is sprs_NAME, S = its class, CREATE = the arguments of S<T>::create
 #define SPRS_SOLVER_SOLVES(X, T, CT, R, NAME, S)                                                                       \
@@ -1013,6 +1059,16 @@ int sprs_svds_destroy(sprs_svds *S) { return solver_destroy<Svds>(S); }
     int sprs_svds_solve_dev_##X(sprs_svds *h, size_t k, int which, const CT *v0, size_t vl, size_t mr, R tol, R *vals, CT *u, size_t ul, CT *v, size_t vvl, \
                                 R *res, size_t *nconv, size_t *restarts, size_t *matvecs) {                            \
         SPRS_G(return svds_solve<T>(impl_of<Svds, T>(h), false, k, which, (const T *)v0, vl, mr, tol, vals, (T *)u, ul, (T *)v, vvl, res, nconv, restarts, matvecs);) \
+    }                                                                                                                  \
+    /* exp(tA) v: ncv = the basis size (0 = min(30, n)) */                                                             \
+    int sprs_expm_create_##X(const sprs_csr *A, size_t n, size_t ncv, sprs_expm **out) { SPRS_G(return expm_create<T>(A, n, ncv, out);) } \
+    int sprs_expm_apply_##X(sprs_expm *h, R t, const CT *v, size_t vl, R tol, size_t ms, R tau0, CT *w, size_t wl, R *err, R *hump, R *t_done, \
+                            size_t *steps, size_t *rejects, size_t *matvecs) {                                         \
+        SPRS_G(return expm_apply<T>(impl_of<Expm, T>(h), true, t, (const T *)v, vl, tol, ms, tau0, (T *)w, wl, err, hump, t_done, steps, rejects, matvecs);) \
+    }                                                                                                                  \
+    int sprs_expm_apply_dev_##X(sprs_expm *h, R t, const CT *v, size_t vl, R tol, size_t ms, R tau0, CT *w, size_t wl, R *err, R *hump, R *t_done, \
+                                size_t *steps, size_t *rejects, size_t *matvecs) {                                     \
+        SPRS_G(return expm_apply<T>(impl_of<Expm, T>(h), false, t, (const T *)v, vl, tol, ms, tau0, (T *)w, wl, err, hump, t_done, steps, rejects, matvecs);) \
     }                                                                                                                  \
     /* LOBPCG: block = the block size (0 = min(8, n / 6)) */                                                           \
     int sprs_lobpcg_create_##X(const sprs_csr *A, size_t n, size_t block, sprs_lobpcg **out) { SPRS_G(return lobpcg_create<T>(A, n, block, out);) } \

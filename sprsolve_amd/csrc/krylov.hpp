@@ -1,8 +1,8 @@
 // Krylov recurrences (host side, C++) over device-resident vectors and scalars: the solver objects behind sprs_bicgstab,
-// sprs_minres / sprs_csminres, sprs_cg, sprs_gmres, sprs_cg_many, sprs_lsmr, sprs_eigsh, sprs_lobpcg and sprs_svds.  One translation unit per solver (bicgstab.hip,
-// minres.hip, cg.hip, gmres.hip, cg_many.hip, lsmr.hip, eigsh.hip, lobpcg.hip, svds.hip), each with its recurrence comment; its kernels are the functors of its *_fuse.hpp, all run by
+// sprs_minres / sprs_csminres, sprs_cg, sprs_gmres, sprs_cg_many, sprs_lsmr, sprs_eigsh, sprs_lobpcg, sprs_svds and sprs_expm.  One translation unit per solver (bicgstab.hip,
+// minres.hip, cg.hip, gmres.hip, cg_many.hip, lsmr.hip, eigsh.hip, lobpcg.hip, svds.hip, expm.hip), each with its recurrence comment; its kernels are the functors of its *_fuse.hpp, all run by
 // fused_kernel (fused_launch.hpp).  BiCGStab and MINRES / CSMINRES follow the reference (src/bicg_stab.rs, src/minres.rs,
-// src/cs_minres.rs); CG, GMRES, the batched CG, LSMR, the two eigensolvers and the truncated SVD have no reference analogue: include/sprsolve_hip.h
+// src/cs_minres.rs); CG, GMRES, the batched CG, LSMR, the two eigensolvers, the truncated SVD and the exponential propagator have no reference analogue: include/sprsolve_hip.h
 // states their recurrences.
 //
 // Two execution modes per solver (sprs_solver_set_mode; the batched CG is fused only):
@@ -300,6 +300,29 @@ class Eigsh : public KrylovBase<T> {
     int rotate(int me, int q, T *out, int64_t ostride);      // out[:, :q] = V[:, :me] S[:, :q]
 };
 
+// w = exp(tA) v for any square A: Arnoldi projection with Expokit's error-controlled sub-stepping (recurrence:
+// include/sprsolve_hip.h, sprs_expm_*; kernels: expm_fuse.hpp, GMRES's multi-vector Gram-Schmidt and the Lanczos norm).  Single
+// GPU, one mode; of KrylovBase it uses the work vectors, the partial slots and spmv() — no literal mode, trace or profile.
+template <class T> struct ExState;      // expm_fuse.hpp
+template <class T>
+class Expm : public KrylovBase<T> {
+   public:
+    StateBlock<ExState<T>> state;        // the host pushes its head and reads the head once a sub-step
+    int m = 30;                          // ncv: the basis size
+    T *dots = nullptr;                   // [m][dots_grid] partials of the multi-dots
+    int dots_grid = 0;
+    int create(const sprs_csr *A, size_t size, size_t ncv);
+    void destroy();
+    // v, w: n entries each, on the host where `host` (w may be v); the six outputs: host
+    int apply(Real<T> t, const T *v, bool host, Real<T> tol, size_t max_steps, Real<T> tau0, T *w, Real<T> *err_out, Real<T> *hump_out,
+              Real<T> *t_done_out, size_t *steps_out, size_t *rejects_out, size_t *matvecs_out);
+
+   private:
+    T *basis(int i) { return this->vec(i); }                 // v_0 .. v_m
+    T *pvec() { return this->vec(m + 1); }
+    T *stage() { return this->vec(m + 2); }                  // the result of a host call or of an unaligned device w
+};
+
 // LOBPCG for the extreme eigenpairs of a Hermitian A, with any of the preconditioners (recurrence: include/sprsolve_hip.h,
 // sprs_lobpcg_*; kernels: lobpcg_fuse.hpp and the Lanczos rotation).  Single GPU, one mode; of KrylovBase it uses the work vectors
 // and spmv() — no literal mode, trace or profile.
@@ -528,3 +551,4 @@ struct sprs_lsmr : sprs_solver_handle {};
 struct sprs_eigsh : sprs_solver_handle {};
 struct sprs_lobpcg : sprs_solver_handle {};
 struct sprs_svds : sprs_solver_handle {};
+struct sprs_expm : sprs_solver_handle {};
