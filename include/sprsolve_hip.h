@@ -1125,19 +1125,24 @@ int sprs_eigsh_solve_dev_c(sprs_eigsh *S, size_t k, int which, const sprs_c32 *v
  *   iteration it = 1, 2, ...:
  *     1. r_c = AX_c - theta_c X_c for c < b, theta_c rounded once to T::Real;  res_c = norm2(r_c), the square root taken in
  *        T::Real of a sum of squares formed in T::Real;  a NaN: SPRS_BREAKDOWN
- *     2. nconv = the number of LEADING c < k with res_c <= tol anorm, anorm = the largest |Ritz value| of any projected problem
- *        so far (all of a problem's Ritz values, not only the first b).  nconv == k: SPRS_OK with iters = it - 1.
+ *     2. column c < b is LOCKED in this iteration when res_c <= tol anorm (anorm: step 5 (8));  nconv = the number of LEADING
+ *        c < k that are locked.  nconv == k: SPRS_OK with iters = it - 1.
  *        it > max_iter: SPRS_INSUFFICIENT_ITER with iters = max_iter (the outputs are the current leading k pairs)
  *     3. W_c = M r_c (W_c = r_c without a preconditioner; a diagonal M inside the residual kernel, an applied one in place)
  *     4. AW_c = A W_c
- *     5. Rayleigh-Ritz on S = [X, P, W], AS = [AX, AP, AW], m = 3 b;  at it = 1: S = [X, W], m = 2 b
+ *     5. Rayleigh-Ritz on S = [X, P, W], AS = [AX, AP, AW];  at it = 1: S = [X, W].  Soft locking: the P_c and W_c of the columns
+ *        locked in step 2 are left out of the projected problem (their rows of C are zero; the lock is taken again from the
+ *        residuals of every iteration, so a column whose residual grows comes back), m = b + 2 (b - locked), b + (b - locked)
+ *        without P.  A converged column's W_c is rounding noise and its P_c the difference of two such: kept in the basis they
+ *        make G singular to working precision, and a G that still passes rule (3) then yields Ritz values far outside A's
+ *        spectrum
  *        (1) G = S^H S, K = S^H AS from their upper triangles (G_ij = conj_dot(S_i, S_j), K_ij = conj_dot(S_i, AS_j), i <= j,
  *            summed in T), the lower triangles their conjugates, the diagonals real
  *        (2) s_i = G_ii^(-1/2);  G^ = diag(s) G diag(s).  A G_ii that is not a positive finite number: failure
  *        (3) Cholesky G^ = L L^H, column by column.  Failure when a pivot G^_jj - sum_q |L_jq|^2 (= L_jj^2) is not greater than
  *            64 m eps(T::Real)
- *        (4) failure with P in the basis: steps (2) - (8) once more on the [X, W] sub-blocks of G and K (m = 2 b), the P rows
- *            of C zero, restarts += 1.  Failure without P: SPRS_BREAKDOWN
+ *        (4) failure with P in the basis: steps (2) - (8) once more on the [X, W] sub-blocks of G and K, the P rows of C zero,
+ *            restarts += 1.  Failure without P: SPRS_BREAKDOWN
  *        (5) K^ = L^-1 diag(s) K diag(s) L^-H, taken Hermitian from its upper triangle with a real diagonal
  *        (6) K^ = Z Theta Z^H by cyclic Jacobi: the order and stopping rule of sprs_eigsh_* (round-robin pairs on m rounded up
  *            to even, off^2 <= eps^2 |K^|_F^2 before every sweep, 30 sweeps, then SPRS_BREAKDOWN).  With u = K^_pq / |K^_pq|,
@@ -1145,7 +1150,9 @@ int sprs_eigsh_solve_dev_c(sprs_eigsh *S, size_t k, int which, const sprs_c32 *v
  *            x_q' = sc x_p + c x_q on K^ and Z;  rows row_p' = c row_p - sc row_q, row_q' = conj(sc) row_p + c row_q on K^;
  *            then K^_pq = K^_qp = 0 and Im K^_pp = Im K^_qq = 0 exactly
  *        (7) Theta ascending (SMALLEST) or descending (LARGEST), ties by index, the columns of Z with it
- *        (8) C = diag(s) L^-H Z;  anorm = max(anorm, max_i |Theta_i|)
+ *        (8) C = diag(s) L^-H Z;  anorm = max(anorm, max_i |K_ii| / G_ii) over the X and W columns i of the problem solved:
+ *            Rayleigh quotients of vectors whose products with A are held, so anorm <= |A|_2 up to the rounding of the Gram
+ *            sums whatever the projected problem returns (a Ritz value of an ill-conditioned basis has no such bound)
  *     6. C_X = the first b columns of C, C_P = C_X with its X rows zero, both rounded once to T:
  *        X = S C_X, P = S C_P, AX = AS C_X, AP = AS C_P (every element summed over the rows of C ascending from zero, one product
  *        and one sum per term, each rounded once);  theta = the first b entries of Theta
@@ -1161,9 +1168,9 @@ int sprs_eigsh_solve_dev_c(sprs_eigsh *S, size_t k, int which, const sprs_c32 *v
  *           vecs_len != k n.  vals_out and res_out hold k entries; the four counters may be NULL.  A sprs_diag of another size:
  *           SPRS_DIM_MISMATCH, of another scalar type: SPRS_INVALID_ARGUMENT.
  * Not provided for this solver: a literal mode, the trace, the profile hooks and a sprs_solver_* kind.
- * Limits: there is no soft locking, converged columns stay in the iteration; with k = block (no guard vectors) convergence can
- * take ten times the iterations, so choose block > k; the block is at most 8 wide; the host does not wait inside an
- * iteration, so up to `poll` iterations' launches run as no-ops after the event. */
+ * Limits: soft locking is in the projected problem only, locked columns still cost their share of every pass; with k = block
+ * (no guard vectors) convergence can take ten times the iterations, so choose block > k; the block is at most 8 wide; the host
+ * does not wait inside an iteration, so up to `poll` iterations' launches run as no-ops after the event. */
 typedef struct sprs_lobpcg sprs_lobpcg;
 #define SPRS_LOBPCG_MAX_BLOCK 8
 int sprs_lobpcg_destroy(sprs_lobpcg *S);       /* NULL is a no-op */

@@ -40,6 +40,7 @@ template <class T>
 struct LobState {
     LobHead<T> hd;
     double theta[LOB_MAXB], res[LOB_MAXB];
+    int lock[LOB_MAXB];                  // LobCheck: column c is soft-locked (res_c <= tol anorm), LobRR leaves P_c and W_c out
     T coef[LOB_MAXM * LZ_MAXM];          // coef[i * LZ_MAXM + c]: [C_X | C_P], 3 b rows and 2 b columns (b and b at the start)
     T ident[LOB_MAXB * LZ_MAXM];         // the identity: LzRotate as the copy of k columns into the caller's vectors
 };
@@ -234,8 +235,9 @@ struct LobResid {
     }
 };
 
-// ---- LobCheck: res_c = |r_c| from LobResid's partials ; a NaN: breakdown ; nconv = the leading c < k with res_c <= tol anorm ;
-// nconv == k: converged (iters stays at the iterations completed)
+// ---- LobCheck: res_c = |r_c| from LobResid's partials ; a NaN: breakdown ; lock_c = res_c <= tol anorm for every c < b (soft
+// locking: LobRR leaves P_c and W_c out of the projected problem) ; nconv = the leading c < k that are locked ; nconv == k:
+// converged (iters stays at the iterations completed)
 template <class T>
 __global__ __launch_bounds__(BLOCK) void lob_check_kernel(LobState<T> *S, const Real<T> *partN, int P, int b) {
     __shared__ Real<T> smD[NWAVE];
@@ -250,8 +252,9 @@ __global__ __launch_bounds__(BLOCK) void lob_check_kernel(LobState<T> *S, const 
     bool nan = false;
     for (int c = 0; c < b; ++c) { S->res[c] = sres[c]; nan = nan || !(sres[c] >= 0.0); }
     if (nan) { H.status = ST_BREAKDOWN; return; }
+    for (int c = 0; c < b; ++c) S->lock[c] = sres[c] <= H.tol * H.anorm ? 1 : 0;
     int nc = 0;
-    while (nc < H.k && sres[nc] <= H.tol * H.anorm) ++nc;
+    while (nc < H.k && S->lock[nc]) ++nc;
     H.nconv = nc;
     if (nc == H.k) H.status = ST_CONVERGED;
 }
@@ -384,15 +387,17 @@ __device__ bool lob_jacobi(CD *sA, CD *sV, int M, double *sc, CD *ss, double *sm
 }
 
 // sums: LobReduce's sums of the partials of a pass of m_in vectors in `layout` (1: [X], the start step; 2: [X, W]; 3: [X, P, W]).
-// it: the iteration this step completes (0: the start step).  Every element of every matrix is written by one thread per phase,
-// with barriers between the phases, and every sum has a fixed order.
+// it: the iteration this step completes (0: the start step).  The problem's index set: every X column, then the P columns (layout
+// 3, the first attempt) and the W columns of the columns that LobCheck did not lock, ascending ; sidx maps the problem's index to
+// the pass's, spos a row of the coefficient block to the problem's index (-1: not in it).  Every element of every matrix is
+// written by one thread per phase, with barriers between the phases, and every sum has a fixed order.
 template <class T>
 __global__ __launch_bounds__(BLOCK) void lob_rr_kernel(LobState<T> *S, const LobCD<T> *__restrict__ sums, int m_in, int layout, int b, long long it) {
     using CD = LobCD<T>;
     __shared__ CD sG[LOB_MAXM * LOB_LD], sK[LOB_MAXM * LOB_LD], sL[LOB_MAXM * LOB_LD], sA[LOB_MAXM * LOB_LD], sV[LOB_MAXM * LOB_LD];
     __shared__ CD srot[LOB_MAXM / 2];
     __shared__ double ssc[LOB_MAXM], sth[LOB_MAXM], scs[LOB_MAXM / 2], smD[NWAVE];
-    __shared__ int sperm[LOB_MAXM], sfail;
+    __shared__ int sperm[LOB_MAXM], sidx[LOB_MAXM], spos[LOB_MAXM], sma, sfail;
     LobHead<T> &H = S->hd;
     if (H.status != ST_RUNNING) return;
     const int tid = threadIdx.x, which = H.which;
@@ -412,10 +417,22 @@ __global__ __launch_bounds__(BLOCK) void lob_rr_kernel(LobState<T> *S, const Lob
     __syncthreads();
     const double epsR = (double)seps<Real<T>>();
     int attempt = 0, ma = m_in;
+    auto act = [&](int i) { return sidx[i]; };
     for (;; ++attempt) {
-        // the problem's index i -> the pass's index: the second attempt leaves the P block out
-        ma = attempt == 1 ? 2 * b : m_in;
-        auto act = [&](int i) { return (attempt == 1 && i >= b) ? i + b : i; };
+        // the problem's index i -> the pass's index: the second attempt leaves the P block out, both the locked columns' P and W
+        if (tid == 0) {
+            int na = 0;
+            for (int c = 0; c < b; ++c) sidx[na++] = c;
+            if (layout == 3 && attempt == 0)
+                for (int c = 0; c < b; ++c)
+                    if (!S->lock[c]) sidx[na++] = b + c;
+            if (layout != 1)
+                for (int c = 0; c < b; ++c)
+                    if (!S->lock[c]) sidx[na++] = (layout == 3 ? 2 * b : b) + c;
+            sma = na;
+        }
+        __syncthreads();
+        ma = sma;
         // (2) the scaling
         if (tid < ma) {
             const double g = sre(sG[act(tid) * LOB_LD + act(tid)]);
@@ -461,7 +478,6 @@ __global__ __launch_bounds__(BLOCK) void lob_rr_kernel(LobState<T> *S, const Lob
         return;
     }
     const int M = (ma + 1) & ~1;
-    auto act = [&](int i) { return (attempt == 1 && i >= b) ? i + b : i; };
     // (5) K^ = L^-1 (s K s) L^-H: a thread per column, then a thread per row, forward substitutions in place in sA
     for (int e = tid; e < M * M; e += BLOCK) {
         const int r = e / M, c = e % M;
@@ -523,20 +539,25 @@ __global__ __launch_bounds__(BLOCK) void lob_rr_kernel(LobState<T> *S, const Lob
     // the coefficient block: rows in the order [X, P, W] (the rows of a block that was left out are zero), columns C_X then C_P
     // (= C_X with the X rows zero) ; at the start b rows and C_X alone
     const int rows = layout == 1 ? b : 3 * b, cols = layout == 1 ? b : 2 * b;
-    const bool uses_p = layout == 3 && attempt == 0;
+    if (tid < rows) spos[tid] = -1;
+    __syncthreads();
+    if (tid < ma) spos[(layout == 2 && sidx[tid] >= b) ? sidx[tid] + b : sidx[tid]] = tid;
+    __syncthreads();
     for (int e = tid; e < rows * cols; e += BLOCK) {
         const int r3 = e / cols, c = e % cols, cx = c % b;
-        int i = r3;                                        // the problem's index of row r3, -1: not in it
-        if (r3 >= 2 * b) i = uses_p ? r3 : r3 - b;
-        else if (r3 >= b) i = uses_p ? r3 : -1;
+        const int i = spos[r3];                            // the problem's index of row r3, -1: not in it
         CD v = szero<CD>();
         if (i >= 0 && !(c >= b && r3 < b)) v = smulr(sV[i * LOB_LD + sperm[cx]], ssc[i]);
         lob_round(v, S->coef[r3 * LZ_MAXM + c]);
     }
     if (tid < b) S->theta[tid] = sth[sperm[tid]];
     if (tid == 0) {
-        double an = H.anorm;
-        for (int i = 0; i < ma; ++i) an = fmax(an, fabs(sth[i]));
+        double an = H.anorm;                               // the Rayleigh quotients of the problem's X and W columns: each <= |A|_2
+        for (int i = 0; i < ma; ++i) {
+            const int pi = sidx[i];
+            if (layout == 3 && pi >= b && pi < 2 * b) continue;
+            an = fmax(an, fabs(sre(sK[pi * LOB_LD + pi])) / sre(sG[pi * LOB_LD + pi]));
+        }
         H.anorm = an; H.matvecs += b; H.iters = it;
     }
 }

@@ -58,7 +58,8 @@ class Lobpcg:
         """-> (vals, X, info): vals the first k Ritz values in the order of `which`, X of shape (k, n) with eigenvector c in row c
         (None with vectors=False), info = dict(res, nconv, iters, restarts, matvecs) with res the absolute residual norms and
         restarts the count of [X, W] fallbacks.  precond: None, a `DiagPrecond`, `ILU0`, `AMG` or `FSAI`.  tol = 0.0 selects
-        1e-10 (f64 / c64) or 1e-4 (f32 / c32); a pair counts as converged at res <= tol * (the largest |Ritz value| seen).
+        1e-10 (f64 / c64) or 1e-4 (f32 / c32); a pair counts as converged at res <= tol * anorm, anorm the largest |Rayleigh
+        quotient| of an X or W column seen (at most |A|_2), and is soft-locked while it stays there.
         X0: a host array of shape (block, n) or a device vector of block * n entries, vector after vector (a device X0 takes
         the device entry point; the results come back as host arrays either way); None: `default_X0()`.  Raises SolverError:
         InsufficientIterNum after max_iter iterations and BreakDown (a NaN, a zero or dependent column of X0) carry what was

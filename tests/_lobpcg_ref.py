@@ -12,7 +12,7 @@ from _eigsh_ref import (BREAKDOWN, EPS64, INSUFFICIENT_ITER, LARGEST, MAX_SWEEPS
 MAX_BLOCK = 8
 
 Result = namedtuple("Result", "status vals X res nconv iters restarts matvecs sweeps")
-RR = namedtuple("RR", "ok theta C sweeps used_p fell_back")
+RR = namedtuple("RR", "ok theta C sweeps used_p fell_back anorm")
 
 
 def default_block(n):
@@ -123,19 +123,21 @@ def herm_from_upper(M):
     return H
 
 
-def rayleigh_ritz(G, K, b, with_p, which, epsR):
+def rayleigh_ritz(G, K, b, with_p, which, epsR, lock=None):
     """G, K: (3 b, 3 b) in the order [X, P, W] (the P rows and columns are ignored unless with_p; (b, b) for the start step).
-    -> RR: theta sorted for `which` (all of the problem's), C with 3 b rows (P rows zero where P was left out) and the columns
-    in theta's order."""
+    lock: b booleans, the soft-locked columns, whose P_c and W_c are left out of the problem (None: none is locked).
+    -> RR: theta sorted for `which` (all of the problem's), C with 3 b rows (zero where a vector was left out) and the columns
+    in theta's order, anorm = the largest |K_ii| / G_ii over the X and W columns of the problem solved."""
     m3 = G.shape[0]
     G = herm_from_upper(np.asarray(G)); K = herm_from_upper(np.asarray(K))
     tries = []
     if m3 == b:
         tries.append(np.arange(b))
     else:
+        free = np.arange(b) if lock is None else np.flatnonzero(~np.asarray(lock, bool))
         if with_p:
-            tries.append(np.arange(3 * b))
-        tries.append(np.concatenate([np.arange(b), np.arange(2 * b, 3 * b)]))
+            tries.append(np.concatenate([np.arange(b), b + free, 2 * b + free]))
+        tries.append(np.concatenate([np.arange(b), 2 * b + free]))
     fell = False
     for t, idx in enumerate(tries):
         out = _project(G[np.ix_(idx, idx)], K[np.ix_(idx, idx)], epsR)
@@ -144,12 +146,14 @@ def rayleigh_ritz(G, K, b, with_p, which, epsR):
             continue
         theta, Cs, sweeps = out
         if theta is None:
-            return RR(False, None, None, sweeps, False, fell)
+            return RR(False, None, None, sweeps, False, fell, 0.0)
         o = order(theta, which)
         C = np.zeros((m3, idx.size), Cs.dtype)
         C[idx] = Cs[:, o]
-        return RR(True, theta[o], C, sweeps, with_p and t == 0 and m3 != b, fell)
-    return RR(False, None, None, 0, False, fell)
+        xw = idx[(idx < b) | (idx >= 2 * b)]
+        rq = float(np.max(np.abs(np.real(np.diag(K))[xw]) / np.real(np.diag(G))[xw]))
+        return RR(True, theta[o], C, sweeps, with_p and t == 0 and m3 != b, fell, rq)
+    return RR(False, None, None, 0, False, fell, 0.0)
 
 
 def lobpcg(indptr, indices, data, k, which, X0, max_iter, tol, prec=None):
@@ -182,7 +186,7 @@ def lobpcg(indptr, indices, data, k, which, X0, max_iter, tol, prec=None):
     most = max(most, rr.sweeps)
     if not rr.ok:
         return Result(BREAKDOWN, zk, None, zk, 0, 0, 0, matvecs, most)
-    anorm = max(anorm, float(np.max(np.abs(rr.theta))))
+    anorm = max(anorm, rr.anorm)
     X, AX = rotate(X, rr.C), rotate(AX, rr.C)
     theta = rr.theta[:b].copy()
     P = np.zeros_like(X); AP = np.zeros_like(X)
@@ -195,8 +199,9 @@ def lobpcg(indptr, indices, data, k, which, X0, max_iter, tol, prec=None):
             res = np.sqrt(np.sum((Rm.real * Rm.real + Rm.imag * Rm.imag).astype(R), axis=1, dtype=R)).astype(np.float64)
         if not np.all(np.isfinite(res)):
             return Result(BREAKDOWN, theta[:k], None, res[:k], 0, it - 1, restarts, matvecs, most)
+        lock = res <= tol * anorm                    # soft locking: these columns' P_c and W_c stay out of the projected problem
         nconv = 0
-        while nconv < k and res[nconv] <= tol * anorm:
+        while nconv < k and lock[nconv]:
             nconv += 1
         if nconv == k or it > max_iter:
             return Result(OK if nconv == k else INSUFFICIENT_ITER, theta[:k].copy(), X[:k].copy(), res[:k].copy(), nconv, it - 1, restarts,
@@ -211,12 +216,12 @@ def lobpcg(indptr, indices, data, k, which, X0, max_iter, tol, prec=None):
             AW = np.stack([A(w) for w in W])
         matvecs += b
         S = np.concatenate([X, P, W]); AS = np.concatenate([AX, AP, AW])
-        rr = rayleigh_ritz(*gram(S, AS), b, with_p, which, epsR)
+        rr = rayleigh_ritz(*gram(S, AS), b, with_p, which, epsR, lock)
         most = max(most, rr.sweeps)
         restarts += 1 if rr.fell_back else 0
         if not rr.ok:
             return Result(BREAKDOWN, theta[:k], None, res[:k], nconv, it, restarts, matvecs, most)
-        anorm = max(anorm, float(np.max(np.abs(rr.theta))))
+        anorm = max(anorm, rr.anorm)
         CX = rr.C[:, :b]
         CP = CX.copy(); CP[:b] = 0.0
         X, P, AX, AP = rotate(S, CX), rotate(S, CP), rotate(AS, CX), rotate(AS, CP)

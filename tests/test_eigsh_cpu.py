@@ -14,6 +14,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _eigsh_ref as ref  # noqa: E402
+import _kron  # noqa: E402
 
 F64, C64, F32, C32 = np.float64, np.complex128, np.float32, np.complex64
 EPS64 = ref.EPS64
@@ -193,6 +194,59 @@ def test_counts_and_eigenpairs(case):
     # every restart replaces the kept vectors by m-term sums V S (S orthogonal to m eps): up to m eps of orthogonality is lost
     # per cycle and CGS2 restores it for the new vectors only, so the defect may grow like cycles * m * eps
     assert orth_defect(o.X) <= 4 * m * (o.restarts + 1) * float(np.finfo(ref.real_dtype(dt)).eps)
+
+
+# ---------------------------------------------------------------------------------------------- several tiles a workgroup
+# kron_sum(40, n2) (tests/_kron.py), k = 4, ncv = 64, at the least n = 40 n2 that gives every workgroup of the in-place basis
+# rotation three tiles and leaves a partial last one on a device of 256 CUs (tests/test_gpu_eigsh.py derives n2 from the device it
+# runs on and compares with the restatement at that size): dtype -> (which, n2, cycles, matvecs) of the checker.  One end a
+# type; the GPU tests check the other end against the factors' spectra alone.
+KRON_N1, KRON_K, KRON_NCV = 40, 4, 64
+KRON_COUNTS = {
+    "float64": ("smallest", 4916, 5, 288),
+    "complex128": ("largest", 2458, 5, 288),
+    "float32": ("largest", 9831, 2, 120),
+    "complex64": ("smallest", 4916, 3, 176),
+}
+
+
+def kron_n2(num_cu, dt, ncv, k):
+    """The least n2 with more than three tiles for every workgroup of the restart's rotation (me = ncv, q = restart_size) and
+    of the final one (q = k), and a partial last tile."""
+    dt = np.dtype(dt)
+    rb = ref.real_dtype(dt).itemsize
+    grid = max(_kron.rotate_grid(num_cu, ncv, q, rb)[0] for q in (ref.restart_size(k, ncv), k))
+    return _kron.n2_for_tiles(KRON_N1, _kron.TILE_ROWS[dt.name], 3 * grid), grid
+
+
+@functools.lru_cache(maxsize=None)
+def kron_checker(n2, k, m, which, dtname):
+    """The restatement on kron_sum(40, n2), the default start vector and tolerance (shared, read-only)."""
+    dt = np.dtype(dtname).type
+    ip, ix, d, _, _ = _kron.kron_sum(KRON_N1, n2, dt)
+    o = ref.eigsh(ip, ix, d, k, ref.SMALLEST if which == "smallest" else ref.LARGEST, ref.default_v0(ip.size - 1, dt), m, 100, ref.default_tol(dt))
+    if o.X is not None:
+        o.X.setflags(write=False)
+    return o
+
+
+@pytest.mark.parametrize("dtname", sorted(KRON_COUNTS))
+def test_kron_counts_and_eigenpairs(dtname):
+    """The recorded sizes are the rule's at 256 CUs, and the restatement finds the four extreme pairs of the factors' spectra
+    there in the recorded cycles, to the bounds of test_counts_and_eigenpairs."""
+    which, n2, cycles, matvecs = KRON_COUNTS[dtname]
+    dt = np.dtype(dtname).type
+    assert kron_n2(256, dt, KRON_NCV, KRON_K)[0] == n2
+    ip, ix, d, lam, nrm = _kron.kron_sum(KRON_N1, n2, dt)
+    o = kron_checker(n2, KRON_K, KRON_NCV, which, dtname)
+    tol = ref.default_tol(dt)
+    assert o.status == ref.OK and o.nconv == KRON_K and (o.restarts, o.matvecs) == (cycles, matvecs)
+    assert o.matvecs == KRON_NCV + (o.restarts - 1) * (KRON_NCV - ref.restart_size(KRON_K, KRON_NCV))
+    err = float(np.max(np.abs(o.vals - wanted(lam, KRON_K, which))))
+    tr = _kron.true_residual(_kron.csr_double(ip, ix, d), o.vals, o.X)
+    print("kron40x%d %s %s: |theta - lambda| %.3e (bound %.3e), true residual %.3e (bound %.3e)" % (n2, dtname, which, err, tol * nrm, tr, 2 * tol * nrm))
+    assert err <= tol * nrm and tr <= 2 * tol * nrm
+    assert orth_defect(o.X) <= 4 * KRON_NCV * (o.restarts + 1) * float(np.finfo(ref.real_dtype(dt)).eps)
 
 
 def _jacobi_check(T):

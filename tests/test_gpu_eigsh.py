@@ -5,7 +5,9 @@ of the basis rotation kernel, every SpMV route, determinism, the invariant-subsp
 The restatement's cycle and product counts (tests/test_eigsh_cpu.py::COUNTS holds and checks them; f64 / c64 at tol 1e-10,
 f32 / c32 at 1e-4, the default start vector) range from 1 cycle of 64 products (chgrid9x8, ncv 64) to 494 cycles of two
 products (hermband700, k = 1, ncv 3, largest, c64).  n = 1320 and 1500 leave a partial last tile in every scalar type (a tile is
-64 rows of c64, 128 of f64 / c32, 256 of f32), n = 72 and n = 30 are less than one tile."""
+64 rows of c64, 128 of f64 / c32, 256 of f32), n = 72 and n = 30 are less than one tile.  The Kronecker family of tests/_kron.py
+gives sizes, computed from the device's CU count, at which every workgroup of the in-place rotation makes several trips and
+the fused kernels walk several chunks."""
 import ctypes as C
 import os
 import sys
@@ -15,13 +17,15 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _eigsh_ref as ref  # noqa: E402
-from test_eigsh_cpu import CASES, _id, checker, count, orth_defect, spectrum, system, true_residual, wanted  # noqa: E402
+import _kron  # noqa: E402
+from test_eigsh_cpu import (CASES, KRON_COUNTS, KRON_K, KRON_N1, KRON_NCV, _id, checker, count, kron_checker, kron_n2, orth_defect,  # noqa: E402
+                            spectrum, system, true_residual, wanted)
 
 pytestmark = pytest.mark.gpu
 
 F64, C64, F32, C32 = np.float64, np.complex128, np.float32, np.complex64
 ALL = [F64, C64, F32, C32]
-_KNOBS = ("spmv_dict", "stream_nt")
+_KNOBS = ("spmv_dict", "stream_nt", "ew_chunk")
 
 
 @pytest.fixture(scope="module")
@@ -36,9 +40,11 @@ def sa():
 @pytest.fixture(autouse=True)
 def _restore_knobs(sa):
     ctx = sa.default_ctx(0)
+    grid = ctx.get("grid")
     yield
     for k in _KNOBS:
         ctx.set(k, -1)
+    ctx.set("grid", grid)
 
 
 def _eps(dt):
@@ -96,6 +102,111 @@ def test_parity(sa, case):
     # a residual estimate that sits on the threshold may fall either way under another summation order
     assert abs(info["matvecs"] - want[1]) <= one_cycle and abs(info["restarts"] - want[0]) <= 1, (info, want)
     assert info["matvecs"] == m + (info["restarts"] - 1) * one_cycle
+
+
+# ---------------------------------------------------------------------------------------------- several tiles a workgroup
+def _kron_solve(sa, n1, n2, dt, k, m, which, **kw):
+    ip, ix, d, _, _ = _kron.kron_sum(n1, n2, dt)
+    n = ip.size - 1
+    E = sa.Eigsh.new(sa.HipCsr.new((n, n), ip, ix, d), n, m)
+    try:
+        return E.solve(k, which, **kw)
+    finally:
+        E.close()
+
+
+def _check_big(n1, n2, dt, k, which, vals, X, info, label):
+    """The bounds of _check_pairs on kron_sum(n1, n2): truth from the factors' spectra, the true residual in double."""
+    ip, ix, d, lam, nrm = _kron.kron_sum(n1, n2, dt)
+    tol = ref.default_tol(dt)
+    assert info["nconv"] == k and vals.shape == (k,) and X.shape == (k, n1 * n2) and np.all(np.isfinite(vals)) and np.all(np.isfinite(X))
+    err = float(np.max(np.abs(vals.astype(F64) - wanted(lam, k, which))))
+    tr = _kron.true_residual(_kron.csr_double(ip, ix, d), vals, X)
+    print("%s: |theta - lambda| %.3e (bound %.3e), true residual %.3e (bound %.3e), cycles %d, products %d"
+          % (label, err, tol * nrm, tr, 2 * tol * nrm, info["restarts"], info["matvecs"]))
+    assert err <= tol * nrm
+    assert tr <= 2 * tol * nrm
+
+
+@pytest.mark.parametrize("dt", ALL, ids=lambda d: np.dtype(d).name)
+def test_rotation_in_place_takes_several_trips(sa, dt):
+    """LzRotate rotates the basis in place (out == V): safe because a tile's rows are read by one workgroup alone and a barrier
+    stands before the LDS tile is overwritten by the next trip.  Up to 1500 rows there are at most 24 tiles and one trip.  Here
+    ncv = 64: the tile and the 64 x 8 coefficient block take 66 to 68 KiB of LDS, per_cu = clamp(160 KiB / lds, 1, 8) = 2 and
+    the grid is 2 num_cu; n = 40 n2 is the least with more than 3 grid tiles and a partial last one, so every workgroup makes three
+    trips and one a fourth on the partial tile.  Both ends against the factors' spectra; the end recorded in
+    test_eigsh_cpu.py::KRON_COUNTS also against the restatement's cycle count at this size."""
+    num_cu = sa.default_ctx(0).get("num_cu")
+    n2, grid = kron_n2(num_cu, dt, KRON_NCV, KRON_K)
+    rows = _kron.TILE_ROWS[np.dtype(dt).name]
+    n = KRON_N1 * n2
+    ntile = (n + rows - 1) // rows
+    assert grid == 2 * num_cu and ntile == 3 * grid + 1 and n % rows != 0
+    print("n %d, %d tiles of %d rows, grid %d: 3 trips a workgroup, 4 for the first" % (n, ntile, rows, grid))
+    one_cycle = KRON_NCV - ref.restart_size(KRON_K, KRON_NCV)
+    recorded = KRON_COUNTS[np.dtype(dt).name][0]
+    for which in ("smallest", "largest"):
+        vals, X, info = _kron_solve(sa, KRON_N1, n2, dt, KRON_K, KRON_NCV, which)
+        _check_big(KRON_N1, n2, dt, KRON_K, which, vals, X, info, "kron40x%d %s %s" % (n2, np.dtype(dt).name, which))
+        assert info["matvecs"] == KRON_NCV + (info["restarts"] - 1) * one_cycle
+        assert info["restarts"] >= 2                         # at least one restart: the in-place rotation of 64 vectors into 8 ran
+        if which == recorded:
+            o = kron_checker(n2, KRON_K, KRON_NCV, which, np.dtype(dt).name)
+            print("cycles: GPU %d, restatement %d" % (info["restarts"], o.restarts))
+            assert o.status == ref.OK and abs(info["restarts"] - o.restarts) <= 1 and abs(info["matvecs"] - o.matvecs) <= one_cycle
+            assert orth_defect(X) <= max(8 * orth_defect(o.X), 64 * _eps(dt))
+
+
+def test_wide_rotation_takes_several_trips(sa):
+    """k = 9, ncv = 24: the restart keeps restart_size = min(k + max(k, 4), ncv - 2) = 18 columns of 24 vectors, the CB = 4 flavour
+    of the rotation (q > 8); 24 KiB of tile and a 24 x 20 coefficient block make per_cu = 5, the final rotation into nine columns
+    (24 x 12) 6.  In c64 (64 rows a tile, the least n for these caps) n is the least with three trips a workgroup of the larger
+    grid, so more for the other, and a partial tile.  Nine pairs at the lower end: the four
+    isolated ones and five from the cluster above them."""
+    dt, k, m = C64, 9, 24
+    p = ref.restart_size(k, m)
+    assert p == 18
+    num_cu = sa.default_ctx(0).get("num_cu")
+    grids = [_kron.rotate_grid(num_cu, m, q, 8) for q in (p, k)]
+    grid = max(g[0] for g in grids)
+    n2 = _kron.n2_for_tiles(KRON_N1, 64, 3 * grid)
+    n = KRON_N1 * n2
+    assert [g[1] for g in grids] == [5, 6] and (n + 63) // 64 == 3 * grid + 1 and n % 64 != 0
+    print("n %d, %d tiles, grids %s: at least 3 trips a workgroup" % (n, (n + 63) // 64, [g[0] for g in grids]))
+    vals, X, info = _kron_solve(sa, KRON_N1, n2, dt, k, m, "smallest", max_restarts=20000)
+    _check_big(KRON_N1, n2, dt, k, "smallest", vals, X, info, "kron40x%d complex128 k=9 ncv=24" % n2)
+    assert info["matvecs"] == m + (m - p) * (info["restarts"] - 1) and info["restarts"] >= 2
+
+
+@pytest.mark.parametrize("dt,nt", [(F64, 1), (F32, -1), (C64, -1), (C32, -1)], ids=["float64-nt", "float32", "complex128", "complex64"])
+def test_fused_walk_takes_several_trips(sa, dt, nt):
+    """The fused kernels of the Lanczos step (GmDots, GmUpdate, GmScale, LzNrm through launch_fused) with the "grid" knob at 8 and
+    ew_chunk at 1: one workgroup an XCD walks its eighth of the packs in trips of 256.  n = 41 * 979 = 40139 is odd and 3 mod 4 (a
+    scalar tail in f64, f32 and c32) and makes ceil(ceil(n / PK / 8) / 256) >= 5 trips, the last XCD's last trip partial.
+    Against truth, and against the default-knob run of the same case: another summation order, so the values agree to tol |A|
+    and the counts within one cycle (test_parity's allowance)."""
+    n1, n2, k, m = 41, 979, 4, 30
+    n = n1 * n2
+    ctx = sa.default_ctx(0)
+    packs = n // (16 // np.dtype(dt).itemsize)
+    trips = -(-(-(-packs // 8)) // 256)                      # fused_kernel: chunk = trips * 256 packs an XCD, one workgroup each
+    assert n % 2 == 1 and n % 4 == 3 and trips >= 5 and 0 < packs - 7 * trips * 256 and (packs - 7 * trips * 256) % 256 != 0
+    nrm = _kron.kron_sum(n1, n2, dt)[4]
+    one_cycle = m - ref.restart_size(k, m)
+    g0 = ctx.get("grid")
+    for which in ("smallest", "largest"):
+        v0, X0, i0 = _kron_solve(sa, n1, n2, dt, k, m, which)
+        ctx.set("grid", 8); ctx.set("ew_chunk", 1); ctx.set("stream_nt", nt)
+        try:
+            v1, X1, i1 = _kron_solve(sa, n1, n2, dt, k, m, which)
+        finally:
+            ctx.set("grid", g0); ctx.set("ew_chunk", -1); ctx.set("stream_nt", -1)
+        print("n %d, %d trips a workgroup, %s: cycles %d (default knobs %d)" % (n, trips, which, i1["restarts"], i0["restarts"]))
+        _check_big(n1, n2, dt, k, which, v1, X1, i1, "kron41x979 %s %s grid 8" % (np.dtype(dt).name, which))
+        _check_big(n1, n2, dt, k, which, v0, X0, i0, "kron41x979 %s %s default" % (np.dtype(dt).name, which))
+        assert np.max(np.abs(v1.astype(F64) - v0.astype(F64))) <= ref.default_tol(dt) * nrm
+        assert abs(i1["restarts"] - i0["restarts"]) <= 1 and abs(i1["matvecs"] - i0["matvecs"]) <= one_cycle
+        assert i1["matvecs"] == m + (i1["restarts"] - 1) * one_cycle
 
 
 # ---------------------------------------------------------------------------------------------- the rotation kernel's edges

@@ -15,6 +15,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _expm_ref as ref  # noqa: E402
+import _kron  # noqa: E402
 from test_expm_cpu import CASES, COUNTS, TENTH_REJECTION, _id, checker, propagator, system, tol_of, true_error, wide  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -37,9 +38,11 @@ def sa():
 @pytest.fixture(autouse=True)
 def _restore_knobs(sa):
     ctx = sa.default_ctx(0)
+    grid = ctx.get("grid")
     yield
-    for k in _KNOBS:
+    for k in _KNOBS + ("ew_chunk",):
         ctx.set(k, -1)
+    ctx.set("grid", grid)
 
 
 def _eps(dt):
@@ -96,6 +99,46 @@ def test_parity(sa, case):
     assert 0.0 <= info["err"] <= bound
     assert info["hump"] >= _norm(ref.start_vector(w.size, dt)) * (1 - w.size * _eps(dt))     # (any order of a sum of n squares)
     assert info["t_done"] == float(np.dtype(ref.real_dtype(dt)).type(t))
+
+
+# ---------------------------------------------------------------------------------------------- several trips a workgroup
+@pytest.mark.parametrize("dt,nt", [(F64, -1), (F32, -1), (C64, -1), (C32, 1)], ids=["float64", "float32", "complex128", "complex64-nt"])
+def test_fused_walk_takes_several_trips(sa, dt, nt):
+    """The fused kernels of the Arnoldi step and of the state update with the "grid" knob at 8 and ew_chunk at 1: one workgroup an
+    XCD walks its eighth of the packs in trips of 256.  kron_sum(41, 979) (tests/_kron.py), n = 40139: odd and 3 mod 4 (a scalar
+    tail in f64, f32 and c32), at least five trips, the last XCD's last trip partial.  ncv = 30, t = 0.25 (|exp(tA)|_2 = e^(4 t)
+    = 2.7), a start vector of norm one.  Truth is vec(E2 V E1^T) from the dense exponentials of the two factors: |w - w_exact|
+    against the bound test_parity applies to the error estimate, for this run and the default-knob run of the same case, which
+    agree to twice that bound and in their counts within one sub-step."""
+    n1, n2, ncv, t = 41, 979, 30, 0.25
+    n = n1 * n2
+    ctx = sa.default_ctx(0)
+    packs = n // (16 // np.dtype(dt).itemsize)
+    trips = -(-(-(-packs // 8)) // 256)                      # fused_kernel: chunk = trips * 256 packs an XCD, one workgroup each
+    assert n % 2 == 1 and n % 4 == 3 and trips >= 5 and 0 < packs - 7 * trips * 256 and (packs - 7 * trips * 256) % 256 != 0
+    ip, ix, d, _, nrm = _kron.kron_sum(n1, n2, dt)
+    v = ref.start_vector(n, dt).astype(wide(dt))
+    v = (v / np.linalg.norm(v)).astype(dt)
+    exact = _kron.expm_exact(n1, n2, t, v, np.dtype(dt).kind == "c")
+    bound = 1.2 * abs(t) * ref.default_tol(dt)
+    A = sa.HipCsr.new((n, n), ip, ix, d)
+    E = sa.Expm.new(A, n, ncv)
+    g0 = ctx.get("grid")
+    w0, i0 = E.apply(t, v)
+    ctx.set("grid", 8); ctx.set("ew_chunk", 1); ctx.set("stream_nt", nt)
+    try:
+        w1, i1 = E.apply(t, v)
+    finally:
+        ctx.set("grid", g0); ctx.set("ew_chunk", -1); ctx.set("stream_nt", -1)
+    E.close()
+    e0, e1 = _norm(w0.astype(wide(dt)) - exact), _norm(w1.astype(wide(dt)) - exact)
+    print("n %d, %d trips a workgroup, |exp(tA)| %.2f: |w - w_exact| %.3e (default knobs %.3e), estimates %.3e and %.3e, bound %.3e, %r / %r"
+          % (n, trips, np.exp(t * nrm), e1, e0, i1["err"], i0["err"], bound, i1, i0))
+    assert np.all(np.isfinite(w1)) and e1 <= bound and e0 <= bound
+    assert 0.0 <= i1["err"] <= bound and i1["t_done"] == float(np.dtype(ref.real_dtype(dt)).type(t))
+    assert _norm(w1.astype(wide(dt)) - w0.astype(wide(dt))) <= 2 * bound
+    assert abs(i1["steps"] - i0["steps"]) <= 1 and abs(i1["rejects"] - i0["rejects"]) <= 1
+    assert i1["matvecs"] == i1["steps"] * (ncv + 1)
 
 
 # ---------------------------------------------------------------------------------------------- a unitary evolution

@@ -7,7 +7,11 @@ The restatement's counts (tests/test_lobpcg_cpu.py::COUNTS holds and checks them
 default start block) range from 11 iterations (chgrid9x8, (4, 8), largest, c32) to 167 (poisson12x11x10, (1, 1), smallest, f64).
 A GPU run may take up to 4 times the restatement's count: a cap, not a parity claim — summation order alone moved the
 restatement's own single-precision counts by a factor of 2.  n = 1320 and 1500 leave a partial last tile in every scalar type (a
-tile is 64 rows of c64, 128 of f64 / c32, 256 of f32), n = 72 and n = 30 are less than one tile."""
+tile is 64 rows of c64, 128 of f64 / c32, 256 of f32), n = 72 and n = 30 are less than one tile.
+
+The Kronecker family of tests/_kron.py (isolated extreme eigenvalues over a cluster, truth from the factors' spectra) carries the
+cases the small matrices cannot: early convergence of the leading columns (soft locking, anorm), and sizes computed from the
+device's CU count at which every walker of the Gram kernel takes several tiles and the fused residual kernel several trips."""
 import ctypes as C
 import os
 import sys
@@ -16,15 +20,17 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _kron  # noqa: E402
 import _lobpcg_ref as ref  # noqa: E402
 from test_eigsh_cpu import orth_defect, spectrum, system, true_residual, wanted  # noqa: E402
-from test_lobpcg_cpu import CASES, EDGE_CASES, _id, checker, count, is_single  # noqa: E402
+from test_lobpcg_cpu import (CASES, EDGE_CASES, KRON_CASES, KRON_N1, _id, _kron_id, check_kron_pairs, checker, count, is_single, kron_checker,  # noqa: E402
+                             kron_X0)
 
 pytestmark = pytest.mark.gpu
 
 F64, C64, F32, C32 = np.float64, np.complex128, np.float32, np.complex64
 ALL = [F64, C64, F32, C32]
-_KNOBS = ("spmv_dict", "stream_nt")
+_KNOBS = ("spmv_dict", "stream_nt", "ew_chunk")
 _ids = lambda v: v if isinstance(v, str) else np.dtype(v).name
 
 
@@ -40,9 +46,11 @@ def sa():
 @pytest.fixture(autouse=True)
 def _restore_knobs(sa):
     ctx = sa.default_ctx(0)
+    grid = ctx.get("grid")
     yield
     for k in _KNOBS:
         ctx.set(k, -1)
+    ctx.set("grid", grid)
 
 
 def _eps(dt):
@@ -111,6 +119,142 @@ def test_parity(sa, case):
 @pytest.mark.parametrize("case", EDGE_CASES, ids=_id)
 def test_fewer_rows_than_one_tile(sa, case):
     _parity(sa, case)
+
+
+# ---------------------------------------------------------------------------------------------- isolated extreme eigenvalues
+_STATUS = {"InsufficientIterNum": ref.INSUFFICIENT_ITER, "BreakDown": ref.BREAKDOWN}
+
+
+def _kron_solve(sa, n1, n2, dt, k, b, which, **kw):
+    """-> (status, vals, X, info) of one solve on kron_sum(n1, n2): an event comes back as its status, not as an exception."""
+    ip, ix, d, _, _ = _kron.kron_sum(n1, n2, dt)
+    n = ip.size - 1
+    S = sa.Lobpcg.new(sa.HipCsr.new((n, n), ip, ix, d), n, b)
+    try:
+        return (ref.OK,) + tuple(S.solve(k, which, **kw))
+    except (sa.error.InsufficientIterNum, sa.error.BreakDown) as e:
+        return _STATUS[type(e).__name__], e.vals, e.X, e.info
+    finally:
+        S.close()
+
+
+@pytest.mark.parametrize("case", KRON_CASES, ids=_kron_id)
+def test_isolated_extreme_eigenvalues(sa, case):
+    """kron_sum(40, n2) (tests/test_lobpcg_cpu.py): the leading columns converge long before the others and are soft-locked.  A
+    solve that says OK holds the bounds of _check_pairs against the factors' spectra; where the restatement converges the GPU run
+    must, within 4 times its iterations (test_parity's cap)."""
+    n2, which, dt, x0 = case
+    o = kron_checker(n2, which, np.dtype(dt).name, x0)
+    n = KRON_N1 * n2
+    max_iter = 4 * o.iters if o.status == ref.OK else 400
+    status, vals, X, info = _kron_solve(sa, KRON_N1, n2, dt, 4, 8, which, max_iter=max_iter, X0=None if x0 == "default" else kron_X0(n, 8, dt, x0))
+    print("iterations: GPU %d (fallbacks %d, status %d), restatement %d (fallbacks %d, status %d)"
+          % (info["iters"], info["restarts"], status, o.iters, o.restarts, o.status))
+    ok = check_kron_pairs(n2, dt, 4, which, status, vals, X, _kron_id(case))
+    assert ok or o.status != ref.OK
+    if ok:
+        assert info["nconv"] == 4 and info["matvecs"] == 8 * (info["iters"] + 1)
+        assert orth_defect(X) <= 64 * _eps(dt)
+
+
+# ---------------------------------------------------------------------------------------------- more than one tile a workgroup
+def gram_walkers(num_cu, dt, m):
+    """Lobpcg::gram's launch rule (csrc/lobpcg.hip): entry blocks of R x R (R = 4; 2 in c64), MB = ceil(m / R) block rows,
+    nb1 = MB (MB + 1) / 2 blocks a triangle, 8 wavefronts; one workgroup holds both triangles when ceil(2 nb1 / 8) <= NBL (6; c64:
+    10; c32: 3), else two share them (nsplit = 2); the small flavour (blocks a wavefront <= NBS = 2; c64: 3) runs two workgroups a
+    CU.  -> (the cap on the walkers GW = min(num_cu per_cu / nsplit, 512), nsplit, per_cu)."""
+    dt = np.dtype(dt)
+    R = 2 if dt == np.dtype(C64) else 4
+    NBL = {np.dtype(F64): 6, np.dtype(F32): 6, np.dtype(C32): 3, np.dtype(C64): 10}[dt]
+    NBS = 3 if dt == np.dtype(C64) else 2
+    MB = (m + R - 1) // R
+    nb1 = MB * (MB + 1) // 2
+    nsplit = 1 if (2 * nb1 + 7) // 8 <= NBL else 2
+    need = ((2 * nb1 if nsplit == 1 else nb1) + 7) // 8
+    per_cu = 2 if need <= NBS else 1
+    return min(num_cu * per_cu // nsplit, 512), nsplit, per_cu
+
+
+def _check_big(n1, n2, dt, k, which, vals, X, label):
+    """The bounds of _check_pairs on kron_sum(n1, n2): truth from the factors' spectra, the true residual in double."""
+    ip, ix, d, lam, nrm = _kron.kron_sum(n1, n2, dt)
+    tol = ref.default_tol(dt)
+    assert vals.shape == (k,) and X.shape == (k, n1 * n2) and np.all(np.isfinite(vals)) and np.all(np.isfinite(X))
+    err = float(np.max(np.abs(vals.astype(F64) - wanted(lam, k, which))))
+    tr = _kron.true_residual(_kron.csr_double(ip, ix, d), vals, X)
+    print("%s: |theta - lambda| %.3e (bound %.3e), true residual %.3e (bound %.3e)" % (label, err, tol * nrm, tr, 2 * tol * nrm))
+    assert err <= tol * nrm
+    assert tr <= 2 * tol * nrm
+
+
+@pytest.mark.parametrize("block", [8, 2])
+@pytest.mark.parametrize("dt", ALL, ids=_ids)
+def test_gram_walk_takes_several_tiles(sa, dt, block):
+    """LobGram's walkers fold tile t while tile t + GW lands in the other LDS buffer.  With at most 24 tiles (n <= 1500) every
+    walker has one tile and the prefetch, the buffer flip and the whole / partial switch inside a walk never run.  Here
+    n = 40 n2 is the least with ntile > 3.5 GW for the widest pass (m = 3 b; m = 2 b at the first iteration has the same or a
+    larger cap, so it is asserted too) and n no multiple of the tile: every walker takes 3 or 4 tiles, both buffers are
+    prefetched into, and the last tile is partial.  Block 8 is the wide register flavour (nsplit = 2 in c64 and c32), block 2
+    the small one with two workgroups a CU.  The numpy restatement is not run at this size: truth is the factors' spectra."""
+    num_cu = sa.default_ctx(0).get("num_cu")
+    rows = _kron.TILE_ROWS[np.dtype(dt).name]
+    caps = [gram_walkers(num_cu, dt, mm * block) for mm in (3, 2)]
+    GW = max(c[0] for c in caps)
+    n2 = _kron.n2_for_tiles(KRON_N1, rows, (7 * GW + 1) // 2)
+    n = KRON_N1 * n2
+    ntile = (n + rows - 1) // rows
+    assert n % rows != 0 and all(ntile >= 3 * c[0] + 1 for c in caps) and ntile > 24
+    if block == 8:
+        assert caps[0][1] == (2 if np.dtype(dt).kind == "c" else 1) and caps[0][2] == 1
+    else:
+        assert caps[0][1] == 1 and caps[0][2] == 2
+    k = 4 if block == 8 else 1
+    print("n %d, %d tiles of %d rows, walkers (m = 3 b, 2 b) %s: %d to %d tiles a walker"
+          % (n, ntile, rows, [c[0] for c in caps], ntile // GW, -(-ntile // min(c[0] for c in caps))))
+    ip, ix, d, _, _ = _kron.kron_sum(KRON_N1, n2, dt)
+    S = sa.Lobpcg.new(sa.HipCsr.new((n, n), ip, ix, d), n, block)
+    for which in ("smallest", "largest"):
+        first = S.solve(k, which, max_iter=1000)
+        print("%s: iters %d, fallbacks %d" % (which, first[2]["iters"], first[2]["restarts"]))
+        _check_big(KRON_N1, n2, dt, k, which, first[0], first[1], "kron40x%d %s b=%d %s" % (n2, np.dtype(dt).name, block, which))
+        assert first[2]["nconv"] == k and first[2]["matvecs"] == block * (first[2]["iters"] + 1)
+        assert orth_defect(first[1]) <= 64 * _eps(dt)
+        _same_bits(first, S.solve(k, which, max_iter=1000))
+    S.close()
+
+
+@pytest.mark.parametrize("dt,nt", [(F64, -1), (F32, 1), (C64, -1), (C32, -1)], ids=["float64", "float32-nt", "complex128", "complex64"])
+def test_fused_walk_takes_several_trips(sa, dt, nt):
+    """The fused residual kernel (LobResid through launch_fused) with the "grid" knob at 8 and ew_chunk at 1: one workgroup an
+    XCD walks its eighth of the packs in trips of 256, n = 41 * 979 = 40139 (odd, and 3 mod 4: a scalar tail in f64, f32 and c32)
+    makes ceil(ceil(n / PK / 8) / 256) >= 5 trips, the last XCD's last trip partial.  Against truth, and against the default-knob
+    run of the same case: another summation order of the residual norms, so the values agree to tol |A| and the iteration counts
+    within this file's cap between summation orders (LOBPCG has no cycle to count in)."""
+    n1, n2 = 41, 979
+    n = n1 * n2
+    ctx = sa.default_ctx(0)
+    pk = 16 // np.dtype(dt).itemsize
+    packs = n // pk
+    trips = -(-(-(-packs // 8)) // 256)                      # fused_kernel: chunk = trips * 256 packs an XCD, one workgroup each
+    assert n % 2 == 1 and n % 4 == 3 and trips >= 5 and 0 < packs - 7 * trips * 256 and (packs - 7 * trips * 256) % 256 != 0
+    g0 = ctx.get("grid")
+    _, _, _, _, nrm = _kron.kron_sum(n1, n2, dt)
+    tol = ref.default_tol(dt)
+    for which in ("smallest", "largest"):
+        st0, v0, X0_, i0 = _kron_solve(sa, n1, n2, dt, 4, 8, which, max_iter=1000)
+        ctx.set("grid", 8); ctx.set("ew_chunk", 1); ctx.set("stream_nt", nt)
+        try:
+            st1, v1, X1, i1 = _kron_solve(sa, n1, n2, dt, 4, 8, which, max_iter=1000)
+        finally:
+            ctx.set("grid", g0); ctx.set("ew_chunk", -1); ctx.set("stream_nt", -1)
+        assert st0 == ref.OK and st1 == ref.OK
+        print("n %d, %d trips a workgroup, %s: iters %d (default knobs %d)" % (n, trips, which, i1["iters"], i0["iters"]))
+        _check_big(n1, n2, dt, 4, which, v1, X1, "kron41x979 %s %s grid 8" % (np.dtype(dt).name, which))
+        _check_big(n1, n2, dt, 4, which, v0, X0_, "kron41x979 %s %s default" % (np.dtype(dt).name, which))
+        assert np.max(np.abs(v1.astype(F64) - v0.astype(F64))) <= tol * nrm
+        assert i1["iters"] <= 4 * i0["iters"] and i0["iters"] <= 4 * i1["iters"]
+        if i1["iters"] == i0["iters"]:                       # the iterates do not depend on the walk, the residual norms' sums do: n eps each
+            assert np.all(np.abs(i1["res"].astype(F64) - i0["res"].astype(F64)) <= 2 * n * _eps(dt) * i0["res"].astype(F64))
 
 
 # ---------------------------------------------------------------------------------------------- preconditioners

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _kron  # noqa: E402
 import _svds_ref as ref  # noqa: E402
 from test_svds_cpu import CASES, _id, checker, count, orth_defect, spectrum_of, system, true_residuals, wanted  # noqa: E402
 
@@ -22,7 +23,7 @@ pytestmark = pytest.mark.gpu
 
 F64, C64, F32, C32 = np.float64, np.complex128, np.float32, np.complex64
 ALL = [F64, C64, F32, C32]
-_KNOBS = ("spmv_dict", "stream_nt")
+_KNOBS = ("spmv_dict", "stream_nt", "ew_chunk")
 _dtid = lambda d: np.dtype(d).name
 
 
@@ -38,9 +39,11 @@ def sa():
 @pytest.fixture(autouse=True)
 def _restore_knobs(sa):
     ctx = sa.default_ctx(0)
+    grid = ctx.get("grid")
     yield
     for k in _KNOBS:
         ctx.set(k, -1)
+    ctx.set("grid", grid)
 
 
 def _eps(dt):
@@ -115,6 +118,102 @@ def test_a_wide_matrix_swaps_the_operators(sa, dt):
         assert U.shape == (4, 67) and V.shape == (4, 130)
         _check_triplets("lsmr67x130", dt, 4, which, s, U, V, info)
     S.close()
+
+
+# ---------------------------------------------------------------------------------------------- several tiles a workgroup
+def _kron_solve(sa, dims, dt, k, m, **kw):
+    ip, ix, d, _, shape = _kron.kron_product(*dims, dt)
+    S = sa.Svds.new(sa.HipCsr.new(shape, ip, ix, d), m)
+    try:
+        return S.solve(k, "largest", **kw)
+    finally:
+        S.close()
+
+
+def _check_big(dims, dt, k, s, U, V, info, label):
+    """The bounds of _check_triplets on kron_product(*dims): truth is the products of the factors' singular values, both true
+    residuals are formed in double."""
+    ip, ix, d, sv, shape = _kron.kron_product(*dims, dt)
+    A = _kron.csr_double(ip, ix, d, shape)
+    nrm, tol = float(sv[0]), ref.default_tol(dt)
+    assert info["nconv"] == k and s.shape == (k,) and U.shape == (k, shape[0]) and V.shape == (k, shape[1])
+    assert np.all(np.isfinite(s)) and np.all(np.isfinite(U)) and np.all(np.isfinite(V))
+    wd = C64 if np.dtype(dt).kind == "c" else F64
+    Uw, Vw = U.astype(wd), V.astype(wd)
+    AH = A.conj().T.tocsr()
+    err = float(np.max(np.abs(s.astype(F64) - sv[:k])))
+    r1 = max(float(np.linalg.norm(A @ Vw[i] - float(s[i]) * Uw[i])) for i in range(k))
+    r2 = max(float(np.linalg.norm(AH @ Uw[i] - float(s[i]) * Vw[i])) for i in range(k))
+    print("%s: |sigma - truth| %.3e (bound %.3e), |A v - s u| %.3e, |A^H u - s v| %.3e (bound %.3e), cycles %d, products %d"
+          % (label, err, tol * nrm, r1, r2, 2 * tol * nrm, info["restarts"], info["matvecs"]))
+    assert err <= tol * nrm
+    assert r1 <= 2 * tol * nrm and r2 <= 2 * tol * nrm
+
+
+def _past_the_cap(num_cu, dt, wide):
+    """kron_product dims whose short side has 3 grid + 1 tiles, the last partial, for the rotation's grid at ncv = 64, k = 6
+    (launch_lz_rotate: 2 num_cu, as in tests/test_gpu_eigsh.py) and whose long side has more, also with a partial tile."""
+    rows = _kron.TILE_ROWS[np.dtype(dt).name]
+    grid = max(_kron.rotate_grid(num_cu, 64, q, ref.real_dtype(dt).itemsize)[0] for q in (ref.restart_size(6, 64), 6))
+    short = _kron.n2_for_tiles(37, rows, 3 * grid)
+    long_ = short + 5
+    while (40 * long_) % rows == 0:
+        long_ += 1
+    dims = (37, 40, short, long_) if wide else (40, 37, long_, short)
+    return dims, grid, rows
+
+
+@pytest.mark.parametrize("dt,wide", [(C64, False), (F64, True), (F32, False), (C32, True)],
+                         ids=["complex128-tall", "float64-wide", "float32-tall", "complex64-wide"])
+def test_rotations_in_place_take_several_trips(sa, dt, wide):
+    """Both bases are rotated in place by LzRotate: at every restart (64 vectors into restart_size = 12 columns, CB = 4) and at
+    the end of every solve (m_eff vectors into k columns).  With ncv = 64 its grid is 2 num_cu; M and N are both past 3 grid tiles
+    with partial last tiles, so every workgroup makes at least three trips on either basis.  A wide matrix swaps the operators:
+    the long basis is then the other one.  The six largest triplets (6, 4.5, 4.4, 3.3, 3.2, 2.4 before the off-diagonals, over a
+    cluster that ends at 2) against the products of the factors' singular values; the cycle count is printed — with one cycle only
+    the final rotation ran."""
+    num_cu = sa.default_ctx(0).get("num_cu")
+    dims, grid, rows = _past_the_cap(num_cu, dt, wide)
+    M, N = dims[0] * dims[2], dims[1] * dims[3]
+    tM, tN = (M + rows - 1) // rows, (N + rows - 1) // rows
+    assert grid == 2 * num_cu and min(tM, tN) == 3 * grid + 1 and M % rows != 0 and N % rows != 0 and (M < N) == wide
+    print("%d x %d, tiles of %d rows: %d and %d, grid %d: at least 3 trips a workgroup on both bases" % (M, N, rows, tM, tN, grid))
+    s, U, V, info = _kron_solve(sa, dims, dt, 6, 64)
+    _check_big(dims, dt, 6, s, U, V, info, "kron %dx%d %s" % (M, N, np.dtype(dt).name))
+    one_cycle = 2 * (64 - ref.restart_size(6, 64))
+    assert info["matvecs"] == 2 * 64 + (info["restarts"] - 1) * one_cycle and info["restarts"] >= 1
+    assert orth_defect(U) <= 4 * 64 * (info["restarts"] + 1) * _eps(dt) and orth_defect(V) <= 4 * 64 * (info["restarts"] + 1) * _eps(dt)
+
+
+@pytest.mark.parametrize("dt,nt", [(F64, -1), (F32, -1), (C64, 1), (C32, -1)], ids=["float64", "float32", "complex128-nt", "complex64"])
+def test_fused_walk_takes_several_trips(sa, dt, nt):
+    """The fused kernels of the bidiagonalisation step with the "grid" knob at 8 and ew_chunk at 1: one workgroup an XCD walks its
+    eighth of the packs in trips of 256.  40139 x 36149 (41 * 979 and 37 * 977: both odd, M = 3 mod 4, scalar tails on both sides)
+    makes at least five trips on either side, the last XCD's last trip partial.  Against truth, and against the default-knob run:
+    another summation order, so the values agree to tol |A| and the counts within one cycle (test_parity's allowance)."""
+    dims, k, m = (41, 37, 979, 977), 4, 12                   # a short basis: several cycles, so restarts run under the walk too
+    M, N = dims[0] * dims[2], dims[1] * dims[3]
+    ctx = sa.default_ctx(0)
+    for n in (M, N):
+        packs = n // (16 // np.dtype(dt).itemsize)
+        trips = -(-(-(-packs // 8)) // 256)
+        assert n % 2 == 1 and trips >= 5 and 0 < packs - 7 * trips * 256 and (packs - 7 * trips * 256) % 256 != 0
+    assert M % 4 == 3
+    nrm = float(_kron.kron_product(*dims, dt)[3][0])
+    one_cycle = 2 * (m - ref.restart_size(k, m))
+    g0 = ctx.get("grid")
+    r0 = _kron_solve(sa, dims, dt, k, m)
+    ctx.set("grid", 8); ctx.set("ew_chunk", 1); ctx.set("stream_nt", nt)
+    try:
+        r1 = _kron_solve(sa, dims, dt, k, m)
+    finally:
+        ctx.set("grid", g0); ctx.set("ew_chunk", -1); ctx.set("stream_nt", -1)
+    print("%d x %d, %d trips a workgroup on the short side: cycles %d (default knobs %d)" % (M, N, trips, r1[3]["restarts"], r0[3]["restarts"]))
+    _check_big(dims, dt, k, *r1, "kron %dx%d %s grid 8" % (M, N, np.dtype(dt).name))
+    _check_big(dims, dt, k, *r0, "kron %dx%d %s default" % (M, N, np.dtype(dt).name))
+    assert np.max(np.abs(r1[0].astype(F64) - r0[0].astype(F64))) <= ref.default_tol(dt) * nrm
+    assert abs(r1[3]["restarts"] - r0[3]["restarts"]) <= 1 and abs(r1[3]["matvecs"] - r0[3]["matvecs"]) <= one_cycle
+    assert r1[3]["matvecs"] == 2 * m + (r1[3]["restarts"] - 1) * one_cycle
 
 
 # ---------------------------------------------------------------------------------------------- the rotation kernel's edges

@@ -1,7 +1,8 @@
 """The LOBPCG eigensolver without a GPU: the C ABI and the Python mirror exist, and the numpy checker of the GPU tests
 (tests/_lobpcg_ref.py) is checked independently of the library — its pairs against numpy.linalg.eigvalsh of the dense matrix,
-its Hermitian Jacobi routine against numpy.linalg.eigh, its [X, W] fallback on a basis built to need it, the 6 b <= n rule — and
-the iteration counts that cap the GPU runs are recorded here."""
+its Hermitian Jacobi routine against numpy.linalg.eigh, its [X, W] fallback on a basis built to need it, the 6 b <= n rule, its
+soft locking and stopping threshold on matrices with isolated extreme eigenvalues (tests/_kron.py) — and the iteration counts
+that cap the GPU runs are recorded here."""
 import ctypes as C
 import functools
 import os
@@ -13,6 +14,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _kron  # noqa: E402
 import _lobpcg_ref as ref  # noqa: E402
 from test_eigsh_cpu import orth_defect, spectrum, system, true_residual, wanted  # noqa: E402
 
@@ -23,22 +25,24 @@ NAMES = sorted(["sprs_lobpcg_%s_%s" % (f, s) for f in ("create", "solve", "solve
 
 # (matrix, k, b) -> (iters, restarts) of the checker, `which` major ("smallest", "largest") and the matrix's dtypes minor, no
 # preconditioner, the default start block, tol 1e-10 (f64 / c64) and 1e-4 (f32 / c32).  test_counts_and_eigenpairs holds them.
+# (Regenerated when anorm became a Rayleigh quotient of held vectors and locked columns left the projected problem: anorm is
+# never larger than the largest Ritz value it replaced, so most counts rose by one or two iterations.)
 COUNTS = {
-    ("poisson12x11x10", 4, 8): ((66, 0), (28, 1), (65, 0), (28, 1)),
-    ("poisson12x11x10", 3, 5): ((81, 0), (32, 0), (80, 0), (31, 0)),
-    ("poisson12x11x10", 1, 1): ((167, 0), (64, 0), (94, 0), (36, 0)),
-    ("symband1500", 4, 8): ((108, 0), (40, 2), (47, 0), (20, 1)),
-    ("symband1500", 3, 5): ((128, 0), (43, 1), (76, 1), (26, 1)),
-    ("symband1500", 1, 1): ((154, 0), (59, 0), (42, 0), (18, 0)),
-    ("hermband700", 4, 8): ((62, 0), (25, 1), (60, 0), (24, 0)),
-    ("hermband700", 3, 5): ((71, 0), (28, 1), (66, 0), (27, 0)),
-    ("hermband700", 1, 1): ((68, 0), (28, 0), (101, 0), (35, 0)),
-    ("chgrid9x8", 4, 8): ((26, 0), (12, 1), (26, 0), (11, 0)),
-    ("chgrid9x8", 3, 5): ((36, 0), (16, 0), (35, 0), (15, 0)),
-    ("chgrid9x8", 1, 1): ((64, 0), (27, 0), (48, 0), (21, 0)),
-    ("symband30", 3, 5): ((28, 0), (12, 1), (29, 0), (12, 0), (19, 0), (8, 0), (20, 0), (9, 0)),
-    ("symband30", 2, 3): ((35, 0), (15, 1), (36, 0), (15, 0), (28, 0), (11, 0), (30, 0), (13, 0)),
-    ("poisson8x8x8", 4, 8): ((47, 0), (48, 0)),
+    ("poisson12x11x10", 4, 8): ((67, 0), (30, 1), (65, 0), (28, 1)),
+    ("poisson12x11x10", 3, 5): ((83, 0), (34, 0), (81, 0), (31, 0)),
+    ("poisson12x11x10", 1, 1): ((169, 0), (66, 0), (94, 0), (36, 0)),
+    ("symband1500", 4, 8): ((115, 0), (42, 2), (47, 0), (20, 1)),
+    ("symband1500", 3, 5): ((129, 0), (46, 1), (60, 0), (26, 1)),
+    ("symband1500", 1, 1): ((156, 0), (60, 0), (42, 0), (18, 0)),
+    ("hermband700", 4, 8): ((64, 0), (26, 1), (61, 0), (24, 0)),
+    ("hermband700", 3, 5): ((72, 0), (29, 1), (67, 0), (27, 0)),
+    ("hermband700", 1, 1): ((69, 0), (29, 0), (101, 0), (35, 0)),
+    ("chgrid9x8", 4, 8): ((26, 0), (12, 1), (27, 0), (12, 0)),
+    ("chgrid9x8", 3, 5): ((37, 0), (16, 0), (36, 0), (16, 0)),
+    ("chgrid9x8", 1, 1): ((64, 0), (27, 0), (49, 0), (22, 0)),
+    ("symband30", 3, 5): ((28, 0), (12, 1), (30, 0), (12, 0), (19, 0), (8, 0), (20, 0), (9, 0)),
+    ("symband30", 2, 3): ((36, 0), (15, 1), (37, 0), (15, 0), (28, 0), (11, 0), (30, 0), (13, 0)),
+    ("poisson8x8x8", 4, 8): ((49, 0), (48, 0)),
 }
 MATRICES = ("poisson12x11x10", "symband1500", "hermband700", "chgrid9x8")
 KB = ((4, 8), (3, 5), (1, 1))
@@ -165,6 +169,92 @@ def test_multiple_eigenvalues_are_found_with_multiplicity():
     for which in WHICH:
         o = checker("poisson8x8x8", 4, 8, which, "float64")
         assert np.max(np.abs(o.vals - wanted(lam, 4, which))) <= 1e-10 * nrm
+
+
+# ---------------------------------------------------------------------------------------------- isolated extreme eigenvalues
+# A = I (x) T1 + T2 (x) I (tests/_kron.py), n = 40 n2: four isolated eigenvalues at each end (about +-4.0, 3.5, 3.2, 3.0) over a
+# cluster.  The leading columns converge tens of iterations before the others; before soft locking their W_c (rounding noise) and
+# P_c stayed in the basis, G went singular to working precision while still passing the Cholesky rule, the projected problem
+# returned Ritz values of 1e11 .. 1e27, anorm took them and the solve ended SPRS_OK with residuals of 1e-2 (c64) or in a
+# breakdown.  Truth is the factors' spectra; the start block is the default or a fixed normal one.
+KRON_N1 = 40
+KRON_MAX_ITER = 400
+KRON_CASES = [(50, which, dt, x0) for dt in (F64, F32, C64, C32) for which in WHICH for x0 in ("default", "normal")] \
+    + [(100, "smallest", C64, "default"), (400, "smallest", C64, "default")]
+_kron_id = lambda c: "kron40x%d-%s-%s-%s" % (c[0], c[1], np.dtype(c[2]).name, c[3])
+
+
+def kron_X0(n, b, dt, kind):
+    """The default start block, or standard normal entries from default_rng(5) (the real parts first, then the imaginary)."""
+    if kind == "default":
+        return ref.default_X0(n, b, dt)
+    rng = np.random.default_rng(5)
+    X0 = rng.standard_normal((b, n))
+    if np.dtype(dt).kind == "c":
+        X0 = X0 + 1j * rng.standard_normal((b, n))
+    return X0.astype(dt)
+
+
+@functools.lru_cache(maxsize=None)
+def kron_checker(n2, which, dtname, x0, k=4, b=8):
+    """The restatement's result on kron_sum(40, n2) at the default tolerance, max_iter 400 (shared, read-only)."""
+    dt = np.dtype(dtname).type
+    ip, ix, d, _, _ = _kron.kron_sum(KRON_N1, n2, dt)
+    o = ref.lobpcg(ip, ix, d, k, ref.SMALLEST if which == "smallest" else ref.LARGEST, kron_X0(ip.size - 1, b, dt, x0), KRON_MAX_ITER,
+                   ref.default_tol(dt))
+    if o.X is not None:
+        o.X.setflags(write=False)
+    return o
+
+
+def check_kron_pairs(n2, dt, k, which, status, vals, X, label):
+    """A run that says OK holds the bounds of test_counts_and_eigenpairs against the factors' spectra; one that does not converge
+    says INSUFFICIENT_ITER, or BREAKDOWN without vectors."""
+    ip, ix, d, lam, nrm = _kron.kron_sum(KRON_N1, n2, dt)
+    tol = ref.default_tol(dt)
+    if status != ref.OK:
+        assert status == ref.INSUFFICIENT_ITER or (status == ref.BREAKDOWN and X is None), status
+        print("%s: status %d (not converged)" % (label, status))
+        return False
+    err = float(np.max(np.abs(np.asarray(vals, F64) - wanted(lam, k, which))))
+    tr = _kron.true_residual(_kron.csr_double(ip, ix, d), vals, X)
+    print("%s: n %d, |theta - lambda| %.3e (bound %.3e), true residual %.3e (bound %.3e)" % (label, ip.size - 1, err, tol * nrm, tr, 2 * tol * nrm))
+    assert err <= tol * nrm
+    assert tr <= 2 * tol * nrm
+    return True
+
+
+@pytest.mark.parametrize("case", KRON_CASES, ids=_kron_id)
+def test_isolated_extreme_eigenvalues(case):
+    n2, which, dt, x0 = case
+    o = kron_checker(n2, which, np.dtype(dt).name, x0)
+    print("iters %d, fallbacks %d, nconv %d, reported residuals %s" % (o.iters, o.restarts, o.nconv, o.res))
+    if check_kron_pairs(n2, dt, 4, which, o.status, o.vals, o.X, _kron_id(case)):
+        nrm = _kron.kron_sum(KRON_N1, n2, dt)[4]
+        assert o.nconv == 4 and np.all(o.res <= ref.default_tol(dt) * nrm * (1 + 1e-12))
+        assert orth_defect(o.X) <= 64 * float(np.finfo(ref.real_dtype(dt)).eps)
+
+
+def test_anorm_never_exceeds_the_norm_and_locked_columns_leave_the_basis():
+    """The stopping threshold is tol anorm: anorm is a Rayleigh quotient of held vectors, so at most |A|_2, whatever the projected
+    problem returns; and a locked column's P and W rows of C are zero."""
+    rng = np.random.default_rng(11)
+    n, b = 90, 3
+    A = rng.standard_normal((n, n)); A = A + A.T
+    S = rng.standard_normal((3 * b, n))
+    S[2 * b] = S[0] + 1e-5 * S[2 * b]                          # W_0 all but inside the span of X: an ill-conditioned G that passes
+    G, K = S @ S.T, S @ (A @ S.T)
+    eps = float(np.finfo(F64).eps)
+    nrm = float(np.linalg.norm(A, 2))
+    rr = ref.rayleigh_ritz(G, K, b, True, ref.SMALLEST, eps)
+    assert rr.ok and 0.0 < rr.anorm <= nrm
+    lock = np.array([True, False, False])
+    lk = ref.rayleigh_ritz(G, K, b, True, ref.SMALLEST, eps, lock)
+    assert lk.ok and lk.C.shape == (3 * b, 3 * b - 2) and np.all(lk.C[b] == 0) and np.all(lk.C[2 * b] == 0) and 0.0 < lk.anorm <= nrm
+    free = np.r_[0:b, b + 1:2 * b, 2 * b + 1:3 * b]
+    Y = (S[free].T @ lk.C[free]).T
+    assert np.max(np.abs(Y @ Y.T - np.eye(3 * b - 2))) <= 1e-10
+    assert np.max(np.abs(Y @ (A @ Y.T) - np.diag(lk.theta))) <= 1e-10 * nrm
 
 
 # ---------------------------------------------------------------------------------------------- the Jacobi routine
