@@ -1,11 +1,10 @@
 // Thick-restart Lanczos (Wu & Simon; = Hermitian Krylov-Schur) with full reorthogonalisation by CGS2: the recurrence of the
-// header's sprs_eigsh_* comment.  The host enqueues whole cycles blind — per step SpMV, 2 x (ceil((j + 1) / gm_b<T>) GmDots +
-// GmUpdate), LzStep, GmScale; per cycle LzRitz — and reads the head of the state once a cycle, to choose between the restart
+// header's sprs_eigsh_* comment.  The host enqueues whole cycles blind — per step SpMV, launch_cgs2 against v_0 .. v_j, LzStep,
+// GmScale; per cycle LzRitz — and reads the head of the state once a cycle, to choose between the restart
 // (LzRotate in place + one copy) and the end (LzRotate into the caller's vectors).  Kernels: eigsh_fuse.hpp, gmres_fuse.hpp.
 #include "krylov.hpp"
 
 #include <algorithm>
-#include <cstddef>
 
 #include "eigsh_fuse.hpp"
 
@@ -25,8 +24,7 @@ int Eigsh<T>::create(const sprs_csr *A, size_t size, size_t ncv) {
 template <class T>
 void Eigsh<T>::destroy() {
     state.destroy();
-    if (dots) (void)hipFree(dots);
-    dots = nullptr; dots_grid = 0;
+    dots.destroy();
     KrylovBase<T>::destroy();
 }
 
@@ -47,60 +45,36 @@ int Eigsh<T>::solve(size_t k, int which, const T *v0, bool v0_host, size_t max_r
 
     const int G = this->ew_grid();
     const int cw = fused_chunked(this->A) ? 1 : 0;
-    if (dots_grid < G) {                                // (the "grid" knob may have grown since the last solve)
-        SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (dots) SPRS_HIP_TRY(c, hipFree(dots));
-        dots = nullptr; dots_grid = 0;
-        SPRS_HIP_TRY(c, hipMalloc((void **)&dots, sizeof(T) * (size_t)LZ_MAXM * (size_t)G));
-        SPRS_HIP_TRY(c, hipMemsetAsync(dots, 0, sizeof(T) * (size_t)LZ_MAXM * (size_t)G, c->stream));
-        dots_grid = G;
-    }
+    SPRS_TRY(dots.ensure(c, LZ_MAXM, G));
 
     Hd &H = state.host->hd;
     St *const d_state = state.dev;
-    SPRS_HIP_TRY(c, hipMemsetAsync(d_state, 0, sizeof(St), c->stream));     // T = 0, anorm = 0, scale = 0, the counters
-    memset(state.host, 0, offsetof(St, h));
-    H.status = ST_RUNNING; H.skip = 1; H.k = (int)k; H.which = which; H.tol = (double)tol;
-    SPRS_TRY(state.push(sizeof(Hd)));
+    SPRS_TRY(lz_begin(state, k, which, tol));                               // T = 0, anorm = 0, scale = 0, the counters
     const Hd *d_head = &d_state->hd;
     const int *d_skip = &d_state->hd.skip;
 
     T *Vb = basis(0), *w = wvec();
     const int64_t vs = (int64_t)this->stride;
     Real<T> *partN = this->dslot(0);
-    auto small = [&](auto kernel, auto... args) -> int {
-        hipLaunchKernelGGL(kernel, dim3(1), dim3(BLOCK), 0, c->stream, args...);
-        SPRS_HIP_TRY(c, hipGetLastError());
-        return SPRS_OK;
-    };
-    auto multi_dot = [&](int j) -> int {
-        constexpr int B = gm_b<T>::value;
-        for (int i0 = 0; i0 <= j; i0 += B)
-            SPRS_TRY(launch_fused<T>(c, n, G, cw, GmDots<T, B, Hd>{d_head, Vb, vs, i0, std::min(B, j + 1 - i0), w, dots, G, {}}));
-        return SPRS_OK;
-    };
     auto step = [&](int j, long long cycle) -> int {
         T *vj = Vb + (size_t)j * this->stride, *vn = Vb + (size_t)(j + 1) * this->stride;
         SPRS_TRY(this->spmv(vj, w, 0, nullptr, nullptr, nullptr, d_skip));                          // w = A v_j
-        SPRS_TRY(multi_dot(j));
-        SPRS_TRY(launch_fused<T>(c, n, G, cw, GmUpdate<T, false, St>{d_state, dots, G, G, j, Vb, vs, w, w, nullptr, Fin{}, nullptr, 0.0}));
-        SPRS_TRY(multi_dot(j));
-        SPRS_TRY(launch_fused<T>(c, n, G, cw, GmUpdate<T, true, St>{d_state, dots, G, G, j, Vb, vs, w, vn, partN, Fin{}, nullptr, 0.0}));
-        SPRS_TRY(small(lz_step_kernel<T>, d_state, (const Real<T> *)partN, G, j, m, cycle));
+        SPRS_TRY(launch_cgs2<T>(c, n, G, cw, d_state, Vb, vs, j + 1, w, vn, partN, dots.p));            // against v_0 .. v_j
+        SPRS_TRY(launch_small(c, lz_step_kernel<T>, 0, d_state, (const Real<T> *)partN, G, j, m, cycle));
         return launch_fused<T>(c, n, G, cw, GmScale<T, Hd>{d_head, vn, 0.0});
     };
 
     // v_0 = v0 / |v0|
     SPRS_HIP_TRY(c, hipMemcpyAsync(Vb, v0, sizeof(T) * n, v0_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
     SPRS_TRY(launch_fused<T>(c, n, G, cw, LzNrm<T>{Vb, partN, 0.0}));
-    SPRS_TRY(small(lz_start_kernel<T>, d_state, (const Real<T> *)partN, G));
+    SPRS_TRY(launch_small(c, lz_start_kernel<T, St>, 0, d_state, (const Real<T> *)partN, G));
     SPRS_TRY(launch_fused<T>(c, n, G, cw, GmScale<T, Hd>{d_head, Vb, 0.0}));
 
     const int p = std::min((int)k + std::max((int)k, 4), m - 2);
     int j0 = 0;
     for (long long cycle = 1;; ++cycle) {
         for (int j = j0; j < m; ++j) SPRS_TRY(step(j, cycle));
-        SPRS_TRY(small(lz_ritz_kernel<T>, d_state, m, p));
+        SPRS_TRY(launch_small(c, lz_ritz_kernel<T>, 0, d_state, m, p));
         SPRS_TRY(state.fetch(sizeof(Hd)));
         if (H.status != ST_RUNNING || (size_t)cycle >= max_restarts) break;
         SPRS_TRY(rotate(m, p, Vb, vs));                                                             // V[:, :p] <- V[:, :m] S[:, :p]
@@ -108,10 +82,8 @@ int Eigsh<T>::solve(size_t k, int which, const T *v0, bool v0_host, size_t max_r
         j0 = p;
     }
 
-    SPRS_TRY(state.fetch(offsetof(St, h)));
-    *nconv_out = (size_t)H.nconv; *restarts_out = (size_t)H.cycle; *matvecs_out = (size_t)H.matvecs;
-    for (size_t i = 0; i < k; ++i) { vals_out[i] = (Real<T>)state.host->theta[i]; res_out[i] = (Real<T>)state.host->res[i]; }
-    if (H.status == ST_BREAKDOWN) return SPRS_BREAKDOWN;
+    const int rc = lz_results(state, k, state.host->theta, vals_out, res_out, nconv_out, restarts_out, matvecs_out);
+    if (rc != SPRS_OK && rc != SPRS_INSUFFICIENT_ITER) return rc;           // a breakdown: no vectors
     if (vecs) {     // X = V[:, :m_eff] S[:, :k]
         if (vecs_host) {
             SPRS_TRY(rotate(H.m_eff, (int)k, Vb, vs));
@@ -123,7 +95,7 @@ int Eigsh<T>::solve(size_t k, int which, const T *v0, bool v0_host, size_t max_r
         SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
     SPRS_TRY(this->end_solve());
-    return H.status == ST_CONVERGED ? SPRS_OK : SPRS_INSUFFICIENT_ITER;
+    return rc;
 }
 
 template class Eigsh<double>;

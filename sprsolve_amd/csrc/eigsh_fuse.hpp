@@ -1,7 +1,7 @@
 // Thick-restart Lanczos (sprs_eigsh_*): the kernels that are its own (the solver itself: Eigsh<T> in eigsh.hip).  No reference
 // analogue — the recurrence is the one stated in the header.  One Lanczos step j of a cycle:
 //   SpMV      w = A v_j                                                   (KrylovBase::spmv, any route, no fused dot)
-//   GmDots / GmUpdate / GmDots / GmUpdate<SECOND>                         (gmres_fuse.hpp, on LzState: CGS2 against v_0 .. v_j,
+//   launch_cgs2                                                           (gmres_fuse.hpp, on LzState: CGS2 against v_0 .. v_j,
 //                                                                          w - sum v_i c_i into the slot of v_{j+1}, partials of its norm)
 //   LzStep    (one workgroup) T_jj, beta, the invariant-subspace threshold, T_{j+1,j}, the count of products ; sets `skip`
 //   GmScale   v_{j+1} *= 1 / beta
@@ -12,6 +12,8 @@
 // `skip` the rest of a cycle's blind launches, the host reads nothing but the head of the state (once a cycle).
 #pragma once
 #include <algorithm>
+#include <cstddef>
+#include <cstring>
 
 #include "gmres_fuse.hpp"
 
@@ -22,16 +24,16 @@ static_assert(LZ_MAXM <= GM_MAXM, "GmUpdate stages one coefficient per basis vec
 constexpr int LZ_LD = LZ_MAXM + 1;          // LzRitz's row stride in LDS (odd: a column walk meets every bank once)
 constexpr int LZ_MAX_SWEEPS = 30;
 
-// What the host reads (once a cycle) ...
+// What the host reads (once a cycle) of a thick-restart solve: this one's, and the truncated SVD's (svds_fuse.hpp) ...
 template <class T>
 struct LzHead {
     int status, skip;
     int nconv, m_eff;           // m_eff: rows of the projected problem (m, or j + 1 of the step that met an invariant subspace)
     int invariant;
     int k, which;               // set by the host per solve
-    long long matvecs, cycle;   // SpMVs that ran ; the cycle of the last step that ran (0: none)
-    Real<T> scale;              // 1 / beta0 or 1 / beta for GmScale
-    double beta, anorm, tscale, tol;
+    long long matvecs, cycle;   // products that ran ; the cycle of the last step that ran (0: none)
+    Real<T> scale;              // 1 / |v0|, or the reciprocal of a step's norm, for GmScale
+    double beta, anorm, pscale, tol;     // pscale: the largest entry of the projected matrix (T, the SVD's B) so far
 };
 // ... what it reads besides when the solve is over (theta, res: everything before h) and the rest of the device-resident state.
 // T is real symmetric whatever the scalar type, and is kept in double.
@@ -63,8 +65,9 @@ struct LzNrm {
 };
 
 // LzStart: beta0 = |v0| from LzNrm's partials ; NaN or 0: breakdown ; scale = 1 / beta0 and the first cycle may run
-template <class T>
-__global__ __launch_bounds__(BLOCK) void lz_start_kernel(LzState<T> *S, const Real<T> *partN, int P) {
+// (St: LzState<T>, or SvState<T> of svds_fuse.hpp)
+template <class T, class St>
+__global__ __launch_bounds__(BLOCK) void lz_start_kernel(St *S, const Real<T> *partN, int P) {
     __shared__ Real<T> smD[NWAVE];
     LzHead<T> &H = S->hd;
     const Real<T> sN = reduce_partials(partN, P, smD);
@@ -87,14 +90,14 @@ __global__ __launch_bounds__(BLOCK) void lz_step_kernel(LzState<T> *S, const Rea
     H.matvecs += 1; H.cycle = cycle;
     if (!(beta >= 0.0)) { H.skip = 1; H.status = ST_BREAKDOWN; return; }
     S->Tm[j * LZ_MAXM + j] = tjj;
-    double sc = fmax(H.tscale, fabs(tjj));
+    double sc = fmax(H.pscale, fabs(tjj));
     H.beta = beta;
     if (beta <= 64.0 * (double)seps<Real<T>>() * sc) {      // an invariant subspace: v_{j+1} is not formed
-        H.tscale = sc; H.m_eff = j + 1; H.invariant = 1; H.skip = 1;
+        H.pscale = sc; H.m_eff = j + 1; H.invariant = 1; H.skip = 1;
         return;
     }
     sc = fmax(sc, beta);
-    H.tscale = sc;
+    H.pscale = sc;
     if (j + 1 < m) { S->Tm[(j + 1) * LZ_MAXM + j] = beta; S->Tm[j * LZ_MAXM + j + 1] = beta; }
     else H.m_eff = m;
     H.scale = Real<T>(1) / ssqrt(sN);
@@ -107,6 +110,43 @@ __device__ __forceinline__ void lz_pair(int i, int r, int M, int &p, int &q) {
     if (i == 0) { a = M - 1; b = r; }
     else { a = (r + i) % (M - 1); b = (r - i + (M - 1)) % (M - 1); }
     p = a < b ? a : b; q = a < b ? b : a;
+}
+
+// The order of `which` of me values: thread tid < me ranks value(tid) — those strictly before it (larger where `largest`, else
+// smaller), ties by lower index — and records sperm[rank] = tid.  The caller's barrier stands between this and a read of sperm.
+template <class F>
+__device__ __forceinline__ void lz_rank(int me, bool largest, F value, int *sperm) {
+    const int tid = threadIdx.x;
+    if (tid >= me) return;
+    const double ti = value(tid);
+    int rank = 0;
+    for (int j = 0; j < me; ++j) {
+        const double tj = value(j);
+        const bool first = largest ? tj > ti : tj < ti;
+        rank += (first || (tj == ti && j < tid)) ? 1 : 0;
+    }
+    sperm[rank] = tid;
+}
+
+// The verdict of a thick-restart cycle (one thread): anorm = the largest |value| seen so far ; nconv = the leading pairs, in the
+// order of sperm, with beta |last[sperm[i]]| <= tol anorm (last: the last row of the projected problem's vectors) ; then an
+// invariant subspace ends the solve (converged where it holds k pairs, else a breakdown) and a running one ends at nconv == k.
+template <class T>
+__device__ __forceinline__ void lz_verdict(LzHead<T> &H, const double *vals, const double *last, const int *sperm, int me, int k, double beta,
+                                           int invariant) {
+    double an = H.anorm;
+    for (int i = 0; i < me; ++i) an = fmax(an, fabs(vals[i]));
+    int nc = 0;
+    const int kk = k < me ? k : me;
+    while (nc < kk && beta * fabs(last[sperm[nc]]) <= H.tol * an) ++nc;
+    H.anorm = an;
+    if (invariant) {
+        if (me >= k) { H.nconv = k; H.status = ST_CONVERGED; }
+        else { H.nconv = nc; H.skip = 1; H.status = ST_BREAKDOWN; }
+    } else {
+        H.nconv = nc;
+        if (nc == k) { H.skip = 1; H.status = ST_CONVERGED; }
+    }
 }
 
 // LzRitz: (theta, S) of T[:m_eff, :m_eff] by cyclic Jacobi (round-robin order, the rotated entry set to exactly zero; stop at
@@ -190,17 +230,7 @@ __global__ __launch_bounds__(BLOCK) void lz_ritz_kernel(LzState<T> *S, int m, in
         if (tid == 0) { H.skip = 1; H.status = ST_BREAKDOWN; }
         return;
     }
-    // the order of `which`: rank by value, ties by index
-    if (tid < me) {
-        const double ti = sA[tid * LZ_LD + tid];
-        int rank = 0;
-        for (int j = 0; j < me; ++j) {
-            const double tj = sA[j * LZ_LD + j];
-            const bool first = which == SPRS_EIGSH_LARGEST ? tj > ti : tj < ti;
-            rank += (first || (tj == ti && j < tid)) ? 1 : 0;
-        }
-        sperm[rank] = tid;
-    }
+    lz_rank(me, which == SPRS_EIGSH_LARGEST, [&](int j) { return sA[j * LZ_LD + j]; }, sperm);
     __syncthreads();
     if (tid < me) {
         const int i = sperm[tid];
@@ -224,21 +254,7 @@ __global__ __launch_bounds__(BLOCK) void lz_ritz_kernel(LzState<T> *S, int m, in
             S->Tm[r * LZ_MAXM + c] = v;
         }
     }
-    if (tid == 0) {
-        double an = H.anorm;
-        for (int i = 0; i < me; ++i) an = fmax(an, fabs(sth[i]));
-        int nc = 0;
-        const int kk = k < me ? k : me;
-        while (nc < kk && beta * fabs(sV[(me - 1) * LZ_LD + sperm[nc]]) <= H.tol * an) ++nc;
-        H.anorm = an;
-        if (invariant) {
-            if (me >= k) { H.nconv = k; H.status = ST_CONVERGED; }
-            else { H.nconv = nc; H.skip = 1; H.status = ST_BREAKDOWN; }
-        } else {
-            H.nconv = nc;
-            if (nc == k) { H.skip = 1; H.status = ST_CONVERGED; }
-        }
-    }
+    if (tid == 0) lz_verdict(H, sth, sV + (me - 1) * LZ_LD, sperm, me, k, beta, invariant);
 }
 
 // ---- LzRotate: out[:, c] = sum_{i < me} V[:, i] coef[i, c] for c < q, from zero, i ascending; out may be V itself.
@@ -339,6 +355,31 @@ static int launch_lz_rotate(sprs_ctx *c, const CF *cf, const T *V, int64_t vstri
     SPRS_HIP_TRY(c, attr);
     SPRS_HIP_TRY(c, hipGetLastError());
     return SPRS_OK;
+}
+
+// ======================================================================= the frame of a thick-restart solve (Eigsh, Svds)
+// Before the first launch: the device state zeroed, the head's status / skip / k / which / tol set and pushed.
+// (Block: the solver's StateBlock of LzState<T> or SvState<T>, krylov.hpp)
+template <class Block, class R>
+static int lz_begin(Block &state, size_t k, int which, R tol) {
+    using St = std::remove_pointer_t<decltype(state.host)>;
+    SPRS_HIP_TRY(state.ctx, hipMemsetAsync(state.dev, 0, sizeof(St), state.ctx->stream));
+    memset(state.host, 0, offsetof(St, h));
+    auto &H = state.host->hd;
+    H.status = ST_RUNNING; H.skip = 1; H.k = (int)k; H.which = which; H.tol = (double)tol;
+    return state.push(sizeof(H));
+}
+// Behind the last cycle: everything before h fetched, the counters and the k values (vals: the state's theta or sigma) and
+// residual estimates copied out.  Returns what the solve returns once its vectors are out; SPRS_BREAKDOWN: there are none.
+template <class Block, class R>
+static int lz_results(Block &state, size_t k, const double *vals, R *vals_out, R *res_out, size_t *nconv_out, size_t *restarts_out, size_t *matvecs_out) {
+    using St = std::remove_pointer_t<decltype(state.host)>;
+    SPRS_TRY(state.fetch(offsetof(St, h)));
+    const auto &H = state.host->hd;
+    *nconv_out = (size_t)H.nconv; *restarts_out = (size_t)H.cycle; *matvecs_out = (size_t)H.matvecs;
+    for (size_t i = 0; i < k; ++i) { vals_out[i] = (R)vals[i]; res_out[i] = (R)state.host->res[i]; }
+    if (H.status == ST_BREAKDOWN) return SPRS_BREAKDOWN;
+    return H.status == ST_CONVERGED ? SPRS_OK : SPRS_INSUFFICIENT_ITER;
 }
 
 }  // namespace sprs

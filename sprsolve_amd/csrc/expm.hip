@@ -1,6 +1,6 @@
 // w = exp(tA) v by Krylov projection with Expokit's error-controlled sub-stepping: the recurrence of the header's sprs_expm_*
-// comment.  The host enqueues one sub-step blind — ExStart, GmScale, m Arnoldi steps (SpMV, 2 x (ceil((j + 1) / gm_b<T>) GmDots +
-// GmUpdate), ExArnoldiStep, GmScale), the SpMV and LzNrm of avnorm, ExStep, ExCombine — and reads the head of the state once a
+// comment.  The host enqueues one sub-step blind — ExStart, GmScale, m Arnoldi steps (SpMV, launch_cgs2 against v_0 .. v_j,
+// ExArnoldiStep, GmScale), the SpMV and LzNrm of avnorm, ExStep, ExCombine — and reads the head of the state once a
 // sub-step.  Kernels: expm_fuse.hpp, gmres_fuse.hpp, eigsh_fuse.hpp (LzNrm).
 #include "krylov.hpp"
 
@@ -27,8 +27,7 @@ int Expm<T>::create(const sprs_csr *A, size_t size, size_t ncv) {
 template <class T>
 void Expm<T>::destroy() {
     state.destroy();
-    if (dots) (void)hipFree(dots);
-    dots = nullptr; dots_grid = 0;
+    dots.destroy();
     KrylovBase<T>::destroy();
 }
 
@@ -53,14 +52,7 @@ int Expm<T>::apply(Real<T> t, const T *v, bool host, Real<T> tol, size_t max_ste
 
     const int G = this->ew_grid();
     const int cw = fused_chunked(this->A) ? 1 : 0;
-    if (dots_grid < G) {                                // (the "grid" knob may have grown since the last solve)
-        SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (dots) SPRS_HIP_TRY(c, hipFree(dots));
-        dots = nullptr; dots_grid = 0;
-        SPRS_HIP_TRY(c, hipMalloc((void **)&dots, sizeof(T) * (size_t)EX_MAXM * (size_t)G));
-        SPRS_HIP_TRY(c, hipMemsetAsync(dots, 0, sizeof(T) * (size_t)EX_MAXM * (size_t)G, c->stream));
-        dots_grid = G;
-    }
+    SPRS_TRY(dots.ensure(c, EX_MAXM, G));
 
     Hd &H = state.host->hd;
     St *const d_state = state.dev;
@@ -83,25 +75,11 @@ int Expm<T>::apply(Real<T> t, const T *v, bool host, Real<T> tol, size_t max_ste
     // what this launch needs (the kernel's few static words count against the 160 KiB too)
     if (lds > ((size_t)64 << 10))
         SPRS_HIP_TRY(c, hipFuncSetAttribute((const void *)ex_step_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    auto small = [&](auto kernel, size_t shared, auto... args) -> int {
-        hipLaunchKernelGGL(kernel, dim3(1), dim3(BLOCK), shared, c->stream, args...);
-        SPRS_HIP_TRY(c, hipGetLastError());
-        return SPRS_OK;
-    };
-    auto multi_dot = [&](int j) -> int {
-        constexpr int B = gm_b<T>::value;
-        for (int i0 = 0; i0 <= j; i0 += B)
-            SPRS_TRY(launch_fused<T>(c, n, G, cw, GmDots<T, B, Hd>{d_head, Vb, vs, i0, std::min(B, j + 1 - i0), p, dots, G, {}}));
-        return SPRS_OK;
-    };
     auto step = [&](int j) -> int {
         T *vj = Vb + (size_t)j * this->stride, *vn = Vb + (size_t)(j + 1) * this->stride;
         SPRS_TRY(this->spmv(vj, p, 0, nullptr, nullptr, nullptr, d_skip));                          // p = A v_j
-        SPRS_TRY(multi_dot(j));
-        SPRS_TRY(launch_fused<T>(c, n, G, cw, GmUpdate<T, false, St>{d_state, dots, G, G, j, Vb, vs, p, p, nullptr, Fin{}, nullptr, 0.0}));
-        SPRS_TRY(multi_dot(j));
-        SPRS_TRY(launch_fused<T>(c, n, G, cw, GmUpdate<T, true, St>{d_state, dots, G, G, j, Vb, vs, p, vn, partN, Fin{}, nullptr, 0.0}));
-        SPRS_TRY(small(ex_arnoldi_step_kernel<T>, 0, d_state, (const Real<T> *)partN, G, j));
+        SPRS_TRY(launch_cgs2<T>(c, n, G, cw, d_state, Vb, vs, j + 1, p, vn, partN, dots.p));            // against v_0 .. v_j
+        SPRS_TRY(launch_small(c, ex_arnoldi_step_kernel<T>, 0, d_state, (const Real<T> *)partN, G, j));
         return launch_fused<T>(c, n, G, cw, GmScale<T, Hd>{d_head, vn, 0.0});
     };
 
@@ -109,12 +87,12 @@ int Expm<T>::apply(Real<T> t, const T *v, bool host, Real<T> tol, size_t max_ste
     SPRS_HIP_TRY(c, hipMemcpyAsync(Vb, v, sizeof(T) * n, in, c->stream));
     SPRS_TRY(launch_fused<T>(c, n, G, cw, LzNrm<T>{Vb, partB, 0.0}));
     for (size_t s = 0; s < max_steps; ++s) {
-        SPRS_TRY(small(ex_start_kernel<T>, 0, d_state, (const Real<T> *)partB, G, m));
+        SPRS_TRY(launch_small(c, ex_start_kernel<T>, 0, d_state, (const Real<T> *)partB, G, m));
         SPRS_TRY(launch_fused<T>(c, n, G, cw, GmScale<T, Hd>{d_head, Vb, 0.0}));
         for (int j = 0; j < m; ++j) SPRS_TRY(step(j));
         SPRS_TRY(this->spmv(basis(m), p, 0, nullptr, nullptr, nullptr, d_skip));                    // avnorm = |A v_m|
         SPRS_TRY(launch_fused<T>(c, n, G, cw, LzNrm<T>{p, partN, 0.0}));
-        SPRS_TRY(small(ex_step_kernel<T>, lds, d_state, (const Real<T> *)partN, G, m));
+        SPRS_TRY(launch_small(c, ex_step_kernel<T>, lds, d_state, (const Real<T> *)partN, G, m));
         SPRS_TRY(launch_fused<T>(c, n, G, cw, ExCombine<T>{d_state, Vb, vs, Vb, last, partB, nullptr, nullptr, 0, 0.0}));
         SPRS_TRY(state.fetch(sizeof(Hd)));
         if (H.status != ST_RUNNING) break;

@@ -3,7 +3,7 @@
 //   ExStart   (one workgroup) beta from the partials of |w|^2, the zero / NaN rules, hump, H = 0 ; clears `skip`
 //   GmScale   v_0 *= 1 / beta                                             (w lives in the slot of v_0 between sub-steps)
 //   m times:  SpMV  p = A v_j                                             (KrylovBase::spmv, any route, no fused dot)
-//             GmDots / GmUpdate / GmDots / GmUpdate<SECOND>               (gmres_fuse.hpp, on ExState: CGS2 against v_0 .. v_j,
+//             launch_cgs2                                                 (gmres_fuse.hpp, on ExState: CGS2 against v_0 .. v_j,
 //                                                                          p - sum v_i c_i into the slot of v_{j+1}, partials of its norm)
 //             ExArnoldiStep (one workgroup) column j of H, hn, the happy-breakdown rule, the count of products ; sets `skip`
 //             GmScale   v_{j+1} *= 1 / hn

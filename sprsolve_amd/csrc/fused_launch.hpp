@@ -50,6 +50,14 @@ static int launch_fused(sprs_ctx *c, size_t n, int grid, int chunked_walk, F f) 
     return SPRS_OK;
 }
 
+// A solver's scalar kernel: one workgroup of BLOCK threads on the context's stream, lds_bytes of dynamic LDS.
+template <class K, class... Args>
+static int launch_small(sprs_ctx *c, K kernel, size_t lds_bytes, Args... args) {
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(BLOCK), lds_bytes, c->stream, args...);
+    SPRS_HIP_TRY(c, hipGetLastError());
+    return SPRS_OK;
+}
+
 // a run-time flag as a template argument: f(std::true_type{}) or f(std::false_type{})
 template <class F>
 static int dispatch_bool(bool flag, F &&f) { return flag ? f(std::true_type{}) : f(std::false_type{}); }

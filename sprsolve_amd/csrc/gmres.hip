@@ -2,12 +2,11 @@
 // krylov.hpp), CGS2, Givens rotations: the recurrence of the header's sprs_gmres_* comment.
 // Fused (gmres_fuse.hpp): the host enqueues whole cycles blind — per cycle SpMV, GmResid, GmStart, GmScale, the steps, GmXUpdate
 // (an applied M: GmUForm, its launches, GmXAdd); per step [GmPrec, or an applied M's launches], SpMV,
-// 2 x (ceil((j + 1) / gm_b<T>) GmDots + GmUpdate), GmStep, GmScale — and reads the head of the state every poll_interval() steps.
-// Distributed operators: the norms travel through fin_for + handoff; a multi-dot's j + 1 coefficients are reduced by one more
-// single-workgroup launch into `coefs` and all-reduced there (red's cells hold two values a slot).
+// launch_cgs2 against v_0 .. v_j, GmStep, GmScale — and reads the head of the state every poll_interval() steps.
+// Distributed operators: the norms travel through fin_for + handoff; the j + 1 coefficients of each of launch_cgs2's GmDots passes
+// are reduced by one more single-workgroup launch into `coefs` and all-reduced there (red's cells hold two values a slot).
 #include "krylov.hpp"
 
-#include <algorithm>
 #include <cmath>
 
 #include "gmres_fuse.hpp"
@@ -34,9 +33,9 @@ int Gmres<T>::create(const sprs_csr *A, size_t size, size_t restart) {
 template <class T>
 void Gmres<T>::destroy() {
     state.destroy();
-    if (dots) (void)hipFree(dots);
+    dots.destroy();
     if (coefs) (void)hipFree(coefs);
-    dots = coefs = nullptr; dots_grid = 0;
+    coefs = nullptr;
     KrylovBase<T>::destroy();
 }
 
@@ -64,14 +63,7 @@ int Gmres<T>::run(const Prec<T, V> &M, const T *rhs, T *x, size_t max_iter, Real
 
     const int G = this->ew_grid();
     const int cw = fused_chunked(this->A) ? 1 : 0;      // XCD-chunked walk of the vector kernels (spmv.hip)
-    if (dots_grid < G) {                                // (the "grid" knob may have grown since the last solve)
-        SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (dots) SPRS_HIP_TRY(c, hipFree(dots));
-        dots = nullptr; dots_grid = 0;
-        SPRS_HIP_TRY(c, hipMalloc((void **)&dots, sizeof(T) * (size_t)GM_MAXM * (size_t)G));
-        SPRS_HIP_TRY(c, hipMemsetAsync(dots, 0, sizeof(T) * (size_t)GM_MAXM * (size_t)G, c->stream));
-        dots_grid = G;
-    }
+    SPRS_TRY(dots.ensure(c, GM_MAXM, G));
 
     GmresHead<T> &H = state.host->hd;
     GmresState<T> *const d_state = state.dev;
@@ -89,22 +81,12 @@ int Gmres<T>::run(const Prec<T, V> &M, const T *rhs, T *x, size_t max_iter, Real
     Real<T> *partN = this->dslot(0), *partR = this->dslot(1);
     const bool dist = this->A->dist != nullptr;
 
-    auto small = [&](auto kernel, auto... args) -> int {
-        hipLaunchKernelGGL(kernel, dim3(1), dim3(BLOCK), 0, c->stream, args...);
-        SPRS_HIP_TRY(c, hipGetLastError());
-        return SPRS_OK;
-    };
-    // the j + 1 dot products of one Gram-Schmidt pass: where their consumer finds them
-    const T *cpart = dots; int64_t cstride = G; int cP = G;
-    auto multi_dot = [&](int j, const T *wv) -> int {
-        constexpr int B = gm_b<T>::value;
-        for (int i0 = 0; i0 <= j; i0 += B)
-            SPRS_TRY(launch_fused<T>(c, n, G, cw, GmDots<T, B>{d_head, Vb, vs, i0, std::min(B, j + 1 - i0), wv, dots, G, {}}));
-        if (dist) {
-            SPRS_TRY(small(gm_reduce_kernel<T>, d_head, (const T *)dots, (int64_t)G, G, j + 1, coefs));
-            SPRS_TRY(allreduce_sum(this->comm(), coefs, (size_t)(j + 1) * (sizeof(T) / sizeof(Real<T>)), sizeof(Real<T>) == 4));
-            cpart = coefs; cstride = 1; cP = 1;
-        }
+    // distributed: the cnt coefficients of a Gram-Schmidt pass reduced into `coefs` and all-reduced there, one value each
+    auto reduce_dots = [&](int cnt, GmCoefs<T> *cf) -> int {
+        if (!dist) return SPRS_OK;
+        SPRS_TRY(launch_small(c, gm_reduce_kernel<T>, 0, d_head, (const T *)dots.p, (int64_t)G, G, cnt, coefs));
+        SPRS_TRY(allreduce_sum(this->comm(), coefs, (size_t)cnt * (sizeof(T) / sizeof(Real<T>)), sizeof(Real<T>) == 4));
+        *cf = GmCoefs<T>{coefs, 1, 1};
         return SPRS_OK;
     };
     auto cycle_begin = [&]() -> int {
@@ -113,7 +95,7 @@ int Gmres<T>::run(const Prec<T, V> &M, const T *rhs, T *x, size_t max_iter, Real
         SPRS_TRY(launch_fused<T>(c, n, G, cw, GmResid<T>{d_head, rhs, Vb, partR, f, T(), T(), 0.0}));
         Part<Real<T>> qR{partR, G};
         SPRS_TRY((this->template handoff<Real<T>, Real<T>>(1, G, partR, &qR)));
-        SPRS_TRY(small(gm_start_kernel<T>, d_state, qR.p, qR.P));
+        SPRS_TRY(launch_small(c, gm_start_kernel<T>, 0, d_state, qR.p, qR.P));
         return launch_fused<T>(c, n, G, cw, GmScale<T>{d_head, Vb, 0.0});
     };
     auto step = [&](int j, long long cycle) -> int {
@@ -124,14 +106,10 @@ int Gmres<T>::run(const Prec<T, V> &M, const T *rhs, T *x, size_t max_iter, Real
         if (applied) SPRS_TRY(M.apply(vj, z));
         else if (pc) SPRS_TRY(launch_fused<T>(c, n, G, cw, GmPrec<T, V>{d_head, dinv, vj, z}));
         SPRS_TRY(this->spmv(pc ? z : vj, w, 0, nullptr, nullptr, nullptr, d_skip));                 // w = A z
-        SPRS_TRY(multi_dot(j, w));
-        SPRS_TRY(launch_fused<T>(c, n, G, cw, GmUpdate<T, false>{d_state, cpart, cstride, cP, j, Vb, vs, w, w, nullptr, Fin{}, nullptr, 0.0}));
-        SPRS_TRY(multi_dot(j, w));
-        const Fin f = this->fin_for(0, partN, nullptr, G);
-        SPRS_TRY(launch_fused<T>(c, n, G, cw, GmUpdate<T, true>{d_state, cpart, cstride, cP, j, Vb, vs, w, vn, partN, f, nullptr, 0.0}));
+        SPRS_TRY(launch_cgs2<T>(c, n, G, cw, d_state, Vb, vs, j + 1, w, vn, partN, dots.p, this->fin_for(0, partN, nullptr, G), reduce_dots));
         Part<Real<T>> qN{partN, G};
         SPRS_TRY((this->template handoff<Real<T>, Real<T>>(0, G, partN, &qN)));
-        SPRS_TRY(small(gm_step_kernel<T>, d_state, qN.p, qN.P, j, m, cycle));
+        SPRS_TRY(launch_small(c, gm_step_kernel<T>, 0, d_state, qN.p, qN.P, j, m, cycle));
         return launch_fused<T>(c, n, G, cw, GmScale<T>{d_head, vn, 0.0});
     };
     auto cycle_end = [&](long long cycle) -> int {

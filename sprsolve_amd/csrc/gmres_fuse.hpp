@@ -2,10 +2,11 @@
 // reference analogue — the recurrence is the one stated in the header (sprs_gmres_*).  One Arnoldi step j of a fused cycle:
 //   [GmPrec   z = M^-1 v_j]                                              (Jacobi only)
 //   SpMV      w = A z                                                    (KrylovBase::spmv, any route)
-//   GmDots    partials of conj(v_i).w, i <= j: B = gm_b<T> basis vectors per launch, ceil((j + 1) / B) launches, ONE read of w each
-//   GmUpdate  h_i from the partials (every workgroup, same order) ; w -= sum v_i h_i in one pass over w
-//   GmDots    the same on the updated w (CGS2's second pass)
-//   GmUpdate  c_i ; h_i += c_i ; w -= sum v_i c_i written straight into the slot of v_{j+1} ; partials of |w|^2
+//   launch_cgs2 (below: the one host sequence of every solver that orthogonalises against a basis), cnt = j + 1:
+//     GmDots    partials of conj(v_i).w, i <= j: B = gm_b<T> basis vectors per launch, ceil((j + 1) / B) launches, ONE read of w each
+//     GmUpdate  h_i from the partials (every workgroup, same order) ; w -= sum v_i h_i in one pass over w
+//     GmDots    the same on the updated w (CGS2's second pass)
+//     GmUpdate  c_i ; h_i += c_i ; w -= sum v_i c_i written straight into the slot of v_{j+1} ; partials of |w|^2
 //   GmStep    (one workgroup) hn = |w| ; the rotations ; g ; its ; the step's events ; at a cycle's end the back substitution
 //   GmScale   v_{j+1} *= 1 / hn
 // and per cycle  SpMV (A x), GmResid (v_0 = rhs - A x, partials of its norm), GmStart (beta, convergence, g_0), GmScale before
@@ -19,6 +20,8 @@
 // cleared by the next cycle's GmStart).  The x update is keyed on the cycle number its GmStep recorded, so it runs exactly
 // once per cycle that made a step, the event's cycle included.
 #pragma once
+#include <algorithm>
+
 #include "fused_launch.hpp"
 
 namespace sprs {
@@ -158,6 +161,33 @@ struct GmUpdate {
         if (fin.counter) finalize_last_block<Real<T>, Real<T>>(fin, false, smD, smD);
     }
 };
+
+// Where a GmUpdate finds the coefficients of the GmDots pass before it: cnt sums of P partials at part[i * pstride ..].
+template <class T> struct GmCoefs { const T *part; int64_t pstride; int P; };
+// launch_cgs2's hook after each GmDots pass: the partials stay where GmDots left them
+struct GmDotsInPlace { template <class T> int operator()(int, GmCoefs<T> *) const { return SPRS_OK; } };
+
+// CGS2 of w (len entries) against the cnt >= 1 vectors of `basis`, every solver's one Gram-Schmidt sequence: ceil(cnt / gm_b<T>)
+// GmDots (i0 ascending), GmUpdate in place on w, the same GmDots again, GmUpdate<SECOND> into `out` with the partials of |out|^2
+// in partN (reduced in the launch where `fin` says so).  St: the state that carries hd.skip and the column h.  dots: cnt x grid
+// partials (DotsBuf of krylov.hpp).  after_dots(cnt, &cf) runs behind each GmDots pass and may move the coefficients (GMRES on a
+// distributed operator: reduced and all-reduced into one value each); it is called before the GmUpdate that reads them is built.
+template <class T, class St, class After = GmDotsInPlace>
+static int launch_cgs2(sprs_ctx *c, size_t len, int grid, int cw, St *d_state, const T *basis, int64_t bs, int cnt, T *w, T *out, Real<T> *partN,
+                       T *dots, Fin fin = Fin{}, After after_dots = After{}) {
+    constexpr int B = gm_b<T>::value;
+    using Hd = decltype(St::hd);
+    GmCoefs<T> cf{dots, grid, grid};
+    auto multi_dot = [&]() -> int {
+        for (int i0 = 0; i0 < cnt; i0 += B)
+            SPRS_TRY(launch_fused<T>(c, len, grid, cw, GmDots<T, B, Hd>{&d_state->hd, basis, bs, i0, std::min(B, cnt - i0), w, dots, grid, {}}));
+        return after_dots(cnt, &cf);
+    };
+    SPRS_TRY(multi_dot());
+    SPRS_TRY(launch_fused<T>(c, len, grid, cw, GmUpdate<T, false, St>{d_state, cf.part, cf.pstride, cf.P, cnt - 1, basis, bs, w, w, nullptr, Fin{}, nullptr, 0.0}));
+    SPRS_TRY(multi_dot());
+    return launch_fused<T>(c, len, grid, cw, GmUpdate<T, true, St>{d_state, cf.part, cf.pstride, cf.P, cnt - 1, basis, bs, w, out, partN, fin, nullptr, 0.0});
+}
 
 // ---- GmResid: v_0 = rhs*1 + v_0*(-1) (v_0 holds A x) + partials of its norm for GmStart
 template <class T>

@@ -19,8 +19,11 @@
 //
 // What the hosts share is written once: KrylovBase (below; krylov_base.hip) with solve(), handoff() (a producer's partials to
 // their consumer: single GPU / mailbox / all-reduce), zero_rhs(), poll_interval(), comm_timeout(); StateBlock (the device +
-// pinned-host pair of the scalar state); with_prec() (the preconditioner's checks, its element type and the Prec<T, V> a run
-// receives: none, Jacobi, or an applied ILU(0) / AMG handle).  The main loops stay apart: BiCGStab's restart, MINRES's deferred
+// pinned-host pair of the scalar state); DotsBuf (the partials of launch_cgs2 of gmres_fuse.hpp, the one Gram-Schmidt sequence
+// of GMRES, Eigsh, Svds and Expm); launch_small (fused_launch.hpp: the one-workgroup scalar kernels); with_prec() (the
+// preconditioner's checks, its element type and the Prec<T, V> a run receives: none, Jacobi, or an applied ILU(0) / AMG
+// handle).  Eigsh and Svds also share the frame of a thick-restart solve (lz_begin / lz_results of eigsh_fuse.hpp) around their
+// own cycle loops.  The main loops stay apart: BiCGStab's restart, MINRES's deferred
 // M3, CG's accounting of idle launches and GMRES's cycles have nothing in common.  Each solver has ONE run and ONE run_literal,
 // whatever it is preconditioned with.
 #pragma once
@@ -92,6 +95,28 @@ struct StateBlock {
         SPRS_HIP_TRY(ctx, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
         SPRS_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         return SPRS_OK;
+    }
+};
+
+// The [maxm][grid] partials of launch_cgs2's multi-dots (gmres_fuse.hpp), held by GMRES, Eigsh, Svds and Expm.
+template <class T>
+struct DotsBuf {
+    T *p = nullptr;
+    int grid = 0;
+    // before a solve enqueues: room for maxm x G partials (the "grid" knob may have grown since the last solve)
+    int ensure(sprs_ctx *c, int maxm, int G) {
+        if (grid >= G) return SPRS_OK;
+        SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (p) SPRS_HIP_TRY(c, hipFree(p));
+        p = nullptr; grid = 0;
+        SPRS_HIP_TRY(c, hipMalloc((void **)&p, sizeof(T) * (size_t)maxm * (size_t)G));
+        SPRS_HIP_TRY(c, hipMemsetAsync(p, 0, sizeof(T) * (size_t)maxm * (size_t)G, c->stream));
+        grid = G;
+        return SPRS_OK;
+    }
+    void destroy() {
+        if (p) (void)hipFree(p);
+        p = nullptr; grid = 0;
     }
 };
 
@@ -249,14 +274,13 @@ class Cg : public KrylovBase<T> {
     int run_literal(const Prec<T, V> &M, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
 };
 
-// Restarted GMRES for any non-singular A (recurrence: include/sprsolve_hip.h, sprs_gmres_*; kernels: gmres_fuse.hpp)
+// Restarted GMRES for any non-singular A (recurrence: include/sprsolve_hip.h, sprs_gmres_*; kernels and launch_cgs2: gmres_fuse.hpp)
 template <class T>
 class Gmres : public KrylovBase<T> {
    public:
     StateBlock<GmresState<T>> state;     // the host pushes and polls only its head (GmresHead)
     int m = 30;                  // restart length
-    T *dots = nullptr;           // [m][dots_grid] partials of the multi-dots
-    int dots_grid = 0;
+    DotsBuf<T> dots;             // [GM_MAXM][grid] partials of the multi-dots
     T *coefs = nullptr;          // distributed: the m reduced coefficients of a pass, all-reduced in place
     int create(const sprs_csr *A, size_t size, size_t restart);
     void destroy();
@@ -277,16 +301,15 @@ class Gmres : public KrylovBase<T> {
 };
 
 // Thick-restart Lanczos for the extreme eigenpairs of a Hermitian A (recurrence: include/sprsolve_hip.h, sprs_eigsh_*; kernels:
-// eigsh_fuse.hpp and GMRES's multi-vector Gram-Schmidt).  Single GPU, one mode; of KrylovBase it uses the work vectors, the
-// partial slots and spmv() — no literal mode, trace or profile.
+// eigsh_fuse.hpp and GMRES's multi-vector Gram-Schmidt through launch_cgs2).  Single GPU, one mode; of KrylovBase it uses the
+// work vectors, the partial slots and spmv() — no literal mode, trace or profile.
 template <class T> struct LzState;      // eigsh_fuse.hpp
 template <class T>
 class Eigsh : public KrylovBase<T> {
    public:
     StateBlock<LzState<T>> state;        // the host pushes its head and reads the head once a cycle
     int m = 32;                          // ncv: the basis size
-    T *dots = nullptr;                   // [m][dots_grid] partials of the multi-dots
-    int dots_grid = 0;
+    DotsBuf<T> dots;                     // [LZ_MAXM][grid] partials of the multi-dots
     int create(const sprs_csr *A, size_t size, size_t ncv);
     void destroy();
     // v0: n entries (host where v0_host); vecs: k contiguous vectors of n entries or null (host where vecs_host: the basis is
@@ -301,7 +324,7 @@ class Eigsh : public KrylovBase<T> {
 };
 
 // w = exp(tA) v for any square A: Arnoldi projection with Expokit's error-controlled sub-stepping (recurrence:
-// include/sprsolve_hip.h, sprs_expm_*; kernels: expm_fuse.hpp, GMRES's multi-vector Gram-Schmidt and the Lanczos norm).  Single
+// include/sprsolve_hip.h, sprs_expm_*; kernels: expm_fuse.hpp, launch_cgs2 of gmres_fuse.hpp and the Lanczos norm).  Single
 // GPU, one mode; of KrylovBase it uses the work vectors, the partial slots and spmv() — no literal mode, trace or profile.
 template <class T> struct ExState;      // expm_fuse.hpp
 template <class T>
@@ -309,8 +332,7 @@ class Expm : public KrylovBase<T> {
    public:
     StateBlock<ExState<T>> state;        // the host pushes its head and reads the head once a sub-step
     int m = 30;                          // ncv: the basis size
-    T *dots = nullptr;                   // [m][dots_grid] partials of the multi-dots
-    int dots_grid = 0;
+    DotsBuf<T> dots;                     // [EX_MAXM][grid] partials of the multi-dots
     int create(const sprs_csr *A, size_t size, size_t ncv);
     void destroy();
     // v, w: n entries each, on the host where `host` (w may be v); the six outputs: host
@@ -377,7 +399,8 @@ class Lsmr : public KrylovBase<T> {
 };
 
 // Thick-restart Lanczos bidiagonalisation for the extreme singular triplets of any A, rectangular included (recurrence:
-// include/sprsolve_hip.h, sprs_svds_*; kernels: svds_fuse.hpp, GMRES's multi-vector Gram-Schmidt and the Lanczos rotation).  Two
+// include/sprsolve_hip.h, sprs_svds_*; kernels: svds_fuse.hpp, launch_cgs2 of gmres_fuse.hpp, the Lanczos rotation, start kernel,
+// head and solve frame (lz_begin / lz_results of eigsh_fuse.hpp).  Two
 // operators and two vector lengths, as LSMR: Op = A and OpH = A^H where rows >= cols, else the other way round, so that Op is
 // M x N with M >= N.  KrylovBase carries the M side (q_0 .. q_{l-1}, w) and the partial slots; the N side (p_0 .. p_l, w') is
 // held here.  Single GPU, one mode — no literal mode, trace or profile.
@@ -394,8 +417,7 @@ class Svds : public KrylovBase<T> {
     int m = 32;                          // ncv: the basis size l
     size_t rows = 0, cols = 0, lenM = 0, lenN = 0, stride_n = 0;
     T *work_n = nullptr;                 // (m + 2) * stride_n
-    T *dots = nullptr;                   // [m][dots_grid] partials of the multi-dots, dots_grid = the larger side's grid
-    int dots_grid = 0;
+    DotsBuf<T> dots;                     // [LZ_MAXM][grid] partials of the multi-dots, grid = the larger side's
     int create(const sprs_csr *A, const sprs_csr *AH_or_null, size_t ncv);
     void destroy();
     // v0: min(rows, cols) entries (host where host); u / v: k contiguous vectors of rows / cols entries, both or neither (host:

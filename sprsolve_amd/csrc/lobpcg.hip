@@ -93,11 +93,6 @@ int Lobpcg<T>::run(const Prec<T, V> &M, size_t k, int which, const T *X0, bool x
     const T *d_coef = d_state->coef;
 
     T *X = this->vec(0), *P = this->vec(b), *W = this->vec(2 * b), *AX = this->vec(3 * b), *AW = this->vec(5 * b);
-    auto small = [&](auto kernel, auto... args) -> int {
-        hipLaunchKernelGGL(kernel, dim3(1), dim3(BLOCK), 0, c->stream, args...);
-        SPRS_HIP_TRY(c, hipGetLastError());
-        return SPRS_OK;
-    };
     // [S] <- [S] C and [AS] <- [AS] C in place: me rows, q columns of the coefficient block
     auto rotate2 = [&](int me, int q) -> int {
         SPRS_TRY((launch_lz_rotate<T, T>(c, d_coef, (const T *)X, vs, (int64_t)n, me, q, X, vs, d_status)));
@@ -110,20 +105,20 @@ int Lobpcg<T>::run(const Prec<T, V> &M, size_t k, int which, const T *X0, bool x
         SPRS_HIP_TRY(c, hipMemcpyAsync(X + (size_t)j * this->stride, X0 + (size_t)j * n, sizeof(T) * n, x0_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
     for (int j = 0; j < b; ++j) SPRS_TRY(this->spmv(X + (size_t)j * this->stride, AX + (size_t)j * this->stride, 0, nullptr, nullptr, nullptr, d_status));
     SPRS_TRY(gram(1, b));
-    SPRS_TRY(small(lob_rr_kernel<T>, d_state, (const LobCD<T> *)gsum, b, 1, b, 0LL));
+    SPRS_TRY(launch_small(c, lob_rr_kernel<T>, 0, d_state, (const LobCD<T> *)gsum, b, 1, b, 0LL));
     SPRS_TRY(rotate2(b, b));
 
     const size_t poll = sprs::poll_interval(c);
     for (size_t it = 1;; ++it) {
         SPRS_TRY(launch_fused<T>(c, n, G, cw, LobResid<T, V>{d_state, X, AX, W, vs, b, M.dinv, rpart, {}, {}}));
-        SPRS_TRY(small(lob_check_kernel<T>, d_state, (const Real<T> *)rpart, G, b));
+        SPRS_TRY(launch_small(c, lob_check_kernel<T>, 0, d_state, (const Real<T> *)rpart, G, b));
         if (it > max_iter) break;
         if (M.applied.h)
             for (int j = 0; j < b; ++j) SPRS_TRY(M.applied.apply(W + (size_t)j * this->stride, W + (size_t)j * this->stride));
         for (int j = 0; j < b; ++j) SPRS_TRY(this->spmv(W + (size_t)j * this->stride, AW + (size_t)j * this->stride, 0, nullptr, nullptr, nullptr, d_status));
         const int layout = it == 1 ? 2 : 3;
         SPRS_TRY(gram(layout, layout * b));
-        SPRS_TRY(small(lob_rr_kernel<T>, d_state, (const LobCD<T> *)gsum, layout * b, layout, b, (long long)it));
+        SPRS_TRY(launch_small(c, lob_rr_kernel<T>, 0, d_state, (const LobCD<T> *)gsum, layout * b, layout, b, (long long)it));
         SPRS_TRY(rotate2(3 * b, 2 * b));
         if (it % poll == 0) {
             SPRS_TRY(state.fetch(sizeof(Hd)));

@@ -317,9 +317,11 @@ __device__ __forceinline__ void lob_backward(const CD *sL, int ma, CD (&y)[LOB_M
 }
 
 // Cyclic Jacobi on the Hermitian sA (M x M, M even, row stride LOB_LD) with sV = I: lz_ritz_kernel's round-robin order and
-// stopping rule, the rotation carrying the phase u of its pivot (sc = s u): columns x_p' = c x_p - conj(sc) x_q,
-// x_q' = sc x_p + c x_q on A and V, rows row_p' = c row_p - sc row_q, row_q' = conj(sc) row_p + c row_q on A, then
-// A_pq = A_qp = 0 and Im A_pp = Im A_qq = 0 exactly.  false: a NaN or the sweep cap.
+// stopping rule, but not its loop: for a real pivot a_pq < 0 with a_pp == a_qq this one rotates with s = -c (tau from |a_pq|,
+// then the phase a_pq / |a_pq| = -1) and lz_ritz_kernel's with s = +c (tau = -0.0 passes its tau >= 0), so one loop for both
+// would change the bits of one solver's eigenvectors.  The rotation carries the phase u of its pivot (sc = s u): columns
+// x_p' = c x_p - conj(sc) x_q, x_q' = sc x_p + c x_q on A and V, rows row_p' = c row_p - sc row_q,
+// row_q' = conj(sc) row_p + c row_q on A, then A_pq = A_qp = 0 and Im A_pp = Im A_qq = 0 exactly.  false: a NaN or the sweep cap.
 template <class CD>
 __device__ bool lob_jacobi(CD *sA, CD *sV, int M, double *sc, CD *ss, double *smD) {
     const int tid = threadIdx.x;
@@ -515,16 +517,8 @@ __global__ __launch_bounds__(BLOCK) void lob_rr_kernel(LobState<T> *S, const Lob
         return;
     }
     // (7) the order of `which`: rank by value, ties by index
-    if (tid < ma) {
-        const double ti = sre(sA[tid * LOB_LD + tid]);
-        int rank = 0;
-        for (int j = 0; j < ma; ++j) {
-            const double tj = sre(sA[j * LOB_LD + j]);
-            const bool first = which == SPRS_EIGSH_LARGEST ? tj > ti : tj < ti;
-            rank += (first || (tj == ti && j < tid)) ? 1 : 0;
-        }
-        sperm[rank] = tid; sth[tid] = ti;
-    }
+    lz_rank(ma, which == SPRS_EIGSH_LARGEST, [&](int j) { return sre(sA[j * LOB_LD + j]); }, sperm);
+    if (tid < ma) sth[tid] = sre(sA[tid * LOB_LD + tid]);
     __syncthreads();
     // (8) C = diag(s) L^-H Z: a thread per column, back substitution in place in sV
     if (tid < ma) {

@@ -1,13 +1,12 @@
 // Thick-restart Lanczos bidiagonalisation (Golub-Kahan; Baglama & Reichel's restart with plain Ritz vectors) with full
 // reorthogonalisation of both bases by CGS2: the recurrence of the header's sprs_svds_* comment.  The host enqueues whole cycles
-// blind — per step SpMV, 2 x (ceil(j / gm_b<T>) GmDots + GmUpdate), SvNorm<alpha>, GmScale, SpMV, 2 x (ceil((j + 1) / gm_b<T>)
-// GmDots + GmUpdate), SvNorm<beta>, GmScale; per cycle SvSvd — and reads the head of the state once a cycle, to choose between
+// blind — per step SpMV, launch_cgs2 against q_0 .. q_{j-1}, SvNorm<alpha>, GmScale, SpMV, launch_cgs2 against p_0 .. p_j,
+// SvNorm<beta>, GmScale; per cycle SvSvd — and reads the head of the state once a cycle, to choose between
 // the restart (LzRotate in place on both bases + one copy) and the end (LzRotate into the caller's vectors).  Kernels:
 // svds_fuse.hpp, eigsh_fuse.hpp, gmres_fuse.hpp.
 #include "krylov.hpp"
 
 #include <algorithm>
-#include <cstddef>
 
 #include "svds_fuse.hpp"
 
@@ -41,8 +40,7 @@ int Svds<T>::create(const sprs_csr *A, const sprs_csr *AH_or_null, size_t ncv) {
 template <class T>
 void Svds<T>::destroy() {
     state.destroy();
-    if (dots) (void)hipFree(dots);
-    dots = nullptr; dots_grid = 0;
+    dots.destroy();
     if (work_n) (void)hipFree(work_n);
     work_n = nullptr;
     KrylovBase<T>::destroy();
@@ -60,52 +58,24 @@ template <class T>
 int Svds<T>::solve(size_t k, int which, const T *v0, bool host, size_t max_restarts, R tol, R *vals_out, T *u, T *v, R *res_out,
                    size_t *nconv_out, size_t *restarts_out, size_t *matvecs_out) {
     using St = SvState<T>;
-    using Hd = SvHead<T>;
+    using Hd = LzHead<T>;
     sprs_ctx *c = this->ctx;
     const size_t M = lenM, N = lenN;
     SPRS_TRY(this->begin_solve());
 
     const int GM = grid_of(M), GN = grid_of(N), G = std::max(GM, GN);
     const int cwM = fused_chunked(Op) ? 1 : 0, cwN = fused_chunked(OpH) ? 1 : 0;    // (a handle's rows are its output's length)
-    if (dots_grid < G) {                                // (the "grid" knob may have grown since the last solve)
-        SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (dots) SPRS_HIP_TRY(c, hipFree(dots));
-        dots = nullptr; dots_grid = 0;
-        SPRS_HIP_TRY(c, hipMalloc((void **)&dots, sizeof(T) * (size_t)LZ_MAXM * (size_t)G));
-        SPRS_HIP_TRY(c, hipMemsetAsync(dots, 0, sizeof(T) * (size_t)LZ_MAXM * (size_t)G, c->stream));
-        dots_grid = G;
-    }
+    SPRS_TRY(dots.ensure(c, LZ_MAXM, G));
 
     Hd &H = state.host->hd;
     St *const d_state = state.dev;
-    SPRS_HIP_TRY(c, hipMemsetAsync(d_state, 0, sizeof(St), c->stream));     // B = 0, anorm = 0, bscale = 0, the counters
-    memset(state.host, 0, offsetof(St, h));
-    H.status = ST_RUNNING; H.skip = 1; H.k = (int)k; H.which = which; H.tol = (double)tol;
-    SPRS_TRY(state.push(sizeof(Hd)));
+    SPRS_TRY(lz_begin(state, k, which, tol));                               // B = 0, anorm = 0, pscale = 0, the counters
     const Hd *d_head = &d_state->hd;
     const int *d_skip = &d_state->hd.skip;
 
     T *Pb = pvec(0), *Qb = qvec(0), *wN = pvec(m + 1), *wM = qvec(m);
     const int64_t ps = (int64_t)stride_n, qs = (int64_t)this->stride;
     R *partN = this->dslot(0);
-    auto small = [&](auto kernel, auto... args) -> int {
-        hipLaunchKernelGGL(kernel, dim3(1), dim3(BLOCK), 0, c->stream, args...);
-        SPRS_HIP_TRY(c, hipGetLastError());
-        return SPRS_OK;
-    };
-    // CGS2 of w (len entries) against the cnt >= 1 vectors of `basis`, the result into `out`, the partials of its norm into partN
-    auto cgs2 = [&](size_t len, int grid, int cw, const T *basis, int64_t bs, int cnt, T *w, T *out) -> int {
-        constexpr int B = gm_b<T>::value;
-        auto multi_dot = [&]() -> int {
-            for (int i0 = 0; i0 < cnt; i0 += B)
-                SPRS_TRY(launch_fused<T>(c, len, grid, cw, GmDots<T, B, Hd>{d_head, basis, bs, i0, std::min(B, cnt - i0), w, dots, grid, {}}));
-            return SPRS_OK;
-        };
-        SPRS_TRY(multi_dot());
-        SPRS_TRY(launch_fused<T>(c, len, grid, cw, GmUpdate<T, false, St>{d_state, dots, grid, grid, cnt - 1, basis, bs, w, w, nullptr, Fin{}, nullptr, 0.0}));
-        SPRS_TRY(multi_dot());
-        return launch_fused<T>(c, len, grid, cw, GmUpdate<T, true, St>{d_state, dots, grid, grid, cnt - 1, basis, bs, w, out, partN, Fin{}, nullptr, 0.0});
-    };
     auto step = [&](int j, long long cycle) -> int {
         T *pj = Pb + (size_t)j * stride_n, *pn = Pb + (size_t)(j + 1) * stride_n, *qj = Qb + (size_t)j * this->stride;
         if (j == 0) {                                                                               // nothing to orthogonalise against
@@ -113,13 +83,13 @@ int Svds<T>::solve(size_t k, int which, const T *v0, bool host, size_t max_resta
             SPRS_TRY(launch_fused<T>(c, M, GM, cwM, LzNrm<T>{qj, partN, 0.0}));
         } else {
             SPRS_TRY(launch_spmv<T>(Op, SpmvPart::Whole, pj, wM, 0, nullptr, nullptr, nullptr, d_skip));     // w = Op p_j
-            SPRS_TRY(cgs2(M, GM, cwM, Qb, qs, j, wM, qj));
+            SPRS_TRY(launch_cgs2<T>(c, M, GM, cwM, d_state, Qb, qs, j, wM, qj, partN, dots.p));
         }
-        SPRS_TRY(small(sv_norm_kernel<T, false>, d_state, (const R *)partN, GM, j, m, cycle));
+        SPRS_TRY(launch_small(c, sv_norm_kernel<T, false>, 0, d_state, (const R *)partN, GM, j, m, cycle));
         SPRS_TRY(launch_fused<T>(c, M, GM, cwM, GmScale<T, Hd>{d_head, qj, 0.0}));
         SPRS_TRY(launch_spmv<T>(OpH, SpmvPart::Whole, qj, wN, 0, nullptr, nullptr, nullptr, d_skip));        // w' = Op^H q_j
-        SPRS_TRY(cgs2(N, GN, cwN, Pb, ps, j + 1, wN, pn));
-        SPRS_TRY(small(sv_norm_kernel<T, true>, d_state, (const R *)partN, GN, j, m, cycle));
+        SPRS_TRY(launch_cgs2<T>(c, N, GN, cwN, d_state, Pb, ps, j + 1, wN, pn, partN, dots.p));
+        SPRS_TRY(launch_small(c, sv_norm_kernel<T, true>, 0, d_state, (const R *)partN, GN, j, m, cycle));
         return launch_fused<T>(c, N, GN, cwN, GmScale<T, Hd>{d_head, pn, 0.0});
     };
     auto rotate_p = [&](int me, int q, T *out, int64_t os) { return launch_lz_rotate<T, R>(c, (const R *)d_state->coefY, (const T *)Pb, ps, (int64_t)N, me, q, out, os); };
@@ -128,14 +98,14 @@ int Svds<T>::solve(size_t k, int which, const T *v0, bool host, size_t max_resta
     // p_0 = v0 / |v0|
     SPRS_HIP_TRY(c, hipMemcpyAsync(Pb, v0, sizeof(T) * N, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
     SPRS_TRY(launch_fused<T>(c, N, GN, cwN, LzNrm<T>{Pb, partN, 0.0}));
-    SPRS_TRY(small(sv_start_kernel<T>, d_state, (const R *)partN, GN));
+    SPRS_TRY(launch_small(c, lz_start_kernel<T, St>, 0, d_state, (const R *)partN, GN));
     SPRS_TRY(launch_fused<T>(c, N, GN, cwN, GmScale<T, Hd>{d_head, Pb, 0.0}));
 
     const int p = std::min((int)k + std::max((int)k, 4), m - 2);
     int j0 = 0;
     for (long long cycle = 1;; ++cycle) {
         for (int j = j0; j < m; ++j) SPRS_TRY(step(j, cycle));
-        SPRS_TRY(small(sv_svd_kernel<T>, d_state, m, p));
+        SPRS_TRY(launch_small(c, sv_svd_kernel<T>, 0, d_state, m, p));
         SPRS_TRY(state.fetch(sizeof(Hd)));
         if (H.status != ST_RUNNING || (size_t)cycle >= max_restarts) break;
         SPRS_TRY(rotate_p(m, p, Pb, ps));                                                           // P[:, :p] <- P[:, :m] Y[:, :p]
@@ -144,10 +114,8 @@ int Svds<T>::solve(size_t k, int which, const T *v0, bool host, size_t max_resta
         j0 = p;
     }
 
-    SPRS_TRY(state.fetch(offsetof(St, h)));
-    *nconv_out = (size_t)H.nconv; *restarts_out = (size_t)H.cycle; *matvecs_out = (size_t)H.matvecs;
-    for (size_t i = 0; i < k; ++i) { vals_out[i] = (R)state.host->sigma[i]; res_out[i] = (R)state.host->res[i]; }
-    if (H.status == ST_BREAKDOWN) return SPRS_BREAKDOWN;
+    const int rc = lz_results(state, k, state.host->sigma, vals_out, res_out, nconv_out, restarts_out, matvecs_out);
+    if (rc != SPRS_OK && rc != SPRS_INSUFFICIENT_ITER) return rc;           // a breakdown: no vectors
     if (u && v) {     // P[:, :m_eff] Y[:, :k] and Q[:, :m_eff] X[:, :k]: V and U, or U and V where Op is A^H
         T *outN = swapped ? u : v, *outM = swapped ? v : u;
         if (host) {
@@ -164,7 +132,7 @@ int Svds<T>::solve(size_t k, int which, const T *v0, bool host, size_t max_resta
         SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
     SPRS_TRY(this->end_solve());
-    return H.status == ST_CONVERGED ? SPRS_OK : SPRS_INSUFFICIENT_ITER;
+    return rc;
 }
 
 template class Svds<double>;

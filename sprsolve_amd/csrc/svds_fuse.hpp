@@ -2,16 +2,16 @@
 // No reference analogue — the recurrence is the one stated in the header.  Op is M x N with M >= N (A, or A^H where A is wide);
 // p_0 .. p_l span the small space, q_0 .. q_{l-1} the large one.  One step j of a cycle:
 //   SpMV      w = Op p_j
-//   GmDots / GmUpdate / GmDots / GmUpdate<SECOND>   (gmres_fuse.hpp, on SvState: CGS2 against q_0 .. q_{j-1}, into the slot of q_j)
+//   launch_cgs2                                     (gmres_fuse.hpp, on SvState: CGS2 against q_0 .. q_{j-1}, into the slot of q_j)
 //   SvNorm<false>  (one workgroup) alpha = B_jj, the rank-deficiency threshold, 1 / alpha, the count of products ; sets `skip`
 //   GmScale   q_j *= 1 / alpha
 //   SpMV      w' = Op^H q_j
-//   GmDots / GmUpdate / GmDots / GmUpdate<SECOND>   (CGS2 against p_0 .. p_j, into the slot of p_{j+1})
+//   launch_cgs2                                     (CGS2 against p_0 .. p_j, into the slot of p_{j+1})
 //   SvNorm<true>   (one workgroup) beta, the invariant-subspace threshold, B_{j,j+1}, 1 / beta, the count, m_eff ; sets `skip`
 //   GmScale   p_{j+1} *= 1 / beta
 // per cycle SvSvd (one workgroup: B = X Sigma Y^T by one-sided Jacobi in LDS, the order, res, anorm, nconv, the events, both
 // coefficient blocks rounded to T::Real, the restarted B) and, where the host restarts, LzRotate twice (eigsh_fuse.hpp) ; per
-// solve LzNrm + SvStart + GmScale before the first cycle and LzRotate twice more for the singular vectors.  At j = 0 of the
+// solve LzNrm + LzStart + GmScale before the first cycle and LzRotate twice more for the singular vectors.  At j = 0 of the
 // first cycle there is nothing to orthogonalise Op p_0 against: the SpMV writes the slot of q_0 and LzNrm forms the partials.
 // The conventions are gmres_fuse.hpp's and eigsh_fuse.hpp's: partials re-reduced in the same order by every consumer, `status`
 // ends the solve and `skip` the rest of a cycle's blind launches, the host reads nothing but the head of the state (once a cycle).
@@ -24,22 +24,12 @@ static_assert(SPRS_SVDS_MAX_NCV == LZ_MAXM, "LzRotate reads the coefficient bloc
 constexpr int SV_MAX_SWEEPS = 30;
 constexpr int SV_TP = 8;                    // SvSvd: threads per column pair (32 pairs at M = 64: all 256 threads)
 
-// What the host reads (once a cycle) ...
-template <class T>
-struct SvHead {
-    int status, skip;
-    int nconv, m_eff;           // m_eff: rows of the projected problem (l, or j + 1 of the step that met an invariant subspace)
-    int invariant;
-    int k, which;               // set by the host per solve
-    long long matvecs, cycle;   // products with either operator that ran ; the cycle of the last step that ran (0: none)
-    Real<T> scale;              // 1 / |v0|, 1 / alpha or 1 / beta for GmScale
-    double beta, anorm, bscale, tol;     // bscale: the largest entry of B so far
-};
-// ... what it reads besides when the solve is over (sigma, res: everything before h) and the rest of the device-resident state.
+// What the host reads once a cycle is LzHead (matvecs: products with either operator ; pscale: the largest entry of B so far) ;
+// what it reads besides when the solve is over (sigma, res: everything before h) and the rest of the device-resident state.
 // B is real upper triangular whatever the scalar type, and is kept in double.
 template <class T>
 struct SvState {
-    SvHead<T> hd;
+    LzHead<T> hd;
     double sigma[LZ_MAXM], res[LZ_MAXM];     // the singular values in the order of `which` and their residual estimates
     T h[LZ_MAXM];                            // GmUpdate's running column of CGS2 coefficients
     double Bm[LZ_MAXM * LZ_MAXM];            // row-major, leading dimension LZ_MAXM
@@ -47,30 +37,17 @@ struct SvState {
     Real<T> coefX[LZ_MAXM * LZ_MAXM];        // the same of X
 };
 
-// SvStart: |v0| from LzNrm's partials ; NaN or 0: breakdown ; scale = 1 / |v0| and the first cycle may run
-template <class T>
-__global__ __launch_bounds__(BLOCK) void sv_start_kernel(SvState<T> *S, const Real<T> *partN, int P) {
-    __shared__ Real<T> smD[NWAVE];
-    SvHead<T> &H = S->hd;
-    const Real<T> sN = reduce_partials(partN, P, smD);
-    if (threadIdx.x != 0) return;
-    const Real<T> beta0 = ssqrt(sN);
-    if (!(beta0 > Real<T>(0))) { H.skip = 1; H.status = ST_BREAKDOWN; return; }
-    H.scale = Real<T>(1) / beta0;
-    H.skip = 0;
-}
-
 // SvNorm: half-step j of cycle `cycle`, the norm from GmUpdate<SECOND>'s (at j = 0 of the first cycle: LzNrm's) partials.
 // BETA = false: alpha = |w| = B_jj ; at or under the threshold Op is rank-deficient along the basis: breakdown.
 // BETA = true:  beta = |w'| ; at or under the threshold an invariant subspace (p_{j+1} is not formed) ; else B_{j,j+1}.
 template <class T, bool BETA>
 __global__ __launch_bounds__(BLOCK) void sv_norm_kernel(SvState<T> *S, const Real<T> *partN, int P, int j, int m, long long cycle) {
     __shared__ Real<T> smD[NWAVE];
-    SvHead<T> &H = S->hd;
+    LzHead<T> &H = S->hd;
     const int skip = H.skip;
     const Real<T> sN = reduce_partials(partN, P, smD);
     if (skip != 0 || threadIdx.x != 0) return;
-    const double v = (double)ssqrt(sN), sc = H.bscale;
+    const double v = (double)ssqrt(sN), sc = H.pscale;
     H.matvecs += 1; H.cycle = cycle;
     if (!(v >= 0.0)) { H.skip = 1; H.status = ST_BREAKDOWN; return; }
     const bool small = v <= 64.0 * (double)seps<Real<T>>() * sc;
@@ -86,7 +63,7 @@ __global__ __launch_bounds__(BLOCK) void sv_norm_kernel(SvState<T> *S, const Rea
         if (j + 1 < m) S->Bm[j * LZ_MAXM + j + 1] = v;
         else H.m_eff = m;
     }
-    H.bscale = fmax(sc, v);
+    H.pscale = fmax(sc, v);
     H.scale = Real<T>(1) / ssqrt(sN);
 }
 
@@ -106,7 +83,7 @@ __global__ __launch_bounds__(BLOCK) void sv_svd_kernel(SvState<T> *S, int m, int
     __shared__ double sa[LZ_MAXM / 2 * SV_TP], sb[LZ_MAXM / 2 * SV_TP], scc[LZ_MAXM / 2 * SV_TP];
     __shared__ double scs[LZ_MAXM / 2], ssn[LZ_MAXM / 2], ssig[LZ_MAXM];
     __shared__ int sperm[LZ_MAXM], srot[LZ_MAXM / 2], sflag[2];
-    SvHead<T> &H = S->hd;
+    LzHead<T> &H = S->hd;
     if (H.status != ST_RUNNING) return;
     const int tid = threadIdx.x, me = H.m_eff, M = (me + 1) & ~1, np2 = M / 2;
     const int k = H.k, which = H.which, invariant = H.invariant;
@@ -184,17 +161,7 @@ __global__ __launch_bounds__(BLOCK) void sv_svd_kernel(SvState<T> *S, int m, int
         if (tid == 0) { H.skip = 1; H.status = ST_BREAKDOWN; }
         return;
     }
-    // the order of `which`: rank by value, ties by index
-    if (tid < me) {
-        const double ti = ssig[tid];
-        int rank = 0;
-        for (int j = 0; j < me; ++j) {
-            const double tj = ssig[j];
-            const bool first = which == SPRS_SVDS_LARGEST ? tj > ti : tj < ti;
-            rank += (first || (tj == ti && j < tid)) ? 1 : 0;
-        }
-        sperm[rank] = tid;
-    }
+    lz_rank(me, which == SPRS_SVDS_LARGEST, [&](int j) { return ssig[j]; }, sperm);
     __syncthreads();
     for (int e = tid; e < me * me; e += BLOCK) {                    // X = G Sigma^-1, in place
         const int row = e / me, c = e % me;
@@ -220,21 +187,7 @@ __global__ __launch_bounds__(BLOCK) void sv_svd_kernel(SvState<T> *S, int m, int
             S->Bm[r * LZ_MAXM + c] = v;
         }
     }
-    if (tid == 0) {
-        double an = H.anorm;
-        for (int i = 0; i < me; ++i) an = fmax(an, ssig[i]);
-        int nc = 0;
-        const int kk = k < me ? k : me;
-        while (nc < kk && beta * fabs(sG[(me - 1) * LZ_LD + sperm[nc]]) <= H.tol * an) ++nc;
-        H.anorm = an;
-        if (invariant) {
-            if (me >= k) { H.nconv = k; H.status = ST_CONVERGED; }
-            else { H.nconv = nc; H.skip = 1; H.status = ST_BREAKDOWN; }
-        } else {
-            H.nconv = nc;
-            if (nc == k) { H.skip = 1; H.status = ST_CONVERGED; }
-        }
-    }
+    if (tid == 0) lz_verdict(H, ssig, sG + (me - 1) * LZ_LD, sperm, me, k, beta, invariant);
 }
 
 }  // namespace sprs
