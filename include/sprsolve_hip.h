@@ -56,6 +56,7 @@ typedef struct sprs_csminres sprs_csminres; /* CSMinRes<T,M>                 (cs
 typedef struct sprs_cg sprs_cg;             /* conjugate gradients (no reference analogue; "conjugate gradients" below) */
 typedef struct sprs_lsmr sprs_lsmr;         /* LSMR least squares on any A, rectangular included ("LSMR" below) */
 typedef struct sprs_cg_many sprs_cg_many;   /* conjugate gradients on several right-hand sides at once ("several right-hand sides" below) */
+typedef struct sprs_cg_shift sprs_cg_shift; /* conjugate gradients on (A + sigma_j I) x_j = rhs for several shifts at once ("shifted systems" below) */
 typedef struct sprs_gmres sprs_gmres;       /* restarted GMRES (no reference analogue; "restarted GMRES" below) */
 typedef struct sprs_comm sprs_comm;         /* RCCL communicator of this rank (multi-GPU section)  */
 typedef struct sprs_gauss_seidel sprs_gauss_seidel; /* GaussSeidel<T>        (gauss_seidel.rs:8-31) */
@@ -477,6 +478,60 @@ int sprs_mul_mat_dev_z(const sprs_csr *A, const sprs_c64 *x_dev, sprs_c64 *y_dev
 int sprs_cgmany_create_z(const sprs_csr *A, size_t size, size_t k, sprs_cg_many **out);
 int sprs_cgmany_solve_z(sprs_cg_many *S, const sprs_diag *P_or_null, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t k, size_t max_iter, double tol, size_t *its_out, double *res_out, int *status_out);
 int sprs_cgmany_solve_dev_z(sprs_cg_many *S, const sprs_diag *P_or_null, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t k, size_t max_iter, double tol, size_t *its_out, double *res_out, int *status_out);
+
+/* ---------------------------------------------------------------- shifted systems: multi-shift conjugate gradients
+ * sprs_cgshift_* on a sprs_cg_shift handle: the solutions of (A + sigma_j I) x_j = rhs, j = 0 .. m - 1, for a Hermitian positive-
+ * definite A and m real shifts (finite, >= 0, 1 <= m <= mmax <= 8), in ONE Krylov run on A: one SpMV and three launches per
+ * iteration whatever m is.  A Krylov space does not change under a shift; started from x = 0, every shifted residual stays
+ * collinear with the residual of CG on A (the "seed"), r_j = zeta_j r, and column j follows from a scalar recurrence
+ * (Jegerlehner's CG-M, in the convention of "conjugate gradients" above: alpha is the step, beta = rho_new / rho).  In exact
+ * arithmetic x_j is CG's own iterate on A + sigma_j I, so each column needs the iterations it would need alone.
+ * The zero start is part of the method: x is OUTPUT ONLY, m contiguous vectors of n entries (numpy's C order of an (m, n) array;
+ * each x_j is an ordinary vector), its contents on entry are ignored.  There is no preconditioner and no precond_solve: a general
+ * M destroys the shift invariance.  Out of scope: negative shifts, complex shifts, a non-zero start, distributed operators
+ * (refused at creation with SPRS_INVALID_ARGUMENT, text in sprs_last_error).
+ * Vectors are of type T; rho, alpha, beta are T; the norms are T::Real; zeta_j, a, b and the column coefficients are DOUBLES
+ * whatever T is.  Every line is one library operation per element, each arithmetic operation rounded once:
+ *     rhs_norm = norm2(rhs);  if rhs_norm <= eps: every x_j = 0, return SPRS_OK with its_out[j] = 0, res_out[j] = rhs_norm
+ *     tol2 = tol * rhs_norm;  r = rhs;  if |r| <= tol2 (tol >= 1): every x_j = 0, SPRS_OK, its_out[j] = 0, res_out[j] = 1
+ *     p = r;  rho = conj_dot(r, r);  x_j = 0;  p_j = r;  zeta_j^(-1) = zeta_j^(0) = 1;  a_old = 1;  b_old = 0;  all columns run
+ *     for n = 0 .. max_iter - 1:
+ *         q = A p;  pq = conj_dot(p, q);  unless re(pq) > 0: every running column ends with SPRS_BREAKDOWN, its_out[j] = n
+ *         alpha = rho / pq;  a = re(alpha)
+ *         for every running column, with z = zeta_j^(n), zp = zeta_j^(n-1), s = sigma_j:
+ *             den = a*b_old*(zp - z) + zp*a_old*(1 + s*a);  zn = z*zp*a_old / den
+ *             if den == 0 or zn is not finite: that column alone ends with SPRS_BREAKDOWN, its_out[j] = n (x_j as after n iterations)
+ *             zeta_j^(n+1) = zn
+ *         r += q*(-alpha);  r_norm = sqrt(sum |r_i|^2);  rho_new = sum |r_i|^2;  beta = rho_new / rho;  b = re(beta)
+ *         for every column that still runs:  t = zn / z;  alpha_j = a*t;  beta_j = b*(t*t)
+ *             x_j += p_j*alpha_j                                   [alpha_j rounded to T::Real; a real times T, as the Jacobi product]
+ *             if |zn| * r_norm <= tol2:  column j ends with SPRS_OK, its_out[j] = n + 1, res_out[j] = |zn| * r_norm / rhs_norm;
+ *                 from then on it is frozen: x_j, p_j and zeta_j are neither read nor written
+ *             else  p_j = r*zn + p_j*beta_j                        [zn, beta_j rounded to T::Real]
+ *         p = r*1 + p*beta;  rho = rho_new;  a_old = a;  b_old = b
+ *         if no column runs: the solve is over
+ *     columns still running: SPRS_INSUFFICIENT_ITER, its_out[j] = max_iter
+ * res_out[j] is the recurrence's |r_j| / |rhs| (0 with an error status).  its_out, res_out, status_out: m entries each, or NULL.
+ * Returns SPRS_OK if every column did, else the status of the lowest-numbered column that did not.
+ * create's mmax is the most shifts a solve may carry (mmax = 0 or > 8: SPRS_INVALID_ARGUMENT); the handle holds 3 + 2 mmax
+ * vectors.  Argument errors return at once and write nothing: m = 0 or m > mmax, a null shifts / rhs / x, a shift that is
+ * negative or not finite (text in sprs_last_error): SPRS_INVALID_ARGUMENT; rhs_len != size: SPRS_INCOMPATIBLE_RHS_SIZE;
+ * x_len != size * m: SPRS_INCOMPATIBLE_X_SIZE.  shifts is a host array in both entry points.  The iterations are enqueued
+ * blind and the device-side state is read every `poll` of them: results do not depend on `poll`, and column j's bits do not
+ * depend on m or on the other shifts.  No literal mode, trace or profile. */
+int sprs_cgshift_destroy(sprs_cg_shift *S);   /* NULL is a no-op */
+int sprs_cgshift_create_d(const sprs_csr *A, size_t size, size_t mmax, sprs_cg_shift **out);
+int sprs_cgshift_solve_d(sprs_cg_shift *S, const double *shifts, size_t m, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out, int *status_out);
+int sprs_cgshift_solve_dev_d(sprs_cg_shift *S, const double *shifts, size_t m, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out, int *status_out);
+int sprs_cgshift_create_z(const sprs_csr *A, size_t size, size_t mmax, sprs_cg_shift **out);
+int sprs_cgshift_solve_z(sprs_cg_shift *S, const double *shifts, size_t m, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out, int *status_out);
+int sprs_cgshift_solve_dev_z(sprs_cg_shift *S, const double *shifts, size_t m, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out, int *status_out);
+int sprs_cgshift_create_s(const sprs_csr *A, size_t size, size_t mmax, sprs_cg_shift **out);
+int sprs_cgshift_solve_s(sprs_cg_shift *S, const float *shifts, size_t m, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out, int *status_out);
+int sprs_cgshift_solve_dev_s(sprs_cg_shift *S, const float *shifts, size_t m, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out, int *status_out);
+int sprs_cgshift_create_c(const sprs_csr *A, size_t size, size_t mmax, sprs_cg_shift **out);
+int sprs_cgshift_solve_c(sprs_cg_shift *S, const float *shifts, size_t m, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out, int *status_out);
+int sprs_cgshift_solve_dev_c(sprs_cg_shift *S, const float *shifts, size_t m, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out, int *status_out);
 
 /* ---------------------------------------------------------------- restarted GMRES
  * GMRES(m) for any non-singular A: right-preconditioned (Jacobi P, or none), the Arnoldi vector orthogonalised by classical

@@ -10,6 +10,7 @@ from .amg import AMG  # noqa: F401
 from .bicg_stab import BiCGStab  # noqa: F401
 from .cg import CG  # noqa: F401
 from .cg_many import CGMany  # noqa: F401
+from .cg_shift import CGShift  # noqa: F401
 from .cs_minres import CSMinRes  # noqa: F401
 from .eigsh import Eigsh  # noqa: F401
 from .expm import Expm, expm_multiply  # noqa: F401

@@ -98,6 +98,9 @@ def _protos():
         P["sprs_cgmany_create_" + s] = [_vp, _sz, _sz, _pp]
         for k in ("solve", "solve_dev"):
             P["sprs_cgmany_%s_%s" % (k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, _sz, re_, _psz, pre, C.POINTER(_int)]
+        P["sprs_cgshift_create_" + s] = [_vp, _sz, _sz, _pp]
+        for k in ("solve", "solve_dev"):
+            P["sprs_cgshift_%s_%s" % (k, s)] = [_vp, pre, _sz, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre, C.POINTER(_int)]
         P["sprs_lsmr_create_" + s] = [_vp, _vp, _pp]
         for k in ("solve", "solve_dev"):
             P["sprs_lsmr_%s_%s" % (k, s)] = [_vp, _vp, _sz, _vp, _sz, re_, _sz, re_, _psz, pre, pre]
@@ -155,7 +158,7 @@ def _protos():
     P["sprs_csr_adjoint"] = [_vp, _int, _pp]
     P["sprs_csr_matmul"] = [_vp, _vp, _pp, C.POINTER(_i64)]
     P["sprs_csr_read"] = [_vp, _vp, _vp, _vp]
-    for k in ("bicgstab", "minres", "csminres", "cg", "gmres", "cgmany", "lsmr", "eigsh", "lobpcg", "svds", "expm"):
+    for k in ("bicgstab", "minres", "csminres", "cg", "gmres", "cgmany", "cgshift", "lsmr", "eigsh", "lobpcg", "svds", "expm"):
         P["sprs_%s_destroy" % k] = [_vp]
     for s in ("d", "zd", "z", "s", "cs", "c"):
         P["sprs_diag_precond_create_" + s] = [_vp, _sz, _vp, _pp]

@@ -552,6 +552,15 @@ int solve_many(CgMany<T> *s, bool host, const sprs_diag *P, const T *rhs, size_t
     return st;
 }
 
+// One multi-shift CG solve.  rhs (n entries) is copied into the solver's residual and x (m contiguous vectors of n, output only)
+// is written in place where it is an aligned device block, else copied out of the solver's own: nothing is staged here.
+template <class T>
+int solve_shift(CgShift<T> *s, bool host, const Real<T> *shifts, size_t m, const T *rhs, size_t rl, T *x, size_t xl, size_t max_iter,
+                Real<T> tol, size_t *its, Real<T> *res, int *status) {
+    if (!s || !rhs || !x) return SPRS_INVALID_ARGUMENT;
+    return s->solve(shifts, m, rhs, rl, host, x, xl, max_iter, tol, its, res, status);
+}
+
 // LSMR's handle: A of any shape, its adjoint handle borrowed (checked here) or built by the solver
 template <class T>
 int lsmr_create(const sprs_csr *A, const sprs_csr *AH, sprs_lsmr **out) {
@@ -963,6 +972,7 @@ int sprs_csminres_destroy(sprs_csminres *S) { return solver_destroy<MinRes>(S); 
 int sprs_cg_destroy(sprs_cg *S) { return solver_destroy<Cg>(S); }
 int sprs_gmres_destroy(sprs_gmres *S) { return solver_destroy<Gmres>(S); }
 int sprs_cgmany_destroy(sprs_cg_many *S) { return solver_destroy<CgMany>(S); }
+int sprs_cgshift_destroy(sprs_cg_shift *S) { return solver_destroy<CgShift>(S); }
 int sprs_lsmr_destroy(sprs_lsmr *S) { return solver_destroy<Lsmr>(S); }
 int sprs_eigsh_destroy(sprs_eigsh *S) { return solver_destroy<Eigsh>(S); }
 int sprs_lobpcg_destroy(sprs_lobpcg *S) { return solver_destroy<Lobpcg>(S); }
@@ -1031,6 +1041,18 @@ int sprs_expm_destroy(sprs_expm *S) { return solver_destroy<Expm>(S); }
     int sprs_cgmany_solve_dev_##X(sprs_cg_many *h, const sprs_diag *P, const CT *rhs, size_t rl, CT *x, size_t xl, size_t k, size_t mi, R tol, \
                                    size_t *its, R *res, int *status) {                                                 \
         SPRS_G(return solve_many<T>(impl_of<CgMany, T>(h), false, P, (const T *)rhs, rl, (T *)x, xl, k, mi, tol, its, res, status);) \
+    }                                                                                                                  \
+    /* multi-shift CG: mmax = the most shifts a solve may carry; x = m contiguous vectors of n, output only */          \
+    int sprs_cgshift_create_##X(const sprs_csr *A, size_t n, size_t mmax, sprs_cg_shift **out) {                       \
+        SPRS_G(return (solver_create<T, sprs_cg_shift, CgShift>(A, n, out, [&](auto *s) { return s->create(A, n, mmax); }));) \
+    }                                                                                                                  \
+    int sprs_cgshift_solve_##X(sprs_cg_shift *h, const R *shifts, size_t m, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, \
+                               size_t *its, R *res, int *status) {                                                     \
+        SPRS_G(return solve_shift<T>(impl_of<CgShift, T>(h), true, shifts, m, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res, status);) \
+    }                                                                                                                  \
+    int sprs_cgshift_solve_dev_##X(sprs_cg_shift *h, const R *shifts, size_t m, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, \
+                                   size_t *its, R *res, int *status) {                                                 \
+        SPRS_G(return solve_shift<T>(impl_of<CgShift, T>(h), false, shifts, m, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res, status);) \
     }                                                                                                                  \
     /* LSMR: A of any shape and its adjoint handle (NULL: built and owned by the solver) */                            \
     int sprs_lsmr_create_##X(const sprs_csr *A, const sprs_csr *AH, sprs_lsmr **out) { SPRS_G(return lsmr_create<T>(A, AH, out);) } \

@@ -1,8 +1,8 @@
 // Krylov recurrences (host side, C++) over device-resident vectors and scalars: the solver objects behind sprs_bicgstab,
-// sprs_minres / sprs_csminres, sprs_cg, sprs_gmres, sprs_cg_many, sprs_lsmr, sprs_eigsh, sprs_lobpcg, sprs_svds and sprs_expm.  One translation unit per solver (bicgstab.hip,
-// minres.hip, cg.hip, gmres.hip, cg_many.hip, lsmr.hip, eigsh.hip, lobpcg.hip, svds.hip, expm.hip), each with its recurrence comment; its kernels are the functors of its *_fuse.hpp, all run by
+// sprs_minres / sprs_csminres, sprs_cg, sprs_gmres, sprs_cg_many, sprs_cg_shift, sprs_lsmr, sprs_eigsh, sprs_lobpcg, sprs_svds and sprs_expm.  One translation unit per solver (bicgstab.hip,
+// minres.hip, cg.hip, gmres.hip, cg_many.hip, cg_shift.hip, lsmr.hip, eigsh.hip, lobpcg.hip, svds.hip, expm.hip), each with its recurrence comment; its kernels are the functors of its *_fuse.hpp, all run by
 // fused_kernel (fused_launch.hpp).  BiCGStab and MINRES / CSMINRES follow the reference (src/bicg_stab.rs, src/minres.rs,
-// src/cs_minres.rs); CG, GMRES, the batched CG, LSMR, the two eigensolvers, the truncated SVD and the exponential propagator have no reference analogue: include/sprsolve_hip.h
+// src/cs_minres.rs); CG, GMRES, the batched and the multi-shift CG, LSMR, the two eigensolvers, the truncated SVD and the exponential propagator have no reference analogue: include/sprsolve_hip.h
 // states their recurrences.
 //
 // Two execution modes per solver (sprs_solver_set_mode; the batched CG is fused only):
@@ -458,6 +458,27 @@ class CgMany {
     int run(const V *dinv, const T *rhs, T *x, int k, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out, int *status_out);
 };
 
+// Multi-shift conjugate gradients: (A + sigma_j I) x_j = rhs for up to mmax <= 8 real shifts sigma_j >= 0 in ONE Krylov run on A
+// (recurrence: include/sprsolve_hip.h, sprs_cgshift_*; cg_shift.hip; kernels: cg_shift_fuse.hpp).  Single GPU, one mode, no
+// preconditioner; of KrylovBase it uses the work vectors, the partial slots and spmv() — no literal mode, trace or profile.
+template <class T> struct CgShiftState;  // cg_shift_fuse.hpp
+template <class T>
+class CgShift : public KrylovBase<T> {
+   public:
+    StateBlock<CgShiftState<T>> state;
+    int mmax = 0;                // the most shifts a solve may carry: work holds r, p, q, then mmax columns of P and mmax of X
+    int create(const sprs_csr *A, size_t size, size_t mmax);
+    void destroy() { state.destroy(); KrylovBase<T>::destroy(); }
+    // shifts: m host values; rhs: n entries, x: m contiguous vectors of n entries (output only), both on the host where `host`;
+    // its_out / res_out / status_out: host arrays of m entries (each may be null)
+    int solve(const Real<T> *shifts, size_t m, const T *rhs, size_t rhs_len, bool host, T *x, size_t x_len, size_t max_iter, Real<T> tol,
+              size_t *its_out, Real<T> *res_out, int *status_out);
+
+   private:
+    int run(const Real<T> *shifts, int m, const T *rhs, bool host, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out,
+            int *status_out);
+};
+
 // ======================================================================= KrylovBase's member templates
 template <class T>
 template <class U, class W>
@@ -569,6 +590,7 @@ struct sprs_csminres : sprs_solver_handle {};
 struct sprs_cg : sprs_solver_handle {};
 struct sprs_gmres : sprs_solver_handle {};
 struct sprs_cg_many : sprs_solver_handle {};
+struct sprs_cg_shift : sprs_solver_handle {};
 struct sprs_lsmr : sprs_solver_handle {};
 struct sprs_eigsh : sprs_solver_handle {};
 struct sprs_lobpcg : sprs_solver_handle {};
