@@ -58,7 +58,8 @@ typedef struct sprs_lsmr sprs_lsmr;         /* LSMR least squares on any A, rect
 typedef struct sprs_cg_many sprs_cg_many;   /* conjugate gradients on several right-hand sides at once ("several right-hand sides" below) */
 typedef struct sprs_cg_shift sprs_cg_shift; /* conjugate gradients on (A + sigma_j I) x_j = rhs for several shifts at once ("shifted systems" below) */
 typedef struct sprs_gmres sprs_gmres;       /* restarted GMRES (no reference analogue; "restarted GMRES" below) */
-typedef struct sprs_comm sprs_comm;         /* RCCL communicator of this rank (multi-GPU section)  */
+typedef struct sprs_idrs sprs_idrs;         /* IDR(s) for non-symmetric systems (no reference analogue; "IDR(s)" below) */
+typedef struct sprs_comm sprs_comm;        /* RCCL communicator of this rank (multi-GPU section)  */
 typedef struct sprs_gauss_seidel sprs_gauss_seidel; /* GaussSeidel<T>        (gauss_seidel.rs:8-31) */
 /* sprs_ilu0, the ILU(0) preconditioner handle, is declared with its section ("ILU(0) preconditioner" below) */
 
@@ -587,6 +588,74 @@ int sprs_gmres_precond_solve_z(sprs_gmres *S, const sprs_diag *P, const sprs_c64
 int sprs_gmres_solve_dev_d(sprs_gmres *S, const sprs_diag *P_or_null, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
 int sprs_gmres_solve_dev_z(sprs_gmres *S, const sprs_diag *P_or_null, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
 
+/* ---------------------------------------------------------------- IDR(s)
+ * IDR(s) for any square non-singular A (Sonneveld & van Gijzen 2008; the bi-orthogonal variant of van Gijzen & Sonneveld, ACM
+ * TOMS 38(1), 2011): a short-recurrence solver on 3 s + 4 vectors with a fixed cost per product with A and no restart; IDR(1)
+ * is mathematically BiCGStab.  Right-preconditioned by nothing, a diagonal, or an applied handle (sprs_ilu0_idrs_*,
+ * sprs_amg_idrs_*, sprs_fsai_idrs_*).  The conventions are BiCGStab's: relative residual against |rhs|, a zero right-hand side
+ * answers x = 0, x is in/out (a non-zero start is honoured) and is left modified on error, the same status codes.  `s` = 0
+ * means 4; s > SPRS_IDRS_MAX_S or s > size is SPRS_INVALID_ARGUMENT with a text (sprs_last_error), and so is a distributed
+ * operator.  One (fused) mode: sprs_solver_set_mode(.., SPRS_SOLVER_IDRS, 1) is SPRS_INVALID_ARGUMENT.
+ *
+ * Shadow space: column c of P holds the U[-1, 1) values of the generators' counter-based stream 200 + 2 c (sprs_lobpcg_*'s
+ * default start block uses streams 100 + ..; the imaginary parts of a complex T: stream 201 + 2 c), rounded to T; the columns
+ * are orthonormalised once at creation, in D (CGS2 against the earlier columns: each pass takes its dot products on the same
+ * vector, then subtracts in ascending order; then a real scale by 1 / norm2), and rounded to T at the end.
+ *
+ * Vectors r, v, vh, t, g_i, u_i, p_i are of type T.  D = double for a real T and complex double for a complex T: M (s x s, the
+ * identity at the start), f, c, alpha, beta, q and omega (1 at the start) are kept and computed in D for every T, in the order
+ * written, and rounded to T only where they multiply a vector.  G = [g_i] and U = [u_i] start at zero.  conj_dot(a, b) =
+ * sum conj(a_i) b_i and norm2 inside the cycles are computed in D too: the operands are widened, so for a single-precision T
+ * every product is exact and only the sum rounds, and the scalars do not depend on the summation order beyond 1e-16 (the
+ * first rn is the library's norm2 in T).  P v is the preconditioner (v itself without one).  kappa = 0.7.
+ *     rhs_norm = norm2(rhs);  if rhs_norm <= eps: x = 0, return SPRS_OK with *its_out = 0, *res_out = rhs_norm
+ *     tol2 = tol * rhs_norm;  r = A x;  r = rhs*1 + r*(-1);  rn = norm2(r);  its = 0
+ *     if rn <= tol2: SPRS_OK, *its_out = 0, *res_out = rn / rhs_norm
+ *     cycle:
+ *         f_i = conj_dot(p_i, r) for i = 0 .. s - 1, all on the same r
+ *         for k = 0 .. s - 1:
+ *             for i = k .. s - 1 in order:  t = f_i;  for j = k .. i - 1 in order: t = t - M_ij*c_j;  c_i = t / M_ii
+ *             v = r;  for i = k .. s - 1 in order: v += g_i*(-c_i);  vh = P v
+ *             w = 0;  for i = k .. s - 1 in order: w += u_i*c_i;  u_k = vh*omega + w
+ *             g_k = A u_k;  its += 1
+ *             q_i = conj_dot(p_i, g_k) for i = 0 .. s - 1, all on the same g_k
+ *             for i = 0 .. k - 1 in order:  t = q_i;  for j = 0 .. i - 1 in order: t = t - M_ij*alpha_j;  alpha_i = t / M_ii
+ *             for i = 0 .. k - 1 in order: g_k += g_i*(-alpha_i);  for i = 0 .. k - 1 in order: u_k += u_i*(-alpha_i)
+ *             for i = k .. s - 1:  m = q_i;  for j = 0 .. k - 1 in order: m = m - M_ij*alpha_j;  M_ik = m
+ *             unless M_kk is finite and not 0: SPRS_BREAKDOWN, *its_out = its (x and r are those before this step)
+ *             beta = f_k / M_kk;  r += g_k*(-beta);  x += u_k*beta;  for i = k + 1 .. s - 1: f_i = f_i - beta*M_ik
+ *             rn = norm2(r);  if rn <= tol2: SPRS_OK, *its_out = its, *res_out = rn / rhs_norm
+ *             if its == max_iter: SPRS_INSUFFICIENT_ITER, *its_out = max_iter
+ *         vh = P r;  t = A vh;  its += 1;  tt = re(conj_dot(t, t));  tr = conj_dot(t, r)
+ *         rho = |tr| / (sqrt(tt) * rn);  omega = tr*(1 / tt);  if rho < kappa: omega = omega * (kappa / rho)
+ *         unless tt > 0 and tt and omega are finite and omega is not 0: SPRS_BREAKDOWN, *its_out = its
+ *         x += vh*omega;  r += t*(-omega);  rn = norm2(r);  the two tests on rn and its as above
+ * max_iter == 0: SPRS_INSUFFICIENT_ITER after the initial residual's test, x untouched.  `its` counts the products with A after
+ * the initial residual; the reported residual is the recursive one.  The k sequential projections of the textbook step are one
+ * multi-dot and a k x k forward solve here, because P^H [g_0 .. g_{k-1}] is lower triangular.
+ * Solver kind SPRS_SOLVER_IDRS for sprs_solver_set_trace / sprs_solver_trace_rows.  Trace row, one per product with A: [its
+ * (after the product), rn before the step, re, im of the step's coefficient (beta, or omega), re, im of its pivot (M_kk, or tt),
+ * k (s for the omega step), 0]. */
+#define SPRS_IDRS_MAX_S 8
+int sprs_idrs_destroy(sprs_idrs *S);           /* NULL is a no-op */
+int sprs_idrs_create_d(const sprs_csr *A, size_t size, size_t s, sprs_idrs **out);
+int sprs_idrs_create_z(const sprs_csr *A, size_t size, size_t s, sprs_idrs **out);
+int sprs_idrs_create_s(const sprs_csr *A, size_t size, size_t s, sprs_idrs **out);
+int sprs_idrs_create_c(const sprs_csr *A, size_t size, size_t s, sprs_idrs **out);
+int sprs_idrs_solve_d(sprs_idrs *S, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_idrs_solve_z(sprs_idrs *S, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_idrs_solve_s(sprs_idrs *S, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_idrs_solve_c(sprs_idrs *S, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_idrs_precond_solve_d(sprs_idrs *S, const sprs_diag *P, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_idrs_precond_solve_z(sprs_idrs *S, const sprs_diag *P, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_idrs_precond_solve_s(sprs_idrs *S, const sprs_diag *P, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_idrs_precond_solve_c(sprs_idrs *S, const sprs_diag *P, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+/* the same on device vectors (16-byte aligned ones are used in place) */
+int sprs_idrs_solve_dev_d(sprs_idrs *S, const sprs_diag *P_or_null, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_idrs_solve_dev_z(sprs_idrs *S, const sprs_diag *P_or_null, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_idrs_solve_dev_s(sprs_idrs *S, const sprs_diag *P_or_null, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_idrs_solve_dev_c(sprs_idrs *S, const sprs_diag *P_or_null, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+
 /* ---------------------------------------------------------------- mixed-precision iterative refinement
  * An answer of H precision (H = f64 for _d, Complex<f64> for _z) at the byte cost of L iterations (L = f32 / Complex<f32>):
  * the residual and the solution stay in H, every correction comes from an inner Krylov solve in L on a copy of A whose values
@@ -1032,6 +1101,32 @@ int sprs_fsai_minres_solve_dev_z(sprs_minres *S, const sprs_fsai *P, const sprs_
 int sprs_fsai_minres_solve_dev_s(sprs_minres *S, const sprs_fsai *P, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
 int sprs_fsai_minres_solve_dev_c(sprs_minres *S, const sprs_fsai *P, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
 
+/* IDR(s) preconditioned by ILU(0), AMG or FSAI: the recurrence of sprs_idrs_* with P = the handle's application */
+int sprs_ilu0_idrs_solve_d(sprs_idrs *S, const sprs_ilu0 *P, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_ilu0_idrs_solve_z(sprs_idrs *S, const sprs_ilu0 *P, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_ilu0_idrs_solve_s(sprs_idrs *S, const sprs_ilu0 *P, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_ilu0_idrs_solve_c(sprs_idrs *S, const sprs_ilu0 *P, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_ilu0_idrs_solve_dev_d(sprs_idrs *S, const sprs_ilu0 *P, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_ilu0_idrs_solve_dev_z(sprs_idrs *S, const sprs_ilu0 *P, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_ilu0_idrs_solve_dev_s(sprs_idrs *S, const sprs_ilu0 *P, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_ilu0_idrs_solve_dev_c(sprs_idrs *S, const sprs_ilu0 *P, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_amg_idrs_solve_d(sprs_idrs *S, const sprs_amg *P, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_amg_idrs_solve_z(sprs_idrs *S, const sprs_amg *P, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_amg_idrs_solve_s(sprs_idrs *S, const sprs_amg *P, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_amg_idrs_solve_c(sprs_idrs *S, const sprs_amg *P, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_amg_idrs_solve_dev_d(sprs_idrs *S, const sprs_amg *P, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_amg_idrs_solve_dev_z(sprs_idrs *S, const sprs_amg *P, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_amg_idrs_solve_dev_s(sprs_idrs *S, const sprs_amg *P, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_amg_idrs_solve_dev_c(sprs_idrs *S, const sprs_amg *P, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_fsai_idrs_solve_d(sprs_idrs *S, const sprs_fsai *P, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_fsai_idrs_solve_z(sprs_idrs *S, const sprs_fsai *P, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_fsai_idrs_solve_s(sprs_idrs *S, const sprs_fsai *P, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_fsai_idrs_solve_c(sprs_idrs *S, const sprs_fsai *P, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_fsai_idrs_solve_dev_d(sprs_idrs *S, const sprs_fsai *P, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_fsai_idrs_solve_dev_z(sprs_idrs *S, const sprs_fsai *P, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_fsai_idrs_solve_dev_s(sprs_idrs *S, const sprs_fsai *P, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_fsai_idrs_solve_dev_c(sprs_idrs *S, const sprs_fsai *P, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+
 /* ---------------------------------------------------------------- multi-GPU (one process per GPU)
  * No reference analogue: the reference is single-process (rayon).  The matrix is row-partitioned;
  * rank r owns rows [r0, r1) and the matching slices of every vector.  A distributed operator is the
@@ -1424,10 +1519,11 @@ int sprs_expm_apply_dev_c(sprs_expm *S, float t, const sprs_c32 *v_dev, size_t v
 
 /* ---------------------------------------------------------------- solver options / instrumentation
  * `solver` is a handle of any of the solver types below, `kind` says which. */
-enum { SPRS_SOLVER_BICGSTAB = 1, SPRS_SOLVER_MINRES = 2, SPRS_SOLVER_CSMINRES = 3, SPRS_SOLVER_CG = 4, SPRS_SOLVER_GMRES = 5, SPRS_SOLVER_LSMR = 6 };
+enum { SPRS_SOLVER_BICGSTAB = 1, SPRS_SOLVER_MINRES = 2, SPRS_SOLVER_CSMINRES = 3, SPRS_SOLVER_CG = 4, SPRS_SOLVER_GMRES = 5, SPRS_SOLVER_LSMR = 6, SPRS_SOLVER_IDRS = 7 };
 /* mode 0 (default): fused kernels, device-resident scalars, lazy host polling.
  * mode 1: "literal" — the reference's op list one kernel per op, every scalar consumed on the
- *         host exactly where the reference consumes it (bicg_stab.rs:122-197). */
+ *         host exactly where the reference consumes it (bicg_stab.rs:122-197).  IDR(s) has no such mode: mode 1 with
+ *         SPRS_SOLVER_IDRS is SPRS_INVALID_ARGUMENT. */
 int sprs_solver_set_mode(void *solver, int kind, int mode);
 /* Per-iteration scalar trace (8 doubles per row: BiCGStab [its, r_norm, rho, alpha, w]; MINRES [its, beta, alpha, c, s, res_norm];
  * CG [its, r_norm, rho, alpha, beta]; LSMR [its, normr, normar, alpha, beta], each scalar in a (re, im) pair — LSMR's scalars

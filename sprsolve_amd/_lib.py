@@ -15,8 +15,9 @@ CSRC = os.path.join(_HERE, "csrc")
  INVALID_ARGUMENT) = range(8)
 ZERO_DIAGONAL, NOT_SQUARE, NOT_CSR = 8, 9, 10
 ERR_HIP, ERR_RCCL, ERR_NO_DEVICE = 100, 101, 102
-SOLVER_BICGSTAB, SOLVER_MINRES, SOLVER_CSMINRES, SOLVER_CG, SOLVER_GMRES, SOLVER_LSMR = 1, 2, 3, 4, 5, 6
+SOLVER_BICGSTAB, SOLVER_MINRES, SOLVER_CSMINRES, SOLVER_CG, SOLVER_GMRES, SOLVER_LSMR, SOLVER_IDRS = 1, 2, 3, 4, 5, 6, 7
 GMRES_MAX_RESTART = 64
+IDRS_MAX_S = 8
 INNER_CG, INNER_GMRES = 0, 1
 EIGSH_MAX_NCV = 64
 EIGSH_LARGEST, EIGSH_SMALLEST = 0, 1
@@ -131,7 +132,9 @@ def _protos():
             P["sprs_%s_solve_%s" % (k, s)] = [_vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
         P["sprs_gmres_create_" + s] = [_vp, _sz, _sz, _pp]
         P["sprs_gmres_solve_" + s] = [_vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
-        for k in ("bicgstab", "minres", "cg", "gmres"):
+        P["sprs_idrs_create_" + s] = [_vp, _sz, _sz, _pp]
+        P["sprs_idrs_solve_" + s] = [_vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
+        for k in ("bicgstab", "minres", "cg", "gmres", "idrs"):
             P["sprs_%s_precond_solve_%s" % (k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
             P["sprs_%s_solve_dev_%s" % (k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
         P["sprs_csminres_solve_dev_" + s] = [_vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
@@ -141,7 +144,7 @@ def _protos():
         P["sprs_amg_mul_vec_" + s] = [_vp, _vp, _sz, _vp, _sz]
         P["sprs_fsai_mul_vec_dev_" + s] = [_vp, _vp, _vp]
         P["sprs_fsai_mul_vec_" + s] = [_vp, _vp, _sz, _vp, _sz]
-        for k in ("cg", "gmres", "bicgstab", "minres"):
+        for k in ("cg", "gmres", "bicgstab", "minres", "idrs"):
             for pc in ("ilu0", "amg", "fsai"):
                 P["sprs_%s_%s_solve_%s" % (pc, k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
                 P["sprs_%s_%s_solve_dev_%s" % (pc, k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
@@ -158,7 +161,7 @@ def _protos():
     P["sprs_csr_adjoint"] = [_vp, _int, _pp]
     P["sprs_csr_matmul"] = [_vp, _vp, _pp, C.POINTER(_i64)]
     P["sprs_csr_read"] = [_vp, _vp, _vp, _vp]
-    for k in ("bicgstab", "minres", "csminres", "cg", "gmres", "cgmany", "cgshift", "lsmr", "eigsh", "lobpcg", "svds", "expm"):
+    for k in ("bicgstab", "minres", "csminres", "cg", "gmres", "cgmany", "cgshift", "idrs", "lsmr", "eigsh", "lobpcg", "svds", "expm"):
         P["sprs_%s_destroy" % k] = [_vp]
     for s in ("d", "zd", "z", "s", "cs", "c"):
         P["sprs_diag_precond_create_" + s] = [_vp, _sz, _vp, _pp]

@@ -776,22 +776,15 @@ int lobpcg_create(const sprs_csr *A, size_t size, size_t block, sprs_lobpcg **ou
     return SPRS_OK;
 }
 
-// The default start block: column c holds U[-1, 1) doubles from the top 53 bits of counter-based splitmix64, seed "PRSOLVE",
-// stream 100 + 2 c (the imaginary parts: stream 101 + 2 c), rounded to T — sprsolve_amd.gen.uniform's values.
-inline double lobpcg_uniform(uint64_t stream, uint64_t i) {
-    uint64_t z = 0x5052534F4C5645ull + stream * 0xD1B54A32D192ED03ull + (i + 1) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z = z ^ (z >> 31);
-    return -1.0 + 2.0 * ((double)(z >> 11) * (1.0 / 9007199254740992.0));
-}
+// The default start block: column c holds gen_uniform's values (internal.hpp) of stream 100 + 2 c (the imaginary parts: stream
+// 101 + 2 c), rounded to T.
 template <class T>
 void lobpcg_default_x0(size_t n, int b, std::vector<T> &X0) {
     X0.resize(n * (size_t)b);
     for (int c = 0; c < b; ++c)
         for (size_t i = 0; i < n; ++i) {
-            T v = sfromr<T>((Real<T>)lobpcg_uniform(100 + 2 * (uint64_t)c, i));
-            if constexpr (is_complex<T>::value) v.im = (Real<T>)lobpcg_uniform(101 + 2 * (uint64_t)c, i);
+            T v = sfromr<T>((Real<T>)gen_uniform(100 + 2 * (uint64_t)c, i));
+            if constexpr (is_complex<T>::value) v.im = (Real<T>)gen_uniform(101 + 2 * (uint64_t)c, i);
             X0[(size_t)c * n + i] = v;
         }
 }
@@ -831,6 +824,7 @@ static int with_base(void *solver, int kind, F &&f) {
         case SPRS_SOLVER_CG: return with_solver<Cg>(h->dtype, h->impl, f);
         case SPRS_SOLVER_GMRES: return with_solver<Gmres>(h->dtype, h->impl, f);
         case SPRS_SOLVER_LSMR: return with_solver<Lsmr>(h->dtype, h->impl, f);
+        case SPRS_SOLVER_IDRS: return with_solver<Idrs>(h->dtype, h->impl, f);
         case SPRS_SOLVER_MINRES:
         case SPRS_SOLVER_CSMINRES: return with_solver<MinRes>(h->dtype, h->impl, f);
     }
@@ -973,6 +967,7 @@ int sprs_cg_destroy(sprs_cg *S) { return solver_destroy<Cg>(S); }
 int sprs_gmres_destroy(sprs_gmres *S) { return solver_destroy<Gmres>(S); }
 int sprs_cgmany_destroy(sprs_cg_many *S) { return solver_destroy<CgMany>(S); }
 int sprs_cgshift_destroy(sprs_cg_shift *S) { return solver_destroy<CgShift>(S); }
+int sprs_idrs_destroy(sprs_idrs *S) { return solver_destroy<Idrs>(S); }
 int sprs_lsmr_destroy(sprs_lsmr *S) { return solver_destroy<Lsmr>(S); }
 int sprs_eigsh_destroy(sprs_eigsh *S) { return solver_destroy<Eigsh>(S); }
 int sprs_lobpcg_destroy(sprs_lobpcg *S) { return solver_destroy<Lobpcg>(S); }
@@ -1126,6 +1121,11 @@ int sprs_expm_destroy(sprs_expm *S) { return solver_destroy<Expm>(S); }
                return (solver_create<T, sprs_gmres, Gmres>(A, n, out, [&](auto *s) { return s->create(A, n, restart); }));) \
     }                                                                                                                  \
     SPRS_SOLVER_SOLVES(X, T, CT, R, gmres, Gmres)                                                                      \
+    /* IDR(s)'s create takes s (0 = 4); the class refuses s > SPRS_IDRS_MAX_S, s > n and a distributed operator with a text */ \
+    int sprs_idrs_create_##X(const sprs_csr *A, size_t n, size_t s_dim, sprs_idrs **out) {                             \
+        SPRS_G(return (solver_create<T, sprs_idrs, Idrs>(A, n, out, [&](auto *s) { return s->create(A, n, s_dim); }));) \
+    }                                                                                                                  \
+    SPRS_SOLVER_SOLVES(X, T, CT, R, idrs, Idrs)                                                                        \
     /* CSMinRes has no precond_solve (cs_minres.rs) */                                                                  \
     int sprs_csminres_create_##X(const sprs_csr *A, size_t n, sprs_csminres **out) {                                   \
         SPRS_G(return (solver_create<T, sprs_csminres, MinRes>(A, n, out, [&](auto *s) { return s->create(A, n, true); }));) \
@@ -1163,6 +1163,7 @@ SPRS_API(c, cplxf, sprs_c32, float)
     SPRS_APPLIED_SOLVES(X, T, CT, R, bicgstab, BicgStab, amg) SPRS_APPLIED_SOLVES(X, T, CT, R, minres, MinRes, amg) \
     SPRS_APPLIED_SOLVES(X, T, CT, R, cg, Cg, fsai) SPRS_APPLIED_SOLVES(X, T, CT, R, gmres, Gmres, fsai) \
     SPRS_APPLIED_SOLVES(X, T, CT, R, bicgstab, BicgStab, fsai) SPRS_APPLIED_SOLVES(X, T, CT, R, minres, MinRes, fsai) \
+    SPRS_APPLIED_SOLVES(X, T, CT, R, idrs, Idrs, ilu0) SPRS_APPLIED_SOLVES(X, T, CT, R, idrs, Idrs, amg) SPRS_APPLIED_SOLVES(X, T, CT, R, idrs, Idrs, fsai) \
     SPRS_APPLIED_LOBPCG(X, T, CT, R, ilu0) SPRS_APPLIED_LOBPCG(X, T, CT, R, amg) SPRS_APPLIED_LOBPCG(X, T, CT, R, fsai)
 SPRS_APPLIED_API(d, double, double, double)
 SPRS_APPLIED_API(z, cplx, sprs_c64, double)
@@ -1184,6 +1185,7 @@ int sprs_diag_precond_create_c(sprs_ctx *c, size_t n, const sprs_c32 *d, sprs_di
 // ------------------------------------------------------------------------------ options / instrumentation
 int sprs_solver_set_mode(void *solver, int kind, int mode) {
     if (mode != 0 && mode != 1) return SPRS_INVALID_ARGUMENT;
+    if (kind == SPRS_SOLVER_IDRS && mode != 0) return SPRS_INVALID_ARGUMENT;   // IDR(s) has one mode
     return with_base(solver, kind, [&](auto *b) { b->mode = mode; return (int)SPRS_OK; });
 }
 int sprs_solver_set_trace(void *solver, int kind, double *trace_host, size_t cap) {

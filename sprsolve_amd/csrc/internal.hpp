@@ -530,6 +530,16 @@ int dist_spmv(const sprs_csr *A, T *x_ext, T *y, int dot_mode, const T *u, T *pa
               const Fin *fin = nullptr);   // fin: handed to the LAST launch of the operator (P and base pointers span all of them)
 int allreduce_sum(sprs_comm *comm, void *dev, size_t count, bool f32 = false);   // in place, on the ctx stream; count elements of f64 (or f32)
 
+// sprsolve_amd.gen.uniform's values on the host: a U[-1, 1) double from the top 53 bits of counter-based splitmix64, seed
+// "PRSOLVE".  LOBPCG's default start block (streams 100 + ..) and IDR(s)'s shadow space (streams 200 + ..) are made of them.
+inline double gen_uniform(uint64_t stream, uint64_t i) {
+    uint64_t z = 0x5052534F4C5645ull + stream * 0xD1B54A32D192ED03ull + (i + 1) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z = z ^ (z >> 31);
+    return -1.0 + 2.0 * ((double)(z >> 11) * (1.0 / 9007199254740992.0));
+}
+
 inline int grid_for(const sprs_ctx *c) {
     int g = c->grid;
     if (g < 8) g = 8;

@@ -1,6 +1,6 @@
 // Krylov recurrences (host side, C++) over device-resident vectors and scalars: the solver objects behind sprs_bicgstab,
-// sprs_minres / sprs_csminres, sprs_cg, sprs_gmres, sprs_cg_many, sprs_cg_shift, sprs_lsmr, sprs_eigsh, sprs_lobpcg, sprs_svds and sprs_expm.  One translation unit per solver (bicgstab.hip,
-// minres.hip, cg.hip, gmres.hip, cg_many.hip, cg_shift.hip, lsmr.hip, eigsh.hip, lobpcg.hip, svds.hip, expm.hip), each with its recurrence comment; its kernels are the functors of its *_fuse.hpp, all run by
+// sprs_minres / sprs_csminres, sprs_cg, sprs_gmres, sprs_cg_many, sprs_cg_shift, sprs_idrs, sprs_lsmr, sprs_eigsh, sprs_lobpcg, sprs_svds and sprs_expm.  One translation unit per solver (bicgstab.hip,
+// minres.hip, cg.hip, gmres.hip, cg_many.hip, cg_shift.hip, idrs.hip, lsmr.hip, eigsh.hip, lobpcg.hip, svds.hip, expm.hip), each with its recurrence comment; its kernels are the functors of its *_fuse.hpp, all run by
 // fused_kernel (fused_launch.hpp).  BiCGStab and MINRES / CSMINRES follow the reference (src/bicg_stab.rs, src/minres.rs,
 // src/cs_minres.rs); CG, GMRES, the batched and the multi-shift CG, LSMR, the two eigensolvers, the truncated SVD and the exponential propagator have no reference analogue: include/sprsolve_hip.h
 // states their recurrences.
@@ -479,6 +479,34 @@ class CgShift : public KrylovBase<T> {
             int *status_out);
 };
 
+// IDR(s) for any square non-singular A, with any of the preconditioners (recurrence: include/sprsolve_hip.h, sprs_idrs_*; idrs.hip;
+// kernels: idrs_fuse.hpp).  Single GPU, one mode; of KrylovBase it uses the work vectors, the partial
+// slots, spmv() and the trace — no literal mode or profile.
+template <class T> struct IdrsState;     // idrs_fuse.hpp
+template <class T>
+class Idrs : public KrylovBase<T> {
+   public:
+    StateBlock<IdrsState<T>> state;      // the host pushes it per solve and reads its head every poll_interval() products
+    int s = 4;                           // the shadow space's dimension: work holds r, v, vh, t, then s columns each of G, U and P
+    DotsBuf<std::conditional_t<is_complex<T>::value, cplx, double>> dots;   // partials in double: [8][grid] for q = P^H g_k, [8][grid] for f = P^H r, |r|^2, conj(r).t, conj(t).t
+    int create(const sprs_csr *A, size_t size, size_t s_dim);
+    void destroy() { state.destroy(); dots.destroy(); KrylovBase<T>::destroy(); }
+    // P: nothing, a diagonal (a `const sprs_diag *` converts) or an applied ILU(0) / AMG / FSAI handle
+    int solve_dev(const Precond<T> &P, const T *rhs, size_t rhs_len, T *x, size_t x_len, size_t max_iter, Real<T> tol,
+                  size_t *its_out, Real<T> *res_out);
+
+   private:
+    friend class KrylovBase<T>;
+    T *gvec(int i) { return this->vec(4 + i); }
+    T *uvec(int i) { return this->vec(4 + s + i); }
+    T *pvec(int i) { return this->vec(4 + 2 * s + i); }
+    template <class V>
+    int run(const Prec<T, V> &M, const T *rhs, T *x, size_t max_iter, Real<T> tol, size_t *its_out, Real<T> *res_out);
+    // (sprs_solver_set_mode refuses mode 1 for this kind: never reached)
+    template <class V>
+    int run_literal(const Prec<T, V> &, const T *, T *, size_t, Real<T>, size_t *, Real<T> *) { return SPRS_INVALID_ARGUMENT; }
+};
+
 // ======================================================================= KrylovBase's member templates
 template <class T>
 template <class U, class W>
@@ -591,6 +619,7 @@ struct sprs_cg : sprs_solver_handle {};
 struct sprs_gmres : sprs_solver_handle {};
 struct sprs_cg_many : sprs_solver_handle {};
 struct sprs_cg_shift : sprs_solver_handle {};
+struct sprs_idrs : sprs_solver_handle {};
 struct sprs_lsmr : sprs_solver_handle {};
 struct sprs_eigsh : sprs_solver_handle {};
 struct sprs_lobpcg : sprs_solver_handle {};
