@@ -69,7 +69,9 @@ typedef struct sprs_gauss_seidel sprs_gauss_seidel; /* GaussSeidel<T>        (ga
 int sprs_ctx_create(int device, void *stream, sprs_ctx **out);
 int sprs_ctx_destroy(sprs_ctx *ctx);               /* NULL is a no-op */
 int sprs_ctx_sync(sprs_ctx *ctx);
-const char *sprs_last_error(const sprs_ctx *ctx);  /* text of the last SPRS_ERR_* on this ctx */
+const char *sprs_last_error(const sprs_ctx *ctx);  /* text of the last SPRS_ERR_* on this ctx, and of a SPRS_INVALID_ARGUMENT that
+                                                      says why ("sprs_<entry>: <text>"; every sprs_*_create_* of a solver says so
+                                                      where the operator holds another scalar type than its suffix) */
 const char *sprs_status_str(int status);
 int sprs_version(void);
 /* Tuning knobs.  Defaults are the measured best on MI355X (profiles/r0*_tuning.md); none changes a result except through

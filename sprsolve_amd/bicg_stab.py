@@ -1,9 +1,6 @@
 """BiCGStab — mirror of the reference's src/bicg_stab.rs."""
 from . import _lib
-from ._solver import _SolverBase
-from .amg import AMG
-from .fsai import FSAI
-from .ilu import ILU0
+from ._solver import _SolverBase, applied_prefix
 
 
 class BiCGStab(_SolverBase):
@@ -18,10 +15,4 @@ class BiCGStab(_SolverBase):
 
     def precond_solve(self, precond, rhs, x, max_iter, tol):
         """bicg_stab.rs:204-366 (right-preconditioned) by a `DiagPrecond` (Jacobi), an `ILU0`, an `AMG` or an `FSAI`."""
-        if isinstance(precond, ILU0):
-            return self._solve(precond, rhs, x, max_iter, tol, True, prefix="ilu0")
-        if isinstance(precond, AMG):
-            return self._solve(precond, rhs, x, max_iter, tol, True, prefix="amg")
-        if isinstance(precond, FSAI):
-            return self._solve(precond, rhs, x, max_iter, tol, True, prefix="fsai")
-        return self._solve(precond, rhs, x, max_iter, tol, True)
+        return self._solve(precond, rhs, x, max_iter, tol, True, prefix=applied_prefix(precond))

@@ -1,9 +1,6 @@
 """Conjugate gradients for Hermitian positive-definite operators (no reference analogue)."""
 from . import _lib
-from ._solver import _SolverBase
-from .amg import AMG
-from .fsai import FSAI
-from .ilu import ILU0
+from ._solver import _SolverBase, applied_prefix
 
 
 class CG(_SolverBase):
@@ -19,10 +16,4 @@ class CG(_SolverBase):
 
     def precond_solve(self, precond, rhs, x, max_iter, tol):
         """Preconditioned by a `DiagPrecond` (Jacobi), an `ILU0`, an `AMG` or an `FSAI`; InvalidPreconditioner where conj(r).M^-1 r is not positive."""
-        if isinstance(precond, ILU0):
-            return self._solve(precond, rhs, x, max_iter, tol, True, prefix="ilu0")
-        if isinstance(precond, AMG):
-            return self._solve(precond, rhs, x, max_iter, tol, True, prefix="amg")
-        if isinstance(precond, FSAI):
-            return self._solve(precond, rhs, x, max_iter, tol, True, prefix="fsai")
-        return self._solve(precond, rhs, x, max_iter, tol, True)
+        return self._solve(precond, rhs, x, max_iter, tol, True, prefix=applied_prefix(precond))

@@ -4,26 +4,23 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .device import dev_len, dev_ptr, is_device_array, pre_sync, sfx
-from .error import check
-
-_ARG_ERRORS = (_lib.INCOMPATIBLE_RHS_SIZE, _lib.INCOMPATIBLE_X_SIZE, _lib.DIM_MISMATCH, _lib.INVALID_ARGUMENT)
+from ._solver import _Handle, column_call
+from .device import dev_len, dev_ptr, is_device_array, pre_sync
 
 
-class CGMany:
+class CGMany(_Handle):
     """`CGMany.new(A, size, k)`: CG (see `CG`) on up to k <= 8 right-hand sides in three launches per iteration whatever k is
     (sprsolve_amd/csrc/spmm.hip, cg_many_fuse.hpp, cg_many.hip).  A block of right-hand sides is a C-contiguous (size, k) array.
     Every column runs the recurrence of include/sprsolve_hip.h (sprs_cg_*) on its own scalars and stops on its own event."""
 
+    NAME = "cgmany"
+    last_status = None  # what the last solve returned: 0, or the status of the lowest-numbered column that did not return 0
+
     def __init__(self, A, size, k):
-        self.A, self.size, self.k, self.dtype = A, int(size), int(k), A.dtype
-        self.s = sfx(self.dtype)
+        self.size, self.k = int(size), int(k)
         if self.k < 0:
             raise ValueError("sprsolve_hip: invalid argument")
-        h = C.c_void_p()
-        check(getattr(_lib.lib(), "sprs_cgmany_create_" + self.s)(A.h, self.size, self.k, C.byref(h)), A.ctx.h)
-        self.h = h
-        self.last_status = None      # what the last solve returned: 0, or the status of the lowest-numbered column that did not return 0
+        self._create(A, self.size, self.k)
 
     @classmethod
     def new(cls, A, size, k):
@@ -63,23 +60,4 @@ class CGMany:
                 from .error import IncompatibleMatrixFormat
                 raise IncompatibleMatrixFormat("Input and output vec dimension do not match")
             fn, rp, xp = getattr(L, "sprs_cgmany_solve_" + self.s), rhs_a.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p)
-        n_out = max(int(k), 1)
-        its = (C.c_size_t * n_out)(); res = (_lib.REAL[self.s] * n_out)(); status = (C.c_int * n_out)()
-        st = fn(self.h, ph, rp, rl, xp, xl, int(k), int(max_iter), float(tol), its, res, status)
-        self.last_status = int(st)
-        if st >= _lib.ERR_HIP or (st in _ARG_ERRORS):
-            from .error import solve_result
-            solve_result(st, 0, 0.0, self.A.ctx.h)
-        return (np.array(its[:k], dtype=np.int64), np.array(res[:k], dtype=np.dtype(_lib.REAL[self.s])),
-                np.array(status[:k], dtype=np.int32))
-
-    def close(self):
-        if self.h:
-            _lib.lib().sprs_cgmany_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return column_call(self, int(k), lambda its, res, status: fn(self.h, ph, rp, rl, xp, xl, int(k), int(max_iter), float(tol), its, res, status))

@@ -4,31 +4,25 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .device import dev_len, dev_ptr, is_device_array, pre_sync, sfx
-from .error import check
-
-_ARG_ERRORS = (_lib.INCOMPATIBLE_RHS_SIZE, _lib.INCOMPATIBLE_X_SIZE, _lib.DIM_MISMATCH, _lib.INVALID_ARGUMENT)
+from ._solver import _Handle, column_call
+from .device import dev_len, dev_ptr, is_device_array, pre_sync
 
 
-class CGShift:
+class CGShift(_Handle):
     """`CGShift.new(A, size, mmax)`: the solutions of (A + sigma_j I) x_j = rhs for up to mmax <= 8 real shifts sigma_j >= 0 and a
     Hermitian positive-definite A, in one CG run on A: one SpMV and three launches per iteration whatever the number of shifts
     (sprsolve_amd/csrc/cg_shift_fuse.hpp, cg_shift.hip; the recurrence: include/sprsolve_hip.h, sprs_cgshift_*).  The method starts
     from x = 0 and takes no preconditioner.  The solutions are m contiguous vectors: a C-contiguous (m, size) array."""
 
+    NAME = "cgshift"
+    SAYS_WHY = True     # a distributed A, mmax out of range; in a solve the number of shifts, a negative or non-finite shift
+    last_status = None  # what the last solve returned: 0, or the status of the lowest-numbered column that did not return 0
+
     def __init__(self, A, size, mmax):
-        self.A, self.size, self.mmax, self.dtype = A, int(size), int(mmax), A.dtype
-        self.s = sfx(self.dtype)
+        self.size, self.mmax = int(size), int(mmax)
         if self.mmax < 0:
             raise ValueError("sprsolve_hip: invalid argument")
-        h = C.c_void_p()
-        self.h = None
-        st = getattr(_lib.lib(), "sprs_cgshift_create_" + self.s)(A.h, self.size, self.mmax, C.byref(h))
-        if st == _lib.INVALID_ARGUMENT:     # a distributed A, mmax out of range: the library says which
-            raise ValueError("sprsolve_hip: invalid argument: " + (_lib.lib().sprs_last_error(A.ctx.h) or b"").decode(errors="replace"))
-        check(st, A.ctx.h)
-        self.h = h
-        self.last_status = None      # what the last solve returned: 0, or the status of the lowest-numbered column that did not return 0
+        self._create(A, self.size, self.mmax)
 
     @classmethod
     def new(cls, A, size, mmax):
@@ -58,24 +52,5 @@ class CGShift:
                 raise TypeError("x must be a C-contiguous %s ndarray (it is written in place)" % self.dtype)
             rl, xl = rhs_a.size, x.size
             fn, rp, xp = getattr(L, "sprs_cgshift_solve_" + self.s), rhs_a.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p)
-        n_out = max(m, 1)
-        its = (C.c_size_t * n_out)(); res = (R * n_out)(); status = (C.c_int * n_out)()
-        st = fn(self.h, sh.ctypes.data_as(C.POINTER(R)), m, rp, rl, xp, xl, int(max_iter), float(tol), its, res, status)
-        self.last_status = int(st)
-        if st == _lib.INVALID_ARGUMENT:     # the number of shifts, a negative or non-finite shift: the library says which
-            raise ValueError("sprsolve_hip: invalid argument: " + (L.sprs_last_error(self.A.ctx.h) or b"").decode(errors="replace"))
-        if st >= _lib.ERR_HIP or (st in _ARG_ERRORS):
-            from .error import solve_result
-            solve_result(st, 0, 0.0, self.A.ctx.h)
-        return (np.array(its[:m], dtype=np.int64), np.array(res[:m], dtype=np.dtype(R)), np.array(status[:m], dtype=np.int32))
-
-    def close(self):
-        if self.h:
-            _lib.lib().sprs_cgshift_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return column_call(self, m, lambda its, res, status: fn(self.h, sh.ctypes.data_as(C.POINTER(R)), m, rp, rl, xp, xl, int(max_iter),
+                                                                float(tol), its, res, status))

@@ -547,10 +547,7 @@ int sprs_amg_create(const sprs_csr *A, double theta, int64_t coarse_max, int64_t
         if (!A || !out) return SPRS_INVALID_ARGUMENT;
         *out = nullptr;
         if (row_out) *row_out = -1;
-        if (A->dist) {                   // (before the shape: a row block with a halo has more columns than rows)
-            snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_amg: distributed operators are not supported (single GPU only)");
-            return SPRS_INVALID_ARGUMENT;
-        }
+        SPRS_TRY(single_gpu_only(A, "sprs_amg"));   // (before the shape: a row block with a halo has more columns than rows)
         if (A->nrows != A->ncols) return SPRS_NOT_SQUARE;
         if (!(theta >= 0.0) || coarse_max < 1 || coarse_max > AMG_COARSE_LIMIT || max_levels < 1 || max_levels > AMG_MAX_LEVELS) {
             snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_amg: theta >= 0, 1 <= coarse_max <= %d and 1 <= max_levels <= %d are required",

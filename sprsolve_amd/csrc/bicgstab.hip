@@ -9,6 +9,7 @@ namespace sprs {
 
 template <class T>
 int BicgStab<T>::create(const sprs_csr *A, size_t size) {
+    SPRS_TRY(size_is_rows(A, size));
     SPRS_TRY(this->init(A, size, 7));   // bicg_stab.rs:28 workspace 7n
     return state.create(this->ctx);
 }

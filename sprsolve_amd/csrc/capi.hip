@@ -24,6 +24,51 @@ static_assert(sizeof(sprs_c32) == sizeof(cplxf), "Complex<f32> layout");
         return SPRS_ERR_HIP;                   \
     }
 
+// ------------------------------------------------------------------------------ knobs
+// sprs_ctx_set / sprs_ctx_get: every knob once.  What a set stores: TRI -1 (any negative) / 0 / 1 (any other); BOOL 0 / 1; INT a value
+// of lo .. hi, anything else refused, rounded down to a multiple of 8 where round8; AUTO_OR_INT -1 for any negative, else as INT;
+// AT_LEAST the value, raised to lo; GET_ONLY is refused.
+namespace {
+struct Knob {
+    const char *name;
+    int sprs_ctx::*field;
+    enum Kind { TRI, BOOL, INT, AUTO_OR_INT, AT_LEAST, GET_ONLY } kind;
+    int64_t lo, hi;
+    bool round8;
+};
+const Knob KNOBS[] = {
+    {"grid", &sprs_ctx::grid, Knob::INT, 8, MAX_GRID, true},
+    {"spmv_grid", &sprs_ctx::spmv_grid, Knob::AUTO_OR_INT, 8, MAX_GRID / 2, true},
+    {"xcd_chunk", &sprs_ctx::xcd_chunk, Knob::TRI, 0, 0, false},
+    {"spmv_dict", &sprs_ctx::spmv_dict, Knob::INT, -1, 2, false},
+    {"spmv_wide", &sprs_ctx::spmv_wide, Knob::TRI, 0, 0, false},
+    {"spmv_uniform", &sprs_ctx::spmv_uniform, Knob::TRI, 0, 0, false},
+    {"spmv_period", &sprs_ctx::spmv_period, Knob::TRI, 0, 0, false},
+    {"spmv_triple", &sprs_ctx::spmv_triple, Knob::TRI, 0, 0, false},
+    {"spmv_seam", &sprs_ctx::spmv_seam, Knob::TRI, 0, 0, false},
+    {"spmv_tile", &sprs_ctx::spmv_tile, Knob::TRI, 0, 0, false},
+    {"spmv_chain", &sprs_ctx::spmv_chain, Knob::TRI, 0, 0, false},
+    {"spmv_fuse", &sprs_ctx::spmv_fuse, Knob::TRI, 0, 0, false},
+    {"bicg_k5", &sprs_ctx::bicg_k5, Knob::AUTO_OR_INT, 0, 2, false},
+    {"p2p_allreduce", &sprs_ctx::p2p_allreduce, Knob::TRI, 0, 0, false},
+    {"p2p_timeout_ms", &sprs_ctx::p2p_timeout_ms, Knob::AT_LEAST, 1, 0, false},
+    {"ew_chunk", &sprs_ctx::ew_chunk, Knob::TRI, 0, 0, false},
+    {"stream_nt", &sprs_ctx::stream_nt, Knob::TRI, 0, 0, false},
+    {"spmv_eqrows", &sprs_ctx::spmv_eqrows, Knob::TRI, 0, 0, false},
+    {"spmv_wideload", &sprs_ctx::spmv_wideload, Knob::TRI, 0, 0, false},
+    {"halo_overlap", &sprs_ctx::halo_overlap, Knob::BOOL, 0, 0, false},
+    {"gs_graph", &sprs_ctx::gs_graph, Knob::BOOL, 0, 0, false},
+    {"poll", &sprs_ctx::poll, Knob::INT, 1, INT64_MAX, false},
+    {"num_cu", &sprs_ctx::num_cu, Knob::GET_ONLY, 0, 0, false},
+    {"device", &sprs_ctx::device, Knob::GET_ONLY, 0, 0, false},
+};
+const Knob *find_knob(const char *key) {
+    for (const Knob &k : KNOBS)
+        if (strcmp(k.name, key) == 0) return &k;
+    return nullptr;
+}
+}  // namespace
+
 extern "C" {
 
 // ------------------------------------------------------------------------------ context
@@ -103,60 +148,27 @@ const char *sprs_last_error(const sprs_ctx *c) { return c ? c->err : "null conte
 
 int sprs_ctx_set(sprs_ctx *c, const char *key, int64_t value) {
     if (!c || !key) return SPRS_INVALID_ARGUMENT;
-    std::string k(key);
-    if (k == "grid") { if (value < 8 || value > MAX_GRID) return SPRS_INVALID_ARGUMENT; c->grid = (int)(value & ~7); }
-    else if (k == "spmv_grid") { if (value > MAX_GRID / 2 || (value >= 0 && value < 8)) return SPRS_INVALID_ARGUMENT; c->spmv_grid = value < 0 ? -1 : (int)(value & ~7); }
-    else if (k == "xcd_chunk") c->xcd_chunk = value < 0 ? -1 : (value ? 1 : 0);
-    else if (k == "spmv_dict") { if (value < -1 || value > 2) return SPRS_INVALID_ARGUMENT; c->spmv_dict = (int)value; }
-    else if (k == "spmv_wide") c->spmv_wide = value < 0 ? -1 : (value ? 1 : 0);
-    else if (k == "spmv_uniform") c->spmv_uniform = value < 0 ? -1 : (value ? 1 : 0);
-    else if (k == "spmv_period") c->spmv_period = value < 0 ? -1 : (value ? 1 : 0);
-    else if (k == "spmv_triple") c->spmv_triple = value < 0 ? -1 : (value ? 1 : 0);
-    else if (k == "spmv_seam") c->spmv_seam = value < 0 ? -1 : (value ? 1 : 0);
-    else if (k == "spmv_tile") c->spmv_tile = value < 0 ? -1 : (value ? 1 : 0);
-    else if (k == "spmv_chain") c->spmv_chain = value < 0 ? -1 : (value ? 1 : 0);
-    else if (k == "spmv_fuse") c->spmv_fuse = value < 0 ? -1 : (value ? 1 : 0);
-    else if (k == "bicg_k5") { if (value > 2) return SPRS_INVALID_ARGUMENT; c->bicg_k5 = value < 0 ? -1 : (int)value; }
-    else if (k == "p2p_allreduce") c->p2p_allreduce = value < 0 ? -1 : (value ? 1 : 0);
-    else if (k == "p2p_timeout_ms") c->p2p_timeout_ms = value < 1 ? 1 : value;
-    else if (k == "ew_chunk") c->ew_chunk = value < 0 ? -1 : (value ? 1 : 0);
-    else if (k == "stream_nt") c->stream_nt = value < 0 ? -1 : (value ? 1 : 0);
-    else if (k == "spmv_eqrows") c->spmv_eqrows = value < 0 ? -1 : (value ? 1 : 0);
-    else if (k == "spmv_wideload") c->spmv_wideload = value < 0 ? -1 : (value ? 1 : 0);
-    else if (k == "halo_overlap") c->halo_overlap = value ? 1 : 0;
-    else if (k == "gs_graph") c->gs_graph = value ? 1 : 0;
-    else if (k == "poll") { if (value < 1) return SPRS_INVALID_ARGUMENT; c->poll = (int)value; }
-    else return SPRS_INVALID_ARGUMENT;
+    const Knob *k = find_knob(key);
+    if (!k) return SPRS_INVALID_ARGUMENT;
+    switch (k->kind) {
+        case Knob::GET_ONLY: return SPRS_INVALID_ARGUMENT;
+        case Knob::TRI: value = value < 0 ? -1 : (value ? 1 : 0); break;
+        case Knob::BOOL: value = value ? 1 : 0; break;
+        case Knob::AT_LEAST: value = std::max(value, k->lo); break;
+        case Knob::AUTO_OR_INT:
+        case Knob::INT:
+            if (k->kind == Knob::AUTO_OR_INT && value < 0) { value = -1; break; }
+            if (value < k->lo || value > k->hi) return SPRS_INVALID_ARGUMENT;
+            if (k->round8) value &= ~(int64_t)7;
+            break;
+    }
+    c->*(k->field) = (int)value;
     return SPRS_OK;
 }
 int64_t sprs_ctx_get(const sprs_ctx *c, const char *key) {
     if (!c || !key) return -1;
-    std::string k(key);
-    if (k == "grid") return c->grid;
-    if (k == "xcd_chunk") return c->xcd_chunk;
-    if (k == "spmv_grid") return c->spmv_grid;
-    if (k == "spmv_dict") return c->spmv_dict;
-    if (k == "spmv_wide") return c->spmv_wide;
-    if (k == "spmv_uniform") return c->spmv_uniform;
-    if (k == "spmv_period") return c->spmv_period;
-    if (k == "spmv_triple") return c->spmv_triple;
-    if (k == "spmv_seam") return c->spmv_seam;
-    if (k == "spmv_tile") return c->spmv_tile;
-    if (k == "spmv_chain") return c->spmv_chain;
-    if (k == "spmv_fuse") return c->spmv_fuse;
-    if (k == "bicg_k5") return c->bicg_k5;
-    if (k == "p2p_allreduce") return c->p2p_allreduce;
-    if (k == "p2p_timeout_ms") return c->p2p_timeout_ms;
-    if (k == "ew_chunk") return c->ew_chunk;
-    if (k == "stream_nt") return c->stream_nt;
-    if (k == "spmv_eqrows") return c->spmv_eqrows;
-    if (k == "spmv_wideload") return c->spmv_wideload;
-    if (k == "halo_overlap") return c->halo_overlap;
-    if (k == "gs_graph") return c->gs_graph;
-    if (k == "poll") return c->poll;
-    if (k == "num_cu") return c->num_cu;
-    if (k == "device") return c->device;
-    return -1;
+    const Knob *k = find_knob(key);
+    return k ? c->*(k->field) : -1;
 }
 
 int sprs_malloc(sprs_ctx *c, size_t bytes, void **dev_out) {
@@ -360,10 +372,7 @@ int mul_mat_dev(const sprs_csr *A, const T *dx, T *dy, size_t k) {
     if (k < 1 || k > 8) return SPRS_INVALID_ARGUMENT;
     sprs_ctx *c = A->ctx;
     CtxLock lock(c);
-    if (A->dist) {
-        snprintf(c->err, sizeof(c->err), "sprs_mul_mat: distributed operators are not supported (single GPU only)");
-        return SPRS_INVALID_ARGUMENT;
-    }
+    SPRS_TRY(single_gpu_only(A, "sprs_mul_mat"));
     SPRS_HIP_TRY(c, hipSetDevice(c->device));
     return launch_spmm<T>(A, dx, dy, (int)k, (int)k, 0, nullptr, nullptr, nullptr);
 }
@@ -376,10 +385,7 @@ int mul_mat_host(const sprs_csr *A, const T *x, size_t x_len, T *y, size_t y_len
     if ((size_t)A->ncols * k != x_len || (size_t)A->nrows * k != y_len) return SPRS_DIM_MISMATCH;
     sprs_ctx *c = A->ctx;
     CtxLock lock(c);
-    if (A->dist) {
-        snprintf(c->err, sizeof(c->err), "sprs_mul_mat: distributed operators are not supported (single GPU only)");
-        return SPRS_INVALID_ARGUMENT;
-    }
+    SPRS_TRY(single_gpu_only(A, "sprs_mul_mat"));
     SPRS_HIP_TRY(c, hipSetDevice(c->device));
     T *dx = nullptr, *dy = nullptr;
     struct Free { T *&a, *&b; ~Free() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); } } guard{dx, dy};   // every return path
@@ -471,19 +477,21 @@ int with_solver(int dtype, void *impl, F &&f) {
     return SPRS_INVALID_ARGUMENT;
 }
 
+// The one way a solver handle of any kind comes to be.  This holds what belongs to the ABI: the null checks, *out zeroed, the
+// handle's scalar type against T, the context lock (the allocations go to the context's stream; recursive, so Lsmr / Svds::create
+// -> sprs_csr_adjoint take it again), an S<T> behind an H, and the unwind.  mk(s) is S<T>::create, which holds every check of the
+// operator and of the creation parameters (krylov.hpp).  entry: "sprs_<name>", as the refusals' texts begin.
 template <class T, class H, template <class> class S, class Mk>
-int solver_create(const sprs_csr *A, size_t size, H **out, Mk mk) {
+int solver_create(const char *entry, const sprs_csr *A, H **out, Mk mk) {
+    if (out) *out = nullptr;
     if (!A || !out) return SPRS_INVALID_ARGUMENT;
-    *out = nullptr;
-    if (A->dtype != dtype_of<T>::value) return SPRS_INVALID_ARGUMENT;
-    // the solvers multiply size-vectors by A in place: the reference leaves a mismatch to UB
-    // (mul_vec_unchecked); we refuse it here rather than index out of bounds on the GPU
-    if ((int64_t)size != A->nrows || (A->dist ? A->ncols < A->nrows : (int64_t)size != A->ncols)) return SPRS_DIM_MISMATCH;
+    if (A->dtype != dtype_of<T>::value) return refuse(A->ctx, entry, "the operator holds another scalar type");
+    CtxLock lock(A->ctx);
     H *h = new H();
     h->dtype = dtype_of<T>::value;
     auto *s = new S<T>();
     h->impl = s;
-    int st = mk(s);
+    const int st = mk(s);
     if (st != SPRS_OK) { s->destroy(); delete s; delete h; return st; }
     *out = h;
     return SPRS_OK;
@@ -497,9 +505,30 @@ int solver_destroy(sprs_solver_handle *h) {
     return SPRS_OK;
 }
 
-// One solve.  Host slices (host = true), and device vectors that are not 16-byte aligned, go through the solver's aligned
-// rhs_buf / x_buf; other device vectors are used in place.  P: what SolverT::solve_dev takes — a sprs_diag (or null), or an
-// ILU(0) or AMG handle's AppliedPrec view (sprs_ilu0_cg_*, sprs_amg_bicgstab_*, ...).
+// Where one solve's vectors live.  Host slices (host = true), and device vectors that are not 16-byte aligned, go through the
+// solver's aligned rhs_buf / x_buf of rcap / xcap entries; other device vectors are used in place.  run(rhs, x) is
+// SolverT::solve_dev on the pointers chosen.  The callers have checked rl and xl: nothing is copied on a mismatch.
+template <class T, class SolverT, class Run>
+int staged_solve(SolverT *s, bool host, const T *rhs, size_t rl, size_t rcap, T *x, size_t xl, size_t xcap, Run run) {
+    sprs_ctx *c = s->ctx;
+    CtxLock lock(c);   // one solve at a time per context (its stream, its scratch)
+    if (!host && ((reinterpret_cast<uintptr_t>(rhs) | reinterpret_cast<uintptr_t>(x)) & 15) == 0) return run(rhs, x);
+    const hipMemcpyKind in = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, out = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    SPRS_HIP_TRY(c, hipSetDevice(c->device));
+    if (!s->rhs_buf) SPRS_HIP_TRY(c, hipMalloc((void **)&s->rhs_buf, sizeof(T) * rcap));
+    if (!s->x_buf) SPRS_HIP_TRY(c, hipMalloc((void **)&s->x_buf, sizeof(T) * xcap));
+    SPRS_HIP_TRY(c, hipMemcpyAsync(s->rhs_buf, rhs, sizeof(T) * rl, in, c->stream));
+    SPRS_HIP_TRY(c, hipMemcpyAsync(s->x_buf, x, sizeof(T) * xl, in, c->stream));
+    const int st = run((const T *)s->rhs_buf, s->x_buf);
+    if (st >= SPRS_ERR_HIP) return st;
+    // x is in/out in the reference and is left modified on Err as well: it is copied back on a solver event too
+    SPRS_HIP_TRY(c, hipMemcpyAsync(x, s->x_buf, sizeof(T) * xl, out, c->stream));
+    SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return st;
+}
+
+// One solve of a square system.  P: what SolverT::solve_dev takes — a sprs_diag (or null), or an ILU(0), AMG or FSAI handle's
+// AppliedPrec view (sprs_ilu0_cg_*, sprs_amg_bicgstab_*, ...).
 template <class T, class SolverT, class P>
 int solve(SolverT *s, bool host, const P &prec, const T *rhs, size_t rl, T *x, size_t xl, size_t max_iter, Real<T> tol,
           size_t *its, Real<T> *res) {
@@ -509,26 +538,24 @@ int solve(SolverT *s, bool host, const P &prec, const T *rhs, size_t rl, T *x, s
     if (rl != s->n) return SPRS_INCOMPATIBLE_RHS_SIZE;
     if (xl != s->n) return SPRS_INCOMPATIBLE_X_SIZE;
     if (M.is_applied) SPRS_TRY(M.applied.check(s->A, s->n));
-    sprs_ctx *c = s->ctx;
-    CtxLock lock(c);   // one solve at a time per context (its stream, its scratch)
-    if (!host && ((reinterpret_cast<uintptr_t>(rhs) | reinterpret_cast<uintptr_t>(x)) & 15) == 0)
-        return s->solve_dev(prec, rhs, rl, x, xl, max_iter, tol, its, res);
-    const hipMemcpyKind in = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, out = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    SPRS_HIP_TRY(c, hipSetDevice(c->device));
-    if (!s->rhs_buf) SPRS_HIP_TRY(c, hipMalloc((void **)&s->rhs_buf, sizeof(T) * s->stride));
-    if (!s->x_buf) SPRS_HIP_TRY(c, hipMalloc((void **)&s->x_buf, sizeof(T) * s->stride));
-    SPRS_HIP_TRY(c, hipMemcpyAsync(s->rhs_buf, rhs, sizeof(T) * rl, in, c->stream));
-    SPRS_HIP_TRY(c, hipMemcpyAsync(s->x_buf, x, sizeof(T) * xl, in, c->stream));
-    int st = s->solve_dev(prec, s->rhs_buf, rl, s->x_buf, xl, max_iter, tol, its, res);
-    if (st >= SPRS_ERR_HIP) return st;
-    // x is in/out in the reference and is left modified on Err as well
-    SPRS_HIP_TRY(c, hipMemcpyAsync(x, s->x_buf, sizeof(T) * xl, out, c->stream));
-    SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return st;
+    return staged_solve<T>(s, host, rhs, rl, s->stride, x, xl, s->stride,
+                           [&](const T *b, T *y) { return s->solve_dev(prec, b, rl, y, xl, max_iter, tol, its, res); });
+}
+
+// One LSMR solve: rhs of nrows, x of ncols entries.
+template <class T>
+int lsmr_solve(Lsmr<T> *s, bool host, const T *rhs, size_t rl, T *x, size_t xl, Real<T> damp, size_t max_iter, Real<T> tol, size_t *its,
+               Real<T> *res, Real<T> *ares) {
+    if (!s || !rhs || !x) return SPRS_INVALID_ARGUMENT;
+    if (rl != s->m || xl != s->nc) return SPRS_DIM_MISMATCH;
+    if (!(damp >= (Real<T>)0)) return SPRS_INVALID_ARGUMENT;
+    return staged_solve<T>(s, host, rhs, rl, s->stride, x, xl, s->stride_n,
+                           [&](const T *b, T *y) { return s->solve_dev(b, rl, y, xl, damp, max_iter, tol, its, res, ares); });
 }
 
 // One batched CG solve (n x k row-major blocks).  Host slices go through the solver's staging buffers; device blocks are
 // read and written in place (the solver copies them into its padded work blocks, so no alignment is asked of them).
+// Apart from staged_solve: no alignment test, one capacity of n kmax + 1, and argument statuses that skip the copy-back too.
 template <class T>
 int solve_many(CgMany<T> *s, bool host, const sprs_diag *P, const T *rhs, size_t rl, T *x, size_t xl, size_t k, size_t max_iter,
                Real<T> tol, size_t *its, Real<T> *res, int *status) {
@@ -561,81 +588,9 @@ int solve_shift(CgShift<T> *s, bool host, const Real<T> *shifts, size_t m, const
     return s->solve(shifts, m, rhs, rl, host, x, xl, max_iter, tol, its, res, status);
 }
 
-// LSMR's handle: A of any shape, its adjoint handle borrowed (checked here) or built by the solver
-template <class T>
-int lsmr_create(const sprs_csr *A, const sprs_csr *AH, sprs_lsmr **out) {
-    if (!A || !out) return SPRS_INVALID_ARGUMENT;
-    *out = nullptr;
-    if (A->dtype != dtype_of<T>::value) return SPRS_INVALID_ARGUMENT;
-    if (A->dist || (AH && AH->dist)) {
-        snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_lsmr: distributed operators are not supported (single GPU only)");
-        return SPRS_INVALID_ARGUMENT;
-    }
-    if (AH && (AH->dtype != A->dtype || AH->ctx != A->ctx)) return SPRS_INVALID_ARGUMENT;
-    if (AH && (AH->nrows != A->ncols || AH->ncols != A->nrows)) return SPRS_DIM_MISMATCH;
-    CtxLock lock(A->ctx);
-    sprs_lsmr *h = new sprs_lsmr();
-    h->dtype = dtype_of<T>::value;
-    auto *s = new Lsmr<T>();
-    h->impl = s;
-    const int st = s->create(A, AH);
-    if (st != SPRS_OK) { s->destroy(); delete s; delete h; return st; }
-    *out = h;
-    return SPRS_OK;
-}
-
-// One LSMR solve: rhs of nrows, x of ncols entries.  Host slices, and device vectors that are not 16-byte aligned, go through the
-// solver's staging buffers.
-template <class T>
-int lsmr_solve(Lsmr<T> *s, bool host, const T *rhs, size_t rl, T *x, size_t xl, Real<T> damp, size_t max_iter, Real<T> tol, size_t *its,
-               Real<T> *res, Real<T> *ares) {
-    if (!s || !rhs || !x) return SPRS_INVALID_ARGUMENT;
-    if (rl != s->m || xl != s->nc) return SPRS_DIM_MISMATCH;                 // nothing is copied on a mismatch
-    if (!(damp >= (Real<T>)0)) return SPRS_INVALID_ARGUMENT;
-    sprs_ctx *c = s->ctx;
-    CtxLock lock(c);
-    if (!host && ((reinterpret_cast<uintptr_t>(rhs) | reinterpret_cast<uintptr_t>(x)) & 15) == 0)
-        return s->solve_dev(rhs, rl, x, xl, damp, max_iter, tol, its, res, ares);
-    const hipMemcpyKind in = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, out = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    SPRS_HIP_TRY(c, hipSetDevice(c->device));
-    if (!s->rhs_buf) SPRS_HIP_TRY(c, hipMalloc((void **)&s->rhs_buf, sizeof(T) * s->stride));
-    if (!s->x_buf) SPRS_HIP_TRY(c, hipMalloc((void **)&s->x_buf, sizeof(T) * s->stride_n));
-    SPRS_HIP_TRY(c, hipMemcpyAsync(s->rhs_buf, rhs, sizeof(T) * rl, in, c->stream));
-    SPRS_HIP_TRY(c, hipMemcpyAsync(s->x_buf, x, sizeof(T) * xl, in, c->stream));
-    const int st = s->solve_dev(s->rhs_buf, rl, s->x_buf, xl, damp, max_iter, tol, its, res, ares);
-    if (st >= SPRS_ERR_HIP) return st;
-    SPRS_HIP_TRY(c, hipMemcpyAsync(x, s->x_buf, sizeof(T) * xl, out, c->stream));   // x is in/out and is left modified on an error too
-    SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return st;
-}
-
-// Eigsh<T> behind a sprs_eigsh: a square single-GPU A, ncv = 0 means min(32, n)
-template <class T>
-int eigsh_create(const sprs_csr *A, size_t size, size_t ncv, sprs_eigsh **out) {
-    if (!A || !out) return SPRS_INVALID_ARGUMENT;
-    *out = nullptr;
-    if (A->dtype != dtype_of<T>::value) return SPRS_INVALID_ARGUMENT;
-    if (A->dist) {
-        snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_eigsh: distributed operators are not supported (single GPU only)");
-        return SPRS_INVALID_ARGUMENT;
-    }
-    if (A->nrows != A->ncols) return SPRS_NOT_SQUARE;
-    if ((int64_t)size != A->nrows) return SPRS_DIM_MISMATCH;
-    if (ncv == 0) ncv = std::min<size_t>(32, size);
-    if (ncv < 3 || ncv > std::min<size_t>(SPRS_EIGSH_MAX_NCV, size)) {
-        snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_eigsh: ncv = %zu is outside 3 .. min(%d, n = %zu)", ncv, SPRS_EIGSH_MAX_NCV, size);
-        return SPRS_INVALID_ARGUMENT;
-    }
-    CtxLock lock(A->ctx);
-    sprs_eigsh *h = new sprs_eigsh();
-    h->dtype = dtype_of<T>::value;
-    auto *s = new Eigsh<T>();
-    h->impl = s;
-    const int st = s->create(A, size, ncv);
-    if (st != SPRS_OK) { s->destroy(); delete s; delete h; return st; }
-    *out = h;
-    return SPRS_OK;
-}
+// a caller's out-pointer, or a slot of the entry point's own where it is null
+template <class V>
+V *or_dummy(V *p, V *slot) { return p ? p : slot; }
 
 // One eigensolve.  v0 is copied into the basis and the vectors are written by the rotation kernel (device) or copied out of
 // the basis (host), so no alignment is asked of either.
@@ -647,38 +602,9 @@ int eigsh_solve(Eigsh<T> *s, bool host, size_t k, int which, const T *v0, size_t
         return SPRS_INVALID_ARGUMENT;
     if (v0_len != s->n) return SPRS_INCOMPATIBLE_RHS_SIZE;
     if (vecs && vecs_len != k * s->n) return SPRS_INCOMPATIBLE_X_SIZE;
-    size_t dummy[3];
+    size_t d[3];
     CtxLock lock(s->ctx);
-    return s->solve(k, which, v0, host, max_restarts, tol, vals, vecs, host, res, nconv ? nconv : dummy, restarts ? restarts : dummy + 1,
-                    matvecs ? matvecs : dummy + 2);
-}
-
-// Expm<T> behind a sprs_expm: a square single-GPU A, ncv = 0 means min(30, n)
-template <class T>
-int expm_create(const sprs_csr *A, size_t size, size_t ncv, sprs_expm **out) {
-    if (!A || !out) return SPRS_INVALID_ARGUMENT;
-    *out = nullptr;
-    if (A->dtype != dtype_of<T>::value) return SPRS_INVALID_ARGUMENT;
-    if (A->dist) {
-        snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_expm: distributed operators are not supported (single GPU only)");
-        return SPRS_INVALID_ARGUMENT;
-    }
-    if (A->nrows != A->ncols) return SPRS_NOT_SQUARE;
-    if ((int64_t)size != A->nrows) return SPRS_DIM_MISMATCH;
-    if (ncv == 0) ncv = std::min<size_t>(30, size);
-    if (ncv < 3 || ncv > std::min<size_t>(SPRS_EXPM_MAX_NCV, size)) {
-        snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_expm: ncv = %zu is outside 3 .. min(%d, n = %zu)", ncv, SPRS_EXPM_MAX_NCV, size);
-        return SPRS_INVALID_ARGUMENT;
-    }
-    CtxLock lock(A->ctx);
-    sprs_expm *h = new sprs_expm();
-    h->dtype = dtype_of<T>::value;
-    auto *s = new Expm<T>();
-    h->impl = s;
-    const int st = s->create(A, size, ncv);
-    if (st != SPRS_OK) { s->destroy(); delete s; delete h; return st; }
-    *out = h;
-    return SPRS_OK;
+    return s->solve(k, which, v0, host, max_restarts, tol, vals, vecs, host, res, or_dummy(nconv, d), or_dummy(restarts, d + 1), or_dummy(matvecs, d + 2));
 }
 
 // One propagation.  v is copied into the basis and w is written by the combination kernel (an aligned device w) or copied out of
@@ -691,42 +617,11 @@ int expm_apply(Expm<T> *s, bool host, Real<T> t, const T *v, size_t v_len, Real<
         return SPRS_INVALID_ARGUMENT;
     if (v_len != s->n) return SPRS_INCOMPATIBLE_RHS_SIZE;
     if (w_len != s->n) return SPRS_INCOMPATIBLE_X_SIZE;
-    size_t dummy[3];
-    Real<T> rdummy[3];
+    size_t d[3];
+    Real<T> rd[3];
     CtxLock lock(s->ctx);
-    return s->apply(t, v, host, tol, max_steps, tau0, w, err ? err : rdummy, hump ? hump : rdummy + 1, t_done ? t_done : rdummy + 2,
-                    steps ? steps : dummy, rejects ? rejects : dummy + 1, matvecs ? matvecs : dummy + 2);
-}
-
-// Svds<T> behind a sprs_svds: a single-GPU A of any shape, its adjoint handle borrowed (checked here) or built by the solver,
-// ncv = 0 means min(32, min(rows, cols))
-template <class T>
-int svds_create(const sprs_csr *A, const sprs_csr *AH, size_t ncv, sprs_svds **out) {
-    if (!A || !out) return SPRS_INVALID_ARGUMENT;
-    *out = nullptr;
-    auto refuse = [&](const char *why) {
-        snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_svds: %s", why);
-        return SPRS_INVALID_ARGUMENT;
-    };
-    if (A->dtype != dtype_of<T>::value) return refuse("the operator holds another scalar type");
-    if (A->dist || (AH && AH->dist)) return refuse("distributed operators are not supported (single GPU only)");
-    if (AH && (AH->dtype != A->dtype || AH->ctx != A->ctx)) return refuse("the adjoint handle holds another scalar type or context");
-    if (AH && (AH->nrows != A->ncols || AH->ncols != A->nrows)) return refuse("the adjoint handle is not cols x rows");
-    const size_t small = (size_t)std::min(A->nrows, A->ncols);
-    if (ncv == 0) ncv = std::min<size_t>(32, small);
-    if (ncv < 3 || ncv > std::min<size_t>(SPRS_SVDS_MAX_NCV, small)) {
-        snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_svds: ncv = %zu is outside 3 .. min(%d, min(rows, cols) = %zu)", ncv, SPRS_SVDS_MAX_NCV, small);
-        return SPRS_INVALID_ARGUMENT;
-    }
-    CtxLock lock(A->ctx);
-    sprs_svds *h = new sprs_svds();
-    h->dtype = dtype_of<T>::value;
-    auto *s = new Svds<T>();
-    h->impl = s;
-    const int st = s->create(A, AH, ncv);
-    if (st != SPRS_OK) { s->destroy(); delete s; delete h; return st; }
-    *out = h;
-    return SPRS_OK;
+    return s->apply(t, v, host, tol, max_steps, tau0, w, or_dummy(err, rd), or_dummy(hump, rd + 1), or_dummy(t_done, rd + 2), or_dummy(steps, d),
+                    or_dummy(rejects, d + 1), or_dummy(matvecs, d + 2));
 }
 
 // One truncated SVD.  v0 is copied into the basis and the vectors are written by the rotation kernel (device) or copied out of
@@ -739,41 +634,9 @@ int svds_solve(Svds<T> *s, bool host, size_t k, int which, const T *v0, size_t v
         return SPRS_INVALID_ARGUMENT;
     if (v0_len != s->lenN) return SPRS_INCOMPATIBLE_RHS_SIZE;
     if (u && (u_len != k * s->rows || v_len != k * s->cols)) return SPRS_INCOMPATIBLE_X_SIZE;
-    size_t dummy[3];
+    size_t d[3];
     CtxLock lock(s->ctx);
-    return s->solve(k, which, v0, host, max_restarts, tol, vals, u, v, res, nconv ? nconv : dummy, restarts ? restarts : dummy + 1,
-                    matvecs ? matvecs : dummy + 2);
-}
-
-// Lobpcg<T> behind a sprs_lobpcg: a square single-GPU A, block = 0 means min(8, n / 6)
-template <class T>
-int lobpcg_create(const sprs_csr *A, size_t size, size_t block, sprs_lobpcg **out) {
-    if (!A || !out) return SPRS_INVALID_ARGUMENT;
-    *out = nullptr;
-    if (A->dtype != dtype_of<T>::value) {
-        snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_lobpcg: the operator holds another scalar type");
-        return SPRS_INVALID_ARGUMENT;
-    }
-    if (A->dist) {
-        snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_lobpcg: distributed operators are not supported (single GPU only)");
-        return SPRS_INVALID_ARGUMENT;
-    }
-    if (A->nrows != A->ncols) return SPRS_NOT_SQUARE;
-    if ((int64_t)size != A->nrows) return SPRS_DIM_MISMATCH;
-    if (block == 0) block = std::min<size_t>(SPRS_LOBPCG_MAX_BLOCK, size / 6);
-    if (block < 1 || block > SPRS_LOBPCG_MAX_BLOCK || 6 * block > size) {
-        snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_lobpcg: block = %zu is outside 1 .. min(%d, n / 6 = %zu)", block, SPRS_LOBPCG_MAX_BLOCK, size / 6);
-        return SPRS_INVALID_ARGUMENT;
-    }
-    CtxLock lock(A->ctx);
-    sprs_lobpcg *h = new sprs_lobpcg();
-    h->dtype = dtype_of<T>::value;
-    auto *s = new Lobpcg<T>();
-    h->impl = s;
-    const int st = s->create(A, size, block);
-    if (st != SPRS_OK) { s->destroy(); delete s; delete h; return st; }
-    *out = h;
-    return SPRS_OK;
+    return s->solve(k, which, v0, host, max_restarts, tol, vals, u, v, res, or_dummy(nconv, d), or_dummy(restarts, d + 1), or_dummy(matvecs, d + 2));
 }
 
 // The default start block: column c holds gen_uniform's values (internal.hpp) of stream 100 + 2 c (the imaginary parts: stream
@@ -799,13 +662,13 @@ int lobpcg_solve(Lobpcg<T> *s, bool host, const P &prec, size_t k, int which, co
     if (k < 1 || k > (size_t)s->b || (which != SPRS_EIGSH_LARGEST && which != SPRS_EIGSH_SMALLEST) || max_iter < 1) return SPRS_INVALID_ARGUMENT;
     if (X0 && x0_len != (size_t)s->b * s->n) return SPRS_INCOMPATIBLE_RHS_SIZE;
     if (vecs && vecs_len != k * s->n) return SPRS_INCOMPATIBLE_X_SIZE;
-    size_t dummy[4];
+    size_t d[4];
     std::vector<T> def;
     bool x0_host = host;
     if (!X0) { lobpcg_default_x0<T>(s->n, s->b, def); X0 = def.data(); x0_host = true; }
     CtxLock lock(s->ctx);
-    return s->solve_dev(M, k, which, X0, x0_host, max_iter, tol, vals, vecs, host, res, nconv ? nconv : dummy, iters ? iters : dummy + 1,
-                        restarts ? restarts : dummy + 2, matvecs ? matvecs : dummy + 3);
+    return s->solve_dev(M, k, which, X0, x0_host, max_iter, tol, vals, vecs, host, res, or_dummy(nconv, d), or_dummy(iters, d + 1),
+                        or_dummy(restarts, d + 2), or_dummy(matvecs, d + 3));
 }
 
 // the S<T> behind a handle, or null where the handle holds another scalar type
@@ -987,7 +850,7 @@ int sprs_expm_destroy(sprs_expm *S) { return solver_destroy<Expm>(S); }
     }
 #define SPRS_SOLVER_API(X, T, CT, R, NAME, S, CREATE)                                                                  \
     int sprs_##NAME##_create_##X(const sprs_csr *A, size_t n, sprs_##NAME **out) {                                     \
-        SPRS_G(return (solver_create<T, sprs_##NAME, S>(A, n, out, [&](auto *s) { return s->create CREATE; }));)       \
+        SPRS_G(return (solver_create<T, sprs_##NAME, S>("sprs_" #NAME, A, out, [&](auto *s) { return s->create CREATE; }));) \
     }                                                                                                                  \
     SPRS_SOLVER_SOLVES(X, T, CT, R, NAME, S)
 
@@ -1026,8 +889,7 @@ int sprs_expm_destroy(sprs_expm *S) { return solver_destroy<Expm>(S); }
     int sprs_mul_mat_dev_##X(const sprs_csr *A, const CT *x, CT *y, size_t k) { return mul_mat_dev<T>(A, (const T *)x, (T *)y, k); } \
     /* batched CG: k = the most columns a solve may carry */                                                           \
     int sprs_cgmany_create_##X(const sprs_csr *A, size_t n, size_t k, sprs_cg_many **out) {                           \
-        SPRS_G(if (k < 1 || k > 8) { if (out) *out = nullptr; return SPRS_INVALID_ARGUMENT; }                          \
-               return (solver_create<T, sprs_cg_many, CgMany>(A, n, out, [&](auto *s) { return s->create(A, n, k); }));) \
+        SPRS_G(return (solver_create<T, sprs_cg_many, CgMany>("sprs_cgmany", A, out, [&](auto *s) { return s->create(A, n, k); }));) \
     }                                                                                                                  \
     int sprs_cgmany_solve_##X(sprs_cg_many *h, const sprs_diag *P, const CT *rhs, size_t rl, CT *x, size_t xl, size_t k, size_t mi, R tol, \
                                size_t *its, R *res, int *status) {                                                     \
@@ -1039,7 +901,7 @@ int sprs_expm_destroy(sprs_expm *S) { return solver_destroy<Expm>(S); }
     }                                                                                                                  \
     /* multi-shift CG: mmax = the most shifts a solve may carry; x = m contiguous vectors of n, output only */          \
     int sprs_cgshift_create_##X(const sprs_csr *A, size_t n, size_t mmax, sprs_cg_shift **out) {                       \
-        SPRS_G(return (solver_create<T, sprs_cg_shift, CgShift>(A, n, out, [&](auto *s) { return s->create(A, n, mmax); }));) \
+        SPRS_G(return (solver_create<T, sprs_cg_shift, CgShift>("sprs_cgshift", A, out, [&](auto *s) { return s->create(A, n, mmax); }));) \
     }                                                                                                                  \
     int sprs_cgshift_solve_##X(sprs_cg_shift *h, const R *shifts, size_t m, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, \
                                size_t *its, R *res, int *status) {                                                     \
@@ -1050,7 +912,9 @@ int sprs_expm_destroy(sprs_expm *S) { return solver_destroy<Expm>(S); }
         SPRS_G(return solve_shift<T>(impl_of<CgShift, T>(h), false, shifts, m, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res, status);) \
     }                                                                                                                  \
     /* LSMR: A of any shape and its adjoint handle (NULL: built and owned by the solver) */                            \
-    int sprs_lsmr_create_##X(const sprs_csr *A, const sprs_csr *AH, sprs_lsmr **out) { SPRS_G(return lsmr_create<T>(A, AH, out);) } \
+    int sprs_lsmr_create_##X(const sprs_csr *A, const sprs_csr *AH, sprs_lsmr **out) {                                 \
+        SPRS_G(return (solver_create<T, sprs_lsmr, Lsmr>("sprs_lsmr", A, out, [&](auto *s) { return s->create(A, AH); }));) \
+    }                                                                                                                  \
     int sprs_lsmr_solve_##X(sprs_lsmr *h, const CT *rhs, size_t rl, CT *x, size_t xl, R damp, size_t mi, R tol, size_t *its, R *res, R *ares) { \
         SPRS_G(return lsmr_solve<T>(impl_of<Lsmr, T>(h), true, (const T *)rhs, rl, (T *)x, xl, damp, mi, tol, its, res, ares);) \
     }                                                                                                                  \
@@ -1058,7 +922,9 @@ int sprs_expm_destroy(sprs_expm *S) { return solver_destroy<Expm>(S); }
         SPRS_G(return lsmr_solve<T>(impl_of<Lsmr, T>(h), false, (const T *)rhs, rl, (T *)x, xl, damp, mi, tol, its, res, ares);) \
     }                                                                                                                  \
     /* thick-restart Lanczos: ncv = the basis size (0 = min(32, n)) */                                                 \
-    int sprs_eigsh_create_##X(const sprs_csr *A, size_t n, size_t ncv, sprs_eigsh **out) { SPRS_G(return eigsh_create<T>(A, n, ncv, out);) } \
+    int sprs_eigsh_create_##X(const sprs_csr *A, size_t n, size_t ncv, sprs_eigsh **out) {                             \
+        SPRS_G(return (solver_create<T, sprs_eigsh, Eigsh>("sprs_eigsh", A, out, [&](auto *s) { return s->create(A, n, ncv); }));) \
+    }                                                                                                                  \
     int sprs_eigsh_solve_##X(sprs_eigsh *h, size_t k, int which, const CT *v0, size_t vl, size_t mr, R tol, R *vals, CT *vecs, size_t xl, \
                              R *res, size_t *nconv, size_t *restarts, size_t *matvecs) {                               \
         SPRS_G(return eigsh_solve<T>(impl_of<Eigsh, T>(h), true, k, which, (const T *)v0, vl, mr, tol, vals, (T *)vecs, xl, res, nconv, restarts, matvecs);) \
@@ -1068,7 +934,9 @@ int sprs_expm_destroy(sprs_expm *S) { return solver_destroy<Expm>(S); }
         SPRS_G(return eigsh_solve<T>(impl_of<Eigsh, T>(h), false, k, which, (const T *)v0, vl, mr, tol, vals, (T *)vecs, xl, res, nconv, restarts, matvecs);) \
     }                                                                                                                  \
     /* truncated SVD: A of any shape and its adjoint handle (NULL: built and owned), ncv = the basis size (0 = min(32, min(rows, cols))) */ \
-    int sprs_svds_create_##X(const sprs_csr *A, const sprs_csr *AH, size_t ncv, sprs_svds **out) { SPRS_G(return svds_create<T>(A, AH, ncv, out);) } \
+    int sprs_svds_create_##X(const sprs_csr *A, const sprs_csr *AH, size_t ncv, sprs_svds **out) {                     \
+        SPRS_G(return (solver_create<T, sprs_svds, Svds>("sprs_svds", A, out, [&](auto *s) { return s->create(A, AH, ncv); }));) \
+    }                                                                                                                  \
     int sprs_svds_solve_##X(sprs_svds *h, size_t k, int which, const CT *v0, size_t vl, size_t mr, R tol, R *vals, CT *u, size_t ul, CT *v, size_t vvl, \
                             R *res, size_t *nconv, size_t *restarts, size_t *matvecs) {                                \
         SPRS_G(return svds_solve<T>(impl_of<Svds, T>(h), true, k, which, (const T *)v0, vl, mr, tol, vals, (T *)u, ul, (T *)v, vvl, res, nconv, restarts, matvecs);) \
@@ -1078,7 +946,9 @@ int sprs_expm_destroy(sprs_expm *S) { return solver_destroy<Expm>(S); }
         SPRS_G(return svds_solve<T>(impl_of<Svds, T>(h), false, k, which, (const T *)v0, vl, mr, tol, vals, (T *)u, ul, (T *)v, vvl, res, nconv, restarts, matvecs);) \
     }                                                                                                                  \
     /* exp(tA) v: ncv = the basis size (0 = min(30, n)) */                                                             \
-    int sprs_expm_create_##X(const sprs_csr *A, size_t n, size_t ncv, sprs_expm **out) { SPRS_G(return expm_create<T>(A, n, ncv, out);) } \
+    int sprs_expm_create_##X(const sprs_csr *A, size_t n, size_t ncv, sprs_expm **out) {                               \
+        SPRS_G(return (solver_create<T, sprs_expm, Expm>("sprs_expm", A, out, [&](auto *s) { return s->create(A, n, ncv); }));) \
+    }                                                                                                                  \
     int sprs_expm_apply_##X(sprs_expm *h, R t, const CT *v, size_t vl, R tol, size_t ms, R tau0, CT *w, size_t wl, R *err, R *hump, R *t_done, \
                             size_t *steps, size_t *rejects, size_t *matvecs) {                                         \
         SPRS_G(return expm_apply<T>(impl_of<Expm, T>(h), true, t, (const T *)v, vl, tol, ms, tau0, (T *)w, wl, err, hump, t_done, steps, rejects, matvecs);) \
@@ -1088,7 +958,9 @@ int sprs_expm_destroy(sprs_expm *S) { return solver_destroy<Expm>(S); }
         SPRS_G(return expm_apply<T>(impl_of<Expm, T>(h), false, t, (const T *)v, vl, tol, ms, tau0, (T *)w, wl, err, hump, t_done, steps, rejects, matvecs);) \
     }                                                                                                                  \
     /* LOBPCG: block = the block size (0 = min(8, n / 6)) */                                                           \
-    int sprs_lobpcg_create_##X(const sprs_csr *A, size_t n, size_t block, sprs_lobpcg **out) { SPRS_G(return lobpcg_create<T>(A, n, block, out);) } \
+    int sprs_lobpcg_create_##X(const sprs_csr *A, size_t n, size_t block, sprs_lobpcg **out) {                         \
+        SPRS_G(return (solver_create<T, sprs_lobpcg, Lobpcg>("sprs_lobpcg", A, out, [&](auto *s) { return s->create(A, n, block); }));) \
+    }                                                                                                                  \
     int sprs_lobpcg_solve_##X(sprs_lobpcg *h, const sprs_diag *P, size_t k, int which, const CT *x0, size_t x0l, size_t mi, R tol, R *vals, CT *vecs, \
                               size_t xl, R *res, size_t *nconv, size_t *iters, size_t *restarts, size_t *matvecs) {    \
         SPRS_G(return lobpcg_solve<T>(impl_of<Lobpcg, T>(h), true, P, k, which, (const T *)x0, x0l, mi, tol, vals, (T *)vecs, xl, res, nconv, iters, restarts, matvecs);) \
@@ -1117,18 +989,17 @@ int sprs_expm_destroy(sprs_expm *S) { return solver_destroy<Expm>(S); }
     SPRS_SOLVER_API(X, T, CT, R, cg, Cg, (A, n))                                                                       \
     /* GMRES' create takes the restart length (0 = 30) */                                                              \
     int sprs_gmres_create_##X(const sprs_csr *A, size_t n, size_t restart, sprs_gmres **out) {                         \
-        SPRS_G(if (restart > SPRS_GMRES_MAX_RESTART) return SPRS_INVALID_ARGUMENT;                                     \
-               return (solver_create<T, sprs_gmres, Gmres>(A, n, out, [&](auto *s) { return s->create(A, n, restart); }));) \
+        SPRS_G(return (solver_create<T, sprs_gmres, Gmres>("sprs_gmres", A, out, [&](auto *s) { return s->create(A, n, restart); }));) \
     }                                                                                                                  \
     SPRS_SOLVER_SOLVES(X, T, CT, R, gmres, Gmres)                                                                      \
     /* IDR(s)'s create takes s (0 = 4); the class refuses s > SPRS_IDRS_MAX_S, s > n and a distributed operator with a text */ \
     int sprs_idrs_create_##X(const sprs_csr *A, size_t n, size_t s_dim, sprs_idrs **out) {                             \
-        SPRS_G(return (solver_create<T, sprs_idrs, Idrs>(A, n, out, [&](auto *s) { return s->create(A, n, s_dim); }));) \
+        SPRS_G(return (solver_create<T, sprs_idrs, Idrs>("sprs_idrs", A, out, [&](auto *s) { return s->create(A, n, s_dim); }));) \
     }                                                                                                                  \
     SPRS_SOLVER_SOLVES(X, T, CT, R, idrs, Idrs)                                                                        \
     /* CSMinRes has no precond_solve (cs_minres.rs) */                                                                  \
     int sprs_csminres_create_##X(const sprs_csr *A, size_t n, sprs_csminres **out) {                                   \
-        SPRS_G(return (solver_create<T, sprs_csminres, MinRes>(A, n, out, [&](auto *s) { return s->create(A, n, true); }));) \
+        SPRS_G(return (solver_create<T, sprs_csminres, MinRes>("sprs_csminres", A, out, [&](auto *s) { return s->create(A, n, true); }));) \
     }                                                                                                                  \
     int sprs_csminres_solve_##X(sprs_csminres *h, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
         SPRS_G(return solve<T>(impl_of<MinRes, T>(h), true, nullptr, (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);) \

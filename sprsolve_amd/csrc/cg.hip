@@ -15,6 +15,7 @@ namespace sprs {
 
 template <class T>
 int Cg<T>::create(const sprs_csr *A, size_t size) {
+    SPRS_TRY(size_is_rows(A, size));
     SPRS_TRY(this->init(A, size, 4));   // r, p, q, z (z only with a preconditioner)
     this->no_p2p = true;                // hand-offs through fin_for + handoff + the all-reduce only
     return state.create(this->ctx);

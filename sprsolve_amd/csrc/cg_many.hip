@@ -13,10 +13,8 @@ template <class T>
 int CgMany<T>::create(const sprs_csr *A_, size_t size, size_t k) {
     A = A_; ctx = A_->ctx; n = size;
     if (k < 1 || k > (size_t)CGM_MAXK) return SPRS_INVALID_ARGUMENT;
-    if (A->dist) {
-        snprintf(ctx->err, sizeof(ctx->err), "sprs_cgmany: distributed operators are not supported (single GPU only)");
-        return SPRS_INVALID_ARGUMENT;
-    }
+    SPRS_TRY(size_is_rows(A, size));
+    SPRS_TRY(single_gpu_only(A, "sprs_cgmany"));
     kmax = (int)k;
     kp = 1; lg = 0;
     while (kp < kmax) { kp <<= 1; ++lg; }

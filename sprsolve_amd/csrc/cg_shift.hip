@@ -20,14 +20,9 @@ namespace sprs {
 template <class T>
 int CgShift<T>::create(const sprs_csr *A_, size_t size, size_t mmax_) {
     this->A = A_; this->ctx = A_->ctx;
-    if (mmax_ < 1 || mmax_ > (size_t)CGS_MAXM) {
-        snprintf(this->ctx->err, sizeof(this->ctx->err), "sprs_cgshift: mmax = %zu is outside 1 .. %d", mmax_, CGS_MAXM);
-        return SPRS_INVALID_ARGUMENT;
-    }
-    if (A_->dist) {
-        snprintf(this->ctx->err, sizeof(this->ctx->err), "sprs_cgshift: distributed operators are not supported (single GPU only)");
-        return SPRS_INVALID_ARGUMENT;
-    }
+    SPRS_TRY(size_is_rows(A_, size));
+    if (mmax_ < 1 || mmax_ > (size_t)CGS_MAXM) return refuse(this->ctx, "sprs_cgshift", "mmax = %zu is outside 1 .. %d", mmax_, CGS_MAXM);
+    SPRS_TRY(single_gpu_only(A_, "sprs_cgshift"));
     mmax = (int)mmax_;
     SPRS_TRY(this->init(A_, size, 3 + 2 * mmax));   // r, p, q ; P's columns ; X's columns (used where the caller's x is not aligned)
     return state.create(this->ctx);

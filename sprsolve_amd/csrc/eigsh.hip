@@ -12,6 +12,12 @@ namespace sprs {
 
 template <class T>
 int Eigsh<T>::create(const sprs_csr *A, size_t size, size_t ncv) {
+    SPRS_TRY(single_gpu_only(A, "sprs_eigsh"));
+    if (A->nrows != A->ncols) return SPRS_NOT_SQUARE;
+    if ((int64_t)size != A->nrows) return SPRS_DIM_MISMATCH;
+    if (ncv == 0) ncv = std::min<size_t>(32, size);
+    if (ncv < 3 || ncv > std::min<size_t>(SPRS_EIGSH_MAX_NCV, size))
+        return refuse(A->ctx, "sprs_eigsh", "ncv = %zu is outside 3 .. min(%d, n = %zu)", ncv, SPRS_EIGSH_MAX_NCV, size);
     m = (int)ncv;
     SPRS_TRY(this->init(A, size, m + 2));   // v_0 .. v_m, w
     sprs_ctx *c = this->ctx;

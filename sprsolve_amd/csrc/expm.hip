@@ -15,6 +15,12 @@ namespace sprs {
 
 template <class T>
 int Expm<T>::create(const sprs_csr *A, size_t size, size_t ncv) {
+    SPRS_TRY(single_gpu_only(A, "sprs_expm"));
+    if (A->nrows != A->ncols) return SPRS_NOT_SQUARE;
+    if ((int64_t)size != A->nrows) return SPRS_DIM_MISMATCH;
+    if (ncv == 0) ncv = std::min<size_t>(30, size);
+    if (ncv < 3 || ncv > std::min<size_t>(SPRS_EXPM_MAX_NCV, size))
+        return refuse(A->ctx, "sprs_expm", "ncv = %zu is outside 3 .. min(%d, n = %zu)", ncv, SPRS_EXPM_MAX_NCV, size);
     m = (int)ncv;
     SPRS_TRY(this->init(A, size, m + 3));   // v_0 .. v_m, p, the staging vector of the result
     sprs_ctx *c = this->ctx;

@@ -328,10 +328,7 @@ int sprs_fsai_create(const sprs_csr *A, int power, sprs_fsai **out, int64_t *row
         if (!A || !out) return SPRS_INVALID_ARGUMENT;
         *out = nullptr;
         if (row_out) *row_out = -1;
-        if (A->dist) {                   // (before the shape: a row block with a halo has more columns than rows)
-            snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_fsai: distributed operators are not supported (single GPU only)");
-            return SPRS_INVALID_ARGUMENT;
-        }
+        SPRS_TRY(single_gpu_only(A, "sprs_fsai"));   // (before the shape: a row block with a halo has more columns than rows)
         if (power != 1 && power != 2) {
             snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_fsai: power must be 1 or 2, got %d", power);
             return SPRS_INVALID_ARGUMENT;

@@ -16,6 +16,7 @@ namespace sprs {
 template <class T>
 int Gmres<T>::create(const sprs_csr *A, size_t size, size_t restart) {
     if (restart > (size_t)GM_MAXM) return SPRS_INVALID_ARGUMENT;
+    SPRS_TRY(size_is_rows(A, size));
     m = restart == 0 ? 30 : (int)restart;
     SPRS_TRY(this->init(A, size, m + 4));   // v_0 .. v_m, w, z, u
     this->no_p2p = true;                    // hand-offs through fin_for + handoff + the all-reduce only

@@ -20,19 +20,11 @@ template <class T>
 int Idrs<T>::create(const sprs_csr *A_, size_t size, size_t s_dim) {
     this->A = A_; this->ctx = A_->ctx;
     sprs_ctx *c = this->ctx;
-    if (s_dim > (size_t)IDRS_MAXS) {
-        snprintf(c->err, sizeof(c->err), "sprs_idrs: s = %zu is larger than SPRS_IDRS_MAX_S = %d", s_dim, IDRS_MAXS);
-        return SPRS_INVALID_ARGUMENT;
-    }
+    SPRS_TRY(size_is_rows(A_, size));
+    if (s_dim > (size_t)IDRS_MAXS) return refuse(c, "sprs_idrs", "s = %zu is larger than SPRS_IDRS_MAX_S = %d", s_dim, IDRS_MAXS);
     s = s_dim == 0 ? 4 : (int)s_dim;
-    if ((size_t)s > size) {
-        snprintf(c->err, sizeof(c->err), "sprs_idrs: s = %d is larger than the system (%zu rows)", s, size);
-        return SPRS_INVALID_ARGUMENT;
-    }
-    if (A_->dist) {
-        snprintf(c->err, sizeof(c->err), "sprs_idrs: distributed operators are not supported (single GPU only)");
-        return SPRS_INVALID_ARGUMENT;
-    }
+    if ((size_t)s > size) return refuse(c, "sprs_idrs", "s = %d is larger than the system (%zu rows)", s, size);
+    SPRS_TRY(single_gpu_only(A_, "sprs_idrs"));
     SPRS_TRY(this->init(A_, size, 4 + 3 * s));          // r, v, vh, t ; G's, U's and P's columns
     SPRS_TRY(state.create(c));
 

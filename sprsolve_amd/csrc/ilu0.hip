@@ -444,10 +444,7 @@ int sprs_ilu0_create_sweeps(const sprs_csr *A, int sweeps, sprs_ilu0 **out, int6
         if (!A || !out) return SPRS_INVALID_ARGUMENT;
         *out = nullptr;
         if (row_out) *row_out = -1;
-        if (A->dist) {                   // (before the shape: a row block with a halo has more columns than rows)
-            snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_ilu0: distributed operators are not supported (single GPU only)");
-            return SPRS_INVALID_ARGUMENT;
-        }
+        SPRS_TRY(single_gpu_only(A, "sprs_ilu0"));   // (before the shape: a row block with a halo has more columns than rows)
         if (sweeps < 0 || sweeps > SPRS_ILU0_MAX_SWEEPS) {
             snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_ilu0: sweeps must be in 0 .. %d (0 = exact solves), got %d", SPRS_ILU0_MAX_SWEEPS, sweeps);
             return SPRS_INVALID_ARGUMENT;

@@ -4,6 +4,7 @@
 #include <hip/hip_ext.h>
 #include <algorithm>
 #include <cmath>
+#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -123,6 +124,16 @@ struct CtxLock {
             return SPRS_ERR_HIP;                                                                    \
         }                                                                                           \
     } while (0)
+
+// An argument an entry point refuses with a reason: sprs_last_error reads "<entry>: <text>", the status is SPRS_INVALID_ARGUMENT.
+__attribute__((format(printf, 3, 4))) static inline int refuse(const sprs_ctx *c, const char *entry, const char *fmt, ...) {
+    const int at = snprintf(c->err, sizeof(c->err), "%s: ", entry);
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(c->err + at, sizeof(c->err) - (size_t)at, fmt, ap);
+    va_end(ap);
+    return SPRS_INVALID_ARGUMENT;
+}
 
 // Launch of an SpMV kernel on the context's stream; timed by the launch itself when a profile is being taken.
 #define SPRS_LAUNCH_SPMV(c, kernel, grid, ...)                                                                            \
@@ -264,6 +275,19 @@ struct sprs_csr {
     sprs_dist_info *dist = nullptr;   // non-null: row block of a matrix partitioned over ranks
     sprs_dict *dict = nullptr;        // non-null: dictionary-compressed stream available (spmv_dict.hip)
 };
+
+// Entry points that take no distributed operator refuse one (A, or the second handle that comes with it: an adjoint, a product's
+// right operand) with this text, on A's context.
+static inline int single_gpu_only(const sprs_csr *A, const char *entry, const sprs_csr *B_or_null = nullptr) {
+    if (!A->dist && !(B_or_null && B_or_null->dist)) return SPRS_OK;
+    return refuse(A->ctx, entry, "distributed operators are not supported (single GPU only)");
+}
+// The linear solvers multiply size-vectors by A in place.  The reference leaves a mismatch to UB (mul_vec_unchecked); they refuse
+// it rather than index out of bounds on the GPU.  A distributed row block carries its halo columns past its rows.
+static inline int size_is_rows(const sprs_csr *A, size_t size) {
+    const bool fits = (int64_t)size == A->nrows && (A->dist ? A->ncols >= A->nrows : (int64_t)size == A->ncols);
+    return fits ? SPRS_OK : SPRS_DIM_MISMATCH;
+}
 
 struct sprs_diag {
     sprs_ctx *ctx = nullptr;

@@ -26,6 +26,13 @@
 // own cycle loops.  The main loops stay apart: BiCGStab's restart, MINRES's deferred
 // M3, CG's accounting of idle launches and GMRES's cycles have nothing in common.  Each solver has ONE run and ONE run_literal,
 // whatever it is preconditioned with.
+//
+// Handles: every S<T> here has create(...) and destroy().  create holds ALL checks of the operator and of the creation parameters,
+// in the order that decides the status when two are wrong: single_gpu_only(), square, size against the rows (size_is_rows() for
+// the linear solvers), the parameter's range and default, the adjoint handle; a refusal with a reason goes through refuse()
+// (internal.hpp).  destroy is safe on an object whose create returned early.  capi.hip adds only what belongs to the ABI, once, in
+// solver_create: null pointers, *out, the handle's scalar type, the context lock, the allocation and the unwind.  A new solver
+// writes there its entry points' signatures and one solver_create call.
 #pragma once
 #include "internal.hpp"
 
@@ -179,6 +186,7 @@ class KrylovBase {
 
     int init(const sprs_csr *A_, size_t size, int nvec_);
     void destroy();
+    __attribute__((noinline)) ~KrylovBase() = default;   // (the two vectors) one copy, not one per kind in solver_create's unwind and solver_destroy
     T *vec(int i) { return work + (size_t)i * stride; }
     T *pslot(int s) { return part + (size_t)s * MAX_GRID; }
     Real<T> *dslot(int s) { return partD + (size_t)s * MAX_GRID; }

@@ -14,6 +14,12 @@ namespace sprs {
 
 template <class T>
 int Lobpcg<T>::create(const sprs_csr *A, size_t size, size_t block) {
+    SPRS_TRY(single_gpu_only(A, "sprs_lobpcg"));
+    if (A->nrows != A->ncols) return SPRS_NOT_SQUARE;
+    if ((int64_t)size != A->nrows) return SPRS_DIM_MISMATCH;
+    if (block == 0) block = std::min<size_t>(SPRS_LOBPCG_MAX_BLOCK, size / 6);
+    if (block < 1 || block > SPRS_LOBPCG_MAX_BLOCK || 6 * block > size)
+        return refuse(A->ctx, "sprs_lobpcg", "block = %zu is outside 1 .. min(%d, n / 6 = %zu)", block, SPRS_LOBPCG_MAX_BLOCK, size / 6);
     b = (int)block;
     SPRS_TRY(this->init(A, size, 6 * b));   // X, P, W, AX, AP, AW: b vectors each
     sprs_ctx *c = this->ctx;

@@ -16,7 +16,11 @@ namespace sprs {
 
 template <class T>
 int Lsmr<T>::create(const sprs_csr *A, const sprs_csr *AH_or_null) {
-    if (AH_or_null) AH = AH_or_null;
+    const sprs_csr *H = AH_or_null;
+    SPRS_TRY(single_gpu_only(A, "sprs_lsmr", H));
+    if (H && (H->dtype != A->dtype || H->ctx != A->ctx)) return SPRS_INVALID_ARGUMENT;
+    if (H && (H->nrows != A->ncols || H->ncols != A->nrows)) return SPRS_DIM_MISMATCH;
+    if (H) AH = H;
     else {
         SPRS_TRY(sprs_csr_adjoint(A, 1, &own_AH));
         AH = own_AH;

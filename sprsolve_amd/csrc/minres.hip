@@ -11,6 +11,7 @@ namespace sprs {
 template <class T>
 int MinRes<T>::create(const sprs_csr *A, size_t size, bool saunders_) {
     saunders = saunders_;
+    SPRS_TRY(size_is_rows(A, size));
     SPRS_TRY(this->init(A, size, 8));   // minres.rs:24 workspace 8n (cs_minres.rs:22 uses 7n)
     return state.create(this->ctx);
 }

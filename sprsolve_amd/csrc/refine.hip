@@ -184,10 +184,7 @@ static int refine_create(const sprs_csr *A, size_t n, const sprs_diag *P, int in
     sprs_ctx *c = A->ctx;
     CtxLock lock(c);
     c->err[0] = 0;                  // an SPRS_INVALID_ARGUMENT of this call that has a text is told from one that has none
-    if (A->dist) {
-        snprintf(c->err, sizeof(c->err), "sprs_refine_create: distributed operators are not supported (single GPU only)");
-        return SPRS_INVALID_ARGUMENT;
-    }
+    SPRS_TRY(single_gpu_only(A, "sprs_refine_create"));
     if ((int64_t)n != A->nrows || (int64_t)n != A->ncols) return SPRS_DIM_MISMATCH;
     auto *s = new Refine<H>();
     const int st = s->create(A, n, P, inner, restart);

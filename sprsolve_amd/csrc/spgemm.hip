@@ -461,10 +461,7 @@ extern "C" {
 int sprs_csr_matmul(const sprs_csr *A, const sprs_csr *B, sprs_csr **out, int64_t *info) {
     if (!A || !B || !out) return SPRS_INVALID_ARGUMENT;
     *out = nullptr;
-    if (A->dist || B->dist) {
-        snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_csr_matmul: distributed operators are not supported (single GPU only)");
-        return SPRS_INVALID_ARGUMENT;
-    }
+    SPRS_TRY(single_gpu_only(A, "sprs_csr_matmul", B));
     if (A->ctx != B->ctx || A->dtype != B->dtype) {
         snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_csr_matmul: the operands must have the same scalar type and context");
         return SPRS_INVALID_ARGUMENT;

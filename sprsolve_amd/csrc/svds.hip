@@ -16,7 +16,15 @@ namespace sprs {
 
 template <class T>
 int Svds<T>::create(const sprs_csr *A, const sprs_csr *AH_or_null, size_t ncv) {
-    if (AH_or_null) AH = AH_or_null;
+    const sprs_csr *H = AH_or_null;
+    SPRS_TRY(single_gpu_only(A, "sprs_svds", H));
+    if (H && (H->dtype != A->dtype || H->ctx != A->ctx)) return refuse(A->ctx, "sprs_svds", "the adjoint handle holds another scalar type or context");
+    if (H && (H->nrows != A->ncols || H->ncols != A->nrows)) return refuse(A->ctx, "sprs_svds", "the adjoint handle is not cols x rows");
+    const size_t small = (size_t)std::min(A->nrows, A->ncols);
+    if (ncv == 0) ncv = std::min<size_t>(32, small);
+    if (ncv < 3 || ncv > std::min<size_t>(SPRS_SVDS_MAX_NCV, small))
+        return refuse(A->ctx, "sprs_svds", "ncv = %zu is outside 3 .. min(%d, min(rows, cols) = %zu)", ncv, SPRS_SVDS_MAX_NCV, small);
+    if (H) AH = H;
     else {
         SPRS_TRY(sprs_csr_adjoint(A, 1, &own_AH));
         AH = own_AH;

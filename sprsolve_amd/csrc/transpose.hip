@@ -118,10 +118,7 @@ extern "C" {
 int sprs_csr_adjoint(const sprs_csr *A, int conjugate, sprs_csr **out) {
     if (!A || !out) return SPRS_INVALID_ARGUMENT;
     *out = nullptr;
-    if (A->dist) {
-        snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_csr_adjoint: distributed operators are not supported (single GPU only)");
-        return SPRS_INVALID_ARGUMENT;
-    }
+    SPRS_TRY(single_gpu_only(A, "sprs_csr_adjoint"));
     try {
         switch (A->dtype) {
             case DT_D: return adjoint_typed<double, double>(A, 0, sprs_csr_create_dev_d, out);

@@ -4,32 +4,24 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .device import DevVec, dev_len, dev_ptr, is_device_array, pre_sync, sfx
-from .error import BreakDown, IncompatibleMatrixFormat, InsufficientIterNum, check
+from ._solver import _Handle, eig_result
+from .device import DevVec, dev_len, dev_ptr, is_device_array, pre_sync
 
 
-class Expm:
+class Expm(_Handle):
     """`Expm.new(A, size, ncv=0)`: the action of exp(tA) on a vector for a square A of any kind, by Arnoldi projection on ncv
     vectors with error-controlled sub-stepping; 3 <= ncv <= min(48, n), 0 means min(30, n).  The recurrence is stated in
     include/sprsolve_hip.h (sprs_expm_*) and runs in C++ on device-resident vectors and scalars (sprsolve_amd/csrc/expm.hip,
     expm_fuse.hpp); the handle holds ncv + 3 work vectors.  Single GPU."""
     NAME = "expm"
+    SAYS_WHY = True     # a distributed A, ncv out of range
 
     def __init__(self, A, size, ncv=0):
         ncv = int(ncv)
         if ncv < 0:
             raise ValueError("ncv must be >= 0")
-        self.A = A                      # borrowed
         self.size = int(size)
-        self.dtype = A.dtype
-        self.s = sfx(self.dtype)
-        self.h = None
-        h = C.c_void_p()
-        st = getattr(_lib.lib(), "sprs_expm_create_" + self.s)(A.h, self.size, ncv, C.byref(h))
-        if st == _lib.INVALID_ARGUMENT:     # a distributed A, ncv out of range: the library says which
-            raise ValueError("sprsolve_hip: invalid argument: " + (_lib.lib().sprs_last_error(A.ctx.h) or b"").decode(errors="replace"))
-        check(st, A.ctx.h)
-        self.h = h
+        self._create(A, self.size, ncv)
         self.ncv = ncv or min(30, self.size)
 
     @classmethod
@@ -67,28 +59,7 @@ class Expm:
                                                         float(tau0), w.ctypes.data_as(C.c_void_p), w.size, *tail)
         info = dict(err=float(err.value), hump=float(hump.value), t_done=float(t_done.value), steps=steps.value, rejects=rejects.value,
                     matvecs=matvecs.value)
-        if st == _lib.OK:
-            return w, info
-        if st == _lib.INCOMPATIBLE_RHS_SIZE:
-            raise IncompatibleMatrixFormat("Input vec dimension doesn't match the matrix size")
-        if st == _lib.INCOMPATIBLE_X_SIZE:
-            raise IncompatibleMatrixFormat("Input and output vec dimension do not match")
-        if st in (_lib.INSUFFICIENT_ITER, _lib.BREAKDOWN):
-            e = InsufficientIterNum(steps.value) if st == _lib.INSUFFICIENT_ITER else BreakDown(steps.value)
-            e.w, e.info = (w if st == _lib.INSUFFICIENT_ITER else None), info
-            raise e
-        check(st, self.A.ctx.h)
-
-    def close(self):
-        if self.h:
-            _lib.lib().sprs_expm_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return eig_result(st, (None if st == _lib.BREAKDOWN else w, info), ("w", "info"), steps.value, self.A.ctx.h)
 
 
 def expm_multiply(A, v, t=1.0, ncv=0, **kw):

@@ -1,9 +1,6 @@
 """Restarted GMRES for general (non-symmetric) operators (no reference analogue)."""
 from . import _lib
-from ._solver import _SolverBase
-from .amg import AMG
-from .fsai import FSAI
-from .ilu import ILU0
+from ._solver import _SolverBase, applied_prefix
 
 
 class GMRES(_SolverBase):
@@ -31,10 +28,4 @@ class GMRES(_SolverBase):
 
     def precond_solve(self, precond, rhs, x, max_iter, tol):
         """Preconditioned from the right by a `DiagPrecond` (Jacobi), an `ILU0`, an `AMG` or an `FSAI`: the residual it reports is the true one's estimate."""
-        if isinstance(precond, ILU0):
-            return self._solve(precond, rhs, x, max_iter, tol, True, prefix="ilu0")
-        if isinstance(precond, AMG):
-            return self._solve(precond, rhs, x, max_iter, tol, True, prefix="amg")
-        if isinstance(precond, FSAI):
-            return self._solve(precond, rhs, x, max_iter, tol, True, prefix="fsai")
-        return self._solve(precond, rhs, x, max_iter, tol, True)
+        return self._solve(precond, rhs, x, max_iter, tol, True, prefix=applied_prefix(precond))

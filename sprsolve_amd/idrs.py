@@ -1,9 +1,6 @@
 """IDR(s) for general (non-symmetric) operators (no reference analogue)."""
 from . import _lib
-from ._solver import _SolverBase
-from .amg import AMG
-from .fsai import FSAI
-from .ilu import ILU0
+from ._solver import _SolverBase, applied_prefix
 
 
 class IDRS(_SolverBase):
@@ -16,18 +13,14 @@ class IDRS(_SolverBase):
     after the initial residual.  One mode: `set_mode('literal')` is refused.  Single GPU."""
     KIND = _lib.SOLVER_IDRS
     NAME = "idrs"
+    SAYS_WHY = True     # s out of range, a distributed A
 
     def __init__(self, A, size, s=4):
         s = int(s)
         if s < 0:
             raise ValueError("s must be >= 0")
         self.s_dim = s or 4
-        self.h = None
-        try:
-            super().__init__(A, size, s)
-        except ValueError:                  # s out of range, a distributed A: the library says which
-            raise ValueError("sprsolve_hip: invalid argument: "
-                             + (_lib.lib().sprs_last_error(A.ctx.h) or b"").decode(errors="replace")) from None
+        super().__init__(A, size, s)
 
     @classmethod
     def new(cls, A, size, s=4):
@@ -39,10 +32,4 @@ class IDRS(_SolverBase):
 
     def precond_solve(self, precond, rhs, x, max_iter, tol):
         """Preconditioned from the right by a `DiagPrecond` (Jacobi), an `ILU0`, an `AMG` or an `FSAI`: the residual it reports is the recursive one."""
-        if isinstance(precond, ILU0):
-            return self._solve(precond, rhs, x, max_iter, tol, True, prefix="ilu0")
-        if isinstance(precond, AMG):
-            return self._solve(precond, rhs, x, max_iter, tol, True, prefix="amg")
-        if isinstance(precond, FSAI):
-            return self._solve(precond, rhs, x, max_iter, tol, True, prefix="fsai")
-        return self._solve(precond, rhs, x, max_iter, tol, True)
+        return self._solve(precond, rhs, x, max_iter, tol, True, prefix=applied_prefix(precond))

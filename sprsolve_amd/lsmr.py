@@ -5,8 +5,8 @@ import numpy as np
 
 from . import _lib
 from ._solver import _SolverBase
-from .device import dev_len, dev_ptr, is_device_array, pre_sync, sfx
-from .error import check, solve_result
+from .device import dev_len, dev_ptr, is_device_array, pre_sync
+from .error import solve_result
 
 
 class LSMR(_SolverBase):
@@ -17,15 +17,9 @@ class LSMR(_SolverBase):
     NAME = "lsmr"
 
     def __init__(self, A, adjoint=None):
-        self.A, self.AH = A, adjoint            # borrowed
+        self.AH = adjoint                       # borrowed
         self.size = A.shape
-        self.dtype = A.dtype
-        self.s = sfx(self.dtype)
-        h = C.c_void_p()
-        st = getattr(_lib.lib(), "sprs_lsmr_create_" + self.s)(A.h, adjoint.h if adjoint is not None else None, C.byref(h))
-        check(st, A.ctx.h)
-        self.h = h
-        self._trace = None
+        self._create(A, adjoint.h if adjoint is not None else None)
 
     @classmethod
     def new(cls, A, adjoint=None):
