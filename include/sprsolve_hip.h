@@ -1129,6 +1129,99 @@ int sprs_fsai_idrs_solve_dev_z(sprs_idrs *S, const sprs_fsai *P, const sprs_c64 
 int sprs_fsai_idrs_solve_dev_s(sprs_idrs *S, const sprs_fsai *P, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
 int sprs_fsai_idrs_solve_dev_c(sprs_idrs *S, const sprs_fsai *P, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
 
+/* ---------------------------------------------------------------- block-Jacobi preconditioner
+ * M = blockdiag(A_bb)^-1 for a square single-GPU CSR handle of any of the four scalar types: the diagonal blocks of A, inverted
+ * on the device at creation and stored densely; applying M is one launch of small dense products, with no levels and no
+ * dependent launches.  The reference has no such preconditioner.  Block b covers the rows and columns [s_b, e_b),
+ * 1 <= m = e_b - s_b <= SPRS_BJACOBI_MAX_BLOCK: several unknowns of one grid node, or one grid line.  The handle owns
+ * everything it derives and borrows nothing from A after creation.
+ * create(A, block_size, block_ptr, nblocks): the checks, in this order.  SPRS_INVALID_ARGUMENT (text in sprs_last_error) for a
+ * distributed A;  SPRS_NOT_SQUARE;  SPRS_INVALID_ARGUMENT (text) unless exactly one of block_size > 0 and block_ptr != NULL is
+ * given, for a block_ptr (nblocks + 1 entries) that does not start at 0, does not increase strictly or does not end at n, for a
+ * block of more than SPRS_BJACOBI_MAX_BLOCK rows, and for a row of A whose column indices are not strictly ascending (the check
+ * of FSAI and ILU(0));  SPRS_INVALID_PRECOND with *row_out = s_b of the lowest singular block (below).  *row_out is -1
+ * otherwise, *out is NULL after every failure.  block_size = bs stands for block_ptr = 0, bs, 2 bs, .., n: the last block takes
+ * what is left (nblocks is not read then).
+ * Every scalar operation is in the handle's scalar type and rounded once, complex products are (ac - bd, ad + bc), the complex
+ * quotient a / b is ((re a re b + im a im b) / d, (im a re b - re a im b) / d) with d = re b re b + im b im b, nothing is fused.
+ * 1. The local matrix.  W[i][j] = the stored a(s_b + i, s_b + j), +0 where nothing is stored.  A missing diagonal entry is no
+ *    error: the elimination pivots.
+ * 2. The inverse: Gauss-Jordan on [W | V], V = I, with implicit row pivoting.  For k = 0 .. m - 1:
+ *      mag(a) = |re a| + |im a| (one addition; |a| for the real types).  Over the rows i not yet used as a pivot row, ascending:
+ *      p = the first of them, and every later one replaces p where mag(W[i][k]) > mag(W[p][k]) (so the lowest row wins a tie and
+ *      a NaN never replaces anything).  mag(W[p][k]) zero or not finite: the block is singular.  Else perm[k] = p, piv = W[p][k];
+ *      W[p][j] = W[p][j] / piv and V[p][j] = V[p][j] / piv for every j;
+ *      for every i != p:  f = W[i][k];  W[i][j] = W[i][j] - f * W[p][j] and V[i][j] = V[i][j] - f * V[p][j] for every j
+ *      (one product and one difference per update).
+ *    The loops run over ALL j = 0 .. m - 1, structural zeros and the columns already eliminated included: the signs of the zeros
+ *    are part of the result.  Every element's updates come in the order of k, so any lane mapping gives the same bits.  Row k of
+ *    the inverse is V[perm[k]].
+ * 3. Application.  out[s_b + i] = sum_j Minv[i][j] * in[s_b + j], j = 0 .. m - 1 ascending from +0, acc = acc + Minv[i][j] * in[..]
+ *    (the row fold of the sliced layouts).  The _dev form is asynchronous on the context's stream; in == out is allowed, and the
+ *    device vectors need the alignment of one element only.  Host slices of the wrong length: SPRS_DIM_MISMATCH.
+ * Storage (csrc/bjacobi_plan.hpp): the inverse blocks sit in slices of 64 lanes, whole consecutive blocks a slice, entry (i, j) of
+ * the block whose row i is at lane l in slot sbase[slice] + 64 j + l; a slice is as wide as its largest block.
+ * sprs_bjacobi_info: rows, blocks, the largest block and the slots of that storage; any pointer may be NULL.
+ * sprs_bjacobi_block_ptr: the nblocks + 1 block starts.  sprs_bjacobi_inverse_*: every inverse block on the host, row-major, one
+ * block after another, sum of m^2 entries (len: what out holds; another length is SPRS_DIM_MISMATCH).
+ * Solvers: as for ILU(0) (same errors); z = P r, z = P v_j and u = P u of the recurrences are one application.  M is Hermitian
+ * positive definite where A is, up to rounding: CG takes it as it takes FSAI.  MINRES with COMPLEX scalars is wired but not
+ * usable in general: its rule for SPRS_INVALID_PRECOND rejects im(conj(v) . M v) > eps * re(..), and with dense complex blocks
+ * that imaginary part is rounding noise of just that size (measured 2.7e-16 .. 2.2e-15 against 2.2e-16), so such a solve ends
+ * with that status after a few iterations.  The rule is the reference's and is not loosened; use CG there. */
+#define SPRS_BJACOBI_MAX_BLOCK 32
+typedef struct sprs_bjacobi sprs_bjacobi;
+int sprs_bjacobi_create(const sprs_csr *A, int64_t block_size, const int64_t *block_ptr_or_null, int64_t nblocks, sprs_bjacobi **out, int64_t *row_out);   /* row_out may be NULL */
+int sprs_bjacobi_destroy(sprs_bjacobi *P);     /* NULL is a no-op */
+int sprs_bjacobi_info(const sprs_bjacobi *P, int64_t *n, int64_t *nblocks, int64_t *max_block, int64_t *slots);
+int sprs_bjacobi_block_ptr(const sprs_bjacobi *P, int64_t *block_ptr_out);
+int sprs_bjacobi_inverse_d(const sprs_bjacobi *P, double *out_host, size_t len);
+int sprs_bjacobi_inverse_z(const sprs_bjacobi *P, sprs_c64 *out_host, size_t len);
+int sprs_bjacobi_inverse_s(const sprs_bjacobi *P, float *out_host, size_t len);
+int sprs_bjacobi_inverse_c(const sprs_bjacobi *P, sprs_c32 *out_host, size_t len);
+int sprs_bjacobi_mul_vec_dev_d(const sprs_bjacobi *P, const double *in_dev, double *out_dev);
+int sprs_bjacobi_mul_vec_dev_z(const sprs_bjacobi *P, const sprs_c64 *in_dev, sprs_c64 *out_dev);
+int sprs_bjacobi_mul_vec_dev_s(const sprs_bjacobi *P, const float *in_dev, float *out_dev);
+int sprs_bjacobi_mul_vec_dev_c(const sprs_bjacobi *P, const sprs_c32 *in_dev, sprs_c32 *out_dev);
+int sprs_bjacobi_mul_vec_d(const sprs_bjacobi *P, const double *in_host, size_t in_len, double *out_host, size_t out_len);
+int sprs_bjacobi_mul_vec_z(const sprs_bjacobi *P, const sprs_c64 *in_host, size_t in_len, sprs_c64 *out_host, size_t out_len);
+int sprs_bjacobi_mul_vec_s(const sprs_bjacobi *P, const float *in_host, size_t in_len, float *out_host, size_t out_len);
+int sprs_bjacobi_mul_vec_c(const sprs_bjacobi *P, const sprs_c32 *in_host, size_t in_len, sprs_c32 *out_host, size_t out_len);
+/* CG, GMRES, BiCGStab and MINRES preconditioned by block-Jacobi: as sprs_ilu0_*_solve_* with P = one application.  IDR(s) and
+ * LOBPCG do not take the handle yet. */
+int sprs_bjacobi_cg_solve_d(sprs_cg *S, const sprs_bjacobi *P, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_bjacobi_cg_solve_z(sprs_cg *S, const sprs_bjacobi *P, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_bjacobi_cg_solve_s(sprs_cg *S, const sprs_bjacobi *P, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_bjacobi_cg_solve_c(sprs_cg *S, const sprs_bjacobi *P, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_bjacobi_cg_solve_dev_d(sprs_cg *S, const sprs_bjacobi *P, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_bjacobi_cg_solve_dev_z(sprs_cg *S, const sprs_bjacobi *P, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_bjacobi_cg_solve_dev_s(sprs_cg *S, const sprs_bjacobi *P, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_bjacobi_cg_solve_dev_c(sprs_cg *S, const sprs_bjacobi *P, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_bjacobi_gmres_solve_d(sprs_gmres *S, const sprs_bjacobi *P, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_bjacobi_gmres_solve_z(sprs_gmres *S, const sprs_bjacobi *P, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_bjacobi_gmres_solve_s(sprs_gmres *S, const sprs_bjacobi *P, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_bjacobi_gmres_solve_c(sprs_gmres *S, const sprs_bjacobi *P, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_bjacobi_gmres_solve_dev_d(sprs_gmres *S, const sprs_bjacobi *P, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_bjacobi_gmres_solve_dev_z(sprs_gmres *S, const sprs_bjacobi *P, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_bjacobi_gmres_solve_dev_s(sprs_gmres *S, const sprs_bjacobi *P, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_bjacobi_gmres_solve_dev_c(sprs_gmres *S, const sprs_bjacobi *P, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_bjacobi_bicgstab_solve_d(sprs_bicgstab *S, const sprs_bjacobi *P, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_bjacobi_bicgstab_solve_z(sprs_bicgstab *S, const sprs_bjacobi *P, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_bjacobi_bicgstab_solve_s(sprs_bicgstab *S, const sprs_bjacobi *P, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_bjacobi_bicgstab_solve_c(sprs_bicgstab *S, const sprs_bjacobi *P, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_bjacobi_bicgstab_solve_dev_d(sprs_bicgstab *S, const sprs_bjacobi *P, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_bjacobi_bicgstab_solve_dev_z(sprs_bicgstab *S, const sprs_bjacobi *P, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_bjacobi_bicgstab_solve_dev_s(sprs_bicgstab *S, const sprs_bjacobi *P, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_bjacobi_bicgstab_solve_dev_c(sprs_bicgstab *S, const sprs_bjacobi *P, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_bjacobi_minres_solve_d(sprs_minres *S, const sprs_bjacobi *P, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_bjacobi_minres_solve_z(sprs_minres *S, const sprs_bjacobi *P, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_bjacobi_minres_solve_s(sprs_minres *S, const sprs_bjacobi *P, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_bjacobi_minres_solve_c(sprs_minres *S, const sprs_bjacobi *P, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_bjacobi_minres_solve_dev_d(sprs_minres *S, const sprs_bjacobi *P, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_bjacobi_minres_solve_dev_z(sprs_minres *S, const sprs_bjacobi *P, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out);
+int sprs_bjacobi_minres_solve_dev_s(sprs_minres *S, const sprs_bjacobi *P, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+int sprs_bjacobi_minres_solve_dev_c(sprs_minres *S, const sprs_bjacobi *P, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out);
+
 /* ---------------------------------------------------------------- multi-GPU (one process per GPU)
  * No reference analogue: the reference is single-process (rayon).  The matrix is row-partitioned;
  * rank r owns rows [r0, r1) and the matching slices of every vector.  A distributed operator is the

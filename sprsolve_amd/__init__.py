@@ -17,6 +17,7 @@ from .expm import Expm, expm_multiply  # noqa: F401
 from .gauss_seidel import GaussSeidel  # noqa: F401
 from .gmres import GMRES  # noqa: F401
 from .fsai import FSAI  # noqa: F401
+from .bjacobi import BlockJacobi  # noqa: F401
 from .idrs import IDRS  # noqa: F401
 from .ilu import ILU0  # noqa: F401
 from .lobpcg import Lobpcg  # noqa: F401

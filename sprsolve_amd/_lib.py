@@ -144,8 +144,13 @@ def _protos():
         P["sprs_amg_mul_vec_" + s] = [_vp, _vp, _sz, _vp, _sz]
         P["sprs_fsai_mul_vec_dev_" + s] = [_vp, _vp, _vp]
         P["sprs_fsai_mul_vec_" + s] = [_vp, _vp, _sz, _vp, _sz]
+        P["sprs_bjacobi_mul_vec_dev_" + s] = [_vp, _vp, _vp]
+        P["sprs_bjacobi_mul_vec_" + s] = [_vp, _vp, _sz, _vp, _sz]
+        P["sprs_bjacobi_inverse_" + s] = [_vp, _vp, _sz]
         for k in ("cg", "gmres", "bicgstab", "minres", "idrs"):
-            for pc in ("ilu0", "amg", "fsai"):
+            for pc in ("ilu0", "amg", "fsai", "bjacobi"):
+                if (pc, k) == ("bjacobi", "idrs"):           # IDR(s) does not take a block-Jacobi handle
+                    continue
                 P["sprs_%s_%s_solve_%s" % (pc, k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
                 P["sprs_%s_%s_solve_dev_%s" % (pc, k, s)] = [_vp, _vp, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre]
     for s in ("d", "z"):          # mixed-precision refinement: H = f64 / c64 over L = f32 / c32; every real scalar is a double
@@ -201,6 +206,10 @@ def _protos():
     P["sprs_fsai_destroy"] = [_vp]
     P["sprs_fsai_info"] = [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]
     P["sprs_fsai_factor"] = [_vp, _int, _pp]
+    P["sprs_bjacobi_create"] = [_vp, _i64, _vp, _i64, _pp, C.POINTER(_i64)]
+    P["sprs_bjacobi_destroy"] = [_vp]
+    P["sprs_bjacobi_info"] = [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]
+    P["sprs_bjacobi_block_ptr"] = [_vp, _vp]
     P["sprs_gauss_seidel_create"] = [_vp, _pp]
     P["sprs_gauss_seidel_destroy"] = [_vp]
     for s in ("d", "s"):

@@ -6,6 +6,7 @@ import numpy as np
 
 from . import _lib, gen
 from .amg import AMG
+from .bjacobi import BlockJacobi
 from .device import DevVec, dev_len, dev_ptr, is_device_array, pre_sync, sfx
 from .error import BreakDown, IncompatibleMatrixFormat, InsufficientIterNum, check, solve_result
 from .fsai import FSAI
@@ -50,9 +51,9 @@ class _Handle:
 
 
 def applied_prefix(precond):
-    """"ilu0" / "amg" / "fsai" for such a handle: the solves it preconditions are sprs_<prefix>_<solver>_solve[_dev]_*.  None for
+    """"ilu0" / "amg" / "fsai" / "bjacobi" for such a handle: the solves it preconditions are sprs_<prefix>_<solver>_solve[_dev]_*.  None for
     anything else."""
-    for cls, prefix in ((ILU0, "ilu0"), (AMG, "amg"), (FSAI, "fsai")):
+    for cls, prefix in ((ILU0, "ilu0"), (AMG, "amg"), (FSAI, "fsai"), (BlockJacobi, "bjacobi")):
         if isinstance(precond, cls):
             return prefix
     return None
@@ -108,7 +109,7 @@ class _SolverBase(_Handle):
 
     # ---- the call itself
     def _solve(self, precond, rhs, x, max_iter, tol, want_precond, prefix=None):
-        """prefix: None for a `DiagPrecond` (or no preconditioner); "ilu0" / "amg" / "fsai" for BiCGStab / MINRES / CG / GMRES with such a handle for the
+        """prefix: None for a `DiagPrecond` (or no preconditioner); "ilu0" / "amg" / "fsai" / "bjacobi" for BiCGStab / MINRES / CG / GMRES with such a handle for the
         preconditioner: the same call under the name sprs_<prefix>_<solver>_solve[_dev]_*."""
         L = _lib.lib()
         its = C.c_size_t(0); res = _lib.REAL[self.s](0.0)

@@ -14,5 +14,5 @@ class BiCGStab(_SolverBase):
         return self._solve(None, rhs, x, max_iter, tol, False)
 
     def precond_solve(self, precond, rhs, x, max_iter, tol):
-        """bicg_stab.rs:204-366 (right-preconditioned) by a `DiagPrecond` (Jacobi), an `ILU0`, an `AMG` or an `FSAI`."""
+        """bicg_stab.rs:204-366 (right-preconditioned) by a `DiagPrecond` (Jacobi), an `ILU0`, an `AMG`, an `FSAI` or a `BlockJacobi`."""
         return self._solve(precond, rhs, x, max_iter, tol, True, prefix=applied_prefix(precond))

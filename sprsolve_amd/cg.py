@@ -15,5 +15,5 @@ class CG(_SolverBase):
         return self._solve(None, rhs, x, max_iter, tol, False)
 
     def precond_solve(self, precond, rhs, x, max_iter, tol):
-        """Preconditioned by a `DiagPrecond` (Jacobi), an `ILU0`, an `AMG` or an `FSAI`; InvalidPreconditioner where conj(r).M^-1 r is not positive."""
+        """Preconditioned by a `DiagPrecond` (Jacobi), an `ILU0`, an `AMG`, an `FSAI` or a `BlockJacobi`; InvalidPreconditioner where conj(r).M^-1 r is not positive."""
         return self._solve(precond, rhs, x, max_iter, tol, True, prefix=applied_prefix(precond))

@@ -1013,7 +1013,7 @@ SPRS_API(z, cplx, sprs_c64, double)
 SPRS_API(s, float, float, float)
 SPRS_API(c, cplxf, sprs_c32, float)
 
-// BiCGStab, MINRES, CG and GMRES preconditioned by an ILU(0) handle (ilu0.hip), an AMG handle (amg.hip) or an FSAI handle (fsai.hip): one path, the handle's AppliedPrec view
+// BiCGStab, MINRES, CG and GMRES preconditioned by an ILU(0) handle (ilu0.hip), an AMG handle (amg.hip), an FSAI handle (fsai.hip) or a block-Jacobi handle (bjacobi.hip): one path, the handle's AppliedPrec view
 #define SPRS_APPLIED_SOLVES(X, T, CT, R, NAME, S, PFX)                                                                 \
     int sprs_##PFX##_##NAME##_solve_##X(sprs_##NAME *h, const sprs_##PFX *P, const CT *rhs, size_t rl, CT *x, size_t xl, size_t mi, R tol, size_t *its, R *res) { \
         SPRS_G(return solve<T>(impl_of<S, T>(h), true, PFX##_prec<T>(P), (const T *)rhs, rl, (T *)x, xl, mi, tol, its, res);)  \
@@ -1035,7 +1035,9 @@ SPRS_API(c, cplxf, sprs_c32, float)
     SPRS_APPLIED_SOLVES(X, T, CT, R, cg, Cg, fsai) SPRS_APPLIED_SOLVES(X, T, CT, R, gmres, Gmres, fsai) \
     SPRS_APPLIED_SOLVES(X, T, CT, R, bicgstab, BicgStab, fsai) SPRS_APPLIED_SOLVES(X, T, CT, R, minres, MinRes, fsai) \
     SPRS_APPLIED_SOLVES(X, T, CT, R, idrs, Idrs, ilu0) SPRS_APPLIED_SOLVES(X, T, CT, R, idrs, Idrs, amg) SPRS_APPLIED_SOLVES(X, T, CT, R, idrs, Idrs, fsai) \
-    SPRS_APPLIED_LOBPCG(X, T, CT, R, ilu0) SPRS_APPLIED_LOBPCG(X, T, CT, R, amg) SPRS_APPLIED_LOBPCG(X, T, CT, R, fsai)
+    SPRS_APPLIED_LOBPCG(X, T, CT, R, ilu0) SPRS_APPLIED_LOBPCG(X, T, CT, R, amg) SPRS_APPLIED_LOBPCG(X, T, CT, R, fsai) \
+    SPRS_APPLIED_SOLVES(X, T, CT, R, cg, Cg, bjacobi) SPRS_APPLIED_SOLVES(X, T, CT, R, gmres, Gmres, bjacobi) \
+    SPRS_APPLIED_SOLVES(X, T, CT, R, bicgstab, BicgStab, bjacobi) SPRS_APPLIED_SOLVES(X, T, CT, R, minres, MinRes, bjacobi)
 SPRS_APPLIED_API(d, double, double, double)
 SPRS_APPLIED_API(z, cplx, sprs_c64, double)
 SPRS_APPLIED_API(s, float, float, float)

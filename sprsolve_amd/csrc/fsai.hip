@@ -178,22 +178,15 @@ int fsai_create(const sprs_csr *A, int power, sprs_fsai **out, int64_t *row_out)
     CtxLock lock(c);
     const int64_t n = A->nrows;
     SPRS_HIP_TRY(c, hipSetDevice(c->device));
-    DevBufs tmp;
     // ---- the ascending-columns check, on the device: the pattern never crosses PCIe
-    int *bad;                            // the lowest row of: [0] a zero diagonal, [1] a pivot that is not positive, [2] unsorted columns
-    SPRS_TRY(tmp.alloc(c, &bad, 3));
-    const int h_none[3] = {INT32_MAX, INT32_MAX, INT32_MAX};
-    int h_bad[3] = {INT32_MAX, INT32_MAX, INT32_MAX};
+    SPRS_TRY(sorted_columns_dev(A, "sprs_fsai"));
+    DevBufs tmp;
+    int *bad;                            // the lowest row of: [0] a zero diagonal, [1] a pivot that is not positive
+    SPRS_TRY(tmp.alloc(c, &bad, 2));
+    const int h_none[2] = {INT32_MAX, INT32_MAX};
+    int h_bad[2] = {INT32_MAX, INT32_MAX};
     const dim3 rgrid((unsigned)((n + BLOCK - 1) / BLOCK));
     SPRS_HIP_TRY(c, hipMemcpyAsync(bad, h_none, sizeof(h_none), hipMemcpyHostToDevice, c->stream));
-    if (n) hipLaunchKernelGGL(fsai_sorted_kernel, rgrid, dim3(BLOCK), 0, c->stream, (int)n, A->row_ptr, A->col_idx, bad + 2);
-    SPRS_HIP_TRY(c, hipGetLastError());
-    SPRS_HIP_TRY(c, hipMemcpyAsync(h_bad, bad, sizeof(h_bad), hipMemcpyDeviceToHost, c->stream));
-    SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (h_bad[2] != INT32_MAX) {
-        snprintf(c->err, sizeof(c->err), "sprs_fsai: the column indices of row %lld are not strictly ascending", (long long)h_bad[2]);
-        return SPRS_INVALID_ARGUMENT;
-    }
     // ---- the pattern P
     const int32_t *p_rp = A->row_ptr, *p_ci = A->col_idx;
     if (power == 2) {
@@ -291,6 +284,22 @@ int fsai_mul_host(const sprs_fsai *Pc, const T *in, size_t in_len, T *out, size_
 namespace sprs {
 
 int fsai_check(const sprs_fsai *P, const sprs_csr *A, int dtype, size_t n) { return applied_check(P, A, dtype, n); }
+
+int sorted_columns_dev(const sprs_csr *A, const char *who) {
+    sprs_ctx *c = A->ctx;
+    const int64_t n = A->nrows;
+    DevBufs tmp;
+    int *bad, h_bad = INT32_MAX;
+    SPRS_TRY(tmp.alloc(c, &bad, 1));
+    SPRS_HIP_TRY(c, hipMemcpyAsync(bad, &h_bad, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    if (n) hipLaunchKernelGGL(fsai_sorted_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, (int)n, A->row_ptr, A->col_idx, bad);
+    SPRS_HIP_TRY(c, hipGetLastError());
+    SPRS_HIP_TRY(c, hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (h_bad == INT32_MAX) return SPRS_OK;
+    snprintf(c->err, sizeof(c->err), "%s: the column indices of row %lld are not strictly ascending", who, (long long)h_bad);
+    return SPRS_INVALID_ARGUMENT;
+}
 
 template <class T>
 int fsai_apply(const sprs_fsai *P, const T *in, T *out) {

@@ -512,9 +512,19 @@ template <class T> int amg_apply(const sprs_amg *P, const T *in, T *out);
 // The same for an FSAI handle: fsai_check as ilu0_check, fsai_apply: out = G^H (G in), two launch_spmv calls; in == out is allowed.
 int fsai_check(const sprs_fsai *P, const sprs_csr *A, int dtype, size_t n);
 template <class T> int fsai_apply(const sprs_fsai *P, const T *in, T *out);
+// The lowest row of A whose column indices do not ascend strictly, looked for on the device (the pattern never crosses PCIe):
+// SPRS_INVALID_ARGUMENT and "<who>: the column indices of row .. are not strictly ascending".  Blocking; the caller holds the
+// context's lock and has set the device.
+int sorted_columns_dev(const sprs_csr *A, const char *who);
+
+// ---- bjacobi.hip
+// The same for a block-Jacobi handle: bjacobi_check as ilu0_check, bjacobi_apply: out = blockdiag(A_bb)^-1 in, one launch; in == out
+// is allowed.
+int bjacobi_check(const sprs_bjacobi *P, const sprs_csr *A, int dtype, size_t n);
+template <class T> int bjacobi_apply(const sprs_bjacobi *P, const T *in, T *out);
 
 // ---- an applied preconditioner: a handle whose application is a chain of launches of its own (ILU(0)'s triangular solves,
-// AMG's cycle, FSAI's two SpMVs), asynchronous on the context's stream.  check: SPRS_INVALID_ARGUMENT for a null handle, another scalar type or
+// AMG's cycle, FSAI's two SpMVs, block-Jacobi's one launch), asynchronous on the context's stream.  check: SPRS_INVALID_ARGUMENT for a null handle, another scalar type or
 // context, or a distributed A; SPRS_DIM_MISMATCH for another size.  apply: out = M in on device vectors, in == out allowed.
 template <class T>
 struct AppliedPrec {
@@ -527,6 +537,7 @@ struct AppliedPrec {
 template <class T> AppliedPrec<T> ilu0_prec(const sprs_ilu0 *P);   // the which = 0 solve
 template <class T> AppliedPrec<T> amg_prec(const sprs_amg *P);
 template <class T> AppliedPrec<T> fsai_prec(const sprs_fsai *P);
+template <class T> AppliedPrec<T> bjacobi_prec(const sprs_bjacobi *P);
 
 // ---- what a solve is preconditioned with, from the C entry points down: nothing (a null sprs_diag), a diagonal (Jacobi) or
 // an applied handle (BiCGStab, MINRES, CG and GMRES; CSMINRES refuses any preconditioner and the batched CG takes a sprs_diag

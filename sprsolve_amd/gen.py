@@ -271,6 +271,46 @@ def convection_diffusion_2d(rows, cols, cx=0.3, cy=0.2, dtype=np.float64):
     return indptr, indices, data, rhs
 
 
+def coupled_grid(rows, cols, bs, dtype=np.float64, spread=1e3, stream=300):
+    """A coupled system with bs unknowns per node of a rows x cols grid, Hermitian positive definite, for block preconditioners (no
+    reference analogue): A = L (x) C + blockdiag(e_p e_p^H).  L is the 5-point Dirichlet Laplacian of the grid (2 on the diagonal
+    per direction, -1 off it), C = Q diag(spread^(k / (bs - 1)), k = 0 .. bs - 1) Q^H symmetrised, Q = I - 2 u u^H / (u^H u) a
+    Householder reflector: the couplings inside a node are as strong as those between nodes, and condition C alone costs a point
+    preconditioner a factor of about `spread`.  Unknown a of node p = i * cols + j is row p * bs + a.  u (bs entries), the e_p
+    (bs each, node after node) and the rhs are `uniform(SEED, ..)` on the streams stream (+ 1: imaginary parts), stream + 2 (+ 3)
+    and stream + 4; the complex dtypes use the imaginary parts, the rhs is real.  The diagonal is made real; the CSR is sorted.
+    Returns (indptr, indices, data, rhs) in dtype."""
+    dt = np.dtype(dtype)
+    cx = dt.kind == "c"
+    nn = rows * cols
+    n = nn * bs
+    u = uniform(SEED, bs, stream=stream) + (1j * uniform(SEED, bs, stream=stream + 1) if cx else 0.0)
+    e = uniform(SEED, n, stream=stream + 2) + (1j * uniform(SEED, n, stream=stream + 3) if cx else 0.0)
+    e = e.reshape(nn, bs)
+    Q = np.eye(bs) - 2.0 * np.outer(u, np.conj(u)) / np.vdot(u, u).real
+    lam = spread ** (np.arange(bs) / float(max(bs - 1, 1)))
+    Cm = (Q * lam) @ np.conj(Q).T
+    Cm = (Cm + np.conj(Cm).T) / 2
+    i, j = np.meshgrid(np.arange(rows), np.arange(cols), indexing="ij")
+    i = i.ravel(); j = j.ravel()
+    node = i * cols + j
+    a, b = np.meshgrid(np.arange(bs), np.arange(bs), indexing="ij")
+    a = a.ravel(); b = b.ravel()
+    diag_blocks = 4.0 * Cm.ravel()[None, :] + (e[:, a] * np.conj(e[:, b]))
+    R = [(node[:, None] * bs + a[None, :]).ravel()]; Cc = [(node[:, None] * bs + b[None, :]).ravel()]; V = [diag_blocks.ravel()]
+    for di, dj in ((-1, 0), (1, 0), (0, -1), (0, 1)):
+        ni = i + di; nj = j + dj
+        ok = (ni >= 0) & (ni < rows) & (nj >= 0) & (nj < cols)
+        p = node[ok]; q = (ni * cols + nj)[ok]
+        R.append((p[:, None] * bs + a[None, :]).ravel()); Cc.append((q[:, None] * bs + b[None, :]).ravel())
+        V.append(np.tile(-Cm.ravel(), p.size))
+    r = np.concatenate(R); c = np.concatenate(Cc); v = np.concatenate(V)
+    v = np.where(r == c, v.real, v)
+    indptr, indices, data = _coo_to_csr(n, r, c, v)
+    rhs = uniform(SEED, n, stream=stream + 4)
+    return indptr, indices, (data if cx else data.real).astype(dt), rhs.astype(dt)
+
+
 def poisson3d(nx, ny, nz, z0=0, z1=None, index_dtype=np.int32, values="poisson", seed=SEED):
     """cfg 5: 7-point 3-D Poisson on an nx*ny*nz grid (x fastest), diag +6, neighbours -1,
     truncated at the faces.  Returns the CSR row block for planes [z0, z1) with GLOBAL column

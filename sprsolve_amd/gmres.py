@@ -27,5 +27,5 @@ class GMRES(_SolverBase):
         return self._solve(None, rhs, x, max_iter, tol, False)
 
     def precond_solve(self, precond, rhs, x, max_iter, tol):
-        """Preconditioned from the right by a `DiagPrecond` (Jacobi), an `ILU0`, an `AMG` or an `FSAI`: the residual it reports is the true one's estimate."""
+        """Preconditioned from the right by a `DiagPrecond` (Jacobi), an `ILU0`, an `AMG`, an `FSAI` or a `BlockJacobi`: the residual it reports is the true one's estimate."""
         return self._solve(precond, rhs, x, max_iter, tol, True, prefix=applied_prefix(precond))

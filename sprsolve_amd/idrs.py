@@ -32,4 +32,7 @@ class IDRS(_SolverBase):
 
     def precond_solve(self, precond, rhs, x, max_iter, tol):
         """Preconditioned from the right by a `DiagPrecond` (Jacobi), an `ILU0`, an `AMG` or an `FSAI`: the residual it reports is the recursive one."""
-        return self._solve(precond, rhs, x, max_iter, tol, True, prefix=applied_prefix(precond))
+        prefix = applied_prefix(precond)
+        if prefix == "bjacobi":                              # (the library has no sprs_bjacobi_idrs_* entry points)
+            raise TypeError("IDRS does not take a BlockJacobi: precond must be a DiagPrecond, ILU0, AMG or FSAI")
+        return self._solve(precond, rhs, x, max_iter, tol, True, prefix=prefix)

@@ -46,7 +46,7 @@ class Lobpcg(_Handle):
         k = int(k)
         which, tol = which_and_tol(which, tol, self.s, WHICH)
         prefix = applied_prefix(precond)
-        if precond is not None and prefix is None and not isinstance(precond, DiagPrecond):
+        if precond is not None and (prefix in (None, "bjacobi")) and not isinstance(precond, DiagPrecond):    # (no sprs_bjacobi_lobpcg_*)
             raise TypeError("precond must be a DiagPrecond, ILU0, AMG or FSAI")
         own = None
         if X0 is not None and not is_device_array(X0) and prefix is not None:     # an applied handle has the device entry only

@@ -13,6 +13,6 @@ class MinRes(_SolverBase):
         return self._solve(None, rhs, x, max_iter, tol, False)
 
     def precond_solve(self, precond, rhs, x, max_iter, tol):
-        """minres.rs:178-341, by a `DiagPrecond` (Jacobi), an `ILU0`, an `AMG` or an `FSAI`; the preconditioner must be Hermitian positive
+        """minres.rs:178-341, by a `DiagPrecond` (Jacobi), an `ILU0`, an `AMG`, an `FSAI` or a `BlockJacobi` (real scalar types only: the header says why); the preconditioner must be Hermitian positive
         definite (InvalidPreconditioner by the reference's rule, minres.rs:279-287)."""
         return self._solve(precond, rhs, x, max_iter, tol, True, prefix=applied_prefix(precond))
