@@ -396,6 +396,45 @@ int sprs_csr_read(const sprs_csr *A, int32_t *row_ptr_host, int32_t *col_idx_hos
  * the short kernel, [4] the largest u_i of the table kernel for this scalar type. */
 int sprs_csr_matmul(const sprs_csr *A, const sprs_csr *B, sprs_csr **out, int64_t *info);
 
+/* ---------------------------------------------------------------- orderings: graph colouring and the symmetric permutation
+ * For square, single-GPU handles (SPRS_NOT_SQUARE; a distributed A is SPRS_INVALID_ARGUMENT, text in sprs_last_error).  The
+ * reference has neither.  sprs_ilu0_create_ordered (below) is built from both.
+ *
+ * sprs_csr_color colours the graph of A's pattern: the vertices are the rows, and i ~ j iff i != j and A stores (i, j) or
+ * (j, i).  Explicit zeros count, the pattern may be non-symmetric, values are never read (the colours do not depend on the
+ * scalar type).  The priority of vertex i is w(i), 64 unsigned bits computed from the seed and i alone:
+ *     z = seed + (i + 1) * 0x9E3779B97F4A7C15            (all arithmetic modulo 2^64)
+ *     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *     z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *     w(i) = z ^ (z >> 31)
+ * and the colouring is greedy first-fit in decreasing order of the pair (w(i), i):
+ *     colour[i] = -1 for all i
+ *     for i in decreasing (w(i), i):  colour[i] = the smallest c >= 0 that no neighbour j of i with colour[j] >= 0 has
+ * The device computes exactly this colouring by Jones-Plassmann rounds, one kernel launch each:
+ *     repeat until no vertex is uncoloured:
+ *         S = the uncoloured i whose (w(i), i) exceeds that of every uncoloured neighbour     (an independent set)
+ *         for i in S, in any order:  colour[i] = the smallest c >= 0 no coloured neighbour of i has
+ * (no neighbour of a vertex of S is written in its round, so the round runs in place and its result does not depend on the
+ * launch geometry; the largest uncoloured vertex is always in S, so at most n rounds run).  colors_host receives n values in
+ * 0 .. *ncolors_out - 1; *ncolors_out is the largest colour + 1 and *rounds_out the number of rounds (both may be NULL).
+ * n = 0: zero colours, zero rounds.  Sorting the rows by colour (stably) gives a permutation under which every colour is a
+ * diagonal block of P A P^T, and the dependency levels of its triangles are at most the colours.
+ * Temporary device memory: 4 bytes per entry + 16 per row.
+ *
+ * sprs_csr_permute builds B = P A P^T as an ordinary, independent handle: it owns its arrays, outlives A, gets whatever
+ * stream format its creation finds, and every entry point takes it.  perm_host[p] is the row of A that becomes row p of B
+ * (new -> old):
+ *     B[p, q] = A[perm[p], perm[q]]
+ *     row p of B:  for each stored (perm[p], j, v) of A:  store (inv[j], v), inv the inverse of perm;  then sort the row by column
+ *                  with a STABLE sort
+ * The columns of every row of B ascend.  The rows of A may be stored in any order and may hold duplicate columns: duplicates
+ * stay duplicates, in their stored order (as in sprs_csr_adjoint), so B's columns ascend strictly exactly where A's rows hold
+ * none.  The values are bit copies.  perm must have A.nrows entries, each in [0, nrows), none twice: otherwise SPRS_INVALID_ARGUMENT with
+ * the offending entry in sprs_last_error.  The construction runs on the device (inverse, row-length gather and scan, one
+ * wavefront per row: csrc/order.hip); only perm crosses PCIe. */
+int sprs_csr_color(const sprs_csr *A, uint64_t seed, int32_t *colors_host, int64_t *ncolors_out, int64_t *rounds_out);
+int sprs_csr_permute(const sprs_csr *A, const int32_t *perm_host, size_t perm_len, sprs_csr **out);
+
 /* ---------------------------------------------------------------- LSMR
  * Fong & Saunders' LSMR: x minimises |rhs - A x|_2, or with damp > 0 |[A; damp I] x - [rhs; 0]|_2, for A of ANY shape (m rows,
  * n columns; rank-deficient and inconsistent systems included; on an under-determined system started from x = 0 the minimum-norm
@@ -858,12 +897,33 @@ int sprs_dist_mul_vec_dev_c(const sprs_csr *A, sprs_c32 *x_ext_dev, sprs_c32 *y_
  * one device copy more); which = 2: k; which = 0: 2k - 2, one for k = 1.  sprs_ilu0_levels reports the level counts of the
  * pattern as for an exact handle and k - 1 / k as the two launch counts.  in == out is allowed for every `which`; `in` is
  * never written unless it is `out`.  sprs_ilu0_sweeps: k, 0 for an exact handle, -1 for NULL.  Everything that takes a
- * sprs_ilu0 (the solves, sprs_ilu0_cg_*, sprs_ilu0_gmres_*, sprs_ilu0_bicgstab_*, sprs_ilu0_minres_*) takes either kind. */
+ * sprs_ilu0 (the solves, sprs_ilu0_cg_*, sprs_ilu0_gmres_*, sprs_ilu0_bicgstab_*, sprs_ilu0_minres_*) takes either kind.
+ *
+ * Ordered ILU(0).  sprs_ilu0_create_ordered(A, sweeps, order, perm_host, perm_len, ...) factorises B = P A P^T in place of A
+ * (the orderings section above): order = SPRS_ORDER_NATURAL is sprs_ilu0_create_sweeps itself (perm ignored);
+ * SPRS_ORDER_MULTICOLOR takes the stable sort of the rows by sprs_csr_color's colours with seed 0 (perm ignored);
+ * SPRS_ORDER_PERM takes perm_host (new -> old, checked as by sprs_csr_permute).  With ord = the inverse of perm:
+ *     B[p, q] = A[perm[p], perm[q]];   L U ~ B by the factorisation loop above, run on B
+ *     which = 0:  out = P^T U^-1 L^-1 P in:   t_p = in[perm[p]];  y = L^-1 t;  z = U^-1 y  (the loops above on B's rows);  out[perm[p]] = z_p
+ *     which = 1:  out = P^T L^-1 P in;   which = 2:  out = P^T U^-1 P in   (the same with one solve)
+ * Vectors go in and come out in A's numbering; in == out is allowed.  The gather is the lower solve's own load and the scatter
+ * the upper solve's own store, so an application costs the launches of the two solves and nothing else; the handle owns one
+ * n-vector in B's numbering.  sprs_ilu0_read returns the values at A's CSR positions: entry (i, j) is l where ord(j) < ord(i)
+ * and u otherwise.  sprs_ilu0_levels reports the levels and launches of B's triangles (at most the number of colours for the
+ * multicolour ordering).  *row_out of SPRS_ZERO_DIAGONAL is given in A's numbering: perm[p] of the smallest offending row p of B.
+ * An ordering together with sweeps != 0 is SPRS_INVALID_ARGUMENT (text in sprs_last_error): with few levels the sweeps have no
+ * purpose.  sprs_ilu0_order: 1 and the n entries of perm in perm_host (may be NULL) for an ordered handle, 0 for a natural one,
+ * -1 for NULL.  The solvers take an ordered handle like any other; it is checked against A, not B. */
 #define SPRS_ILU0_MAX_SWEEPS 4096
+#define SPRS_ORDER_NATURAL 0
+#define SPRS_ORDER_MULTICOLOR 1
+#define SPRS_ORDER_PERM 2
 typedef struct sprs_ilu0 sprs_ilu0;
 int sprs_ilu0_create(const sprs_csr *A, sprs_ilu0 **out, int64_t *row_out);   /* row_out may be NULL */
 int sprs_ilu0_create_sweeps(const sprs_csr *A, int sweeps, sprs_ilu0 **out, int64_t *row_out);   /* row_out may be NULL */
 int sprs_ilu0_sweeps(const sprs_ilu0 *P);
+int sprs_ilu0_create_ordered(const sprs_csr *A, int sweeps, int order, const int32_t *perm_host, size_t perm_len, sprs_ilu0 **out, int64_t *row_out);   /* perm_host, row_out may be NULL */
+int sprs_ilu0_order(const sprs_ilu0 *P, int32_t *perm_host);
 int sprs_ilu0_destroy(sprs_ilu0 *P);           /* NULL is a no-op */
 int sprs_ilu0_levels(const sprs_ilu0 *P, int64_t *lower_levels, int64_t *upper_levels, int64_t *lower_launches, int64_t *upper_launches);   /* any pointer may be NULL */
 int sprs_ilu0_read(const sprs_ilu0 *P, void *val_host);

@@ -25,6 +25,7 @@ from .lsmr import LSMR  # noqa: F401
 from .device import Context, DevVec, default_ctx  # noqa: F401
 from .mat import HipCsr, MatVecMul  # noqa: F401
 from .minres import MinRes  # noqa: F401
+from .order import color_order, inverse_permutation  # noqa: F401
 from .precond import DiagPrecond  # noqa: F401
 from .refine import Refine  # noqa: F401
 from .svds import Svds  # noqa: F401

@@ -18,6 +18,7 @@ ERR_HIP, ERR_RCCL, ERR_NO_DEVICE = 100, 101, 102
 SOLVER_BICGSTAB, SOLVER_MINRES, SOLVER_CSMINRES, SOLVER_CG, SOLVER_GMRES, SOLVER_LSMR, SOLVER_IDRS = 1, 2, 3, 4, 5, 6, 7
 GMRES_MAX_RESTART = 64
 IDRS_MAX_S = 8
+ORDER_NATURAL, ORDER_MULTICOLOR, ORDER_PERM = 0, 1, 2
 INNER_CG, INNER_GMRES = 0, 1
 EIGSH_MAX_NCV = 64
 EIGSH_LARGEST, EIGSH_SMALLEST = 0, 1
@@ -166,6 +167,8 @@ def _protos():
     P["sprs_csr_adjoint"] = [_vp, _int, _pp]
     P["sprs_csr_matmul"] = [_vp, _vp, _pp, C.POINTER(_i64)]
     P["sprs_csr_read"] = [_vp, _vp, _vp, _vp]
+    P["sprs_csr_color"] = [_vp, C.c_uint64, _vp, C.POINTER(_i64), C.POINTER(_i64)]
+    P["sprs_csr_permute"] = [_vp, _vp, _sz, _pp]
     for k in ("bicgstab", "minres", "csminres", "cg", "gmres", "cgmany", "cgshift", "idrs", "lsmr", "eigsh", "lobpcg", "svds", "expm"):
         P["sprs_%s_destroy" % k] = [_vp]
     for s in ("d", "zd", "z", "s", "cs", "c"):
@@ -194,6 +197,8 @@ def _protos():
     P["sprs_ilu0_create"] = [_vp, _pp, C.POINTER(_i64)]
     P["sprs_ilu0_create_sweeps"] = [_vp, _int, _pp, C.POINTER(_i64)]
     P["sprs_ilu0_sweeps"] = [_vp]
+    P["sprs_ilu0_create_ordered"] = [_vp, _int, _int, _vp, _sz, _pp, C.POINTER(_i64)]
+    P["sprs_ilu0_order"] = [_vp, _vp]
     P["sprs_ilu0_destroy"] = [_vp]
     P["sprs_ilu0_levels"] = [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]
     P["sprs_ilu0_read"] = [_vp, _vp]

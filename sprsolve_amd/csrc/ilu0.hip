@@ -25,6 +25,11 @@
 // slice is full whatever the levels look like and neighbouring lanes gather neighbouring x.  A sweep reads the previous
 // sweep's vector and writes another one (never in place), so its result does not depend on the launch geometry; the handle
 // owns the three vectors the sweeps alternate between.
+//
+// An ORDERED handle (sprs_ilu0_create_ordered) is the exact handle of B = P A P^T: order.hip permutes A's arrays,
+// the creation above runs on them unchanged, and the factor values go back to A's CSR positions for sprs_ilu0_read.  Its solves
+// work in B's numbering on the handle's own y and apply P^T F^-1 P without a launch of their own: tri_row gathers its right-hand
+// side at in[perm[row]] and stores its result at ext[perm[row]] as well (the ORD template flag; ORD_NONE is the natural path).
 #include <algorithm>
 
 #include "device.hpp"
@@ -80,31 +85,43 @@ struct TriDev {
 
 // One row by one lane: sigma over the row's entries in ascending column order, then the row's own element.  `in` and `out` may
 // be the same vector; out[c] of an entry was written by an earlier level.
-template <class T, bool UPPER>
-__device__ __forceinline__ void tri_row(const TriDev<T> &F, int s, int t, const T *in, T *out) {
+// ORD (an ordered handle; `out` is then a vector of the handle's, in the permuted numbering the factors are stored in):
+// ORD_GATHER reads the row's right-hand side at in[perm[row]], ORD_SCATTER also stores the row's result at ext[perm[row]] — the
+// two ends of P^T F^-1 P folded into the solves' own load and store.  `in` may be `ext`: a lane touches its own row's element only.
+enum : int { ORD_NONE = 0, ORD_GATHER = 1, ORD_SCATTER = 2 };
+template <class T>
+struct OrdDev {
+    const int32_t *perm;                 // new -> old
+    T *ext;
+};
+
+template <class T, bool UPPER, int ORD>
+__device__ __forceinline__ void tri_row(const TriDev<T> &F, int s, int t, const T *in, T *out, const OrdDev<T> &O) {
     const int p = s * ILU_SLICE + t;
     const int row = F.prow[p];
     if (row < 0) return;
     const T sigma = sell_fold<T>(F.M, p, out);
-    const T d = ssub(in[row], sigma);                                // (in[row] is loaded after the fold, not held across it)
-    if (UPPER) out[row] = sdiv(d, F.piv[p]);
-    else out[row] = d;
+    const int old = ORD ? O.perm[row] : row;
+    T d = ssub(in[(ORD & ORD_GATHER) ? old : row], sigma);           // (in[row] is loaded after the fold, not held across it)
+    if (UPPER) d = sdiv(d, F.piv[p]);
+    out[row] = d;
+    if (ORD & ORD_SCATTER) O.ext[old] = d;
 }
 
 // a level of more than BLOCK rows: one wavefront per slice
-template <class T, bool UPPER>
-__global__ __launch_bounds__(BLOCK) void tri_level_kernel(TriDev<T> F, int s0, int s1, const T *in, T *out) {
+template <class T, bool UPPER, int ORD>
+__global__ __launch_bounds__(BLOCK) void tri_level_kernel(TriDev<T> F, int s0, int s1, const T *in, T *out, OrdDev<T> O) {
     const int s = s0 + (int)blockIdx.x * NWAVE + (int)(threadIdx.x >> 6);
-    if (s < s1) tri_row<T, UPPER>(F, s, threadIdx.x & (WAVE - 1), in, out);
+    if (s < s1) tri_row<T, UPPER, ORD>(F, s, threadIdx.x & (WAVE - 1), in, out, O);
 }
 
 // levels [l0, l1) of at most BLOCK rows (NWAVE slices) each: one workgroup, a barrier between two levels
-template <class T, bool UPPER>
-__global__ __launch_bounds__(BLOCK) void tri_batch_kernel(TriDev<T> F, int l0, int l1, const T *in, T *out) {
+template <class T, bool UPPER, int ORD>
+__global__ __launch_bounds__(BLOCK) void tri_batch_kernel(TriDev<T> F, int l0, int l1, const T *in, T *out, OrdDev<T> O) {
     const int w = threadIdx.x >> 6, t = threadIdx.x & (WAVE - 1);
     for (int l = l0; l < l1; ++l) {
         const int s = F.lvl_slice[l] + w;
-        if (s < F.lvl_slice[l + 1]) tri_row<T, UPPER>(F, s, t, in, out);
+        if (s < F.lvl_slice[l + 1]) tri_row<T, UPPER, ORD>(F, s, t, in, out, O);
         __syncthreads();
     }
 }
@@ -198,6 +215,10 @@ struct sprs_ilu0 {
     int sweeps = 0;                      // 0: exact level-scheduled solves; k >= 1: k Jacobi sweeps on natural-order factors
     void *sbuf[2] = {nullptr, nullptr};  // device, n of T each: with ybuf the vectors the sweeps alternate between (sweeps > 0)
     void *in_tmp = nullptr, *out_tmp = nullptr;   // staging of the host entry points (lazily allocated)
+    // An ordered handle (sprs_ilu0_create_ordered): L, U and ybuf live in the numbering of B = P A P^T, fval and every vector that
+    // goes in or comes out in A's.
+    int32_t *perm = nullptr;             // device, n: row perm[p] of A is row p of B; null = natural order
+    std::vector<int32_t> h_perm;
 };
 
 namespace {
@@ -208,19 +229,32 @@ TriDev<T> tri_dev(const IluTri &F) {
 }
 
 // out = F^-1 in: the launches of the factor's plan, asynchronous on the context's stream
-template <class T, bool UPPER>
-int tri_solve(sprs_ctx *c, const IluTri &F, const T *in, T *out) {
+template <class T, bool UPPER, int ORD = ORD_NONE>
+int tri_solve(sprs_ctx *c, const IluTri &F, const T *in, T *out, OrdDev<T> O = OrdDev<T>{nullptr, nullptr}) {
     const TriDev<T> D = tri_dev<T>(F);
     for (const IluLaunch &p : F.plan) {
         if (p.batch) {
-            hipLaunchKernelGGL((tri_batch_kernel<T, UPPER>), dim3(1), dim3(BLOCK), 0, c->stream, D, p.l0, p.l1, in, out);
+            hipLaunchKernelGGL((tri_batch_kernel<T, UPPER, ORD>), dim3(1), dim3(BLOCK), 0, c->stream, D, p.l0, p.l1, in, out, O);
         } else {
             const int s0 = F.h_lvl_slice[p.l0], s1 = F.h_lvl_slice[p.l1];
-            hipLaunchKernelGGL((tri_level_kernel<T, UPPER>), dim3((s1 - s0 + NWAVE - 1) / NWAVE), dim3(BLOCK), 0, c->stream, D, s0, s1, in, out);
+            hipLaunchKernelGGL((tri_level_kernel<T, UPPER, ORD>), dim3((s1 - s0 + NWAVE - 1) / NWAVE), dim3(BLOCK), 0, c->stream, D, s0, s1, in, out, O);
         }
     }
     SPRS_HIP_TRY(c, hipGetLastError());
     return SPRS_OK;
+}
+
+// An ordered handle's solves: P^T F^-1 P with the handle's y as the vector in the permuted numbering, no launch beyond the
+// factors' plans.  An application gathers in its lower solve, runs the upper solve in place on y and scatters from it.
+template <class T>
+int ordered_apply(const sprs_ilu0 *P, int which, const T *in, T *out) {
+    sprs_ctx *c = P->ctx;
+    T *y = (T *)P->ybuf;
+    const OrdDev<T> O{P->perm, out};
+    if (which == 1) return tri_solve<T, false, ORD_GATHER | ORD_SCATTER>(c, P->L, in, y, O);
+    if (which == 2) return tri_solve<T, true, ORD_GATHER | ORD_SCATTER>(c, P->U, in, y, O);
+    SPRS_TRY((tri_solve<T, false, ORD_GATHER>(c, P->L, in, y, O)));
+    return tri_solve<T, true, ORD_SCATTER>(c, P->U, (const T *)y, y, O);
 }
 
 // The k-sweep solves of the header on the stream: which = 1 costs k - 1 launches, which = 2 k, which = 0 2k - 2 (one for k = 1).
@@ -313,10 +347,10 @@ int build_tri(IluTri &F, const std::vector<int32_t> &lvl_ptr, const std::vector<
 }
 
 template <class T>
-int ilu0_create(const sprs_csr *A, int sweeps, sprs_ilu0 **out, int64_t *row_out) {
-    sprs_ctx *c = A->ctx;
+int ilu0_create(const CsrView &A, int sweeps, sprs_ilu0 **out, int64_t *row_out) {
+    sprs_ctx *c = A.ctx;
     CtxLock lock(c);
-    const int64_t n = A->nrows, nnz = A->nnz;
+    const int64_t n = A.nrows, nnz = A.nnz;
     SPRS_HIP_TRY(c, hipSetDevice(c->device));
     // the pattern on the host: its checks, the diagonal positions and both level rules
     std::vector<int32_t> rp, ci;
@@ -343,7 +377,7 @@ int ilu0_create(const sprs_csr *A, int sweeps, sprs_ilu0 **out, int64_t *row_out
     group_by_level(ulevel, nulev, uptr, urows);
 
     auto *P = new sprs_ilu0();
-    P->ctx = c; P->dtype = A->dtype; P->n = n; P->nnz = nnz; P->sweeps = sweeps;
+    P->ctx = c; P->dtype = A.dtype; P->n = n; P->nnz = nnz; P->sweeps = sweeps;
     int32_t *d_dpos = nullptr, *d_rows = nullptr, *d_lptr = nullptr;
     int *d_bad = nullptr;
     auto fail = [&](int st) {
@@ -359,14 +393,14 @@ int ilu0_create(const sprs_csr *A, int sweeps, sprs_ilu0 **out, int64_t *row_out
     if (!dev_upload(&d_dpos, dpos.data(), dpos.size()) || !dev_upload(&d_rows, lrows.data(), lrows.size()) ||
         !dev_upload(&d_lptr, lptr.data(), lptr.size()) || hipMalloc((void **)&d_bad, sizeof(int)) != hipSuccess) return fail(SPRS_ERR_HIP);
     int bad = INT32_MAX;
-    if ((nnz && hipMemcpyAsync(a, A->val, sizeof(T) * (size_t)nnz, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) ||
+    if ((nnz && hipMemcpyAsync(a, A.val, sizeof(T) * (size_t)nnz, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) ||
         hipMemcpyAsync(d_bad, &bad, sizeof(int), hipMemcpyHostToDevice, c->stream) != hipSuccess) return fail(SPRS_ERR_HIP);
     // the factorisation: level by level, on the lower solve's plan
     for (const IluLaunch &p : make_plan(lptr)) {
-        if (p.batch) hipLaunchKernelGGL((ilu_batch_kernel<T>), dim3(1), dim3(BLOCK), 0, c->stream, d_lptr, p.l0, p.l1, d_rows, A->row_ptr, A->col_idx, d_dpos, a);
+        if (p.batch) hipLaunchKernelGGL((ilu_batch_kernel<T>), dim3(1), dim3(BLOCK), 0, c->stream, d_lptr, p.l0, p.l1, d_rows, A.row_ptr, A.col_idx, d_dpos, a);
         else {
             const int cnt = lptr[p.l1] - lptr[p.l0];
-            hipLaunchKernelGGL((ilu_level_kernel<T>), dim3((cnt + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, cnt, d_rows + lptr[p.l0], A->row_ptr, A->col_idx, d_dpos, a);
+            hipLaunchKernelGGL((ilu_level_kernel<T>), dim3((cnt + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, cnt, d_rows + lptr[p.l0], A.row_ptr, A.col_idx, d_dpos, a);
         }
     }
     if (n) hipLaunchKernelGGL((ilu_pivot_check_kernel<T>), dim3((int)std::min<int64_t>((n + BLOCK - 1) / BLOCK, 2048)), dim3(BLOCK), 0, c->stream,
@@ -393,6 +427,53 @@ int ilu0_create(const sprs_csr *A, int sweeps, sprs_ilu0 **out, int64_t *row_out
     return SPRS_OK;
 }
 
+// the factor values of B's entries at the positions of A's arrays they came from
+template <class T>
+__global__ __launch_bounds__(BLOCK) void ilu_unpermute_kernel(int64_t nnz, const int32_t *__restrict__ src, const T *__restrict__ fb, T *__restrict__ fa) {
+    for (int64_t q = (int64_t)blockIdx.x * BLOCK + threadIdx.x; q < nnz; q += (int64_t)gridDim.x * BLOCK) fa[src[q]] = fb[q];
+}
+
+// The ordered handle: the exact handle of B = P A P^T (built here on raw arrays, no operator handle), its factor values moved
+// back to A's positions, and the permutation for the solves.  perm: a checked permutation.
+template <class T>
+int ilu0_create_ordered(const sprs_csr *A, std::vector<int32_t> perm, sprs_ilu0 **out, int64_t *row_out) {
+    sprs_ctx *c = A->ctx;
+    CtxLock lock(c);
+    SPRS_HIP_TRY(c, hipSetDevice(c->device));
+    const int64_t n = A->nrows, nnz = A->nnz;
+    SPRS_TRY(sorted_columns_dev(A, "sprs_ilu0"));   // (the permutation ranks a row's columns: they must be distinct)
+    DevBufs tmp;
+    int32_t *d_perm, *rp = nullptr, *ci = nullptr, *src = nullptr;
+    void *val = nullptr;
+    T *fa;
+    SPRS_TRY(tmp.alloc(c, &d_perm, (size_t)n + 2));
+    SPRS_TRY(tmp.alloc(c, &fa, (size_t)nnz + 2));
+    if (n) SPRS_HIP_TRY(c, hipMemcpyAsync(d_perm, perm.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    SPRS_TRY(csr_permute_arrays(A, d_perm, &rp, &ci, &val, &src));
+    tmp.p.push_back(rp); tmp.p.push_back(ci); tmp.p.push_back(val); tmp.p.push_back(src);
+    const CsrView B{c, A->dtype, n, n, nnz, rp, ci, val};
+    sprs_ilu0 *P = nullptr;
+    int64_t row = -1;
+    const int st = ilu0_create<T>(B, 0, &P, &row);
+    if (st == SPRS_ZERO_DIAGONAL && row_out && row >= 0) *row_out = perm[(size_t)row];
+    SPRS_TRY(st);
+    if (nnz) {
+        hipLaunchKernelGGL((ilu_unpermute_kernel<T>), dim3((unsigned)std::min<int64_t>((nnz + BLOCK - 1) / BLOCK, 4 * (int64_t)grid_for(c))), dim3(BLOCK), 0, c->stream,
+                           nnz, src, (const T *)P->fval, fa);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+            sprs_ilu0_destroy(P);
+            snprintf(c->err, sizeof(c->err), "sprs_ilu0: moving the factors to A's positions failed on the device");
+            return SPRS_ERR_HIP;
+        }
+    }
+    (void)hipFree(P->fval);
+    P->fval = fa; tmp.release(fa);
+    P->perm = d_perm; tmp.release(d_perm);
+    P->h_perm = std::move(perm);
+    *out = P;
+    return SPRS_OK;
+}
+
 template <class T>
 int ilu0_solve_host(const sprs_ilu0 *Pc, int which, const T *in, size_t in_len, T *out, size_t out_len) {
     if (!Pc || !in || !out || Pc->dtype != dtype_of<T>::value || which < 0 || which > 2) return SPRS_INVALID_ARGUMENT;
@@ -413,6 +494,7 @@ int ilu0_apply(const sprs_ilu0 *P, int which, const T *in, T *out) {
     CtxLock lock(c);   // ybuf is per-handle scratch
     SPRS_HIP_TRY(c, hipSetDevice(c->device));
     if (P->sweeps) return sweeps_apply<T>(P, which, in, out);
+    if (P->perm) return ordered_apply<T>(P, which, in, out);
     if (which == 1) return tri_solve<T, false>(c, P->L, in, out);
     if (which == 2) return tri_solve<T, true>(c, P->U, in, out);
     SPRS_TRY((tri_solve<T, false>(c, P->L, in, (T *)P->ybuf)));
@@ -451,10 +533,10 @@ int sprs_ilu0_create_sweeps(const sprs_csr *A, int sweeps, sprs_ilu0 **out, int6
         }
         if (A->nrows != A->ncols) return SPRS_NOT_SQUARE;
         switch (A->dtype) {
-            case DT_D: return ilu0_create<double>(A, sweeps, out, row_out);
-            case DT_Z: return ilu0_create<cplx>(A, sweeps, out, row_out);
-            case DT_S: return ilu0_create<float>(A, sweeps, out, row_out);
-            case DT_C: return ilu0_create<cplxf>(A, sweeps, out, row_out);
+            case DT_D: return ilu0_create<double>(csr_view(A), sweeps, out, row_out);
+            case DT_Z: return ilu0_create<cplx>(csr_view(A), sweeps, out, row_out);
+            case DT_S: return ilu0_create<float>(csr_view(A), sweeps, out, row_out);
+            case DT_C: return ilu0_create<cplxf>(csr_view(A), sweeps, out, row_out);
         }
         return SPRS_INVALID_ARGUMENT;)
 }
@@ -463,11 +545,48 @@ int sprs_ilu0_create(const sprs_csr *A, sprs_ilu0 **out, int64_t *row_out) { ret
 
 int sprs_ilu0_sweeps(const sprs_ilu0 *P) { return P ? P->sweeps : -1; }
 
+int sprs_ilu0_create_ordered(const sprs_csr *A, int sweeps, int order, const int32_t *perm_host, size_t perm_len, sprs_ilu0 **out, int64_t *row_out) {
+    if (order == SPRS_ORDER_NATURAL) return sprs_ilu0_create_sweeps(A, sweeps, out, row_out);
+    SPRS_G(
+        if (!A || !out) return SPRS_INVALID_ARGUMENT;
+        *out = nullptr;
+        if (row_out) *row_out = -1;
+        SPRS_TRY(single_gpu_only(A, "sprs_ilu0"));
+        if (order != SPRS_ORDER_MULTICOLOR && order != SPRS_ORDER_PERM) return refuse(A->ctx, "sprs_ilu0", "order must be SPRS_ORDER_NATURAL, _MULTICOLOR or _PERM, got %d", order);
+        if (sweeps != 0) return refuse(A->ctx, "sprs_ilu0", "an ordering takes exact solves only (sweeps = 0), got sweeps = %d: with few levels the sweeps have no purpose", sweeps);
+        if (A->nrows != A->ncols) return SPRS_NOT_SQUARE;
+        std::vector<int32_t> perm;
+        if (order == SPRS_ORDER_MULTICOLOR) {
+            std::vector<int32_t> colors;
+            int64_t ncolors = 0;
+            SPRS_TRY(csr_color_host(A, 0, colors, &ncolors, nullptr));
+            perm = color_major_perm(colors, ncolors);
+        } else {
+            if (!perm_host && perm_len) return SPRS_INVALID_ARGUMENT;
+            SPRS_TRY(perm_check(A->ctx, "sprs_ilu0", perm_host, perm_len, A->nrows));
+            perm.assign(perm_host, perm_host + perm_len);
+        }
+        switch (A->dtype) {
+            case DT_D: return ilu0_create_ordered<double>(A, std::move(perm), out, row_out);
+            case DT_Z: return ilu0_create_ordered<cplx>(A, std::move(perm), out, row_out);
+            case DT_S: return ilu0_create_ordered<float>(A, std::move(perm), out, row_out);
+            case DT_C: return ilu0_create_ordered<cplxf>(A, std::move(perm), out, row_out);
+        }
+        return SPRS_INVALID_ARGUMENT;)
+}
+
+int sprs_ilu0_order(const sprs_ilu0 *P, int32_t *perm_host) {
+    if (!P) return -1;
+    if (!P->perm) return 0;
+    if (perm_host) std::copy(P->h_perm.begin(), P->h_perm.end(), perm_host);
+    return 1;
+}
+
 int sprs_ilu0_destroy(sprs_ilu0 *P) {
     if (!P) return SPRS_OK;
     if (P->ctx) { (void)hipSetDevice(P->ctx->device); (void)hipStreamSynchronize(P->ctx->stream); }
     P->L.release(); P->U.release();
-    for (void *p : {P->fval, P->ybuf, P->sbuf[0], P->sbuf[1], P->in_tmp, P->out_tmp}) if (p) (void)hipFree(p);
+    for (void *p : {P->fval, P->ybuf, P->sbuf[0], P->sbuf[1], P->in_tmp, P->out_tmp, (void *)P->perm}) if (p) (void)hipFree(p);
     delete P;
     return SPRS_OK;
 }

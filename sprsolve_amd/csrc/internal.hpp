@@ -428,22 +428,36 @@ bool dev_upload(U **dst, const U *src, size_t count) {
     return count == 0 || hipMemcpy(*dst, src, sizeof(U) * count, hipMemcpyHostToDevice) == hipSuccess;
 }
 
+// The device arrays of a single-GPU CSR matrix without the handle around them: what a set-up that runs on raw arrays (ILU(0) on a
+// permuted copy) is given, so that it cannot read handle state that is not there.
+struct CsrView {
+    sprs_ctx *ctx;
+    int dtype;
+    int64_t nrows, ncols, nnz;
+    const int32_t *row_ptr, *col_idx;
+    const void *val;
+};
+inline CsrView csr_view(const sprs_csr *A) { return CsrView{A->ctx, A->dtype, A->nrows, A->ncols, A->nnz, A->row_ptr, A->col_idx, A->val}; }
+
 // A's pattern (and, where val_host is given, its nnz values) on the host, with the check that every row's columns ascend
 // strictly: SPRS_INVALID_ARGUMENT and a text that starts with `who`.  The caller holds the context's lock and has set the device.
-inline int host_pattern(const sprs_csr *A, const char *who, std::vector<int32_t> &rp, std::vector<int32_t> &ci, void *val_host = nullptr) {
-    sprs_ctx *c = A->ctx;
-    rp.assign((size_t)A->nrows + 1, 0); ci.resize((size_t)A->nnz);
-    SPRS_HIP_TRY(c, hipMemcpyAsync(rp.data(), A->row_ptr, sizeof(int32_t) * rp.size(), hipMemcpyDeviceToHost, c->stream));
-    if (A->nnz) SPRS_HIP_TRY(c, hipMemcpyAsync(ci.data(), A->col_idx, sizeof(int32_t) * ci.size(), hipMemcpyDeviceToHost, c->stream));
-    if (A->nnz && val_host) SPRS_HIP_TRY(c, hipMemcpyAsync(val_host, A->val, dtype_size(A->dtype) * (size_t)A->nnz, hipMemcpyDeviceToHost, c->stream));
+inline int host_pattern(const CsrView &A, const char *who, std::vector<int32_t> &rp, std::vector<int32_t> &ci, void *val_host = nullptr) {
+    sprs_ctx *c = A.ctx;
+    rp.assign((size_t)A.nrows + 1, 0); ci.resize((size_t)A.nnz);
+    SPRS_HIP_TRY(c, hipMemcpyAsync(rp.data(), A.row_ptr, sizeof(int32_t) * rp.size(), hipMemcpyDeviceToHost, c->stream));
+    if (A.nnz) SPRS_HIP_TRY(c, hipMemcpyAsync(ci.data(), A.col_idx, sizeof(int32_t) * ci.size(), hipMemcpyDeviceToHost, c->stream));
+    if (A.nnz && val_host) SPRS_HIP_TRY(c, hipMemcpyAsync(val_host, A.val, dtype_size(A.dtype) * (size_t)A.nnz, hipMemcpyDeviceToHost, c->stream));
     SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (int64_t i = 0; i < A->nrows; ++i)
+    for (int64_t i = 0; i < A.nrows; ++i)
         for (int32_t k = rp[i] + 1; k < rp[i + 1]; ++k)
             if (ci[k] <= ci[k - 1]) {
                 snprintf(c->err, sizeof(c->err), "%s: the column indices of row %lld are not strictly ascending", who, (long long)i);
                 return SPRS_INVALID_ARGUMENT;
             }
     return SPRS_OK;
+}
+inline int host_pattern(const sprs_csr *A, const char *who, std::vector<int32_t> &rp, std::vector<int32_t> &ci, void *val_host = nullptr) {
+    return host_pattern(csr_view(A), who, rp, ci, val_host);
 }
 
 // position of the diagonal entry of row i in ci (columns strictly ascending), or -1
@@ -502,6 +516,19 @@ int applied_check(const H *P, const sprs_csr *A, int dtype, size_t n) {
 // U^-1 in (2) on device vectors, asynchronous on the context's stream; in == out is allowed.
 int ilu0_check(const sprs_ilu0 *P, const sprs_csr *A, int dtype, size_t n);
 template <class T> int ilu0_apply(const sprs_ilu0 *P, int which, const T *in, T *out);
+
+// ---- order.hip
+// perm (host, new -> old) is a permutation of 0 .. n - 1, or SPRS_INVALID_ARGUMENT with "<who>: ..." in the context's text.
+int perm_check(const sprs_ctx *c, const char *who, const int32_t *perm, size_t len, int64_t n);
+// The colours of sprs_csr_color on the host (the header's rule); ncolors / rounds may be null.  Blocking; takes the lock itself.
+int csr_color_host(const sprs_csr *A, uint64_t seed, std::vector<int32_t> &colors, int64_t *ncolors, int64_t *rounds);
+// The stable sort of the rows by colour: perm (new -> old), rows of one colour ascending.
+std::vector<int32_t> color_major_perm(const std::vector<int32_t> &colors, int64_t ncolors);
+// B = P A P^T on raw device arrays (the contract of sprs_csr_permute; perm_dev a checked permutation): *rp (n + 1), *ci, *val
+// (nnz entries of A's scalar type; at least one is allocated) and, where src is not null, *src (per entry of B its position in
+// A's arrays) are hipMalloc'd arrays that belong to the caller.  No handle is created.  Blocking; the caller holds the lock and
+// has set the device.
+int csr_permute_arrays(const sprs_csr *A, const int32_t *perm_dev, int32_t **rp, int32_t **ci, void **val, int32_t **src);
 
 // ---- amg.hip
 // The same for an AMG handle: amg_check as ilu0_check, amg_apply: out = one V(1,1) cycle on in; in == out is allowed.

@@ -16,22 +16,34 @@ class ILU0(MatVecMul):
     `GMRES.precond_solve` take it in place of a `DiagPrecond`.  The handle owns its factors: A may be closed afterwards.
     `ILU0.new(A, sweeps=k)`, k >= 1: the same factors, each triangular solve replaced by k Jacobi sweeps from zero (the header's
     statement): one fully parallel launch per sweep instead of one per dependency level, 2k - 2 launches per application.  With
-    k at least the level count the sweeps return the exact solves bit for bit; a handful is usually enough for a preconditioner."""
+    k at least the level count the sweeps return the exact solves bit for bit; a handful is usually enough for a preconditioner.
+    `ILU0.new(A, order="multicolor")` or `order=perm` (int32, new -> old): the factorisation of P A P^T, applied as
+    P^T U^-1 L^-1 P on vectors in A's numbering; under the multicolour ordering a solve has at most as many levels as colours."""
 
     def __init__(self, handle, ctx, dtype, n, nnz):
         self.h, self.ctx, self.dtype, self.n, self.nnz = handle, ctx, np.dtype(dtype), int(n), int(nnz)
         self.s = sfx(self.dtype)
 
     @classmethod
-    def new(cls, A, sweeps=0):
+    def new(cls, A, sweeps=0, order=None):
         """sweeps = 0: exact level-scheduled solves; 1 .. 4096: that many Jacobi sweeps per triangular solve.
+        order = None: A's own row order; "multicolor": rows sorted by `A.color(0)`; an int32 permutation (new -> old): that one.
         Raises IncompatibleMatrixFormat (not square), ValueError (distributed A, unsorted or duplicate columns, a sweep count
-        outside 0 .. 4096) or ZeorDiagonalElem(row): a missing diagonal entry, or a pivot that is exactly zero or not finite."""
+        outside 0 .. 4096, a bad permutation, an ordering together with sweeps) or ZeorDiagonalElem(row), row in A's numbering:
+        a missing diagonal entry, or a pivot that is exactly zero or not finite."""
         sweeps = int(sweeps)
         if not 0 <= sweeps <= 4096:
             raise ValueError("sprsolve_hip: invalid argument: sweeps must be in 0 .. 4096 (0 = exact solves), got %d" % sweeps)
         h = C.c_void_p(); row = C.c_int64(-1)
-        st = _lib.lib().sprs_ilu0_create_sweeps(A.h, sweeps, C.byref(h), C.byref(row))
+        if order is None:
+            st = _lib.lib().sprs_ilu0_create_sweeps(A.h, sweeps, C.byref(h), C.byref(row))
+        elif isinstance(order, str):
+            if order != "multicolor":
+                raise ValueError("sprsolve_hip: invalid argument: order must be None, \"multicolor\" or a permutation, got %r" % order)
+            st = _lib.lib().sprs_ilu0_create_ordered(A.h, sweeps, _lib.ORDER_MULTICOLOR, None, 0, C.byref(h), C.byref(row))
+        else:
+            perm = np.ascontiguousarray(order, dtype=np.int32)
+            st = _lib.lib().sprs_ilu0_create_ordered(A.h, sweeps, _lib.ORDER_PERM, perm.ctypes.data_as(C.c_void_p), perm.size, C.byref(h), C.byref(row))
         if st == _lib.ZERO_DIAGONAL:
             raise ZeorDiagonalElem(row.value)
         if st == _lib.INVALID_ARGUMENT:
@@ -43,6 +55,15 @@ class ILU0(MatVecMul):
     def sweeps(self):
         """Jacobi sweeps per triangular solve; 0 for exact solves."""
         return int(_lib.lib().sprs_ilu0_sweeps(self.h))
+
+    @property
+    def order(self):
+        """The permutation (int32, new -> old) of an ordered handle, None for one in A's own order."""
+        if _lib.lib().sprs_ilu0_order(self.h, None) != 1:
+            return None
+        perm = np.empty(self.n, np.int32)
+        _lib.lib().sprs_ilu0_order(self.h, perm.ctypes.data_as(C.c_void_p))
+        return perm
 
     @property
     def levels(self):

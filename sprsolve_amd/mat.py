@@ -11,6 +11,7 @@ import numpy as np
 from . import _lib
 from .device import DevVec, default_ctx, dev_len, dev_ptr, dev_sfx, is_device_array, pre_sync, sfx
 from .error import check
+from .order import color_order
 
 
 class MatVecMul:
@@ -35,6 +36,7 @@ class HipCsr(MatVecMul):
     def __init__(self, handle, ctx, dtype, shape, keepalive=None):
         self.h, self.ctx, self.dtype, self.shape = handle, ctx, np.dtype(dtype), tuple(shape)
         self._keep = keepalive
+        self.color_rounds = None          # Jones-Plassmann rounds of the last color() call
 
     # -------------------------------------------------------------- constructors
     @classmethod
@@ -105,6 +107,37 @@ class HipCsr(MatVecMul):
         check(st, self.ctx.h)
         out = HipCsr(h, self.ctx, self.dtype, (self.shape[0], other.shape[1]))
         return (out, [int(v) for v in inf]) if info else out
+
+    def _refused(self, st):
+        if st == _lib.INVALID_ARGUMENT:
+            raise ValueError("sprsolve_hip: invalid argument: " + (_lib.lib().sprs_last_error(self.ctx.h) or b"").decode(errors="replace"))
+        check(st, self.ctx.h)
+
+    def color(self, seed=0):
+        """(colors, ncolors): the greedy first-fit colouring of the pattern's graph (i ~ j iff i != j and (i, j) or (j, i) is
+        stored) in decreasing (splitmix64(seed, i), i), computed on the device by Jones-Plassmann rounds (csrc/order.hip); the
+        header states the rule as a loop.  colors: int32, one per row.  The rounds it took are kept in `self.color_rounds`.
+        Raises IncompatibleMatrixFormat (not square) or ValueError (distributed)."""
+        colors = np.empty(self.shape[0], np.int32)
+        nc, rounds = C.c_int64(0), C.c_int64(0)
+        self._refused(_lib.lib().sprs_csr_color(self.h, int(seed) & 0xFFFFFFFFFFFFFFFF, colors.ctypes.data_as(C.c_void_p), C.byref(nc), C.byref(rounds)))
+        self.color_rounds = rounds.value
+        return colors, nc.value
+
+    @staticmethod
+    def color_order(colors):
+        """(perm, color_ptr): the stable sort of the rows by colour (sprsolve_amd.order.color_order)."""
+        return color_order(colors)
+
+    def permute(self, perm):
+        """B = P A P^T as an independent handle built on the device: perm[p] (int32, new -> old) is the row of self that becomes
+        row p, so B equals scipy's `A[perm][:, perm]`; columns ascending, values bit copies.  Raises ValueError for a perm of the
+        wrong length, with a value out of range or a duplicate, and for a distributed operator; IncompatibleMatrixFormat when
+        not square."""
+        perm = np.ascontiguousarray(perm, dtype=np.int32)
+        h = C.c_void_p()
+        self._refused(_lib.lib().sprs_csr_permute(self.h, perm.ctypes.data_as(C.c_void_p), perm.size, C.byref(h)))
+        return HipCsr(h, self.ctx, self.dtype, self.shape)
 
     def __matmul__(self, other):
         if not isinstance(other, HipCsr):
