@@ -1028,9 +1028,45 @@ int sprs_ilu0_minres_solve_dev_c(sprs_minres *S, const sprs_ilu0 *P, const sprs_
  * owns the level vectors, so calls on one context serialise.  Host slices of the wrong length: SPRS_DIM_MISMATCH.
  * Solvers: as for ILU(0) (same errors); z = P r, z = P v_j and u = P u of the recurrences are one cycle.  The cycle is
  * Hermitian positive definite when A is, so it is a valid CG preconditioner; on an indefinite A, CG ends in
- * SPRS_INVALID_PRECOND as with any preconditioner that is not positive definite. */
+ * SPRS_INVALID_PRECOND as with any preconditioner that is not positive definite.
+ *
+ * create_dev(A, theta, coarse_max, max_levels, seed) builds the same handle without the host: every step of a
+ * level runs in HBM, and the three serial aggregation passes are replaced by a rule that a few parallel rounds reproduce exactly.
+ * The refusals, their order and *row_out are create's (unsorted or duplicate columns are looked for on the device: the smallest
+ * such row is named).  Everything above holds as it stands — omega, theta_l, the strength test, the products, P, R, the stop
+ * rules, the coarse LU (on the host, from a download of the coarsest operator), the cycle — except "Aggregation", which reads:
+ *   G:  i ~ j when (i, j) or (j, i) is a strong stored entry; w(i, j) = the largest |a|^2 among those of the two that are strong.
+ *   key(i) = (splitmix64(seed, i), i), compared lexicographically; splitmix64 is sprs_csr_color's:
+ *     z = seed + (i + 1) * 0x9E3779B97F4A7C15;  z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) * 0x94D049BB133111EB;  z ^ z >> 31.
+ *   1. root[.] = -1;  for i in decreasing key(i):
+ *          if root[i] < 0 and root[j] < 0 for every j ~ i:   root[i] = i;  root[j] = i for every j ~ i
+ *      (a vertex without neighbours is a root on its own).
+ *   2. snap = root;  for every i with snap[i] < 0:
+ *          j* = the j ~ i with snap[j] >= 0 of largest w(i, j), the smallest such j among equals;   root[i] = snap[j*]
+ *      After a maximal pass 1 a free vertex has an aggregated neighbour, so j* exists and there is no pass 3; the device checks
+ *      it (a row without j* is SPRS_ERR_HIP, "internal error", never an unplaced row).
+ *   3. agg(i) = the number of roots below root[i]: aggregates are numbered by ascending root.
+ * The device runs pass 1 as rounds.  Every vertex is undecided at first.  A round: an undecided vertex that is aggregated or has
+ * an aggregated neighbour stops being undecided (it can never be a root); if none is undecided pass 1 is over; otherwise the
+ * round counts, and every undecided vertex whose key is the largest among the undecided vertices within two edges of it becomes
+ * a root and takes its neighbours.  Two winners of a round are more than two edges apart, a root decided earlier lies beyond two
+ * edges, and "never a root" is final because aggregation only grows: the rounds give loop 1's root[] whatever the launch geometry.
+ * No floating-point atomic is used; integer atomics count and hand out list slots whose order reaches no result.  The same seed
+ * gives the same handle, byte for byte; another seed gives other aggregates.  Aggregates are not bounded in size (a hub takes all
+ * its neighbours).
+ * A device-built handle keeps no host copy and no second device copy of its operators: sprs_amg_level_read unpacks the CSR arrays
+ * from the sliced-row layout (which holds every row's length, columns and values in stored order) and reads the aggregates from
+ * the 4 bytes a row kept in HBM.  sprs_amg_setup_info: *setup = 0 (create) or 1 (create_dev); rounds[l] = pass 1's rounds on
+ * level l for l < rounds_len (0 for the coarsest level, beyond it, and throughout a host-built handle).  sprs_amg_setup_stage_ms:
+ * a diagnostic, off unless the environment variable SPRS_CREATE_TRACE is set when create_dev runs (it then drains the stream at
+ * every stage boundary; otherwise creation pays no such drain and every entry is 0): host-clock milliseconds per stage, summed
+ * over the levels, in the order diagonal and omega, graph, rounds, pass 2 and numbering, A T, prolongator, adjoint, A P, R (A P),
+ * packing, coarse download and LU; entries beyond the eleventh and every entry of a host-built handle are 0. */
 typedef struct sprs_amg sprs_amg;
 int sprs_amg_create(const sprs_csr *A, double theta, int64_t coarse_max, int64_t max_levels, sprs_amg **out, int64_t *row_out);   /* row_out may be NULL */
+int sprs_amg_create_dev(const sprs_csr *A, double theta, int64_t coarse_max, int64_t max_levels, uint64_t seed, sprs_amg **out, int64_t *row_out);   /* row_out may be NULL */
+int sprs_amg_setup_info(const sprs_amg *P, int64_t *setup, int64_t *rounds, size_t rounds_len);   /* setup may be NULL; rounds may be NULL when rounds_len is 0 */
+int sprs_amg_setup_stage_ms(const sprs_amg *P, double *ms, size_t ms_len);
 int sprs_amg_destroy(sprs_amg *P);             /* NULL is a no-op */
 int sprs_amg_info(const sprs_amg *P, int64_t *levels, int64_t *launches, int64_t *tail_level, int64_t *lu_rows);   /* any pointer may be NULL */
 int sprs_amg_level_info(const sprs_amg *P, int64_t level, int64_t *rows, int64_t *nnz, int64_t *p_nnz, double *omega);

@@ -203,6 +203,9 @@ def _protos():
     P["sprs_ilu0_levels"] = [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]
     P["sprs_ilu0_read"] = [_vp, _vp]
     P["sprs_amg_create"] = [_vp, _dbl, _i64, _i64, _pp, C.POINTER(_i64)]
+    P["sprs_amg_create_dev"] = [_vp, _dbl, _i64, _i64, C.c_uint64, _pp, C.POINTER(_i64)]
+    P["sprs_amg_setup_info"] = [_vp, C.POINTER(_i64), _vp, _sz]
+    P["sprs_amg_setup_stage_ms"] = [_vp, _vp, _sz]
     P["sprs_amg_destroy"] = [_vp]
     P["sprs_amg_info"] = [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]
     P["sprs_amg_level_info"] = [_vp, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), _pd]

@@ -10,22 +10,33 @@ from .mat import MatVecMul
 
 
 class AMG(MatVecMul):
-    """`AMG.new(A, theta=0.08, coarse_max=256, max_levels=16)`: a smoothed-aggregation hierarchy of a square single-GPU `HipCsr`,
-    built at creation (aggregation on the host, the sparse products on the device).  As a `MatVecMul` it applies one V(1,1) cycle with damped Jacobi (csrc/amg.hip);
-    `CG.precond_solve` and `GMRES.precond_solve` take it in place of a `DiagPrecond`.  The handle owns its hierarchy: A may be
-    closed afterwards."""
+    """`AMG.new(A, theta=0.08, coarse_max=256, max_levels=16, setup="host", seed=0)`: a smoothed-aggregation hierarchy of a
+    square single-GPU `HipCsr`, built at creation.  `setup="host"`: the serial aggregation on the host, the sparse products on the
+    device.  `setup="device"`: the parallel aggregation rule of `sprs_amg_create_dev` (greedy in decreasing splitmix64(seed, i))
+    and every other step of a level in HBM; other aggregates, so another hierarchy, in the same handle.  As a `MatVecMul` it
+    applies one V(1,1) cycle with damped Jacobi (csrc/amg.hip); `precond_solve` of `CG`, `GMRES`, `BiCGStab`, `MinRes` and `IDRS`
+    and `Lobpcg.solve` take it in place of a `DiagPrecond`.  The handle owns its hierarchy: A may be closed afterwards."""
+
+    STAGES = ("diag", "graph", "rounds", "pass2", "AT", "prolongator", "adjoint", "AP", "RAP", "packing", "LU")
 
     def __init__(self, handle, ctx, dtype, n):
         self.h, self.ctx, self.dtype, self.n = handle, ctx, np.dtype(dtype), int(n)
         self.s = sfx(self.dtype)
 
     @classmethod
-    def new(cls, A, theta=0.08, coarse_max=256, max_levels=16):
+    def new(cls, A, theta=0.08, coarse_max=256, max_levels=16, setup="host", seed=0):
         """Raises IncompatibleMatrixFormat (not square), ValueError (distributed A, unsorted or duplicate columns, a parameter out
-        of range) or ZeorDiagonalElem(row): a missing, zero or non-finite diagonal entry of the level being built, or such a
-        pivot of the coarse LU."""
+        of range, a `setup` that is neither "host" nor "device") or ZeorDiagonalElem(row): a missing, zero or non-finite diagonal
+        entry of the level being built, or such a pivot of the coarse LU.  `seed` orders the device aggregation; the host one
+        ignores it."""
+        if setup not in ("host", "device"):
+            raise ValueError("sprsolve_hip: invalid argument: setup must be \"host\" or \"device\", not %r" % (setup,))
         h = C.c_void_p(); row = C.c_int64(-1)
-        st = _lib.lib().sprs_amg_create(A.h, float(theta), int(coarse_max), int(max_levels), C.byref(h), C.byref(row))
+        if setup == "device":
+            st = _lib.lib().sprs_amg_create_dev(A.h, float(theta), int(coarse_max), int(max_levels), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                C.byref(h), C.byref(row))
+        else:
+            st = _lib.lib().sprs_amg_create(A.h, float(theta), int(coarse_max), int(max_levels), C.byref(h), C.byref(row))
         if st == _lib.ZERO_DIAGONAL:
             raise ZeorDiagonalElem(row.value)
         if st == _lib.INVALID_ARGUMENT:
@@ -35,9 +46,10 @@ class AMG(MatVecMul):
 
     @property
     def info(self):
-        """dict(levels, launches, tail_level, lu_rows, rows, nnz, p_nnz, omega): the number of levels, the kernel launches of
-        one application, the first level that runs inside the one-workgroup tail kernel (== levels: none), the rows of the
-        coarse LU (0: Jacobi sweeps) and per level the rows, nnz(A_l), nnz(P_l) and the Jacobi weight."""
+        """dict(levels, launches, tail_level, lu_rows, rows, nnz, p_nnz, omega, setup, rounds): the number of levels, the kernel
+        launches of one application, the first level that runs inside the one-workgroup tail kernel (== levels: none), the rows
+        of the coarse LU (0: Jacobi sweeps), per level the rows, nnz(A_l), nnz(P_l) and the Jacobi weight, how the hierarchy was
+        built ("host" / "device") and per aggregated level the pass-1 rounds of the device aggregation (zeros for "host")."""
         L = _lib.lib()
         v = [C.c_int64() for _ in range(4)]
         check(L.sprs_amg_info(self.h, *[C.byref(x) for x in v]), self.ctx.h)
@@ -48,7 +60,20 @@ class AMG(MatVecMul):
             check(L.sprs_amg_level_info(self.h, l, C.byref(r), C.byref(z), C.byref(p), C.byref(w)), self.ctx.h)
             per.append((r.value, z.value, p.value, w.value))
         out.update(rows=[p[0] for p in per], nnz=[p[1] for p in per], p_nnz=[p[2] for p in per], omega=[p[3] for p in per])
+        how = C.c_int64()
+        rounds = np.zeros(max(out["levels"] - 1, 0), np.int64)
+        check(L.sprs_amg_setup_info(self.h, C.byref(how), rounds.ctypes.data_as(C.c_void_p), rounds.size), self.ctx.h)
+        out.update(setup=("host", "device")[how.value], rounds=rounds.tolist())
         return out
+
+    @property
+    def setup_ms(self):
+        """Milliseconds of the device set-up per stage (`AMG.STAGES`): a diagnostic, taken only when the environment variable
+        SPRS_CREATE_TRACE was set at creation (the set-up then drains the stream at every stage boundary); zeros otherwise and
+        for a host-built handle."""
+        ms = np.zeros(len(self.STAGES))
+        check(_lib.lib().sprs_amg_setup_stage_ms(self.h, ms.ctypes.data_as(C.c_void_p), ms.size), self.ctx.h)
+        return dict(zip(self.STAGES, ms.tolist()))
 
     def level(self, l, which="A"):
         """(indptr, indices, data) of A_l, P_l or R_l (which = "A" / "P" / "R")."""

@@ -1,7 +1,8 @@
 // Smoothed-aggregation algebraic multigrid: the hierarchy (built at creation: the aggregation and the prolongator formula on the
 // host, serial; the three sparse products of every level on the device, spgemm.hip, with the bits of the serial loop) and the
-// V(1,1) cycle that applies it as a preconditioner.  No reference analogue; the rules and the order of every sum are stated in
-// the header (sprs_amg_*) and restated by tests/_amg_ref.py.
+// V(1,1) cycle that applies it as a preconditioner.  sprs_amg_create_dev builds the same handle without the host: a parallel
+// aggregation rule and every other step of a level in HBM (amg_setup.hpp, included below).  No reference analogue; the rules
+// and the order of every sum are stated in the header (sprs_amg_*) and restated by tests/_amg_ref.py and tests/_amg_par_ref.py.
 //
 // ilu0.hip's two ideas carry the device side:
 //  * every operator of the hierarchy (A_l, P_l, R_l) is stored in the sliced-row layout of sell.hpp (position = row) and ONE
@@ -25,6 +26,7 @@ constexpr int AMG_TAIL_ROWS = 1024;      // levels of at most this many rows run
 constexpr int AMG_COARSE_LIMIT = 1024;   // largest coarse_max: the dense LU is applied by the tail kernel (AMG_COARSE_LIMIT <= AMG_TAIL_ROWS)
 constexpr int AMG_COARSE_SWEEPS = 8;     // damped-Jacobi sweeps in place of the LU when the coarsest level has more than coarse_max rows
 constexpr int AMG_MAX_LEVELS = 32;
+constexpr int AMG_STAGES = 11;           // stages of the device set-up that sprs_amg_setup_stage_ms reports
 }  // namespace sprs
 
 namespace {
@@ -306,9 +308,12 @@ struct AmgLevel {
     void *diag = nullptr;        // device, n of T
     double omega = 0;
     void *b = nullptr, *x = nullptr, *x2 = nullptr, *r = nullptr;   // device, n of T each
-    // host copies for sprs_amg_level_read (values as bytes of T)
+    // host copies for sprs_amg_level_read (values as bytes of T): the host set-up's, empty on a device-built handle
     std::vector<int32_t> a_ip, a_ix, p_ip, p_ix, r_ip, r_ix, agg;
     std::vector<char> a_v, p_v, r_v;
+    // the device set-up keeps the aggregates in HBM (n of int32; null on the coarsest level) and unpacks A, P, R on demand
+    int32_t *agg_dev = nullptr;
+    int64_t rounds = 0;          // pass-1 rounds of the device aggregation
 };
 
 }  // namespace
@@ -324,6 +329,8 @@ struct sprs_amg {
     void *tail_desc = nullptr;   // device, levels of TailLevel<T>
     int64_t launches = 0;
     void *in_tmp = nullptr, *out_tmp = nullptr;   // staging of the host entry points (lazily allocated)
+    int setup = 0;               // 0: built by sprs_amg_create (host), 1: by sprs_amg_create_dev
+    double stage_ms[AMG_STAGES] = {0};            // device set-up under SPRS_CREATE_TRACE: host clock per stage (SetupClock); zeros otherwise
 };
 
 namespace {
@@ -333,6 +340,48 @@ void keep_host(const HCsr<T> &M, std::vector<int32_t> &ip, std::vector<int32_t> 
     ip = M.ip; ix = M.ix;
     v.resize(sizeof(T) * M.v.size());
     if (!M.v.empty()) memcpy(v.data(), M.v.data(), v.size());
+}
+
+// the coarse solve: dense no-pivot LU of Ac in the k-i-j order, kept column-major -> -1, or the row of a pivot nobody may divide by
+template <class T>
+int64_t dense_lu(const HCsr<T> &Ac, std::vector<T> &lu) {
+    const size_t m = (size_t)Ac.n;
+    lu.assign(m * m, szero<T>());
+    for (int32_t i = 0; i < Ac.n; ++i)
+        for (int32_t p = Ac.ip[i]; p < Ac.ip[i + 1]; ++p) lu[(size_t)Ac.ix[p] * m + i] = Ac.v[p];
+    for (size_t k = 0; k < m; ++k) {
+        const T piv = lu[k * m + k];
+        if (bad_pivot(piv)) return (int64_t)k;
+        for (size_t i = k + 1; i < m; ++i) lu[k * m + i] = sdiv(lu[k * m + i], piv);
+        for (size_t j = k + 1; j < m; ++j) {                 // (the j loop outside: column-major; each entry sees the same one update)
+            const T ukj = lu[j * m + k];
+            for (size_t i = k + 1; i < m; ++i) lu[j * m + i] = ssub(lu[j * m + i], smul(lu[k * m + i], ukj));
+        }
+    }
+    return -1;
+}
+
+// What both set-ups end with, once every level's operators, diagonal and vectors are in place: the tail and the launch count.
+template <class T>
+int finish_handle(sprs_amg *P) {
+    using R = Real<T>;
+    const int nlev = (int)P->lv.size();
+    // the tail: every level of at most AMG_TAIL_ROWS rows (levels only shrink)
+    P->tail = nlev;
+    for (int l = nlev - 1; l >= 0 && P->lv[l].n <= AMG_TAIL_ROWS; --l) P->tail = l;
+    std::vector<TailLevel<T>> td((size_t)nlev);
+    for (int l = 0; l < nlev; ++l) {
+        const AmgLevel &D = P->lv[l];
+        td[l] = TailLevel<T>{D.A.dev<T>(), D.P.dev<T>(), D.R.dev<T>(), (const T *)D.diag, (R)D.omega, D.n, (T *)D.b, (T *)D.x, (T *)D.x2, (T *)D.r};
+    }
+    TailLevel<T> *dt = nullptr;
+    if (!dev_upload(&dt, td.data(), td.size())) { P->tail_desc = dt; return SPRS_ERR_HIP; }
+    P->tail_desc = dt;
+    // launches of one application: five per level above the tail (three down, two up), the tail's one, and where the
+    // coarsest level is above the tail its Jacobi sweeps
+    const int upper = std::min(P->tail, nlev - 1);
+    P->launches = 5 * (int64_t)upper + (P->tail < nlev ? 1 : AMG_COARSE_SWEEPS);
+    return SPRS_OK;
 }
 
 template <class T>
@@ -392,24 +441,12 @@ int amg_create(const sprs_csr *A, double theta_d, int64_t coarse_max, int64_t ma
     }
     const int nlev = (int)H.size();
     const HCsr<T> &Ac = H[nlev - 1].A;
-    // the coarse solve: dense no-pivot LU in the k-i-j order, kept column-major
     std::vector<T> lu;
     int lu_n = 0;
     if (Ac.n <= coarse_max) {
         lu_n = Ac.n;
-        const size_t m = (size_t)lu_n;
-        lu.assign(m * m, szero<T>());
-        for (int32_t i = 0; i < Ac.n; ++i)
-            for (int32_t p = Ac.ip[i]; p < Ac.ip[i + 1]; ++p) lu[(size_t)Ac.ix[p] * m + i] = Ac.v[p];
-        for (size_t k = 0; k < m; ++k) {
-            const T piv = lu[k * m + k];
-            if (bad_pivot(piv)) { if (row_out) *row_out = (int64_t)k; return SPRS_ZERO_DIAGONAL; }
-            for (size_t i = k + 1; i < m; ++i) lu[k * m + i] = sdiv(lu[k * m + i], piv);
-            for (size_t j = k + 1; j < m; ++j) {             // (the j loop outside: column-major; each entry sees the same one update)
-                const T ukj = lu[j * m + k];
-                for (size_t i = k + 1; i < m; ++i) lu[j * m + i] = ssub(lu[j * m + i], smul(lu[k * m + i], ukj));
-            }
-        }
+        const int64_t bad = dense_lu(Ac, lu);
+        if (bad >= 0) { if (row_out) *row_out = bad; return SPRS_ZERO_DIAGONAL; }
     }
 
     // the device side
@@ -437,24 +474,31 @@ int amg_create(const sprs_csr *A, double theta_d, int64_t coarse_max, int64_t ma
         if (!dev_upload(&dl, lu.data(), lu.size())) { P->lu = dl; return SPRS_ERR_HIP; }
         P->lu = dl;
     }
-    // the tail: every level of at most AMG_TAIL_ROWS rows (levels only shrink)
-    P->tail = nlev;
-    for (int l = nlev - 1; l >= 0 && P->lv[l].n <= AMG_TAIL_ROWS; --l) P->tail = l;
-    std::vector<TailLevel<T>> td((size_t)nlev);
-    for (int l = 0; l < nlev; ++l) {
-        const AmgLevel &D = P->lv[l];
-        td[l] = TailLevel<T>{D.A.dev<T>(), D.P.dev<T>(), D.R.dev<T>(), (const T *)D.diag, (R)D.omega, D.n, (T *)D.b, (T *)D.x, (T *)D.x2, (T *)D.r};
-    }
-    TailLevel<T> *dt = nullptr;
-    if (!dev_upload(&dt, td.data(), td.size())) { P->tail_desc = dt; return SPRS_ERR_HIP; }
-    P->tail_desc = dt;
-    // launches of one application: five per level above the tail (three down, two up), the tail's one, and where the
-    // coarsest level is above the tail its Jacobi sweeps
-    const int upper = std::min(P->tail, nlev - 1);
-    P->launches = 5 * (int64_t)upper + (P->tail < nlev ? 1 : AMG_COARSE_SWEEPS);
+    SPRS_TRY(finish_handle<T>(P));
     *out = guard.release();
     return SPRS_OK;
 }
+
+// host clock of the device set-up's stages, a diagnostic like CreateTrace and behind the same switch: with SPRS_CREATE_TRACE set,
+// lap() drains the stream and books the time since the last lap; without it lap() does nothing and creation pays no drain
+struct SetupClock {
+    bool on;
+    double *ms, t0;
+    explicit SetupClock(double *stage_ms) : on(getenv("SPRS_CREATE_TRACE") != nullptr), ms(stage_ms), t0(CreateTrace::now()) {}
+    int lap(sprs_ctx *c, int stage) {
+        if (!on) return SPRS_OK;
+        SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        const double t = CreateTrace::now();
+        ms[stage] += t - t0; t0 = t;
+        return SPRS_OK;
+    }
+};
+
+}  // namespace
+
+#include "amg_setup.hpp"
+
+namespace {
 
 template <class T, int OP>
 void launch_op(sprs_ctx *c, const SellMat &M, const T *x, const T *y, const T *d, Real<T> omega, T *o) {
@@ -542,18 +586,24 @@ template AppliedPrec<cplxf> amg_prec<cplxf>(const sprs_amg *);
 
 extern "C" {
 
+// the refusals both creations share, in this order
+static int amg_create_args(const sprs_csr *A, double theta, int64_t coarse_max, int64_t max_levels, sprs_amg **out, int64_t *row_out) {
+    if (!A || !out) return SPRS_INVALID_ARGUMENT;
+    *out = nullptr;
+    if (row_out) *row_out = -1;
+    SPRS_TRY(single_gpu_only(A, "sprs_amg"));   // (before the shape: a row block with a halo has more columns than rows)
+    if (A->nrows != A->ncols) return SPRS_NOT_SQUARE;
+    if (!(theta >= 0.0) || coarse_max < 1 || coarse_max > AMG_COARSE_LIMIT || max_levels < 1 || max_levels > AMG_MAX_LEVELS) {
+        snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_amg: theta >= 0, 1 <= coarse_max <= %d and 1 <= max_levels <= %d are required",
+                 AMG_COARSE_LIMIT, AMG_MAX_LEVELS);
+        return SPRS_INVALID_ARGUMENT;
+    }
+    return SPRS_OK;
+}
+
 int sprs_amg_create(const sprs_csr *A, double theta, int64_t coarse_max, int64_t max_levels, sprs_amg **out, int64_t *row_out) {
     SPRS_G(
-        if (!A || !out) return SPRS_INVALID_ARGUMENT;
-        *out = nullptr;
-        if (row_out) *row_out = -1;
-        SPRS_TRY(single_gpu_only(A, "sprs_amg"));   // (before the shape: a row block with a halo has more columns than rows)
-        if (A->nrows != A->ncols) return SPRS_NOT_SQUARE;
-        if (!(theta >= 0.0) || coarse_max < 1 || coarse_max > AMG_COARSE_LIMIT || max_levels < 1 || max_levels > AMG_MAX_LEVELS) {
-            snprintf(A->ctx->err, sizeof(A->ctx->err), "sprs_amg: theta >= 0, 1 <= coarse_max <= %d and 1 <= max_levels <= %d are required",
-                     AMG_COARSE_LIMIT, AMG_MAX_LEVELS);
-            return SPRS_INVALID_ARGUMENT;
-        }
+        SPRS_TRY(amg_create_args(A, theta, coarse_max, max_levels, out, row_out));
         switch (A->dtype) {
             case DT_D: return amg_create<double>(A, theta, coarse_max, max_levels, out, row_out);
             case DT_Z: return amg_create<cplx>(A, theta, coarse_max, max_levels, out, row_out);
@@ -563,12 +613,37 @@ int sprs_amg_create(const sprs_csr *A, double theta, int64_t coarse_max, int64_t
         return SPRS_INVALID_ARGUMENT;)
 }
 
+int sprs_amg_create_dev(const sprs_csr *A, double theta, int64_t coarse_max, int64_t max_levels, uint64_t seed, sprs_amg **out, int64_t *row_out) {
+    SPRS_G(
+        SPRS_TRY(amg_create_args(A, theta, coarse_max, max_levels, out, row_out));
+        switch (A->dtype) {
+            case DT_D: return amg_create_dev<double>(A, theta, coarse_max, max_levels, seed, out, row_out);
+            case DT_Z: return amg_create_dev<cplx>(A, theta, coarse_max, max_levels, seed, out, row_out);
+            case DT_S: return amg_create_dev<float>(A, theta, coarse_max, max_levels, seed, out, row_out);
+            case DT_C: return amg_create_dev<cplxf>(A, theta, coarse_max, max_levels, seed, out, row_out);
+        }
+        return SPRS_INVALID_ARGUMENT;)
+}
+
+int sprs_amg_setup_info(const sprs_amg *P, int64_t *setup, int64_t *rounds, size_t rounds_len) {
+    if (!P || (!rounds && rounds_len)) return SPRS_INVALID_ARGUMENT;
+    if (setup) *setup = P->setup;
+    for (size_t l = 0; l < rounds_len; ++l) rounds[l] = l < P->lv.size() ? P->lv[l].rounds : 0;
+    return SPRS_OK;
+}
+
+int sprs_amg_setup_stage_ms(const sprs_amg *P, double *ms, size_t ms_len) {
+    if (!P || (!ms && ms_len)) return SPRS_INVALID_ARGUMENT;
+    for (size_t s = 0; s < ms_len; ++s) ms[s] = s < (size_t)AMG_STAGES ? P->stage_ms[s] : 0.0;
+    return SPRS_OK;
+}
+
 int sprs_amg_destroy(sprs_amg *P) {
     if (!P) return SPRS_OK;
     if (P->ctx) { (void)hipSetDevice(P->ctx->device); (void)hipStreamSynchronize(P->ctx->stream); }
     for (AmgLevel &D : P->lv) {
         D.A.release(); D.P.release(); D.R.release();
-        for (void *p : {D.diag, D.b, D.x, D.x2, D.r}) if (p) (void)hipFree(p);
+        for (void *p : {D.diag, D.b, D.x, D.x2, D.r, (void *)D.agg_dev}) if (p) (void)hipFree(p);
     }
     for (void *p : {P->lu, P->tail_desc, P->in_tmp, P->out_tmp}) if (p) (void)hipFree(p);
     delete P;
@@ -597,6 +672,19 @@ int sprs_amg_level_info(const sprs_amg *P, int64_t level, int64_t *rows, int64_t
 int sprs_amg_level_read(const sprs_amg *P, int64_t level, int which, int32_t *row_ptr, int32_t *col_idx, void *val, int32_t *agg) {
     if (!P || level < 0 || level >= (int64_t)P->lv.size() || which < 0 || which > 2) return SPRS_INVALID_ARGUMENT;
     const AmgLevel &D = P->lv[(size_t)level];
+    if (P->setup == 1) {                                                // device-built: nothing was kept for this call
+        SPRS_G(
+            sprs_ctx *c = P->ctx;
+            const bool last = level + 1 == (int64_t)P->lv.size();
+            if (last && (which != 0 || (agg && D.n))) return SPRS_INVALID_ARGUMENT;   // the coarsest level has no P, R or aggregates
+            CtxLock lock(c);
+            SPRS_HIP_TRY(c, hipSetDevice(c->device));
+            SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+            if (row_ptr || col_idx || val)
+                SPRS_TRY(sell_unpack_host(c, which == 0 ? D.A : which == 1 ? D.P : D.R, dtype_size(P->dtype), row_ptr, col_idx, val));
+            if (agg && D.n) SPRS_HIP_TRY(c, hipMemcpy(agg, D.agg_dev, sizeof(int32_t) * (size_t)D.n, hipMemcpyDeviceToHost));
+            return SPRS_OK;)
+    }
     const std::vector<int32_t> &ip = which == 0 ? D.a_ip : which == 1 ? D.p_ip : D.r_ip, &ix = which == 0 ? D.a_ix : which == 1 ? D.p_ix : D.r_ix;
     const std::vector<char> &v = which == 0 ? D.a_v : which == 1 ? D.p_v : D.r_v;
     if (which != 0 && ip.empty()) return SPRS_INVALID_ARGUMENT;       // the coarsest level has no P, R or aggregates

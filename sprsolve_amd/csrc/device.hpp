@@ -8,6 +8,15 @@ namespace sprs {
 constexpr int WAVE = 64;
 constexpr int NWAVE = BLOCK / WAVE;
 
+// The priority of vertex i under `seed`: splitmix64 at counter i (= sprsolve_amd.gen.splitmix64_keys(seed, i)).  The colouring
+// (order.hip) and the AMG aggregation (amg_setup.hpp) are both greedy in decreasing (vertex_key(seed, i), i).
+__device__ __forceinline__ uint64_t vertex_key(uint64_t seed, int i) {
+    uint64_t z = seed + ((uint64_t)i + 1) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int off = WAVE / 2; off > 0; off >>= 1) v = v + __shfl_down(v, off, WAVE);

@@ -405,6 +405,15 @@ template <class T>
 int spgemm_dev(sprs_ctx *c, const char *who, int64_t nrA, int64_t nrB, int64_t ncB, const int32_t *a_rp, const int32_t *a_ci, const T *a_v,
                const int32_t *b_rp, const int32_t *b_ci, const T *b_v, int32_t **c_rp, int32_t **c_ci, T **c_v, int64_t *c_nnz, int64_t *info);
 
+// ---- transpose.hip
+// The conjugate transpose (conj != 0) or transpose of raw device CSR arrays (nr x nc, nnz entries; the contract of sprs_csr_adjoint:
+// row j holds column j's entries in ascending source row, stored order kept): no handle is created.  On SPRS_OK *rp (nc + 1), *ci
+// and *v (nnz entries; at least one is allocated) are hipMalloc'd arrays that belong to the caller.  A column outside [0, nc):
+// SPRS_INVALID_ARGUMENT with a text that starts with `who`.  Blocking; the caller holds the context's lock and has set the device.
+template <class T>
+int adjoint_dev(sprs_ctx *c, const char *who, int64_t nr, int64_t nc, int64_t nnz, const int32_t *a_rp, const int32_t *a_ci, const T *a_v, int conj,
+                int32_t **rp, int32_t **ci, T **v);
+
 // ---- blas1.hip  (all on ctx->stream, asynchronous)
 template <class T, class S> int launch_axpy(sprs_ctx *c, size_t n, S a, const T *x, T *y);
 template <class T> int launch_axpby(sprs_ctx *c, size_t n, T a, const T *x, T b, T *y);

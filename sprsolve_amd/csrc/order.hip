@@ -32,13 +32,6 @@ using namespace sprs;
 namespace {
 
 // ---- colouring
-__device__ __forceinline__ uint64_t jp_weight(uint64_t seed, int i) {     // = gen.splitmix64_keys(seed, i)
-    uint64_t z = seed + ((uint64_t)i + 1) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 // the colour of a vertex as round `parity` sees it: -1 while it had none when the round began
 __device__ __forceinline__ int jp_decode(int v, int parity) {
     if (v >= -1) return v;
@@ -77,7 +70,7 @@ struct JpRow {
 // neighbour j of vertex i (weight wi) is uncoloured in this round and stronger
 __device__ __forceinline__ bool jp_beats(int j, int i, uint64_t wi, int n, uint64_t seed, int parity, const int32_t *color) {
     if ((unsigned)j >= (unsigned)n || j == i || jp_decode(color[j], parity) >= 0) return false;
-    const uint64_t wj = jp_weight(seed, j);
+    const uint64_t wj = vertex_key(seed, j);
     return wj > wi || (wj == wi && j > i);
 }
 
@@ -108,7 +101,7 @@ __global__ __launch_bounds__(BLOCK) void jp_round_kernel(int n, uint64_t seed, i
     }
     const int deg = R.deg();
     if (open && deg <= WAVE) {
-        const uint64_t wi = jp_weight(seed, i);
+        const uint64_t wi = vertex_key(seed, i);
         bool top = true;
         for (int k = 0; k < deg && top; ++k) top = !jp_beats(R.at(k, ci, tj), i, wi, n, seed, parity, color);
         if (top) {
@@ -127,7 +120,7 @@ __global__ __launch_bounds__(BLOCK) void jp_round_kernel(int n, uint64_t seed, i
         const int r = __shfl(i, src);
         const JpRow Q{__shfl(R.a0, src), __shfl(R.a1, src), __shfl(R.t0, src), __shfl(R.t1, src)};
         const int qdeg = Q.deg();
-        const uint64_t wr = jp_weight(seed, r);
+        const uint64_t wr = vertex_key(seed, r);
         bool beaten = false;
         for (int k = lane; k < qdeg; k += WAVE) beaten |= jp_beats(Q.at(k, ci, tj), r, wr, n, seed, parity, color);
         if (__ballot(beaten)) continue;

@@ -9,7 +9,8 @@
 //           bisection in A's row_ptr) and val (conjugated on request) of every entry at its sorted position
 // No slot is handed out by an atomic counter, so two constructions give the same arrays.  The finished arrays go through
 // sprs_csr_create_dev_* like any matrix built in HBM (row blocks, dictionary streams, tile and chain plans) and are then owned
-// by the new handle.
+// by the new handle.  adjoint_dev (internal.hpp) is the same three passes on raw arrays without the handle: the AMG set-up
+// forms R = P^H with it (amg_setup.hpp).
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
@@ -51,13 +52,11 @@ __global__ __launch_bounds__(BLOCK) void adj_fill_kernel(int64_t nnz, int64_t nr
     }
 }
 
-template <class T, class CT>
-int adjoint_typed(const sprs_csr *A, int conj, int (*create_dev)(sprs_ctx *, int64_t, int64_t, int64_t, const int32_t *, const int32_t *, const CT *, int, sprs_csr **),
-                  sprs_csr **out) {
-    sprs_ctx *c = A->ctx;
-    CtxLock lock(c);
-    SPRS_HIP_TRY(c, hipSetDevice(c->device));
-    const int64_t nr = A->nrows, nc = A->ncols, nnz = A->nnz;
+// the three passes on raw arrays (internal.hpp, adjoint_dev)
+template <class T>
+int adjoint_arrays(sprs_ctx *c, const char *who, int64_t nr, int64_t nc, int64_t nnz, const int32_t *a_rp, const int32_t *a_ci, const T *a_v, int conj,
+                   int32_t **rp_out, int32_t **ci_out, T **v_out) {
+    *rp_out = nullptr; *ci_out = nullptr; *v_out = nullptr;
     const int grid = (int)std::min<int64_t>(std::max<int64_t>((nnz + BLOCK - 1) / BLOCK, 1), 4 * (int64_t)grid_for(c));
     DevBufs tmp;
     int32_t *cnt, *rp, *ci, *key, *ent, *key_s, *ent_s;
@@ -73,7 +72,7 @@ int adjoint_typed(const sprs_csr *A, int conj, int (*create_dev)(sprs_ctx *, int
     // count
     SPRS_HIP_TRY(c, hipMemsetAsync(cnt, 0, sizeof(int32_t) * ((size_t)nc + 1), c->stream));
     if (nnz > 0) {
-        hipLaunchKernelGGL(adj_count_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, nnz, nc, A->col_idx, cnt, key, ent);
+        hipLaunchKernelGGL(adj_count_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, nnz, nc, a_ci, cnt, key, ent);
         SPRS_HIP_TRY(c, hipGetLastError());
     }
     // scan: row_ptr of the result (nc + 1 entries, the last one = nnz)
@@ -90,28 +89,59 @@ int adjoint_typed(const sprs_csr *A, int conj, int (*create_dev)(sprs_ctx *, int
     SPRS_HIP_TRY(c, hipMemcpyAsync(&total, rp + nc, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
     if ((int64_t)total != nnz) {
-        snprintf(c->err, sizeof(c->err), "sprs_csr_adjoint: %lld of %lld column indices are outside [0, %lld)", (long long)(nnz - total), (long long)nnz, (long long)nc);
+        snprintf(c->err, sizeof(c->err), "%s: %lld of %lld column indices are outside [0, %lld)", who, (long long)(nnz - total), (long long)nnz, (long long)nc);
         return SPRS_INVALID_ARGUMENT;
     }
     // fill
     if (nnz > 0) {
         SPRS_HIP_TRY(c, rocprim::radix_sort_pairs(scratch, sort_bytes, key, key_s, ent, ent_s, (size_t)nnz, 0u, (unsigned int)bits, c->stream));
-        hipLaunchKernelGGL((adj_fill_kernel<T>), dim3(grid), dim3(BLOCK), 0, c->stream, nnz, nr, conj, A->row_ptr, ent_s,
-                           reinterpret_cast<const T *>(A->val), ci, vv);
+        hipLaunchKernelGGL((adj_fill_kernel<T>), dim3(grid), dim3(BLOCK), 0, c->stream, nnz, nr, conj, a_rp, ent_s, a_v, ci, vv);
         SPRS_HIP_TRY(c, hipGetLastError());
     }
     SPRS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    // the sort's 16 bytes per entry, the counts and rocprim's scratch go before creation allocates its own arrays
-    for (void *q : {(void *)cnt, (void *)key, (void *)ent, (void *)key_s, (void *)ent_s, (void *)scratch}) tmp.free(q);
+    tmp.release(rp); tmp.release(ci); tmp.release(vv);                 // (the sort's 16 bytes per entry, the counts and rocprim's scratch go here)
+    *rp_out = rp; *ci_out = ci; *v_out = vv;
+    return SPRS_OK;
+}
+
+template <class T, class CT>
+int adjoint_typed(const sprs_csr *A, int conj, int (*create_dev)(sprs_ctx *, int64_t, int64_t, int64_t, const int32_t *, const int32_t *, const CT *, int, sprs_csr **),
+                  sprs_csr **out) {
+    sprs_ctx *c = A->ctx;
+    CtxLock lock(c);
+    SPRS_HIP_TRY(c, hipSetDevice(c->device));
+    const int64_t nr = A->nrows, nc = A->ncols, nnz = A->nnz;
+    int32_t *rp, *ci;
+    T *vv;
+    SPRS_TRY(adjoint_arrays<T>(c, "sprs_csr_adjoint", nr, nc, nnz, A->row_ptr, A->col_idx, reinterpret_cast<const T *>(A->val), conj, &rp, &ci, &vv));
+    DevBufs own;                                                       // released if creation fails
+    own.p = {(void *)rp, (void *)ci, (void *)vv};
     sprs_csr *H = nullptr;
     SPRS_TRY(create_dev(c, nc, nr, nnz, rp, ci, reinterpret_cast<const CT *>(vv), 1, &H));
     H->owns_arrays = true;                                             // adopted, and from here on released with the handle
-    tmp.release(rp); tmp.release(ci); tmp.release(vv);
+    own.p.clear();
     *out = H;
     return SPRS_OK;
 }
 
 }  // namespace
+
+namespace sprs {
+
+template <class T>
+int adjoint_dev(sprs_ctx *c, const char *who, int64_t nr, int64_t nc, int64_t nnz, const int32_t *a_rp, const int32_t *a_ci, const T *a_v, int conj,
+                int32_t **rp_out, int32_t **ci_out, T **v_out) {
+    return adjoint_arrays<T>(c, who, nr, nc, nnz, a_rp, a_ci, a_v, conj, rp_out, ci_out, v_out);
+}
+#define SPRS_ADJOINT_INST(T)                                                                                                              \
+    template int adjoint_dev<T>(sprs_ctx *, const char *, int64_t, int64_t, int64_t, const int32_t *, const int32_t *, const T *, int, \
+                                int32_t **, int32_t **, T **);
+SPRS_ADJOINT_INST(double)
+SPRS_ADJOINT_INST(cplx)
+SPRS_ADJOINT_INST(float)
+SPRS_ADJOINT_INST(cplxf)
+
+}  // namespace sprs
 
 extern "C" {
 
