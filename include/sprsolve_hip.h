@@ -1742,6 +1742,103 @@ int sprs_solver_get_fused_launches(const void *solver, int kind, int64_t *k2_fus
  * launches: sprs_solver_get_profile neither times nor counts them.  Zero for the other solvers and with "bicg_k5" 0. */
 int sprs_solver_get_chain_k5_launches(const void *solver, int kind, int64_t *launches);
 
+/* ---------------------------------------------------------------- on-chip batch solvers: many small systems, one workgroup each
+ * (no reference analogue; csrc/batch.hip, csrc/batch_plan.hpp)
+ * nbatch systems A_b x_b = rhs_b that share ONE square CSR pattern (n rows, nnz entries, int32 indices, every row's columns
+ * strictly ascending) and have their own values: a C-contiguous (nbatch, nnz) block.  Vectors are C-contiguous (nbatch, n) blocks.
+ * One workgroup of B(n) threads runs one whole solve with every vector of the recurrence in the CU's LDS; one launch serves the
+ * batch; no workgroup waits for another and every loop is bounded by max_iter.  The matrix values stay in HBM / L2, the pattern
+ * once and each system's values in the 64-row sliced, slice-column-major layout of csrc/sell.hpp.
+ *
+ * create / create_dev (the arrays on the host / on the device; both are copied, the handle owns its copies):
+ *   SPRS_INVALID_ARGUMENT for a NULL ctx / pattern / out, n < 0, nnz < 0, nbatch < 0, row_ptr[0] != 0, row_ptr[n] != nnz, a row_ptr
+ *   that decreases, a column outside [0, n), NULL values while nbatch * nnz > 0, and — with "the column indices of row .. are not
+ *   strictly ascending" in sprs_last_error and *row_out = that row — for the lowest such row.  nbatch == 0 or n == 0 is allowed:
+ *   every call on such a handle does nothing and returns SPRS_OK.  Whether every row stores its diagonal is recorded (the
+ *   smallest row without one); it matters only when Jacobi is asked for.  row_out may be NULL (-1 where no row is to blame).
+ * set_values[_dev]: replaces the values of all systems (pattern and plan stay).  read: the values back, (nbatch, nnz).
+ * info: n, nnz, nbatch, the threads per workgroup B(n), and the LDS bytes a CG / a BiCGStab workgroup asks for; any pointer may be
+ *   NULL.  sprs_batch_max_rows(solver, dtype): the row cap of a solver (SPRS_BATCH_*) for a scalar type (0 f64, 1 c64, 2 f32,
+ *   3 c32), -1 for another code.
+ * mul_vec[_dev]: y_b = A_b x_b for every system in one launch (any n); lengths other than nbatch * n: SPRS_DIM_MISMATCH.
+ *
+ * The plan (batch_plan.hpp).  B(n) = min(256, 64 ceil(n / 64)), 64 for n = 0.  CG keeps 5 vectors of n in LDS (x, r, z, p, q),
+ * BiCGStab 8 (x, r, r0, y, p, v, t, z), plus 128 bytes of reduction scratch.  With 64 KiB of vectors per workgroup (two workgroups
+ * and more per CU) max_rows(solver, T) = floor(65536 / (NV sizeof(T))) rounded down to a multiple of 64: BiCGStab 1024 (f64),
+ * 512 (c64), 2048 (f32), 1024 (c32); CG 1600, 768, 3264, 1600.  A solve on a handle with n above the solver's cap is
+ * SPRS_INVALID_ARGUMENT with n and the cap in sprs_last_error; nothing is truncated and nothing falls back.
+ *
+ * solve(B, precond, rhs, rhs_len, x, x_len, max_iter, tol, its_out, res_out, status_out): precond SPRS_BATCH_NONE or
+ * SPRS_BATCH_JACOBI (another value: SPRS_INVALID_ARGUMENT); x is in/out; its_out / res_out / status_out are host arrays of
+ * nbatch entries (any may be NULL).  rhs_len != nbatch * n: SPRS_INCOMPATIBLE_RHS_SIZE; x_len != nbatch * n:
+ * SPRS_INCOMPATIBLE_X_SIZE.  Jacobi on a pattern without a full diagonal: SPRS_ZERO_DIAGONAL for the whole call, nothing is
+ * launched, the row in sprs_last_error (and in its_out[0] where its_out is given).  Otherwise the call returns SPRS_OK or the status
+ * of the lowest-numbered system that did not return SPRS_OK; solver events are per system and never abort the batch.
+ * Jacobi: dinv_i = one / a_ii in T (DiagPrecond::new with V = T), formed by each workgroup from its system's values; a zero value
+ * is not checked.  z = r * dinv_i is a product in T.
+ * BiCGStab: the recurrence of sprs_bicgstab_solve_* / sprs_bicgstab_precond_solve_* per system, statement for statement (zero
+ * right-hand side, early exit, restart, BreakDown, omega = 0, InsufficientIterNum); CG: the recurrence of sprs_cg_* above.  An event
+ * other than SPRS_OK reports *res_out = 0 (SPRS_INVALID_PRECOND: re(rho_new)).
+ *
+ * The arithmetic.  Every scalar operation is in T (T::Real for norms), rounded once, nothing fused; complex products and quotients
+ * are the naive formulas.  Row fold: sigma = +0; for the stored j ascending: sigma = sigma + a_ij * x_j.  A sum over rows
+ * (conj_dot(a, b) = sum conj(a_i) b_i; norm2 = sqrt of sum |a_i|^2 in T::Real): thread t folds from +0 over i = t, t + B, ..
+ * ascending; inside each wavefront of 64 the butterfly v[l] += v[l + off], off = 32 .. 1; then the B / 64 wavefronts left to right
+ * from wavefront 0.  Every thread of the workgroup holds the same bits, so every branch on a scalar is workgroup-uniform.  A given
+ * input gives the same bytes on every call and for every nbatch.
+ * Limits: one pattern per batch; n up to the cap; one system per workgroup (systems far below 64 rows waste lanes); Jacobi only; no
+ * mixed precision; single GPU. */
+typedef struct sprs_batch sprs_batch;
+enum { SPRS_BATCH_BICGSTAB = 0, SPRS_BATCH_CG = 1 };
+enum { SPRS_BATCH_NONE = 0, SPRS_BATCH_JACOBI = 1 };
+int sprs_batch_destroy(sprs_batch *B);     /* NULL is a no-op */
+int sprs_batch_info(const sprs_batch *B, int64_t *n, int64_t *nnz, int64_t *nbatch, int64_t *threads, int64_t *lds_cg, int64_t *lds_bicgstab);
+int sprs_batch_max_rows(int solver, int dtype);
+int sprs_batch_create_d(sprs_ctx *ctx, int64_t n, int64_t nnz, int64_t nbatch, const int32_t *row_ptr_host, const int32_t *col_idx_host, const double *values_host, sprs_batch **out, int64_t *row_out);
+int sprs_batch_create_dev_d(sprs_ctx *ctx, int64_t n, int64_t nnz, int64_t nbatch, const int32_t *row_ptr_dev, const int32_t *col_idx_dev, const double *values_dev, sprs_batch **out, int64_t *row_out);
+int sprs_batch_set_values_d(sprs_batch *B, const double *values_host);
+int sprs_batch_set_values_dev_d(sprs_batch *B, const double *values_dev);
+int sprs_batch_read_d(const sprs_batch *B, double *values_host);
+int sprs_batch_mul_vec_d(const sprs_batch *B, const double *x_host, size_t x_len, double *y_host, size_t y_len);
+int sprs_batch_mul_vec_dev_d(const sprs_batch *B, const double *x_dev, size_t x_len, double *y_dev, size_t y_len);
+int sprs_batch_bicgstab_solve_d(sprs_batch *B, int precond, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out, int *status_out);
+int sprs_batch_bicgstab_solve_dev_d(sprs_batch *B, int precond, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out, int *status_out);
+int sprs_batch_cg_solve_d(sprs_batch *B, int precond, const double *rhs, size_t rhs_len, double *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out, int *status_out);
+int sprs_batch_cg_solve_dev_d(sprs_batch *B, int precond, const double *rhs_dev, size_t rhs_len, double *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out, int *status_out);
+int sprs_batch_create_z(sprs_ctx *ctx, int64_t n, int64_t nnz, int64_t nbatch, const int32_t *row_ptr_host, const int32_t *col_idx_host, const sprs_c64 *values_host, sprs_batch **out, int64_t *row_out);
+int sprs_batch_create_dev_z(sprs_ctx *ctx, int64_t n, int64_t nnz, int64_t nbatch, const int32_t *row_ptr_dev, const int32_t *col_idx_dev, const sprs_c64 *values_dev, sprs_batch **out, int64_t *row_out);
+int sprs_batch_set_values_z(sprs_batch *B, const sprs_c64 *values_host);
+int sprs_batch_set_values_dev_z(sprs_batch *B, const sprs_c64 *values_dev);
+int sprs_batch_read_z(const sprs_batch *B, sprs_c64 *values_host);
+int sprs_batch_mul_vec_z(const sprs_batch *B, const sprs_c64 *x_host, size_t x_len, sprs_c64 *y_host, size_t y_len);
+int sprs_batch_mul_vec_dev_z(const sprs_batch *B, const sprs_c64 *x_dev, size_t x_len, sprs_c64 *y_dev, size_t y_len);
+int sprs_batch_bicgstab_solve_z(sprs_batch *B, int precond, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out, int *status_out);
+int sprs_batch_bicgstab_solve_dev_z(sprs_batch *B, int precond, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out, int *status_out);
+int sprs_batch_cg_solve_z(sprs_batch *B, int precond, const sprs_c64 *rhs, size_t rhs_len, sprs_c64 *x, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out, int *status_out);
+int sprs_batch_cg_solve_dev_z(sprs_batch *B, int precond, const sprs_c64 *rhs_dev, size_t rhs_len, sprs_c64 *x_dev, size_t x_len, size_t max_iter, double tol, size_t *its_out, double *res_out, int *status_out);
+int sprs_batch_create_s(sprs_ctx *ctx, int64_t n, int64_t nnz, int64_t nbatch, const int32_t *row_ptr_host, const int32_t *col_idx_host, const float *values_host, sprs_batch **out, int64_t *row_out);
+int sprs_batch_create_dev_s(sprs_ctx *ctx, int64_t n, int64_t nnz, int64_t nbatch, const int32_t *row_ptr_dev, const int32_t *col_idx_dev, const float *values_dev, sprs_batch **out, int64_t *row_out);
+int sprs_batch_set_values_s(sprs_batch *B, const float *values_host);
+int sprs_batch_set_values_dev_s(sprs_batch *B, const float *values_dev);
+int sprs_batch_read_s(const sprs_batch *B, float *values_host);
+int sprs_batch_mul_vec_s(const sprs_batch *B, const float *x_host, size_t x_len, float *y_host, size_t y_len);
+int sprs_batch_mul_vec_dev_s(const sprs_batch *B, const float *x_dev, size_t x_len, float *y_dev, size_t y_len);
+int sprs_batch_bicgstab_solve_s(sprs_batch *B, int precond, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out, int *status_out);
+int sprs_batch_bicgstab_solve_dev_s(sprs_batch *B, int precond, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out, int *status_out);
+int sprs_batch_cg_solve_s(sprs_batch *B, int precond, const float *rhs, size_t rhs_len, float *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out, int *status_out);
+int sprs_batch_cg_solve_dev_s(sprs_batch *B, int precond, const float *rhs_dev, size_t rhs_len, float *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out, int *status_out);
+int sprs_batch_create_c(sprs_ctx *ctx, int64_t n, int64_t nnz, int64_t nbatch, const int32_t *row_ptr_host, const int32_t *col_idx_host, const sprs_c32 *values_host, sprs_batch **out, int64_t *row_out);
+int sprs_batch_create_dev_c(sprs_ctx *ctx, int64_t n, int64_t nnz, int64_t nbatch, const int32_t *row_ptr_dev, const int32_t *col_idx_dev, const sprs_c32 *values_dev, sprs_batch **out, int64_t *row_out);
+int sprs_batch_set_values_c(sprs_batch *B, const sprs_c32 *values_host);
+int sprs_batch_set_values_dev_c(sprs_batch *B, const sprs_c32 *values_dev);
+int sprs_batch_read_c(const sprs_batch *B, sprs_c32 *values_host);
+int sprs_batch_mul_vec_c(const sprs_batch *B, const sprs_c32 *x_host, size_t x_len, sprs_c32 *y_host, size_t y_len);
+int sprs_batch_mul_vec_dev_c(const sprs_batch *B, const sprs_c32 *x_dev, size_t x_len, sprs_c32 *y_dev, size_t y_len);
+int sprs_batch_bicgstab_solve_c(sprs_batch *B, int precond, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out, int *status_out);
+int sprs_batch_bicgstab_solve_dev_c(sprs_batch *B, int precond, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out, int *status_out);
+int sprs_batch_cg_solve_c(sprs_batch *B, int precond, const sprs_c32 *rhs, size_t rhs_len, sprs_c32 *x, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out, int *status_out);
+int sprs_batch_cg_solve_dev_c(sprs_batch *B, int precond, const sprs_c32 *rhs_dev, size_t rhs_len, sprs_c32 *x_dev, size_t x_len, size_t max_iter, float tol, size_t *its_out, float *res_out, int *status_out);
+
 #ifdef __cplusplus
 }
 #endif

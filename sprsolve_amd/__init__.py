@@ -7,6 +7,7 @@ package does not load it, using it does, and there is no CPU fallback.
 """
 from . import error, precond, vecalg  # noqa: F401
 from .amg import AMG  # noqa: F401
+from .batch import BatchCsr  # noqa: F401
 from .bicg_stab import BiCGStab  # noqa: F401
 from .cg import CG  # noqa: F401
 from .cg_many import CGMany  # noqa: F401

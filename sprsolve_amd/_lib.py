@@ -26,6 +26,8 @@ LOBPCG_MAX_BLOCK = 8
 SVDS_MAX_NCV = 64
 SVDS_LARGEST, SVDS_SMALLEST = 0, 1
 EXPM_MAX_NCV = 48
+BATCH_BICGSTAB, BATCH_CG = 0, 1
+BATCH_NONE, BATCH_JACOBI = 0, 1
 
 
 class c64(C.Structure):
@@ -148,6 +150,14 @@ def _protos():
         P["sprs_bjacobi_mul_vec_dev_" + s] = [_vp, _vp, _vp]
         P["sprs_bjacobi_mul_vec_" + s] = [_vp, _vp, _sz, _vp, _sz]
         P["sprs_bjacobi_inverse_" + s] = [_vp, _vp, _sz]
+        for k in ("create", "create_dev"):
+            P["sprs_batch_%s_%s" % (k, s)] = [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _pp, C.POINTER(_i64)]
+        for k in ("set_values", "set_values_dev", "read"):
+            P["sprs_batch_%s_%s" % (k, s)] = [_vp, _vp]
+        for k in ("mul_vec", "mul_vec_dev"):
+            P["sprs_batch_%s_%s" % (k, s)] = [_vp, _vp, _sz, _vp, _sz]
+        for k in ("bicgstab_solve", "bicgstab_solve_dev", "cg_solve", "cg_solve_dev"):
+            P["sprs_batch_%s_%s" % (k, s)] = [_vp, _int, _vp, _sz, _vp, _sz, _sz, re_, _psz, pre, C.POINTER(_int)]
         for k in ("cg", "gmres", "bicgstab", "minres", "idrs"):
             for pc in ("ilu0", "amg", "fsai", "bjacobi"):
                 if (pc, k) == ("bjacobi", "idrs"):           # IDR(s) does not take a block-Jacobi handle
@@ -218,6 +228,9 @@ def _protos():
     P["sprs_bjacobi_destroy"] = [_vp]
     P["sprs_bjacobi_info"] = [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]
     P["sprs_bjacobi_block_ptr"] = [_vp, _vp]
+    P["sprs_batch_destroy"] = [_vp]
+    P["sprs_batch_info"] = [_vp] + [C.POINTER(_i64)] * 6
+    P["sprs_batch_max_rows"] = [_int, _int]
     P["sprs_gauss_seidel_create"] = [_vp, _pp]
     P["sprs_gauss_seidel_destroy"] = [_vp]
     for s in ("d", "s"):

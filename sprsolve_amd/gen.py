@@ -271,6 +271,64 @@ def convection_diffusion_2d(rows, cols, cx=0.3, cy=0.2, dtype=np.float64):
     return indptr, indices, data, rhs
 
 
+def batch_convection_diffusion(rows, cols, nbatch, dtype=np.float64, hermitian=False, seed=SEED):
+    """nbatch systems on ONE 5-point pattern of a rows x cols grid with values of their own, for the batch solvers (`BatchCsr`; no
+    reference analogue).  System b is convection_diffusion_2d with its own coefficients drawn from splitmix streams: cx_b, cy_b in
+    U[-0.9, 0.9) (streams 400, 401) and a diagonal shift 10^U[-2, 0.5) (stream 402) added to the diagonal 4 — from nearly singular
+    to strongly dominant, so the systems need visibly different iteration counts.  The complex dtypes multiply every entry by
+    1 + 0.25i.
+    hermitian=True: the Hermitian positive-definite variant for CG, cx = cy = 0: the real dtypes have the neighbours -1 and the
+    diagonal 4 + shift_b; the complex dtypes have -1 + g_b i below the diagonal and -1 - g_b i above it (as complex_hermitian_grid
+    places its imaginary parts), g_b in U[0.1, 0.6) (stream 403), and the real diagonal 4 sqrt(1 + g_b^2) + shift_b, which keeps
+    every system strictly diagonally dominant.
+    rhs_b = A_b x with x[i*cols + j] = 1 + (i + 2j) / (rows + cols) (times 1 - 0.5i for the complex dtypes), every product and the
+    row sums (left to right) formed in the dtype.  Returns (indptr, indices, values (nbatch, nnz), rhs (nbatch, n))."""
+    dt = np.dtype(dtype)
+    cplx = dt.kind == "c"
+    i, j = np.meshgrid(np.arange(rows), np.arange(cols), indexing="ij")
+    i = i.ravel(); j = j.ravel()
+    vid = i * cols + j
+    n = rows * cols
+    R = [vid]; Cc = [vid]; K = [np.zeros(n, np.int64)]            # kind 0: the diagonal; 1 .. 4: the neighbours below
+    for kind, (di, dj) in enumerate(((-1, 0), (1, 0), (0, -1), (0, 1)), start=1):
+        ni = i + di; nj = j + dj
+        ok = (ni >= 0) & (ni < rows) & (nj >= 0) & (nj < cols)
+        R.append(vid[ok]); Cc.append((ni * cols + nj)[ok]); K.append(np.full(int(ok.sum()), kind, np.int64))
+    indptr, indices, kind = _coo_to_csr(n, np.concatenate(R), np.concatenate(Cc), np.concatenate(K))
+    cx = uniform(seed, nbatch, -0.9, 0.9, stream=400)
+    cy = uniform(seed, nbatch, -0.9, 0.9, stream=401)
+    shift = 10.0 ** uniform(seed, nbatch, -2.0, 0.5, stream=402)
+    g = uniform(seed, nbatch, 0.1, 0.6, stream=403)
+    table = np.zeros((nbatch, 5), np.complex128)
+    if not hermitian:
+        fac = (1.0 + 0.25j) if cplx else 1.0
+        table[:, 0] = (4.0 + shift) * fac
+        for k, v in ((1, -1.0 - cy), (2, -1.0 + cy), (3, -1.0 - cx), (4, -1.0 + cx)):
+            table[:, k] = v * fac
+    elif cplx:
+        table[:, 0] = 4.0 * np.sqrt(1.0 + g * g) + shift
+        table[:, 1] = table[:, 3] = -1.0 + 1j * g                 # the neighbours at a smaller index: below the diagonal
+        table[:, 2] = table[:, 4] = -1.0 - 1j * g
+    else:
+        table[:, 0] = 4.0 + shift
+        table[:, 1:] = -1.0
+    values = (table if cplx else table.real)[:, kind].astype(dt)
+    xs = ((1.0 + (i + 2.0 * j) / float(rows + cols)) * ((1.0 - 0.5j) if cplx else 1.0)).astype(dt)
+    xg = xs[indices][None, :]
+    if cplx:                                                      # the naive product, component by component (as _complex_rhs)
+        prod = np.empty(values.shape, dt)
+        prod.real = values.real * xg.real - values.imag * xg.imag
+        prod.imag = values.real * xg.imag + values.imag * xg.real
+    else:
+        prod = values * xg
+    rhs = np.zeros((nbatch, n), dt)
+    if nbatch and n:
+        for e in range(5):                                        # entry e of every row that has one: the row sums left to right
+            rows_e = np.nonzero(np.diff(indptr) > e)[0]
+            rhs[:, rows_e] = rhs[:, rows_e] + prod[:, indptr[rows_e] + e]
+    return indptr, indices, np.ascontiguousarray(values), rhs
+
+
 def coupled_grid(rows, cols, bs, dtype=np.float64, spread=1e3, stream=300):
     """A coupled system with bs unknowns per node of a rows x cols grid, Hermitian positive definite, for block preconditioners (no
     reference analogue): A = L (x) C + blockdiag(e_p e_p^H).  L is the 5-point Dirichlet Laplacian of the grid (2 on the diagonal
